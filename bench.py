@@ -1,16 +1,23 @@
 #!/usr/bin/env python3
 """bench.py -- BASELINE.json's metric on its config, one JSON line on rank 0.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run times the headline leg alone (set-up, warm-up, K timed steps, the result line).  --full adds
+everything else below: the int32 and PairHMM legs, configs 4 and 5 (unless --no-extra-configs), the corpus
+and one-shot legs, the kernel-only and roofline figures (back-to-back launches and HIP events of their own)
+and the CPU baselines.
+--dump-outputs DIR writes the scores of the headline leg's last timed step as DIR/sw_scores.npy (float64; a
+rank r > 0 writes DIR/sw_scores_rank<r>.npy); the inputs are seeded, so runs with the same arguments compare.
 
 A STEP is one pass of the hot path over one batch in the reference's own timing window
 (smithWaterman/hipvers.cpp:475-483): kernel launch -> results resident in HOST memory, with
 the inputs already resident in HBM when the clock starts.  Every step is clocked on its own (median and
-min are reported beside the mean); the launch inside it is bracketed by HIP events on the launch stream
-(kernel-only duration, the roofline's denominator).  Before the W untimed warm-up steps the device is
-warmed BY TIME (--warm-seconds of back-to-back launches), so a short run (--steps 20) and a long one
-(--steps 500) report the same figures.
+min are reported beside the mean); with --full, the launch inside every fourth step is bracketed by HIP
+events on the launch stream (kernel-only duration, the roofline's denominator).  Before the W untimed warm-up
+steps the device is warmed BY TIME (--warm-seconds of back-to-back launches), so a short run (--steps 20)
+and a long one (--steps 500) report the same figures.
 
 Headline (`value`): Smith-Waterman GCUPS on BASELINE config 2 -- per GPU one batch of 65 536 pairs, 150x150,
 iid ACGT + 25 % related pairs, int32 affine-gap scores computed in packed int16 lanes (bit-identical; the
@@ -195,14 +202,19 @@ def parse_args(argv=None):
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--warm-seconds", type=float, default=0.5, help="back-to-back launches before every timed leg")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra-configs", action="store_true", help="headline legs only (PMC profiling passes)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baselines")
+    ap.add_argument("--no-extra-configs", action="store_true", help="with --full: headline legs only (PMC profiling passes)")
     # The control plane (barriers, max of the ranks' clocks, the per-rank table: host scalars only) runs on gloo by
     # default; "nccl" (= RCCL) puts the same three calls on device tensors.  The data path has no collective.
     ap.add_argument("--dist-backend", default="gloo", choices=["nccl", "gloo"])
     # rehearsal of the multi-rank control flow on a box with fewer GPUs than ranks (never for numbers):
     ap.add_argument("--share-device", action="store_true", help="map every rank to device 0")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true", help="all legs, kernel-only / roofline figures and CPU baselines (default: the headline leg alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the headline leg's results of its last timed step as DIR/<name>.npy")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def self_launch(args):
@@ -354,9 +366,10 @@ def main():
                 dev.launch()
             ctx.sync()
 
-    def timed(dev, fetch, steps, warmup, unbind=None):
-        """-> dict: wall clock over `steps` steps (max over ranks), per-step host times, per-step kernel times, and
-        the kernel-only figure from back-to-back launches."""
+    def timed(dev, fetch, steps, warmup, unbind=None, snapshot=None):
+        """-> dict: wall clock over `steps` steps (max over ranks), per-step host times and, with --full, per-step
+        kernel times and the kernel-only figure from back-to-back launches.  snapshot(): called once the last timed
+        step's results are on the host, its value kept as "last"."""
         warm(dev)
         for _ in range(warmup):
             dev.launch()
@@ -367,7 +380,7 @@ def main():
         t0 = time.perf_counter()
         for k in range(steps):
             ta = time.perf_counter()
-            if k % 4 == 0:  # HIP events around the launch on its stream, on every fourth step of the timed region: the
+            if args.full and k % 4 == 0:  # HIP events around the launch on its stream, on every fourth step of the timed region: the
                 ctx.timer_start()  # two records and the query cost 6-8 us of host time, 3-4 % of a 0.2 ms step
                 dev.launch()
                 ctx.timer_mark()
@@ -384,22 +397,25 @@ def main():
         torch.cuda.synchronize()
         ctx.sync()
         mine = time.perf_counter() - t0
+        last = snapshot() if snapshot is not None else None
         barrier()
         dt = agd.max_over_ranks(mine, device=red_dev)
+        t = {"dt": dt, "steps": steps, "step_ms": {"median": float(np.median(per)) * 1e3, "min": float(per.min()) * 1e3,
+                                                  "mean": float(per.mean()) * 1e3, "max": float(per.max()) * 1e3}, "last": last}
+        if not args.full:
+            return t
         if unbind is not None:  # the kernel-only figure is the fill with its results left in HBM
             unbind()
         ctx.timer_start()
         for _ in range(steps):
             dev.launch()
         b2b = ctx.timer_stop() / steps
-        return {"dt": dt, "steps": steps, "step_ms": {"median": float(np.median(per)) * 1e3, "min": float(per.min()) * 1e3,
-                                                     "mean": float(per.mean()) * 1e3, "max": float(per.max()) * 1e3},
-                "launch_ms": float(kern.mean()), "launch_ms_min": float(kern.min()), "back_to_back_launch_ms": b2b}
+        return dict(t, launch_ms=float(kern.mean()), launch_ms_min=float(kern.min()), back_to_back_launch_ms=b2b)
 
     few = lambda: (max(20, args.steps // 5), max(3, args.warmup // 5))  # (the other legs: 20 steps -- one slow step among ten moved a leg by 5-8 % from run to run)
     traffic = {}
     tfile = os.path.join(ROOT, "profiles", "traffic.json")
-    if os.path.exists(tfile):
+    if args.full and os.path.exists(tfile):  # quoted by the roofline figures only
         traffic = json.load(open(tfile))
 
     def roof(alg_bytes, launch_ms, key, in_hbm_ms=None):
@@ -417,10 +433,12 @@ def main():
 
     def leg(t, units, per_unit_name):
         """Throughput fields of one leg: whole-job units over the max-over-ranks wall clock of its steps."""
-        return {"value": n_gpus * units * t["steps"] / t["dt"], "steps": t["steps"], "ms_per_step": t["dt"] / t["steps"] * 1e3,
-                "step_ms": t["step_ms"], "window": WINDOW,
-                "kernel_only": {per_unit_name: n_gpus * units / (t["back_to_back_launch_ms"] * 1e-3),
-                                "launch_ms": t["back_to_back_launch_ms"], "what": "back-to-back launches, HIP events, results stay in HBM (unbound)"}}
+        r = {"value": n_gpus * units * t["steps"] / t["dt"], "steps": t["steps"], "ms_per_step": t["dt"] / t["steps"] * 1e3,
+             "step_ms": t["step_ms"], "window": WINDOW}
+        if args.full:
+            r["kernel_only"] = {per_unit_name: n_gpus * units / (t["back_to_back_launch_ms"] * 1e-3),
+                                "launch_ms": t["back_to_back_launch_ms"], "what": "back-to-back launches, HIP events, results stay in HBM (unbound)"}
+        return r
 
     # ---------------- Smith-Waterman, BASELINE config 2 (per rank: its own seed => its own shard)
     sw = synth.sw_pairs(SW_PAIRS, SW_LEN, SW_LEN, seed=2 + 1000 * rank, related_frac=0.25)
@@ -428,33 +446,40 @@ def main():
     sw_dev = ctx.sw_batch(sw)
     sw_dev.bind_scores(sw_out)  # a batch in file order writes its scores into the page-locked array itself: no copy kernel behind the fill
     sw_info = sw_dev.info()
-    sw_t = timed(sw_dev, lambda: sw_dev.scores(sw_out), args.steps, args.warmup, unbind=lambda: sw_dev.bind_scores(None))
-    sw_sum = int(sw_out.astype(np.int64).sum())
+    sw_t = timed(sw_dev, lambda: sw_dev.scores(sw_out), args.steps, args.warmup, unbind=lambda: sw_dev.bind_scores(None),
+                 snapshot=lambda: sw_out.copy())
+    sw_sum = int(sw_t["last"].astype(np.int64).sum())
     sw_dev.close()
     sw_cells = sw.cells(sentinel=False)  # 65536 * 22500
-    # the same batch through the int32 kernel (BASELINE config 2 as worded); scores must be the same
-    ctx.set_option(agx.OPT_SW_KERNEL, agx.SW_KERNEL_INT32)
-    i32_dev = ctx.sw_batch(sw)
-    ctx.set_option(agx.OPT_SW_KERNEL, agx.SW_KERNEL_AUTO)
-    i32_info = i32_dev.info()
-    i32_out = agx.host_array(sw.n_pairs, np.int32)
-    i32_dev.bind_scores(i32_out)
-    i32_t = timed(i32_dev, lambda: i32_dev.scores(i32_out), *few(), unbind=lambda: i32_dev.bind_scores(None))
-    i32_same = bool(np.array_equal(i32_out, sw_out))
-    i32_dev.close()
+    if args.full:
+        # the same batch through the int32 kernel (BASELINE config 2 as worded); scores must be the same
+        ctx.set_option(agx.OPT_SW_KERNEL, agx.SW_KERNEL_INT32)
+        i32_dev = ctx.sw_batch(sw)
+        ctx.set_option(agx.OPT_SW_KERNEL, agx.SW_KERNEL_AUTO)
+        i32_info = i32_dev.info()
+        i32_out = agx.host_array(sw.n_pairs, np.int32)
+        i32_dev.bind_scores(i32_out)
+        i32_t = timed(i32_dev, lambda: i32_dev.scores(i32_out), *few(), unbind=lambda: i32_dev.bind_scores(None))
+        i32_same = bool(np.array_equal(i32_out, sw_out))
+        i32_dev.close()
 
-    # ---------------- PairHMM, BASELINE config 3
-    ph = synth.phmm_regions(PH_REGIONS, PH_READS, PH_HAPS, PH_R, PH_H, seed=3 + 1000 * rank)
-    ph_out = (agx.host_array(ph.n_pairs, np.float64), None)
-    ph_dev = ctx.phmm_batch(ph, agx.PHMM_F32_FMA)
-    ph_dev.bind_results(ph_out[0])  # a batch in output order writes its log10 likelihoods into the page-locked array itself
-    ph_info = ph_dev.info()
-    ph_t = timed(ph_dev, lambda: ph_dev.results(ph_out, want_sums=False), args.steps, args.warmup, unbind=lambda: ph_dev.bind_results(None))
-    ph_rescued = ph_dev.info().n_rescued
-    ph_sum = float(ph_out[0].sum())
-    ph_dev.close()
+        # ---------------- PairHMM, BASELINE config 3
+        ph = synth.phmm_regions(PH_REGIONS, PH_READS, PH_HAPS, PH_R, PH_H, seed=3 + 1000 * rank)
+        ph_out = (agx.host_array(ph.n_pairs, np.float64), None)
+        ph_dev = ctx.phmm_batch(ph, agx.PHMM_F32_FMA)
+        ph_dev.bind_results(ph_out[0])  # a batch in output order writes its log10 likelihoods into the page-locked array itself
+        ph_info = ph_dev.info()
+        ph_t = timed(ph_dev, lambda: ph_dev.results(ph_out, want_sums=False), args.steps, args.warmup, unbind=lambda: ph_dev.bind_results(None))
+        ph_rescued = ph_dev.info().n_rescued
+        ph_sum = float(ph_out[0].sum())
+        ph_dev.close()
 
-    extra = not args.no_extra_configs
+    if args.dump_outputs:  # what a caller of the timed path receives: this rank's scores of the last timed step
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "sw_scores.npy" if rank == 0 else "sw_scores_rank%d.npy" % rank),
+                sw_t["last"].astype(np.float64))
+
+    extra = args.full and not args.no_extra_configs
     if extra:
         # ---------------- weak legs of the two 8-GPU configs: every rank its own 1/8-size shard
         c4 = synth.sw_pairs(C4_PAIRS // 8, 32, 512, seed=4 + 1000 * rank)
@@ -597,8 +622,6 @@ def main():
         return
 
     sw_leg = leg(sw_t, sw_cells / 1e9, "gcups")
-    ph_leg = leg(ph_t, ph.n_pairs, "pairs_per_s")
-    i32_leg = leg(i32_t, sw_cells / 1e9, "gcups")
     out = {
         "metric": "Smith-Waterman affine-gap score-only GCUPS (config 2: 65536 pairs 150x150 per GPU)",
         "value": sw_leg["value"], "unit": "GCUPS", "n_gpus": n_gpus, "steps": args.steps, "warmup": args.warmup,
@@ -608,28 +631,31 @@ def main():
                    "pairs_per_gpu": SW_PAIRS, "len": SW_LEN, "cells_counted_per_pair": SW_LEN * SW_LEN,
                    "parallelism": "pairs sharded per GPU, no collective", "window": WINDOW,
                    "warm_seconds_before_each_leg": args.warm_seconds},
-        "step_ms": sw_leg["step_ms"], "kernel_only": sw_leg["kernel_only"],
-        "roofline": roof(sw.algorithmic_bytes(), sw_t["launch_ms"], "sw_fill", sw_t["back_to_back_launch_ms"]),
+        "step_ms": sw_leg["step_ms"],
         "sw": {"waves": sw_info.n_waves, "launches_per_step": sw_info.n_launches,
-               "useful_cell_fraction": sw_info.cells / max(1, sw_info.padded_cells),
-               "valu": {"ops_per_cell": "6.75 instructions per 2 cells (DNA-coded rising cell with column classes): v_pk_maximum3_f16 x2.5, v_pk_max_u16, v_perm_b32, v_add3_u32, v_sub_u32 x1.25",
-                        "frac_of_instruction_mix_ceiling": sw_info.padded_cells * (6.75 / 2 / VALU_PACKED) / (sw_t["back_to_back_launch_ms"] * 1e-3),
-                        "priced_on": "kernel_only.launch_ms (the fill with its results left in HBM)"},
-               "score_checksum": sw_sum},
-        "sw_int32": dict(i32_leg, metric="config 2 through the int32 kernel (AGX_SW_KERNEL_INT32: 32-bit state, one pair at a time per lane group, DNA-coded match: 7.5 instructions per cell)", unit="GCUPS",
-                         scores_identical_to_packed=i32_same, useful_cell_fraction=i32_info.cells / max(1, i32_info.padded_cells),
-                         roofline=roof(sw.algorithmic_bytes(), i32_t["launch_ms"], "sw_fill_int32", i32_t["back_to_back_launch_ms"])),
-        "pairhmm": dict(ph_leg, metric="PairHMM forward pairs/s (config 3: 65536 pairs R=100 H=300 fp32 per GPU)", unit="pairs/s",
-                        dtype="f32 (two haplotypes per lane group, packed FMA, two reads per group behind one another (read trains); double rescue)",
-                        gcups=n_gpus * ph.cells() * ph_t["steps"] / ph_t["dt"] / 1e9, rescued_in_f64=int(ph_rescued),
-                        waves=ph_info.n_waves, launches_per_step=ph_info.n_launches,
-                        useful_cell_fraction=ph_info.cells / max(1, ph_info.padded_cells),
-                        roofline=roof(ph.algorithmic_bytes(), ph_t["launch_ms"], "phmm_fill", ph_t["back_to_back_launch_ms"]),
-                        valu={"ops_per_cell": "9 instructions per 2 cells (fast cell): v_pk_fma_f32 x4, v_pk_mul_f32 x2, v_pk_add_f32, v_perm_b32 x2",
-                              "frac_of_instruction_mix_ceiling": ph_info.padded_cells * (9 / 2 / VALU_PACKED) / (ph_t["back_to_back_launch_ms"] * 1e-3),
-                              "priced_on": "kernel_only.launch_ms (the fill with its results left in HBM)"},
-                        log10_checksum=ph_sum),
+               "useful_cell_fraction": sw_info.cells / max(1, sw_info.padded_cells), "score_checksum": sw_sum},
     }
+    if args.full:
+        ph_leg = leg(ph_t, ph.n_pairs, "pairs_per_s")
+        i32_leg = leg(i32_t, sw_cells / 1e9, "gcups")
+        out["kernel_only"] = sw_leg["kernel_only"]
+        out["roofline"] = roof(sw.algorithmic_bytes(), sw_t["launch_ms"], "sw_fill", sw_t["back_to_back_launch_ms"])
+        out["sw"]["valu"] = {"ops_per_cell": "6.75 instructions per 2 cells (DNA-coded rising cell with column classes): v_pk_maximum3_f16 x2.5, v_pk_max_u16, v_perm_b32, v_add3_u32, v_sub_u32 x1.25",
+                             "frac_of_instruction_mix_ceiling": sw_info.padded_cells * (6.75 / 2 / VALU_PACKED) / (sw_t["back_to_back_launch_ms"] * 1e-3),
+                             "priced_on": "kernel_only.launch_ms (the fill with its results left in HBM)"}
+        out["sw_int32"] = dict(i32_leg, metric="config 2 through the int32 kernel (AGX_SW_KERNEL_INT32: 32-bit state, one pair at a time per lane group, DNA-coded match: 7.5 instructions per cell)", unit="GCUPS",
+                               scores_identical_to_packed=i32_same, useful_cell_fraction=i32_info.cells / max(1, i32_info.padded_cells),
+                               roofline=roof(sw.algorithmic_bytes(), i32_t["launch_ms"], "sw_fill_int32", i32_t["back_to_back_launch_ms"]))
+        out["pairhmm"] = dict(ph_leg, metric="PairHMM forward pairs/s (config 3: 65536 pairs R=100 H=300 fp32 per GPU)", unit="pairs/s",
+                             dtype="f32 (two haplotypes per lane group, packed FMA, two reads per group behind one another (read trains); double rescue)",
+                             gcups=n_gpus * ph.cells() * ph_t["steps"] / ph_t["dt"] / 1e9, rescued_in_f64=int(ph_rescued),
+                             waves=ph_info.n_waves, launches_per_step=ph_info.n_launches,
+                             useful_cell_fraction=ph_info.cells / max(1, ph_info.padded_cells),
+                             roofline=roof(ph.algorithmic_bytes(), ph_t["launch_ms"], "phmm_fill", ph_t["back_to_back_launch_ms"]),
+                             valu={"ops_per_cell": "9 instructions per 2 cells (fast cell): v_pk_fma_f32 x4, v_pk_mul_f32 x2, v_pk_add_f32, v_perm_b32 x2",
+                                   "frac_of_instruction_mix_ceiling": ph_info.padded_cells * (9 / 2 / VALU_PACKED) / (ph_t["back_to_back_launch_ms"] * 1e-3),
+                                   "priced_on": "kernel_only.launch_ms (the fill with its results left in HBM)"},
+                             log10_checksum=ph_sum)
     if extra:
         c4_leg, c5_leg = leg(c4_t, c4.cells(sentinel=False) / 1e9, "gcups"), leg(c5_t, c5.n_pairs, "pairs_per_s")
 
@@ -663,24 +689,25 @@ def main():
         out["corpus_10s"] = corpus_legs
         out["multi_one_process"] = multi_one
         out["one_shot"] = one
-    # the figures of the other legs that a reader of the first few keys should not have to dig for
-    summ = {"int32_gcups": i32_leg["value"], "int32_ms_per_step": i32_leg["ms_per_step"], "int32_scores_identical_to_packed": i32_same,
-            "pairhmm_config3_f32_pairs_per_s": ph_leg["value"], "pairhmm_config3_ms_per_step": ph_leg["ms_per_step"]}
-    if extra:
-        summ.update({"config4_shard_gcups": out["config4"]["value"], "config4_total_gcups": out["config4"]["total"]["value"],
-                     "config4_total_n_shards": out["config4"]["total"]["n_shards"],
-                     "config5_shard_f64_pairs_per_s": out["config5"]["value"], "config5_total_f64_pairs_per_s": out["config5"]["total"]["value"],
-                     "multi_one_process_config4_ms": multi_one.get("config4", {}).get("ms"), "multi_one_process_config5_ms": multi_one.get("config5", {}).get("ms"),
-                     "multi_one_process_config4_page_locked_ms": multi_one.get("config4_page_locked_source", {}).get("ms"),
-                     "one_shot_config2_pinned_ms_min": one["config2_pinned"]["ms_min"], "one_shot_config3_ms_min": one["config3_pageable"]["ms_min"],
-                     "corpus_10s_f64_pairs_per_s": corpus_legs.get("f64", {}).get("pairs_per_s"),
-                     "corpus_10s_f32_fma_pairs_per_s": corpus_legs.get("f32_fma", {}).get("pairs_per_s"),
-                     "corpus_10s_f64_useful_cell_fraction": corpus_legs.get("f64", {}).get("useful_cell_fraction"),
-                     "corpus_10s_f32_fma_useful_cell_fraction": corpus_legs.get("f32_fma", {}).get("useful_cell_fraction")})
-    out["config"]["int32_gcups"], out["config"]["int32_ms_per_step"] = i32_leg["value"], i32_leg["ms_per_step"]
-    out["config"]["other_legs"] = summ
+    if args.full:
+        # the figures of the other legs that a reader of the first few keys should not have to dig for
+        summ = {"int32_gcups": i32_leg["value"], "int32_ms_per_step": i32_leg["ms_per_step"], "int32_scores_identical_to_packed": i32_same,
+                "pairhmm_config3_f32_pairs_per_s": ph_leg["value"], "pairhmm_config3_ms_per_step": ph_leg["ms_per_step"]}
+        if extra:
+            summ.update({"config4_shard_gcups": out["config4"]["value"], "config4_total_gcups": out["config4"]["total"]["value"],
+                         "config4_total_n_shards": out["config4"]["total"]["n_shards"],
+                         "config5_shard_f64_pairs_per_s": out["config5"]["value"], "config5_total_f64_pairs_per_s": out["config5"]["total"]["value"],
+                         "multi_one_process_config4_ms": multi_one.get("config4", {}).get("ms"), "multi_one_process_config5_ms": multi_one.get("config5", {}).get("ms"),
+                         "multi_one_process_config4_page_locked_ms": multi_one.get("config4_page_locked_source", {}).get("ms"),
+                         "one_shot_config2_pinned_ms_min": one["config2_pinned"]["ms_min"], "one_shot_config3_ms_min": one["config3_pageable"]["ms_min"],
+                         "corpus_10s_f64_pairs_per_s": corpus_legs.get("f64", {}).get("pairs_per_s"),
+                         "corpus_10s_f32_fma_pairs_per_s": corpus_legs.get("f32_fma", {}).get("pairs_per_s"),
+                         "corpus_10s_f64_useful_cell_fraction": corpus_legs.get("f64", {}).get("useful_cell_fraction"),
+                         "corpus_10s_f32_fma_useful_cell_fraction": corpus_legs.get("f32_fma", {}).get("useful_cell_fraction")})
+        out["config"]["int32_gcups"], out["config"]["int32_ms_per_step"] = i32_leg["value"], i32_leg["ms_per_step"]
+        out["config"]["other_legs"] = summ
     out["control_plane"] = control
-    if not args.no_cpu_baseline and n_gpus == 1:  # the CPU baseline is reported at N=1 only
+    if args.full and not args.no_cpu_baseline and n_gpus == 1:  # the CPU baseline is reported at N=1 only
         cores = host_cores()
         n_par = max(1, min(cores, 64))
         out["cpu_baseline"] = _sw_ref_or_port(synth.sw_pairs(16384, SW_LEN, SW_LEN, seed=2, related_frac=0.25), "16384 of the 65536 config-2 pairs")

@@ -39,3 +39,13 @@ def test_launcher_source_order():
         if not line.startswith((" ", "\t")):           # module level only
             assert not line.startswith(("import torch", "from torch", "import accelerating_genomics_amd")), line
     assert json  # keep the import used
+
+
+def test_steps_below_one_is_refused_before_any_work():
+    r = run_bench("--gpus", "1", "--steps", "0", "--warmup", "0")
+    assert r.returncode == 2 and "--steps must be at least 1" in r.stderr and r.stdout.strip() == ""
+
+
+def test_full_and_dump_outputs_are_options():
+    r = run_bench("--help")
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs DIR" in r.stdout

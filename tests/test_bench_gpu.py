@@ -42,7 +42,7 @@ def test_nccl_control_plane_at_world_size_1():
 
 
 def test_bare_gpus_2_on_one_device_runs_two_ranks():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-device", *QUICK],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-device", "--full", *QUICK],
                        capture_output=True, text=True, timeout=1100, env=clean_env(), cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     assert "starting 2 ranks (parent has imported torch: False, libagx: False, HIP libraries mapped: False)" in r.stderr
@@ -60,3 +60,28 @@ def test_ranks_that_would_share_a_gpu_are_refused_without_the_rehearsal_flag():
         assert r.returncode == 0
     else:
         assert r.returncode != 0 and "is not a 2-GPU number" in r.stderr and r.stdout.strip() == "", r.stderr[-2000:]
+
+
+def test_plain_run_is_the_headline_leg_and_dumps_its_last_step(tmp_path, oracle):
+    """A plain run: the headline leg alone, exactly --steps timed steps, and --dump-outputs writes the scores of the
+    last timed step (float64, one per config-2 pair) -- the oracle's scores of the same seeded batch."""
+    import numpy as np
+
+    import accelerating_genomics_amd.synth as synth
+    from tests import oracle_api
+
+    d = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2",
+                        "--warm-seconds", "0.05", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, env=clean_env(), cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    out = json_line(r.stdout)
+    assert out["steps"] == 7 and out["unit"] == "GCUPS" and out["higher_is_better"] is True and out["value"] > 100.0
+    assert out["dtype"] == "int16x2 lanes, int32 scores" and out["ms_per_step"] > 0.0
+    for moved in ("sw_int32", "pairhmm", "config4", "config5", "roofline", "kernel_only", "cpu_baseline", "one_shot"):
+        assert moved not in out, moved
+    assert sorted(os.listdir(d)) == ["sw_scores.npy"]
+    got = np.load(d / "sw_scores.npy")
+    assert got.dtype == np.float64 and got.shape == (65536,)
+    assert int(got.sum()) == out["sw"]["score_checksum"]
+    b = synth.sw_pairs(65536, 150, 150, seed=2, related_frac=0.25)
+    assert np.array_equal(got, oracle_api.sw_batch_mt(oracle, b).astype(np.float64))

@@ -30,6 +30,6 @@ out = {"sw_fill": pick(raw, "sw_fill_pk2<38"), "phmm_fill": pick(raw, "phmm_fill
 json.dump(out, open("profiles/traffic.json", "w"), indent=1)
 print(json.dumps(out, indent=1))
 P
-python3 bench.py --steps 20 --warmup 5 > gpurun_out/${TAG}_bench_steps20.json 2> gpurun_out/${TAG}_bench_steps20.err; echo "bench rc=$?"
+python3 bench.py --full --steps 20 --warmup 5 > profiles/${TAG}_bench_steps20.json; echo "bench rc=$?"   # the bench line goes to profiles/ itself, its stderr to this script's
 cp profiles/traffic.json gpurun_out/${TAG}_traffic.json
 cp gpurun_out/prof_$TAG/summary.md gpurun_out/${TAG}_bench_rocprofv3_summary.md
