@@ -176,21 +176,52 @@ __device__ __forceinline__ void pk2_fill(const SwParams &prm, const uint32_t *__
     const uint32_t lx_mask = FAST ? 0xfffu : 0x7fffu;
     const int lxA = (int)(g.lx_ly[0] & lx_mask), lxB = (int)(g.lx_ly[1] & lx_mask);
     const int lyA = (int)(g.lx_ly[0] >> 16), lyB = (int)(g.lx_ly[1] >> 16);
-    const int nqA = (lyA + 3) >> 2, nqB = (lyB + 3) >> 2;
+
+    // The row stream: quad q (rows 4q .. 4q + 3) of pair A / pair B.  Every lane loads, unconditionally, quad
+    // min(q, last) of its half -- word 0 of the zero block when the half has no rows (vacant, idle lane, empty y) --
+    // so that the load is one instruction of the straight-line step code, not a branch of its own.  Only the group's
+    // first lane uses what it read, and only while q < nq (row_sel); everything else reads as "matches nothing".
+    // row_sel is applied where the quad is used, a quad of steps after the load: applied next to the load, it would
+    // draw the wait for the load there.
+    const uint32_t no_row = FAST ? 0x1f1f1f1fu : 0u; // rows beyond the sequence match nothing
+    const uint32_t *ybA = lyA > 0 ? img + g.y_dw[0] : img, *ybB = lyB > 0 ? img + g.y_dw[1] : img;
+    const uint32_t lastA = lyA > 0 ? (uint32_t)((lyA + 3) >> 2) - 1u : 0u, lastB = lyB > 0 ? (uint32_t)((lyB + 3) >> 2) - 1u : 0u;
+    const int nqA = feeder ? (lyA + 3) >> 2 : 0, nqB = feeder ? (lyB + 3) >> 2 : 0;
+    auto loadA = [&](int q) -> uint32_t { return ybA[min((uint32_t)q, lastA)]; };
+    auto loadB = [&](int q) -> uint32_t { return ybB[min((uint32_t)q, lastB)]; };
+    auto row_selA = [&](int q, uint32_t v) -> uint32_t { return q < nqA ? v : no_row; };
+    auto row_selB = [&](int q, uint32_t v) -> uint32_t { return q < nqB ? v : no_row; };
 
     // this lane's C symbols of both short sequences -> one register per column:
     //   general: (a << shift) | (b << shift) << 16;   FAST: the v_perm_b32 selector {sel_a, 0x0c, sel_b, 0x0c}
     uint32_t xq[C];
+    // quads in flight: narrow lanes run a quad of steps in fewer than 200 instructions (C = 4: about 175) and keep two
+    constexpr int PF = C < 8 ? 2 : 1;
+    uint32_t nextA[PF], nextB[PF]; // the quads the next PF quads of steps read, as loaded (before row_sel)
     {
         const uint32_t o = (uint32_t)gl * C, d0 = o >> 2, sh = o & 3u;
-        // FAST: a vacant half (its record points at the zero block, offset 0) and idle lanes read zeros: all padding
+        // FAST: a vacant half and idle lanes (their records point at the zero block, offset 0: pk2_body zeroes idle lanes'
+        // records) read zeros there -- at most word (G C + 3) / 4 of the kSwPackedMaxShort / 4 + 1 -- and become
+        // all padding.  Every word of both halves and the first row quads go out back to back, then ONE wait.
         const uint32_t fillA = (FAST && !(active && g.x_dw[0])) ? 0x0c0c0c0cu : 0u;
         const uint32_t fillB = (FAST && !(active && g.x_dw[1])) ? 0x0c0c0c0cu : 0u;
         uint32_t ra[XW + 1], rb[XW + 1];
 #pragma unroll
         for (int k = 0; k <= XW; ++k) {
-            ra[k] = (active ? img[g.x_dw[0] + d0 + k] : 0u) | fillA;
-            rb[k] = (active ? img[g.x_dw[1] + d0 + k] : 0u) | fillB;
+            ra[k] = img[g.x_dw[0] + d0 + k];
+            rb[k] = img[g.x_dw[1] + d0 + k];
+        }
+#pragma unroll
+        for (int r = 0; r < PF; ++r) {
+            nextA[r] = loadA(r);
+            nextB[r] = loadB(r);
+        }
+        __builtin_amdgcn_s_waitcnt(0x0f70); // vmcnt(0)
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int k = 0; k <= XW; ++k) {
+            ra[k] |= fillA;
+            rb[k] |= fillB;
         }
 #pragma unroll
         for (int k = 0; k < XW; ++k) {
@@ -215,11 +246,6 @@ __device__ __forceinline__ void pk2_fill(const SwParams &prm, const uint32_t *__
         }
     }
 
-    const uint32_t *ypA = img + g.y_dw[0], *ypB = img + g.y_dw[1];
-    const uint32_t no_row = FAST ? 0x1f1f1f1fu : 0u; // rows beyond the sequence match nothing
-    auto quadA = [&](int q) -> uint32_t { return (feeder && q < nqA) ? ypA[q] : no_row; };
-    auto quadB = [&](int q) -> uint32_t { return (feeder && q < nqB) ? ypB[q] : no_row; };
-
     // state per owned column, both pairs packed, biased: z = H + gf + B and e = max(P, 0) + B
     uint32_t z[C], e[C];
 #pragma unroll
@@ -243,8 +269,6 @@ __device__ __forceinline__ void pk2_fill(const SwParams &prm, const uint32_t *__
     const int capA_t = (nlA && lxA > 0 && lyA > 0) ? lyA + G - 2 : -1, capB_t = (nlB && lxB > 0 && lyB > 0) ? lyB + G - 2 : -1;
     uint32_t cornerA = z_init + (uint32_t)kEnd * prm.age2, cornerB = cornerA; // (taken from the last column: its class offset comes off at the end)
 
-    uint32_t a0 = quadA(0), a1 = quadA(1), a2 = quadA(2);
-    uint32_t b0 = quadB(0), b1 = quadB(1), b2 = quadB(2);
     const int steps = (int)w.steps;
     uint32_t rowsA = 0, rowsB = 0;
     int t = 0;
@@ -320,23 +344,48 @@ __device__ __forceinline__ void pk2_fill(const SwParams &prm, const uint32_t *__
         ++t;
     };
 
-    const int quads = steps >> 2;
-    for (int q = 0; q < quads; ++q) {
-        rowsA = a0;
-        a0 = a1;
-        a1 = a2;
-        a2 = quadA(q + 3);
-        rowsB = b0;
-        b0 = b1;
-        b1 = b2;
-        b2 = quadB(q + 3);
+    // The row stream runs PF quads ahead: the load issued at the top of a quad is first read at the top of the quad PF
+    // later -- four steps, about 1100 instructions at C = 38 -- so the wait the compiler places there finds it landed.
+    // rowsA / rowsB are made before the load: the steps' heads read registers that no load is pending on.  With
+    // PF = 2 the loop takes two quads with a register each (copying one into the other would draw the wait one
+    // quad early).
+    auto quad_of_steps = [&]() __attribute__((always_inline)) {
         step(std::integral_constant<int, 0>{});
         step(std::integral_constant<int, 1>{});
         step(std::integral_constant<int, 2>{});
         step(std::integral_constant<int, 3>{});
+    };
+    auto take = [&](int q, int r) __attribute__((always_inline)) {
+        rowsA = row_selA(q, nextA[r]);
+        rowsB = row_selB(q, nextB[r]);
+        nextA[r] = loadA(q + PF);
+        nextB[r] = loadB(q + PF);
+    };
+    const int quads = steps >> 2;
+    int q = 0;
+    if constexpr (PF == 1) {
+        for (; q < quads; ++q) {
+            take(q, 0);
+            quad_of_steps();
+        }
+    } else {
+        for (; q + 1 < quads; q += 2) {
+            take(q, 0);
+            quad_of_steps();
+            take(q + 1, 1);
+            quad_of_steps();
+        }
+        if (q < quads) { // an odd number of quads
+            rowsA = row_selA(q, nextA[0]);
+            rowsB = row_selB(q, nextB[0]);
+            quad_of_steps();
+            ++q;
+            nextA[0] = nextA[1];
+            nextB[0] = nextB[1];
+        }
     }
-    rowsA = a0;
-    rowsB = b0;
+    rowsA = row_selA(q, nextA[0]);
+    rowsB = row_selB(q, nextB[0]);
 #pragma unroll 1
     while (t < steps) {
         step(std::integral_constant<int, 0>{});
@@ -399,10 +448,18 @@ __device__ __forceinline__ void pk2_body(const SwParams &prm, const uint32_t *__
     const bool start = gl == 0;
     const bool feeder = active && start;
 
-    SwGroup2 g;
+    // idle lanes read the wave's first record (no branch around the load, one wait) and zero it: their image reads
+    // then go to the zero block
+    SwGroup2 g = groups[w.first_group + (active ? grp : 0)];
+    __builtin_amdgcn_s_waitcnt(0x0f70); // vmcnt(0)
+    __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-    for (int k = 0; k < 2; ++k) g.x_dw[k] = g.y_dw[k] = g.lx_ly[k] = g.out[k] = 0;
-    if (active) g = groups[w.first_group + grp];
+    for (int k = 0; k < 2; ++k) {
+        g.x_dw[k] = active ? g.x_dw[k] : 0u;
+        g.y_dw[k] = active ? g.y_dw[k] : 0u;
+        g.lx_ly[k] = active ? g.lx_ly[k] : 0u;
+        g.out[k] = active ? g.out[k] : 0u;
+    }
     // bit 16 of the wave record's class word: set by the pack kernel when every pair of the wave is DNA-coded
     if (__builtin_amdgcn_readfirstlane(w.reserved >> 16) & 1u)
         pk2_fill<C, true, KCC>(prm, img, g, w, scores, lane, G, gl, active, start, feeder);
@@ -423,7 +480,7 @@ __global__ void __launch_bounds__(256) sw_fill_pk2(const SwParams prm, const uin
 
 // Mixed batches: ONE launch for every lane-tiling class.  Each wavefront reads its class (columns per lane)
 // from its record and runs that class's fill; the kernel is allocated the registers of the widest class
-// (202-206 VGPRs as its code objects state them -- tools/kernel_resources.py --, two waves per SIMD: the fill is bound by
+// (214 VGPRs as its code object states them -- tools/kernel_resources.py --, two waves per SIMD: the fill is bound by
 // VALU issue, not by occupancy).  Against one launch
 // per class this (a) lets the planner use every width, so padding shrinks, (b) dispatches the waves of ALL
 // classes longest first, (c) has no stream fork/join and no per-launch ramp.
