@@ -144,11 +144,19 @@ __device__ __forceinline__ void bytes_head(uint32_t &zl, uint32_t &fl, uint32_t 
 // lane additionally carries (j mod 4) |ge|: from one column to the next the offset rises by |ge|, which is exactly what
 // the horizontal gap subtracts -- f = max(z_left, f) with no subtraction, except where the class wraps (every fourth
 // column: minus 4 |ge|) -- and the diagonal adds |ge| through its constant (minus 3 |ge| at a wrap: the host asks for
-// this variant only when mismatch + |gf| >= 3 |ge|, so that constant is not negative).  The floor and the running
-// maximum exist once per class (each rises by |ge| per step; a class's maximum takes its columns two at a time), what a
-// lane hands to its right neighbour loses the last column's class offset on arrival, and the classes' maxima are
-// brought to one offset at the end.  Per column (two cells) 6 + 1/4 + 1/2 instructions and ten per step, against
-// 7 + 1/2 and two.
+// this variant only when mismatch + |gf| >= 3 |ge|, so that constant is not negative).  The floor exists once per class
+// and rises by |ge| per step.  What a lane hands to its right neighbour still carries the last column's class offset
+// c_end: the lane's first column takes it off once, after the horizontal gap's maximum (max(z - c, f - c) =
+// max(z, f) - c), and its diagonal through its constant (hdf = hd0 - c_end).  Per column (two cells) 6 + 1/4 + 1/2
+// instructions, against 7 + 1/2.
+//
+// The running maximum of KC = 4 is kept per OFFSET rather than per class: z of step t in class k carries
+// (t + 2 + k) |ge|, so inside a quad of steps (t = t0 + s) every z of class k at phase s shares the offset of
+// maximum m = s + k, m = 0 .. KC + 2.  The KC + 3 maxima rise by 4 |ge| once per quad (7 instructions a quad where four
+// classes rising every step took 16), and they take each step's z one step LATE, from the values the next step's cells
+// read anyway: the chain of maxima then has the whole step to run in, not the few instructions left behind the last
+// column, where each dependent v_pk_maximum3_f16 drew an s_nop.  The tail steps (steps mod 4) run at phase 0 and
+// rotate the maxima by one place after each step; the last step's z are taken behind the loop.
 template <int C, bool FAST, int KC>
 __device__ __forceinline__ void pk2_fill(const SwParams &prm, const uint32_t *__restrict__ img, const SwGroup2 &g, const SwWave &w,
                                          int32_t *__restrict__ scores, int lane, int G, int gl, bool active, bool start, bool feeder)
@@ -157,6 +165,7 @@ __device__ __forceinline__ void pk2_fill(const SwParams &prm, const uint32_t *__
     constexpr bool RISE = KC > 0;
     constexpr int NK = KC > 1 ? KC : 1;               // floors / running maxima kept
     constexpr int kEnd = KC > 1 ? (C - 1) % KC : 0;   // class of the lane's last column
+    constexpr int NM = KC > 1 ? KC + 3 : NK;          // running maxima kept: KC > 1, one per offset within a quad of steps
     const uint32_t sh_sym = prm.shift;         // general: symbols live as byte << shift
     const uint32_t col_pad = 0x100u << sh_sym; // never equals (byte << shift)
     const uint32_t ge = in_vgpr(prm.age2), gf = in_vgpr(RISE ? prm.agf2 - prm.age2 : prm.agf2); // |ge|; |gf| (RISE: |gf| - |ge|)
@@ -166,6 +175,10 @@ __device__ __forceinline__ void pk2_fill(const SwParams &prm, const uint32_t *__
     const uint32_t hd0 = in_vgpr((FAST ? prm.hd2 - prm.delta2 : prm.hd2) + (RISE ? prm.age2 : 0u)); // first column's diagonal; KC > 1: every non-wrapping one's
     const uint32_t hdw = in_vgpr((FAST ? prm.hd2 - prm.delta2 : prm.hd2) + prm.age2 - (uint32_t)NK * prm.age2); // KC > 1: a wrapping column's diagonal
     const uint32_t ge_wrap = in_vgpr((uint32_t)NK * prm.age2), c_end = in_vgpr((uint32_t)kEnd * prm.age2);
+    // KC > 1: the first column's diagonal, which takes off the class offset its left neighbour's last column carried
+    // (hd0 - c_end >= mismatch + |gf| - 2 |ge| >= 0 in both halves)
+    const uint32_t hdf = KC > 1 && kEnd > 0 ? in_vgpr((FAST ? prm.hd2 - prm.delta2 : prm.hd2) + prm.age2 - (uint32_t)kEnd * prm.age2) : hd0;
+    const uint32_t ge4 = in_vgpr(4u * prm.age2); // KC > 1: what the maxima rise by per quad of steps
     uint32_t zb = (RISE ? z0 + prm.age2 : z0) + (uint32_t)kEnd * prm.age2; // column 0 as the first lane takes it over: z0 + r(t - 1) (+ what every lane takes off on arrival)
     uint32_t floorv[NK];                                          // P~ >= 0 at H's offset: B + r(t - 1) (+ class); in VGPRs: as an
 #pragma unroll                                                    // SGPR operand it drew an s_nop after every group of four
@@ -255,10 +268,12 @@ __device__ __forceinline__ void pk2_fill(const SwParams &prm, const uint32_t *__
     }
     // the horizontal gap state needs no clamp: Q >= z_left >= gf always; "no gap open yet" is Q = gf,
     // whose successor gf + ge loses against every z_left
-    uint32_t z_last = z_init + (uint32_t)kEnd * prm.age2, f_last = z_last, diag_in = z0;
-    uint32_t best[NK]; // :335, one per class
+    uint32_t z_last = z_init + (uint32_t)kEnd * prm.age2, f_last = z_last, diag_in = z0 + (uint32_t)kEnd * prm.age2;
+    // :335.  KC > 1: one per offset, maximum m at (t0 + 2 + m) |ge| in the quad of steps t0 .. t0 + 3 (H = 0 to begin
+    // with); otherwise one per class, at z's offset of the step
+    uint32_t best[NM];
 #pragma unroll
-    for (int k = 0; k < NK; ++k) best[k] = z_init + (uint32_t)k * prm.age2;
+    for (int k = 0; k < NM; ++k) best[k] = z_init + (uint32_t)(KC > 1 ? k + 1 : k) * prm.age2;
     uint32_t yc = 0;         // general: the row symbols of both pairs
     uint32_t ta = 0, tb = 0; // FAST: the row tables of pair A / pair B
 
@@ -273,22 +288,38 @@ __device__ __forceinline__ void pk2_fill(const SwParams &prm, const uint32_t *__
     uint32_t rowsA = 0, rowsB = 0;
     int t = 0;
 
-    // K = which byte of the quads this step reads (the tail loop shifts the quads instead: K = 0)
-    auto step = [&](auto kc) __attribute__((always_inline)) {
+    // KC > 1: z of phase S go to the maxima S .. S + KC - 1, every class's columns two at a time
+    auto take_max = [&](auto sc) __attribute__((always_inline)) {
+        constexpr int S = decltype(sc)::value;
+#pragma unroll
+        for (int k = 0; k < NK; ++k) {
+#pragma unroll
+            for (int j = k; j < C; j += 2 * NK) {
+                if (j + NK < C)
+                    best[S + k] = umax3(best[S + k], z[j], z[j + NK]);
+                else
+                    best[S + k] = umax2(best[S + k], z[j]);
+            }
+        }
+    };
+
+    // K = which byte of the quads this step reads (the tail loop shifts the quads instead: K = 0); S = the step's phase
+    // in its quad for the maxima of KC > 1 (S = 4: a tail step, which rotates the maxima instead); CAP = look for the corner.
+    // KC > 1: phases 1 .. 3 take the previous step's z before their cells overwrite them; phase 3 and the tail take
+    // their own z behind their cells as well.
+    auto step = [&](auto kc, auto sc, auto cc) __attribute__((always_inline)) {
         constexpr int K = decltype(kc)::value;
+        constexpr int S = decltype(sc)::value;
+        constexpr bool CAP = decltype(cc)::value;
         uint32_t zl, fl;
         if constexpr (FAST)
             fast_head<K>(zl, fl, ta, tb, rowsA, rowsB, kv, start_mask, z_last, f_last, zb);
         else
             bytes_head(zl, fl, yc, rowsA, rowsB, 0x0c040c00u + 0x00010001u * K, sh_sym, start_mask, z_last, f_last, zb);
-        if constexpr (KC > 1 && kEnd > 0) { // what the left neighbour's last column carried for its class comes off
-            zl -= c_end;
-            fl -= c_end;
-        }
-        if constexpr (RISE) {
-#pragma unroll
-            for (int k = 0; k < NK; ++k) best[k] += ge;
-        }
+        if constexpr (KC > 1 && S > 0 && S < 4)
+            take_max(std::integral_constant<int, S - 1>{});
+        else if constexpr (KC <= 1 && RISE)
+            best[0] += ge;
         uint32_t zd = diag_in; // H[r-1][first column - 1] + gf
         diag_in = zl;
         uint32_t zleft = zl, f = fl;
@@ -301,12 +332,13 @@ __device__ __forceinline__ void pk2_fill(const SwParams &prm, const uint32_t *__
                 ev = umax3(up, e[j], floorv[j % NK]);
                 f = umax2(zleft, f);
                 if (KC == 1 && j > 0) f -= ge; // (first column: see above)
+                if (KC > 1 && kEnd > 0 && j == 0) f -= c_end;
                 if (wrap) f -= ge_wrap;
             } else {
                 ev = umax3(up, e[j] - ge, bias);
                 f = umax2(zleft, f - ge);
             }
-            const uint32_t hdc = KC > 1 ? (wrap ? hdw : hd0) : (j ? hd : hd0);
+            const uint32_t hdc = KC > 1 ? (wrap ? hdw : j ? hd0 : hdf) : (j ? hd : hd0);
             uint32_t u;                                        // H_diag + match / + mismatch, :332
             if constexpr (FAST)
                 u = (zd + hdc) + __builtin_amdgcn_perm(tb, ta, xq[j]); // mismatch, plus delta on a match
@@ -319,18 +351,13 @@ __device__ __forceinline__ void pk2_fill(const SwParams &prm, const uint32_t *__
             zd = up;
             zleft = zn;
         }
-        // :335 -- every class's maximum takes that class's columns two at a time
+        // :335
+        if constexpr (KC <= 1) {
 #pragma unroll
-        for (int k = 0; k < NK; ++k) {
-#pragma unroll
-            for (int j = k; j < C; j += 2 * NK) {
-                if (j + NK < C)
-                    best[k] = umax3(best[k], z[j], z[j + NK]);
-                else
-                    best[k] = umax2(best[k], z[j]);
-            }
-        }
-        if constexpr (FAST) {
+            for (int j = 0; j < C; j += 2) best[0] = umax3(best[0], z[j], z[j + 1]);
+        } else if constexpr (S >= 3)
+            take_max(std::integral_constant<int, S == 3 ? 3 : 0>{});
+        if constexpr (FAST && CAP) {
             cornerA = t == capA_t ? zleft : cornerA;
             cornerB = t == capB_t ? zleft : cornerB;
         }
@@ -349,11 +376,19 @@ __device__ __forceinline__ void pk2_fill(const SwParams &prm, const uint32_t *__
     // rowsA / rowsB are made before the load: the steps' heads read registers that no load is pending on.  With
     // PF = 2 the loop takes two quads with a register each (copying one into the other would draw the wait one
     // quad early).
-    auto quad_of_steps = [&]() __attribute__((always_inline)) {
-        step(std::integral_constant<int, 0>{});
-        step(std::integral_constant<int, 1>{});
-        step(std::integral_constant<int, 2>{});
-        step(std::integral_constant<int, 3>{});
+    auto rise4 = [&]() __attribute__((always_inline)) {
+        if constexpr (KC > 1) {
+#pragma unroll
+            for (int m = 0; m < NM; ++m) best[m] += ge4;
+        }
+    };
+    // (the rise at the quad's end: at its start the scheduler left the last step's cells more s_nop)
+    auto quad_of_steps = [&](auto cc) __attribute__((always_inline)) {
+        step(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{}, cc);
+        step(std::integral_constant<int, 1>{}, std::integral_constant<int, 1>{}, cc);
+        step(std::integral_constant<int, 2>{}, std::integral_constant<int, 2>{}, cc);
+        step(std::integral_constant<int, 3>{}, std::integral_constant<int, 3>{}, cc);
+        rise4();
     };
     auto take = [&](int q, int r) __attribute__((always_inline)) {
         rowsA = row_selA(q, nextA[r]);
@@ -362,23 +397,48 @@ __device__ __forceinline__ void pk2_fill(const SwParams &prm, const uint32_t *__
         nextB[r] = loadB(q + PF);
     };
     const int quads = steps >> 2;
+    // FAST: the corner falls at step capA_t / capB_t of a group's last lane, so the quads before the wave's first such
+    // step run without looking for it (a loop of their own: a branch around the test inside the loop is if-converted)
+    int cap_first = 0x7fffffff;
+    if constexpr (FAST) {
+        cap_first = min(capA_t < 0 ? 0x7fffffff : capA_t, capB_t < 0 ? 0x7fffffff : capB_t);
+        for (int o = 32; o > 0; o >>= 1) cap_first = min(cap_first, __shfl_xor(cap_first, o));
+        cap_first = __builtin_amdgcn_readfirstlane(cap_first);
+    }
+    const int quads_free = min(quads, cap_first >> 2);
+    constexpr std::integral_constant<bool, false> no_cap{};
+    constexpr std::integral_constant<bool, FAST> cap{};
     int q = 0;
     if constexpr (PF == 1) {
+        if constexpr (FAST) {
+            for (; q < quads_free; ++q) {
+                take(q, 0);
+                quad_of_steps(no_cap);
+            }
+        }
         for (; q < quads; ++q) {
             take(q, 0);
-            quad_of_steps();
+            quad_of_steps(cap);
         }
     } else {
+        if constexpr (FAST) {
+            for (; q + 1 < quads_free; q += 2) {
+                take(q, 0);
+                quad_of_steps(no_cap);
+                take(q + 1, 1);
+                quad_of_steps(no_cap);
+            }
+        }
         for (; q + 1 < quads; q += 2) {
             take(q, 0);
-            quad_of_steps();
+            quad_of_steps(cap);
             take(q + 1, 1);
-            quad_of_steps();
+            quad_of_steps(cap);
         }
         if (q < quads) { // an odd number of quads
             rowsA = row_selA(q, nextA[0]);
             rowsB = row_selB(q, nextB[0]);
-            quad_of_steps();
+            quad_of_steps(cap);
             ++q;
             nextA[0] = nextA[1];
             nextB[0] = nextB[1];
@@ -388,9 +448,20 @@ __device__ __forceinline__ void pk2_fill(const SwParams &prm, const uint32_t *__
     rowsB = row_selB(q, nextB[0]);
 #pragma unroll 1
     while (t < steps) {
-        step(std::integral_constant<int, 0>{});
+        step(std::integral_constant<int, 0>{}, std::integral_constant<int, 4>{}, cap);
         rowsA >>= 8;
         rowsB >>= 8;
+        if constexpr (KC > 1) { // one step on: maximum m + 1 becomes maximum m, maximum 0 moves to the top
+            const uint32_t b0 = best[0];
+#pragma unroll
+            for (int m = 0; m + 1 < NM; ++m) best[m] = best[m + 1];
+            best[NM - 1] = b0 + (uint32_t)NM * prm.age2;
+        }
+    }
+    if constexpr (KC > 1) { // the maxima now stand at (steps + 2 + m) |ge|: all to the top one's offset, then to r(steps - 1)
+#pragma unroll
+        for (int m = 0; m + 1 < NM; ++m) best[NM - 1] = umax2(best[NM - 1], best[m] + (uint32_t)(NM - 1 - m) * prm.age2);
+        best[0] = best[NM - 1] - (uint32_t)NM * prm.age2;
     }
 
     if constexpr (FAST) {
@@ -404,8 +475,6 @@ __device__ __forceinline__ void pk2_fill(const SwParams &prm, const uint32_t *__
         if (nlB) cand = (cand & 0xffffu) | ((cornerB + match2 + (((uint32_t)(steps - 1 - capB_t) * ge1 - off_end) << 16)) & 0xffff0000u);
         best[0] = umax2(best[0], cand);
     }
-#pragma unroll
-    for (int k = 1; k < NK; ++k) best[0] = umax2(best[0], best[k] - (uint32_t)k * prm.age2); // the classes at one offset
     uint32_t bestv = best[0];
     // max over the group's lanes (G need not be a power of two), both halves at once
     for (int o = 1; o < G; o <<= 1) {
