@@ -3,14 +3,17 @@
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <chrono>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <exception>
+#include <functional>
 #include <mutex>
 #include <new>
+#include <thread>
 #include <vector>
 
 #include "../../include/agx.h"
@@ -53,6 +56,27 @@ static inline const char *agx_tune(const char *name)
     (void)name;
     return nullptr;
 #endif
+}
+
+// A knob's value: e (pass the agx_tune("NAME") call itself, so that the name stays where the knob list's test finds it) read
+// as an integer or a real number; dflt when the knob is unset or its value fails the knob's own rule ok.
+static inline long agx_knob_int(const char *e, long dflt, bool (*ok)(long) = nullptr)
+{
+    if (!e) return dflt;
+    const long v = atol(e);
+    return !ok || ok(v) ? v : dflt;
+}
+static inline double agx_knob_real(const char *e, double dflt, bool (*ok)(double) = nullptr)
+{
+    if (!e) return dflt;
+    const double v = atof(e);
+    return !ok || ok(v) ? v : dflt;
+}
+
+// the create traces' clock (AGX_TRACE_CREATE)
+static inline double agx_now_ms()
+{
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
 constexpr int kAuxStreams = 3;
@@ -132,6 +156,31 @@ struct PinBuf {
     void release();
 };
 
+// The exits of a batch create.  A create queues copies and kernels on the context's copy and planning streams that read its
+// pinned staging and write pooled device blocks (the batch's own and its temporaries).  On success it has waited for them, or
+// hands them on with the batch (the pieces of agx_sw_score, finished later); an error exit -- a return or an exception -- may
+// leave them running, and a block handed back to its pool could be taken by another create mid-transfer.  So a DrainOnError
+// is declared after the owners of those blocks and runs first as the create leaves: it joins the upload thread (which may
+// still be queuing), drains both streams unless the create set ok, and then calls release, which frees the temporaries and
+// destroys the half-built batch.  A success path gains no wait.
+template <typename F>
+struct DrainOnError {
+    agx_ctx *ctx; // null: a plan-only batch, nothing was queued
+    F release;
+    std::thread *uploader = nullptr;
+    bool ok = false;
+    DrainOnError(agx_ctx *c, F f, std::thread *t = nullptr) : ctx(c), release(f), uploader(t) {}
+    DrainOnError(const DrainOnError &) = delete;
+    ~DrainOnError()
+    {
+        if (uploader && uploader->joinable()) uploader->join();
+        if (!ok && ctx)
+            for (hipStream_t s : {ctx->copy, ctx->plan})
+                if (s) (void)hipStreamSynchronize(s);
+        release();
+    }
+};
+
 static inline int agx_bind(const agx_ctx *c)
 {
     if (!c) {
@@ -161,3 +210,30 @@ void agx_copy_preload();
 // *busy (may be NULL) receives the context's own mutex: a shard holds it while it uses the context, so that two
 // host threads calling agx_*_devices at once take turns per (device, slot) instead of interleaving on its streams.
 int agx_shared_ctx(int device, int slot, agx_ctx **out, std::mutex **busy = nullptr);
+
+// Contiguous shards balanced by weight: cut[0] = 0, cut[n_shards] = n_units, shard d ends behind the first unit
+// at which the running sum of weight(i) + 1, in unit order, reaches d / n_shards of the total (dist.shard_bounds mirrors it).
+template <typename T, typename W>
+void agx_cut_by_weight(int64_t n_units, int n_shards, T *cut, W weight)
+{
+    for (int d = 0; d <= n_shards; ++d) cut[d] = (T)n_units;
+    cut[0] = 0;
+    double total = 0;
+    for (int64_t i = 0; i < n_units; ++i) total += weight(i) + 1.0;
+    double acc = 0;
+    int d = 1;
+    for (int64_t i = 0; i < n_units && d < n_shards; ++i) {
+        acc += weight(i) + 1.0;
+        while (d < n_shards && acc >= total * d / n_shards) cut[d++] = (T)(i + 1);
+    }
+}
+
+// The body of agx_*_devices (fn: its name, for the messages).  Checks, in this order: a device is visible (AGX_E_NODEVICE), the
+// caller's args_ok (AGX_E_ARG), every ordinal in range (AGX_E_NODEVICE).  Then cuts(cut) fills the n_devices + 1 shard
+// boundaries, and shard(ctx, lo, hi) runs for every shard with work, one host thread each (agx_fan_out), on a process-wide
+// context of devices[k] whose lock it holds.  The first failing shard in shard order is reported as "device %d: ...".
+int agx_run_shards(const char *fn, const int *devices, int n_devices, bool args_ok, const std::function<int(int64_t *cut)> &cuts,
+                   const std::function<int(agx_ctx *ctx, int64_t lo, int64_t hi)> &shard);
+// agx_*_multi: devices 0 .. n - 1 into devs[1024], n = n_devices, or every visible device when n_devices <= 0 or exceeds them;
+// returns n, 0 (with the error text set) when no device is visible
+int agx_first_devices(int n_devices, int *devs);

@@ -7,11 +7,9 @@
 #include <array>
 #include <atomic>
 #include <cfloat>
-#include <chrono>
 #include <cmath>
 #include <memory>
 #include <mutex>
-#include <string>
 #include <thread>
 #include <unordered_map>
 
@@ -21,15 +19,8 @@
 namespace {
 
 // LDS bytes a wave may spend on several read tables (8 waves/CU fit 160 KiB); AGX_PHMM_TAB_BUDGET overrides (experiments)
-size_t tab_budget()
-{
-    static const size_t v = [] {
-        const char *e = agx_tune("AGX_PHMM_TAB_BUDGET");
-        const long n = e ? atol(e) : 0;
-        return n > 0 ? (size_t)n : (size_t)20 * 1024;
-    }();
-    return v;
-}
+bool positive(long n) { return n > 0; }
+size_t tab_budget() { static const size_t v = (size_t)agx_knob_int(agx_tune("AGX_PHMM_TAB_BUDGET"), 20 * 1024, positive); return v; }
 constexpr uint32_t kHapSlack = 44;       // zero bytes after every haplotype: any tiling reads in bounds
 
 struct Plan {
@@ -52,24 +43,13 @@ struct ClassLaunch {
 // Tuning knob for experiments (not part of the ABI): AGX_PHMM_MAX_C caps the columns per lane.
 int max_cols_per_lane()
 {
-    static const int v = [] {
-        const char *e = agx_tune("AGX_PHMM_MAX_C");
-        const int n = e ? atoi(e) : 0;
-        return n >= 4 ? n : kPhClasses[kPhNumClasses - 1];
-    }();
+    static const int v = (int)agx_knob_int(agx_tune("AGX_PHMM_MAX_C"), kPhClasses[kPhNumClasses - 1], [](long n) { return n >= 4; });
     return v;
 }
 
 // AGX_PHMM_FORCE_C pins the class (calibration runs only); a class table without that width
 // ignores it (e.g. the double rescue plan of a packed float batch forced to an odd width).
-int force_cols_per_lane_raw()
-{
-    static const int v = [] {
-        const char *e = agx_tune("AGX_PHMM_FORCE_C");
-        return e ? atoi(e) : 0;
-    }();
-    return v;
-}
+int force_cols_per_lane_raw() { static const int v = (int)agx_knob_int(agx_tune("AGX_PHMM_FORCE_C"), 0); return v; }
 
 constexpr int stripe_cols() { return AGX_PH_STRIPE_COLS; }
 
@@ -94,14 +74,7 @@ int force_cols_per_lane(const ClassTable &ct)
 }
 
 // AGX_PHMM_TAIL_BETA overrides the planner's tail term (experiments); negative = unset
-double tail_beta_override()
-{
-    static const double v = [] {
-        const char *e = agx_tune("AGX_PHMM_TAIL_BETA");
-        return e ? atof(e) : -1.0;
-    }();
-    return v;
-}
+double tail_beta_override() { static const double v = agx_knob_real(agx_tune("AGX_PHMM_TAIL_BETA"), -1.0); return v; }
 
 // allowed: bit ci set = class ci may be used; *cost_out: the lane time estimate of the choice;
 // beta: lanes' worth of extra weight on a wave's own duration (steps * C), see make_plan
@@ -133,15 +106,7 @@ void choose_tiling(int precision, uint32_t R, uint32_t H, uint64_t allowed, uint
 }
 
 // AGX_PHMM_MAX_CLASSES: upper bound on the kernel classes a mixed batch may spread over (default 6)
-int max_classes()
-{
-    static const int v = [] {
-        const char *e = agx_tune("AGX_PHMM_MAX_CLASSES");
-        const int n = e ? atoi(e) : 0;
-        return n > 0 ? n : 6;
-    }();
-    return v;
-}
+int max_classes() { static const int v = (int)agx_knob_int(agx_tune("AGX_PHMM_MAX_CLASSES"), 6, positive); return v; }
 
 // Uniform batches (most pairs share one (R, H) shape): the launch lasts ceil(waves / SIMDs)
 // wave-times, so the tiling of that shape is chosen with that quantisation.
@@ -220,8 +185,6 @@ struct PlanSeed {
     bool gatk_prior = false;
 };
 
-double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
 // Cuts [0, n) into at most `parts` pieces of about equal size whose inner boundaries satisfy is_cut(i) (i starts a new
 // run): every O(pairs) pass of the planner that works run by run is threaded over such pieces.
 template <typename F>
@@ -243,7 +206,7 @@ std::vector<size_t> cut_at_runs(size_t n, int parts, F is_cut)
 // trains: 0 = read trains where they pay (packed plans of enough waves), 1 = never, 2 = wherever two reads can share a group
 int make_plan(const PlanSeed &seed, std::vector<Plan> gen, int kind, int slots, bool rows_f64, bool lut_rows, bool trace, int trains, PlanOut &po)
 {
-    const double tm0 = now_ms();
+    const double tm0 = agx_now_ms();
     double tm1 = tm0, tm2 = tm0, tm3 = tm0, tm4 = tm0;
     const ClassTable ct = class_table(kind);
     const bool gatk_prior = seed.gatk_prior;
@@ -378,7 +341,7 @@ int make_plan(const PlanSeed &seed, std::vector<Plan> gen, int kind, int slots, 
         }
     };
     double beta = tail_beta_override() >= 0 ? tail_beta_override() : 0.0;
-    tm1 = now_ms();
+    tm1 = agx_now_ms();
     tile_all(beta);
     // Tail regime (as in the SW planner): a batch whose waves fill the chip's resident capacity (3 waves
     // per SIMD for the packed kernel, 2 for the others) less than 1.6 times lasts as long as its longest
@@ -412,7 +375,7 @@ int make_plan(const PlanSeed &seed, std::vector<Plan> gen, int kind, int slots, 
             });
         }
     }
-    tm2 = now_ms();
+    tm2 = agx_now_ms();
     {
         std::atomic<int64_t> unfit{-1};
         agx_parallel_for(n, 16384, [&](int64_t lo, int64_t hi, int) {
@@ -477,7 +440,7 @@ int make_plan(const PlanSeed &seed, std::vector<Plan> gen, int kind, int slots, 
                 });
         }
     }
-    tm3 = now_ms();
+    tm3 = agx_now_ms();
     // order: class, lanes per group (wide first), then long reads first, read, haplotype -- a wave's
     // groups then have similar row counts, and haplotypes of one read stay adjacent (one LDS table).
     // `gen` is (read, haplotype)-ordered: two stable counting passes, by read length, then by class.
@@ -492,7 +455,7 @@ int make_plan(const PlanSeed &seed, std::vector<Plan> gen, int kind, int slots, 
         counting_sort(tmp, plan, (size_t)ct.n * 64 + 1, [](const Plan &p) { return (size_t)p.cls * 64 + (size_t)(64 - p.G); });
     }
     std::vector<Plan>().swap(gen);
-    tm4 = now_ms();
+    tm4 = agx_now_ms();
     // Waves and records.  The greedy filling below runs on pieces of `plan` that start where the read, the class or
     // the group width changes (a wave never spans such a piece's end; a packed group's partner is the next haplotype of
     // the SAME read, so no group does either); the pieces' records are then laid end to end.
@@ -739,7 +702,7 @@ int make_plan(const PlanSeed &seed, std::vector<Plan> gen, int kind, int slots, 
     }
     if (trace)
         fprintf(stderr, "[phmm make_plan kind %d] pairing+shapes %.2f, tiling %.2f, assign %.2f, sort %.2f, waves+records %.2f ms (%d pieces)\n",
-                kind, tm1 - tm0, tm2 - tm1, tm3 - tm2, tm4 - tm3, now_ms() - tm4, pieces);
+                kind, tm1 - tm0, tm2 - tm1, tm3 - tm2, tm4 - tm3, agx_now_ms() - tm4, pieces);
     if (trace && po.padded > 0) {
         const double t = (double)po.padded;
         fprintf(stderr, "[phmm make_plan kind %d] %zu waves, padded cells %.4g: useful %.3f, columns beyond H %.3f, skew %.3f, steps beyond the group's read %.3f, "
@@ -831,8 +794,7 @@ int create_batch(agx_ctx *ctx, const agx_phmm_desc *d, const double *const prob[
     }
 
     const bool trace = agx_tune("AGX_TRACE_CREATE") != nullptr;
-    auto now = [] { return now_ms(); };
-    const double t_begin = now();
+    const double t_begin = agx_now_ms();
     // ---- enumerate the pairs in output order: region, read, haplotype (threads over regions)
     std::unique_ptr<PlanSeed> seed_holder(new PlanSeed());
     PlanSeed &seed = *seed_holder;
@@ -985,12 +947,16 @@ int create_batch(agx_ctx *ctx, const agx_phmm_desc *d, const double *const prob[
         agx_set_error("packed image exceeds 16 GiB; split the batch");
         return AGX_E_LIMIT;
     }
-    PinBuf img_pin;
+    // the create's staging blocks and its batch (made below) go back at every exit, an error exit draining the streams first
+    PinBuf img_pin, stage, h_reads;
+    DevBuf d_reads;
+    agx_phmm_batch *b = nullptr;
+    DrainOnError done(ctx, [&] {
+        agx_phmm_batch_destroy(b);
+        for (PinBuf *x : {&img_pin, &stage, &h_reads}) x->release();
+        d_reads.release();
+    });
     std::vector<uint32_t> img_heap;
-    struct ImgGuard {
-        PinBuf &p;
-        ~ImgGuard() { p.release(); }
-    } img_guard{img_pin};
     uint32_t *img = nullptr;
     if (ctx) {
         rc = img_pin.alloc(ctx, img_dw * 4);
@@ -1066,7 +1032,7 @@ int create_batch(agx_ctx *ctx, const agx_phmm_desc *d, const double *const prob[
             }
         });
     }
-    if (trace) fprintf(stderr, "[phmm create] enumerate %.2f ms\n", now() - t_begin);
+    if (trace) fprintf(stderr, "[phmm create] enumerate %.2f ms\n", agx_now_ms() - t_begin);
     // A packed float batch cannot reuse its records for the double rescue pass: that pass has a plan of its own, made
     // from the kept seed when a fill first counts a pair below the float range (ensure_rescue_plan).
     // double modes on plain DNA run the kernel whose read tables carry the priors (other rows, other LDS sizes)
@@ -1129,19 +1095,12 @@ int create_batch(agx_ctx *ctx, const agx_phmm_desc *d, const double *const prob[
         agx_set_error("a read table of %zu bytes does not fit the 160 KiB LDS", stripe_lds);
         return AGX_E_LIMIT;
     }
-    const double t_plan = now();
+    const double t_plan = agx_now_ms();
     const int64_t padded = pmain.padded + pstripe.padded;
 
-    const double t_pack = now();
+    const double t_pack = agx_now_ms();
     // ---- upload
-    agx_phmm_batch *b = new agx_phmm_batch();
-    struct Guard { // error paths: free whatever the batch holds
-        agx_phmm_batch *&b;
-        ~Guard()
-        {
-            if (b) agx_phmm_batch_destroy(b);
-        }
-    } guard{b};
+    b = new agx_phmm_batch();
     agx_ctx_retain(ctx);
     b->ctx = ctx;
     b->precision = precision;
@@ -1190,6 +1149,7 @@ int create_batch(agx_ctx *ctx, const agx_phmm_desc *d, const double *const prob[
     if (!ctx) { // planning only
         *out = b;
         b = nullptr;
+        done.ok = true;
         return AGX_OK;
     }
     // Everything goes through one pinned staging block and the context's copy stream: one DMA per array,
@@ -1220,11 +1180,6 @@ int create_batch(agx_ctx *ctx, const agx_phmm_desc *d, const double *const prob[
     size_t stage_bytes = 0;
     for (const Piece &pc : pieces)
         if (pc.src) stage_bytes += (pc.bytes + 255) & ~(size_t)255;
-    PinBuf stage;
-    struct StageGuard {
-        PinBuf &s;
-        ~StageGuard() { s.release(); }
-    } stage_guard{stage};
     rc = stage.alloc(ctx, stage_bytes);
     for (const Piece &pc : pieces)
         if (!rc) rc = pc.dst->alloc(ctx, pc.bytes);
@@ -1254,21 +1209,12 @@ int create_batch(agx_ctx *ctx, const agx_phmm_desc *d, const double *const prob[
     // The fast cell's table rows -- two float4 of derived constants per read position, several double divisions each --
     // are the same in every wave that uses a read and in every launch of the batch: made here, once (phmm_pk_rows), the
     // waves copy them into LDS instead of deriving them (3 % of config 3's launch).
-    PinBuf h_reads;
-    struct ReadsGuard {
-        PinBuf &p;
-        ~ReadsGuard() { p.release(); }
-    } reads_guard{h_reads};
     if (e == hipSuccess && b->fast && !probs && n_reads && !agx_tune("AGX_PHMM_NO_ROWS")) {
         const size_t n_rows = (reads_end_dw - zero_dw) / 5 * 4;
         rc = b->pk_rows.alloc(ctx, std::max<size_t>(n_rows, 1) * 32);
-        DevBuf d_reads;
         if (!rc) rc = h_reads.alloc(ctx, (size_t)n_reads * sizeof(PhTab));
         if (!rc) rc = d_reads.alloc(ctx, (size_t)n_reads * sizeof(PhTab));
-        if (rc) {
-            d_reads.release();
-            return rc;
-        }
+        if (rc) return rc;
         PhTab *hr = (PhTab *)h_reads.p;
         for (uint32_t r = 0; r < n_reads; ++r) hr[r] = PhTab{read_dw[r], (uint32_t)(d->read_off[r + 1] - d->read_off[r])};
         b->rows_base_dw = (uint32_t)zero_dw;
@@ -1278,8 +1224,6 @@ int create_batch(agx_ctx *ctx, const agx_phmm_desc *d, const double *const prob[
         if (e == hipSuccess && agx_phmm_pk_rows_launch((const uint32_t *)b->img.p, (const PhTab *)d_reads.p, n_reads, lut_f, gatk_prior ? mis_f : nullptr,
                                                        b->pk_rows.p, b->rows_base_dw, cs))
             e = hipErrorLaunchFailure;
-        if (e == hipSuccess) e = hipStreamSynchronize(cs);
-        d_reads.release();
     }
     if (e == hipSuccess) e = hipStreamSynchronize(cs);
     if (e != hipSuccess) {
@@ -1288,9 +1232,10 @@ int create_batch(agx_ctx *ctx, const agx_phmm_desc *d, const double *const prob[
     }
     if (trace)
         fprintf(stderr, "[agx_phmm_batch_create] %lld pairs: plan+order %.2f ms, waves+pack %.2f ms, alloc+H2D %.2f ms (%.1f MB)\n",
-                (long long)n_pairs, t_plan - t_begin, t_pack - t_plan, now() - t_pack, img_dw * 4 / 1e6);
+                (long long)n_pairs, t_plan - t_begin, t_pack - t_plan, agx_now_ms() - t_pack, img_dw * 4 / 1e6);
     *out = b;
     b = nullptr;
+    done.ok = true; // the copy stream synchronised above
     return AGX_OK;
 }
 
@@ -1455,10 +1400,7 @@ static int launch_rescue_plan(agx_phmm_batch *b)
         size_t stage_bytes = 0;
         for (const Piece &pc : pieces) stage_bytes += (pc.bytes + 255) & ~(size_t)255;
         PinBuf stage;
-        struct StageGuard {
-            PinBuf &s;
-            ~StageGuard() { s.release(); }
-        } stage_guard{stage};
+        DrainOnError done(b->ctx, [&] { stage.release(); }); // the records' blocks stay with the batch
         rc = stage.alloc(b->ctx, stage_bytes);
         for (const Piece &pc : pieces)
             if (!rc) rc = pc.dst->alloc(b->ctx, pc.bytes);
@@ -1474,6 +1416,7 @@ static int launch_rescue_plan(agx_phmm_batch *b)
             at += (pc.bytes + 255) & ~(size_t)255;
         }
         AGX_HIP(hipStreamSynchronize(cs));
+        done.ok = true;
         b->rescue.launches = pr.launches;
         broken.done = true;
     }
@@ -1692,103 +1635,52 @@ int agx_phmm_shard_cuts(const agx_phmm_desc *d, int n_shards, uint32_t *cut)
         agx_set_error("agx_phmm_shard_cuts: bad arguments");
         return AGX_E_ARG;
     }
-    // whole regions stay together; contiguous shards balanced by cells
-    const uint32_t ng = d->n_regions;
-    for (int k = 0; k <= n_shards; ++k) cut[k] = ng;
-    cut[0] = 0;
-    double total = 0;
-    for (uint32_t g = 0; g < ng; ++g) {
+    for (uint32_t g = 0; g < d->n_regions; ++g) {
         const uint32_t r0 = d->region_read[g], r1 = d->region_read[g + 1], h0 = d->region_hap[g], h1 = d->region_hap[g + 1];
         if (r1 < r0 || h1 < h0 || r1 > d->n_reads || h1 > d->n_haps) {
             agx_set_error("region %u: ranges out of order or out of bounds", g);
             return AGX_E_ARG;
         }
-        total += (double)(d->read_off[r1] - d->read_off[r0]) * (double)(d->hap_off[h1] - d->hap_off[h0]) + 1.0;
     }
-    double acc = 0;
-    int k = 1;
-    for (uint32_t g = 0; g < ng && k < n_shards; ++g) {
+    // whole regions stay together, weighed by cells
+    agx_cut_by_weight((int64_t)d->n_regions, n_shards, cut, [d](int64_t g) {
         const uint32_t r0 = d->region_read[g], r1 = d->region_read[g + 1], h0 = d->region_hap[g], h1 = d->region_hap[g + 1];
-        acc += (double)(d->read_off[r1] - d->read_off[r0]) * (double)(d->hap_off[h1] - d->hap_off[h0]) + 1.0;
-        while (k < n_shards && acc >= total * k / n_shards) cut[k++] = g + 1;
-    }
+        return (double)(d->read_off[r1] - d->read_off[r0]) * (double)(d->hap_off[h1] - d->hap_off[h0]);
+    });
     return AGX_OK;
 }
 
 int agx_phmm_forward_devices(const int *devices, int n_devices, const agx_phmm_desc *d, int precision, double *log10_lik)
 {
     AGX_GUARD_BEGIN
-    const int avail = agx_device_count();
-    if (avail <= 0) {
-        agx_set_error("no HIP device is visible (this library has no CPU fallback)");
-        return AGX_E_NODEVICE;
-    }
-    if (!devices || n_devices < 1 || n_devices > 1024 || !d ||
-        (d->n_regions && (!d->region_read || !d->region_hap || !d->read_off || !d->hap_off || !log10_lik))) {
-        agx_set_error("agx_phmm_forward_devices: bad arguments");
-        return AGX_E_ARG;
-    }
-    for (int k = 0; k < n_devices; ++k)
-        if (devices[k] < 0 || devices[k] >= avail) {
-            agx_set_error("agx_phmm_forward_devices: device %d out of range [0,%d)", devices[k], avail);
-            return AGX_E_NODEVICE;
-        }
-    std::vector<uint32_t> cut((size_t)n_devices + 1);
-    int rc = agx_phmm_shard_cuts(d, n_devices, cut.data());
-    if (rc) return rc;
-    const uint32_t ng = d->n_regions;
-    std::vector<int64_t> first_out((size_t)ng + 1, 0);
-    for (uint32_t g = 0; g < ng; ++g)
-        first_out[g + 1] = first_out[g] + (int64_t)(d->region_read[g + 1] - d->region_read[g]) * (d->region_hap[g + 1] - d->region_hap[g]);
-    std::vector<int> rcs((size_t)n_devices, AGX_OK), slot((size_t)n_devices, 0);
-    for (int k = 0; k < n_devices; ++k) // shards sharing a device get contexts of their own
-        for (int j = 0; j < k; ++j) slot[(size_t)k] += devices[j] == devices[k];
-    std::vector<std::string> errs((size_t)n_devices);
-    auto shard = [&](int k) {
-        const uint32_t lo = cut[(size_t)k], hi = cut[(size_t)k + 1];
-        if (hi <= lo) return;
-        int r;
-        try {
-            agx_phmm_desc sub = *d;
-            sub.region_read = d->region_read + lo; // absolute read/hap indices stay valid
-            sub.region_hap = d->region_hap + lo;
-            sub.n_regions = hi - lo;
-            agx_ctx *c = nullptr;
-            std::mutex *busy = nullptr;
-            r = agx_shared_ctx(devices[k], slot[(size_t)k], &c, &busy); // created once per process: pools stay warm
-            if (!r) {
-                std::lock_guard<std::mutex> turn(*busy); // concurrent callers take turns on this (device, slot)
-                r = agx_phmm_forward(c, &sub, precision, log10_lik + first_out[lo]);
-            }
-        } catch (const std::exception &ex) {
-            agx_set_error("shard %d: %s", k, ex.what());
-            r = AGX_E_NOMEM;
-        }
-        if (r) errs[(size_t)k] = agx_last_error();
-        rcs[(size_t)k] = r;
+    std::vector<int64_t> first_out; // [g]: the first result of region g
+    auto cuts = [&](int64_t *cut) {
+        std::vector<uint32_t> c((size_t)n_devices + 1);
+        const int rc = agx_phmm_shard_cuts(d, n_devices, c.data());
+        if (rc) return rc;
+        std::copy(c.begin(), c.end(), cut);
+        first_out.assign((size_t)d->n_regions + 1, 0);
+        for (uint32_t g = 0; g < d->n_regions; ++g)
+            first_out[g + 1] = first_out[g] + (int64_t)(d->region_read[g + 1] - d->region_read[g]) * (d->region_hap[g + 1] - d->region_hap[g]);
+        return AGX_OK;
     };
-    agx_fan_out(n_devices, shard);
-    for (int k = 0; k < n_devices; ++k)
-        if (rcs[(size_t)k]) {
-            agx_set_error("device %d: %s", devices[k], errs[(size_t)k].c_str());
-            return rcs[(size_t)k];
-        }
-    return AGX_OK;
+    auto shard = [&](agx_ctx *c, int64_t lo, int64_t hi) {
+        agx_phmm_desc sub = *d;
+        sub.region_read = d->region_read + lo; // absolute read/hap indices stay valid
+        sub.region_hap = d->region_hap + lo;
+        sub.n_regions = (uint32_t)(hi - lo);
+        return agx_phmm_forward(c, &sub, precision, log10_lik + first_out[(size_t)lo]);
+    };
+    const bool args_ok = d && (!d->n_regions || (d->region_read && d->region_hap && d->read_off && d->hap_off && log10_lik));
+    return agx_run_shards("agx_phmm_forward_devices", devices, n_devices, args_ok, cuts, shard);
     AGX_GUARD_END("agx_phmm_forward_devices")
 }
 
 int agx_phmm_forward_multi(int n_devices, const agx_phmm_desc *d, int precision, double *log10_lik)
 {
-    const int avail = agx_device_count();
-    if (avail <= 0) {
-        agx_set_error("no HIP device is visible (this library has no CPU fallback)");
-        return AGX_E_NODEVICE;
-    }
-    if (n_devices <= 0 || n_devices > avail) n_devices = avail;
-    n_devices = std::min(n_devices, 1024);
     int devs[1024];
-    for (int k = 0; k < n_devices; ++k) devs[k] = k;
-    return agx_phmm_forward_devices(devs, n_devices, d, precision, log10_lik);
+    n_devices = agx_first_devices(n_devices, devs);
+    return n_devices ? agx_phmm_forward_devices(devs, n_devices, d, precision, log10_lik) : AGX_E_NODEVICE;
 }
 
 void agx_pairHMM(double *likelihood, double *M, double *X, double *Y, char *R, char *H, int read_len, int haplotype_len,

@@ -4,6 +4,7 @@
 #include <sched.h>
 #include <condition_variable>
 #include <deque>
+#include <string>
 #include <thread>
 
 #include "agx_internal.h"
@@ -528,6 +529,92 @@ int agx_shared_ctx(int device, int slot, agx_ctx **out, std::mutex **busy)
     return AGX_OK;
 }
 
+// ------------------------------------------------------------------ multi-device entry points
+
+namespace {
+
+int no_device()
+{
+    agx_set_error("no HIP device is visible (this library has no CPU fallback)");
+    return AGX_E_NODEVICE;
+}
+
+int check_ordinals(const char *fn, const int *devices, int n, int avail)
+{
+    for (int k = 0; k < n; ++k)
+        if (devices[k] < 0 || devices[k] >= avail) {
+            agx_set_error("%s: device %d out of range [0,%d)", fn, devices[k], avail);
+            return AGX_E_NODEVICE;
+        }
+    return AGX_OK;
+}
+
+// shards sharing a device get contexts of their own: a shard's slot is the number of earlier entries naming its device
+std::vector<int> shard_slots(const int *devices, int n)
+{
+    std::vector<int> slot((size_t)n, 0);
+    for (int k = 0; k < n; ++k)
+        for (int j = 0; j < k; ++j) slot[(size_t)k] += devices[j] == devices[k];
+    return slot;
+}
+
+} // namespace
+
+int agx_run_shards(const char *fn, const int *devices, int n_devices, bool args_ok, const std::function<int(int64_t *cut)> &cuts,
+                   const std::function<int(agx_ctx *ctx, int64_t lo, int64_t hi)> &shard)
+{
+    const int avail = agx_device_count();
+    if (avail <= 0) return no_device();
+    if (!args_ok || !devices || n_devices < 1 || n_devices > 1024) {
+        agx_set_error("%s: bad arguments", fn);
+        return AGX_E_ARG;
+    }
+    int rc = check_ordinals(fn, devices, n_devices, avail);
+    if (rc) return rc;
+    // results land in disjoint slices of the caller's array: no exchange step
+    std::vector<int64_t> cut((size_t)n_devices + 1);
+    rc = cuts(cut.data());
+    if (rc) return rc;
+    const std::vector<int> slot = shard_slots(devices, n_devices);
+    std::vector<int> rcs((size_t)n_devices, AGX_OK);
+    std::vector<std::string> errs((size_t)n_devices);
+    agx_fan_out(n_devices, [&](int k) {
+        const int64_t lo = cut[(size_t)k], hi = cut[(size_t)k + 1];
+        if (hi <= lo) return;
+        int r;
+        try {
+            agx_ctx *c = nullptr;
+            std::mutex *busy = nullptr;
+            r = agx_shared_ctx(devices[k], slot[(size_t)k], &c, &busy); // created once per process: pools stay warm
+            if (!r) {
+                std::lock_guard<std::mutex> turn(*busy); // concurrent callers take turns on this (device, slot)
+                r = shard(c, lo, hi);
+            }
+        } catch (const std::exception &ex) {
+            agx_set_error("shard %d: %s", k, ex.what());
+            r = AGX_E_NOMEM;
+        }
+        if (r) errs[(size_t)k] = agx_last_error();
+        rcs[(size_t)k] = r;
+    });
+    for (int k = 0; k < n_devices; ++k)
+        if (rcs[(size_t)k]) {
+            agx_set_error("device %d: %s", devices[k], errs[(size_t)k].c_str());
+            return rcs[(size_t)k];
+        }
+    return AGX_OK;
+}
+
+int agx_first_devices(int n_devices, int *devs)
+{
+    const int avail = agx_device_count();
+    if (avail <= 0) return no_device(), 0;
+    if (n_devices <= 0 || n_devices > avail) n_devices = avail;
+    n_devices = std::min(n_devices, 1024);
+    for (int k = 0; k < n_devices; ++k) devs[k] = k;
+    return n_devices;
+}
+
 extern "C" {
 
 const char *agx_version(void)
@@ -733,24 +820,20 @@ int agx_ctx_timer_elapsed(agx_ctx *c, float *ms)
 int agx_warmup_devices(const int *devices, int n_devices)
 {
     AGX_GUARD_BEGIN
+    int first[1024];
+    if (!devices) {
+        n_devices = agx_first_devices(n_devices, first);
+        devices = first;
+    }
     const int avail = agx_device_count();
-    if (avail <= 0) {
-        agx_set_error("no HIP device is visible (this library has no CPU fallback)");
-        return AGX_E_NODEVICE;
-    }
-    if (!devices && (n_devices <= 0 || n_devices > avail)) n_devices = avail;
-    std::vector<int> slot_of((size_t)avail, 0);
-    for (int k = 0; k < n_devices; ++k) {
-        const int dev = devices ? devices[k] : k;
-        if (dev < 0 || dev >= avail) {
-            agx_set_error("agx_warmup_devices: device %d out of range [0,%d)", dev, avail);
-            return AGX_E_NODEVICE;
-        }
+    if (avail <= 0) return no_device();
+    int rc = check_ordinals("agx_warmup_devices", devices, n_devices, avail);
+    const std::vector<int> slot = shard_slots(devices, std::max(n_devices, 0));
+    for (int k = 0; !rc && k < n_devices; ++k) {
         agx_ctx *c = nullptr;
-        const int rc = agx_shared_ctx(dev, slot_of[(size_t)dev]++, &c); // shards sharing a device have contexts of their own
-        if (rc) return rc;
+        rc = agx_shared_ctx(devices[k], slot[(size_t)k], &c);
     }
-    return AGX_OK;
+    return rc;
     AGX_GUARD_END("agx_warmup_devices")
 }
 

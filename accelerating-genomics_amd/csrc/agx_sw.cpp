@@ -13,11 +13,9 @@
 #include "agx_sw.h"
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <memory>
 #include <mutex>
-#include <string>
 #include <thread>
 
 #include "agx_internal.h"
@@ -32,40 +30,12 @@ struct Tiling {
 
 // Tuning build only (see agx_tune): AGX_SW_TAIL_BETA, AGX_SW_MAX_C, AGX_SW_FORCE_C, AGX_SW_MAX_CLASSES,
 // AGX_SW_WAVES_PER_CLASS, AGX_SW_SORT_WAVES, AGX_SW_KERNEL.  The shipped library runs on the defaults.
-inline double tail_beta_override()
-{
-    static const double v = [] {
-        const char *e = agx_tune("AGX_SW_TAIL_BETA");
-        return e ? atof(e) : -1.0;
-    }();
-    return v;
-}
-int max_cols_per_lane()
-{
-    static const int v = [] {
-        const char *e = agx_tune("AGX_SW_MAX_C");
-        const int n = e ? atoi(e) : 0;
-        return n >= 4 ? n : AGX_SW_MAX_COLS_PER_LANE;
-    }();
-    return v;
-}
-int force_cols_per_lane()
-{
-    static const int v = [] {
-        const char *e = agx_tune("AGX_SW_FORCE_C");
-        return e ? atoi(e) : 0;
-    }();
-    return v;
-}
-int max_classes_override() // 0 = none
-{
-    static const int v = [] {
-        const char *e = agx_tune("AGX_SW_MAX_CLASSES");
-        const int n = e ? atoi(e) : 0;
-        return n > 0 ? n : 0;
-    }();
-    return v;
-}
+bool positive(long n) { return n > 0; }
+bool at_least_4(long n) { return n >= 4; }
+inline double tail_beta_override() { static const double v = agx_knob_real(agx_tune("AGX_SW_TAIL_BETA"), -1.0); return v; }
+int max_cols_per_lane() { static const int v = (int)agx_knob_int(agx_tune("AGX_SW_MAX_C"), AGX_SW_MAX_COLS_PER_LANE, at_least_4); return v; }
+int force_cols_per_lane() { static const int v = (int)agx_knob_int(agx_tune("AGX_SW_FORCE_C"), 0); return v; }
+int max_classes_override() { static const int v = (int)agx_knob_int(agx_tune("AGX_SW_MAX_CLASSES"), 0, positive); return v; } // 0 = none
 int tuned_kernel() // 0 = no override
 {
     static const int v = [] {
@@ -206,22 +176,8 @@ Tiling choose_tiling_uniform(const double *costs, int slots, int lx, int ly, int
 
 // agx_sw_score sends a large batch through in pieces (upload of piece k + 1 beside the fill of piece k); tuning build:
 // AGX_SW_PIECE_MB, AGX_SW_PIECE_MIN_PAIRS
-inline uint64_t piece_bytes()
-{
-    static const uint64_t v = [] {
-        const char *e = agx_tune("AGX_SW_PIECE_MB");
-        return (uint64_t)(e && atoi(e) > 0 ? atoi(e) : 32) << 20;
-    }();
-    return v;
-}
-inline int64_t piece_min_pairs()
-{
-    static const int64_t v = [] {
-        const char *e = agx_tune("AGX_SW_PIECE_MIN_PAIRS");
-        return (int64_t)(e && atoi(e) > 0 ? atoi(e) : 32768);
-    }();
-    return v;
-}
+inline uint64_t piece_bytes() { static const uint64_t v = (uint64_t)agx_knob_int(agx_tune("AGX_SW_PIECE_MB"), 32, positive) << 20; return v; }
+inline int64_t piece_min_pairs() { static const int64_t v = agx_knob_int(agx_tune("AGX_SW_PIECE_MIN_PAIRS"), 32768, positive); return v; }
 constexpr size_t kRawPad = 64;       // bytes in front of and behind the uploaded sequences (16-byte aligned pieces, agx_sw_pack_kernel.hip)
 constexpr uint8_t kClsEmpty = 255;   // an empty side: nothing to fill
 constexpr uint8_t kClsUntiled = 254; // pass A done, no tiling yet
@@ -247,11 +203,6 @@ struct Bucket {
     size_t wave0 = 0, n_waves = 0;
     int cls = 0, G = 0;
 };
-
-inline double now_ms()
-{
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
 
 } // namespace
 
@@ -355,7 +306,6 @@ struct DevPlan {
     DevBuf d_len, d_buckets, d_padded, keys_a, keys_b, vals_a, vals_b, wkeys_a, wkeys_b, wids_a, wids_b, waves_tmp, temp;
     std::vector<uint32_t> hist; // pairs per (class, G) bucket
     size_t img_dw = 0;
-    bool started = false;
     hipEvent_t uploaded = nullptr; // recorded on the copy stream behind this batch's sequences
     hipEvent_t done = nullptr; // recorded behind this batch's planning kernels (its own: two creates may be in flight on one context)
     void release()
@@ -373,7 +323,6 @@ struct DevPlan {
 
 // everything a create leaves behind while its device work is still in flight
 struct SwPending {
-    agx_ctx *ctx = nullptr;
     DevBuf d_raw, d_off, d_code, d_flag;
     PinBuf h_groups, h_waves, h_flag, h_dense, h_dense_off;
     DevPlan dp;
@@ -382,8 +331,8 @@ struct SwPending {
     bool device_plan = false, matrix = false;
     ~SwPending()
     {
-        // kernels may still read the temporaries when an error path (or a destroy without finish) gets here
-        if (ctx && dp.started && ctx->plan) (void)hipStreamSynchronize(ctx->plan);
+        // a deferred batch destroyed before finish_create: its kernels may still read the temporaries (tail covers the
+        // copy and planning streams)
         if (tail) (void)hipStreamSynchronize(tail);
         if (ready) (void)hipEventDestroy(ready);
         dp.release();
@@ -486,7 +435,6 @@ int launch_device_plan(agx_ctx *ctx, DevPlan &dp, agx_sw_batch *b, uint32_t n_pa
     if (!rc) rc = dp.waves_tmp.alloc(ctx, std::max<size_t>(n_waves, 1) * sizeof(SwWave));
     if (!rc) rc = dp.temp.alloc(ctx, temp_bytes);
     if (rc) return rc;
-    dp.started = true;
     AGX_HIP(hipMemcpyAsync(dp.d_len.p, dp.h_len.p, 2 * pw, hipMemcpyHostToDevice, ps));
     AGX_HIP(hipMemcpyAsync(dp.d_buckets.p, dp.h_buckets.p, dp.h_buckets.bytes, hipMemcpyHostToDevice, ps));
     AGX_HIP(hipMemsetAsync(dp.d_padded.p, 0, 8, ps));
@@ -597,7 +545,7 @@ int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matri
     prm.bias2 = twice(bias);
 
     const bool trace = agx_tune("AGX_TRACE_CREATE") != nullptr;
-    const double t_begin = now_ms();
+    const double t_begin = agx_now_ms();
     if (n_pairs > 0 && !bases) {
         for (int64_t p = 0; p < 2 * n_pairs; ++p)
             if (len[p]) {
@@ -701,7 +649,7 @@ int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matri
     std::vector<uint8_t> present((size_t)longest_short + 1, 0);
     for (const Worker &w : wk)
         for (size_t lx = 0; lx < present.size() && lx < w.present.size(); ++lx) present[lx] |= w.present[lx];
-    const double t_pass_a = now_ms();
+    const double t_pass_a = agx_now_ms();
 
     // ---- kernel family.  The packed int16 kernels cover shorter sides up to 64 x 40 columns; one longer
     // pair moves the whole batch to the int32 kernel, which also has the wide classes (up to 64 x 160).
@@ -753,14 +701,9 @@ int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matri
         }
     }
 
-    agx_sw_batch *b = new agx_sw_batch();
-    struct Guard { // error paths: free whatever the batch holds
-        agx_sw_batch *&b;
-        ~Guard()
-        {
-            if (b) agx_sw_batch_destroy(b);
-        }
-    } guard{b};
+    std::unique_ptr<SwPending> tmp(new SwPending()); // released when this function leaves, or kept by the batch (defer)
+    tmp->matrix = matrix != nullptr;
+    agx_sw_batch *b = new agx_sw_batch();            // destroyed by `done` below on an error exit
     agx_ctx_retain(ctx);
     b->ctx = ctx;
     b->n_pairs = n_pairs;
@@ -779,9 +722,6 @@ int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matri
 
     // ---- the caller's arrays start travelling now, while the plan is made: a helper thread drives the
     // copies (a pageable source makes hipMemcpyAsync block while the runtime stages it)
-    std::unique_ptr<SwPending> tmp(new SwPending()); // released when this function leaves, or kept by the batch (defer)
-    tmp->ctx = ctx;
-    tmp->matrix = matrix != nullptr;
     DevBuf &d_raw = tmp->d_raw, &d_off = tmp->d_off, &d_code = tmp->d_code, &d_flag = tmp->d_flag;
     PinBuf &h_groups = tmp->h_groups, &h_waves = tmp->h_waves, &h_flag = tmp->h_flag, &h_dense = tmp->h_dense, &h_dense_off = tmp->h_dense_off;
     // `bases` is normally dense; a caller whose sequences are islands in a much larger array gets a dense
@@ -879,13 +819,9 @@ int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matri
         }
     };
     std::thread uploader;
-    struct Joiner {
-        std::thread &t;
-        ~Joiner()
-        {
-            if (t.joinable()) t.join();
-        }
-    } joiner{uploader};
+    // every exit from here: the uploader joined (it uses what is declared above), then on an error the streams drained before
+    // the batch and tmp give their blocks back
+    DrainOnError done(ctx, [&] { agx_sw_batch_destroy(b); }, &uploader);
     if (ctx && n_pairs > 0) {
         // page-locked arrays (agx_host_alloc) go down without the runtime staging anything: hipMemcpyAsync returns at once,
         // and the helper thread -- 50 us to start and join, a tenth of a config-2-sized call -- is not needed
@@ -1025,7 +961,7 @@ int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matri
             b->file_order = true;
         }
     }
-    double t_plan = now_ms(), t_sort = t_plan;
+    double t_plan = agx_now_ms(), t_sort = t_plan;
 
     // ---- pass B: lane tiling per pair, then the batch-level rules.  Host-only work from here to the records.
     if (!planned && !device_plan) {
@@ -1099,10 +1035,7 @@ int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matri
             waves_est += w.waves;
             for (int c = 0; c < kSwNumClasses; ++c) work[c] += w.class_work[c];
         }
-        static const double per_class = [] {
-            const char *e = agx_tune("AGX_SW_WAVES_PER_CLASS");
-            return e && atof(e) > 0 ? atof(e) : 4096.0;
-        }();
+        static const double per_class = agx_knob_real(agx_tune("AGX_SW_WAVES_PER_CLASS"), 4096.0, [](double v) { return v > 0; });
         // The biased packed kernel runs every class in ONE launch (sw_fill_pk2_any), so from about two wavefronts
         // per SIMD on it keeps them all: padding shrinks (useful cells 0.908 -> 0.932 on config 4's per-GPU shard)
         // and nothing is forked or joined: 131 072 mixed pairs 5.62 -> 6.02 TCUPS, 262 144 6.05 -> 6.39, 65 536
@@ -1161,7 +1094,7 @@ int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matri
             }
         }
     }
-    t_plan = now_ms();
+    t_plan = agx_now_ms();
 
     // ---- pass C: order = class, then lanes per group (wide first), then long rows first, then file
     // order; waves end up homogeneous and the longest waves of a launch are dispatched first.
@@ -1177,7 +1110,7 @@ int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matri
         });
         while (!plan.empty() && plan.back().cls == kClsEmpty) plan.pop_back();
     }
-    t_sort = now_ms();
+    t_sort = agx_now_ms();
     } // !planned && !device_plan
 
     // what the rest of the function needs of a plan, whoever made it
@@ -1228,7 +1161,7 @@ int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matri
         rc = launch_device_plan(ctx, dp, b, (uint32_t)n_pairs, (uint32_t)entries, longest_long, slots, (uint32_t)img0, n_groups, n_waves);
         if (!rc) rc = h_flag.alloc(ctx, 2 * sizeof(uint32_t));
         if (rc) return rc;
-        t_waves = t_records = now_ms();
+        t_waves = t_records = agx_now_ms();
     } else {
     // ---- pass D: every (class, G) bucket is regular, so waves, records and offsets need no scan but the
     // prefix sum of the image words.
@@ -1341,7 +1274,7 @@ int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matri
             }
         });
     }
-    t_waves = now_ms();
+    t_waves = agx_now_ms();
 
     // ---- group records, written straight into pinned staging when there is a device
     groups_bytes = n_groups * (packed ? sizeof(SwGroup2) : sizeof(SwGroup));
@@ -1382,7 +1315,7 @@ int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matri
                         reinterpret_cast<SwGroup *>(groups_data)[q.group0 + (size_t)g] = SwGroup{xd, yd, ll, outi};
                 }
         });
-    t_records = now_ms();
+    t_records = agx_now_ms();
 
     } // host-made plan
     b->launches = launches;
@@ -1399,6 +1332,7 @@ int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matri
                     (long long)n_pairs, t_pass_a - t_begin, t_plan - t_pass_a, t_sort - t_plan, t_waves - t_sort, t_records - t_waves);
         *out = b;
         b = nullptr;
+        done.ok = true;
         return AGX_OK;
     }
 
@@ -1408,7 +1342,7 @@ int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matri
         agx_set_error("%s", up_err);
         return up_rc;
     }
-    const double t_joined = now_ms();
+    const double t_joined = agx_now_ms();
     rc = b->img.alloc(ctx, std::max<size_t>(img_dw, 4) * 4);
     if (!rc && !device_plan) rc = b->groups.alloc(ctx, groups_bytes); // (the device planner has written its own already)
     if (!rc && !device_plan) rc = b->waves.alloc(ctx, waves_bytes);
@@ -1463,6 +1397,7 @@ int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matri
             b->pending = tmp.release();
             *out = b;
             b = nullptr;
+            done.ok = true; // finish_create waits for tail
             return AGX_OK;
         }
     }
@@ -1484,9 +1419,10 @@ int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matri
                 "[agx_sw_batch_create] %lld pairs%s: pass A %.2f ms | tiling %.2f, sort %.2f, waves %.2f, records %.2f | waited %.2f ms more "
                 "for the upload of %.1f MB | device pack + sync %.2f ms\n",
                 (long long)n_pairs, device_plan ? " (planned on the device)" : "", t_pass_a - t_begin, t_plan - t_pass_a, t_sort - t_plan, t_waves - t_sort, t_records - t_waves,
-                t_joined - t_records, raw_bytes / 1e6, now_ms() - t_joined);
+                t_joined - t_records, raw_bytes / 1e6, agx_now_ms() - t_joined);
     *out = b;
     b = nullptr;
+    done.ok = true; // ts synchronised above, and it covers the copy stream
     return AGX_OK;
 }
 
@@ -1675,19 +1611,19 @@ int agx_sw_score(agx_ctx *ctx, const uint8_t *bases, const uint64_t *off, const 
         return rc;
     };
     const bool trace = agx_tune("AGX_TRACE_CREATE") != nullptr;
-    const double t_begin = now_ms();
+    const double t_begin = agx_now_ms();
     for (int k = 0; k < pieces; ++k) {
         const int64_t lo = cut(k), hi = cut(k + 1);
-        const double ta = now_ms();
+        const double ta = agx_now_ms();
         int rc = renumber(create_batch(ctx, nullptr, nullptr, bases, off + 2 * lo, len + 2 * lo, hi - lo, &bs[(size_t)k], true), lo);
         if (!rc) rc = agx_sw_batch_launch(bs[(size_t)k]);
         if (rc) return rc;
-        if (trace) fprintf(stderr, "[agx_sw_score] piece %d of %d queued in %.2f ms (at %.2f)\n", k, pieces, now_ms() - ta, now_ms() - t_begin);
+        if (trace) fprintf(stderr, "[agx_sw_score] piece %d of %d queued in %.2f ms (at %.2f)\n", k, pieces, agx_now_ms() - ta, agx_now_ms() - t_begin);
     }
     for (int k = 0; k < pieces; ++k) {
         const int rc = renumber(finish_create(bs[(size_t)k]), cut(k));
         if (rc) return rc;
-        if (trace) fprintf(stderr, "[agx_sw_score] piece %d finished at %.2f ms\n", k, now_ms() - t_begin);
+        if (trace) fprintf(stderr, "[agx_sw_score] piece %d finished at %.2f ms\n", k, agx_now_ms() - t_begin);
     }
     for (int k = 0; k < pieces; ++k) {
         const int rc = agx_sw_batch_scores(bs[(size_t)k], scores + cut(k));
@@ -1705,17 +1641,7 @@ int agx_sw_shard_cuts(const uint32_t *len, int64_t n_pairs, int n_shards, int64_
         agx_set_error("agx_sw_shard_cuts: bad arguments");
         return AGX_E_ARG;
     }
-    // contiguous shards balanced by cells
-    for (int d = 0; d <= n_shards; ++d) cut[d] = n_pairs;
-    cut[0] = 0;
-    double total = 0;
-    for (int64_t p = 0; p < n_pairs; ++p) total += (double)len[2 * p] * len[2 * p + 1] + 1.0;
-    double acc = 0;
-    int d = 1;
-    for (int64_t p = 0; p < n_pairs && d < n_shards; ++p) {
-        acc += (double)len[2 * p] * len[2 * p + 1] + 1.0;
-        while (d < n_shards && acc >= total * d / n_shards) cut[d++] = p + 1;
-    }
+    agx_cut_by_weight(n_pairs, n_shards, cut, [len](int64_t p) { return (double)len[2 * p] * len[2 * p + 1]; }); // by cells
     return AGX_OK;
 }
 
@@ -1723,70 +1649,19 @@ int agx_sw_score_devices(const int *devices, int n_devices, const uint8_t *bases
                          int64_t n_pairs, int32_t *scores)
 {
     AGX_GUARD_BEGIN
-    const int avail = agx_device_count();
-    if (avail <= 0) {
-        agx_set_error("no HIP device is visible (this library has no CPU fallback)");
-        return AGX_E_NODEVICE;
-    }
-    if (!devices || n_devices < 1 || n_devices > 1024 || n_pairs < 0 || (n_pairs > 0 && (!off || !len || !scores))) {
-        agx_set_error("agx_sw_score_devices: bad arguments");
-        return AGX_E_ARG;
-    }
-    for (int k = 0; k < n_devices; ++k)
-        if (devices[k] < 0 || devices[k] >= avail) {
-            agx_set_error("agx_sw_score_devices: device %d out of range [0,%d)", devices[k], avail);
-            return AGX_E_NODEVICE;
-        }
-    // results land in disjoint slices of the caller's array: no exchange step
-    std::vector<int64_t> cut((size_t)n_devices + 1);
-    int rc = agx_sw_shard_cuts(len, n_pairs, n_devices, cut.data());
-    if (rc) return rc;
-    std::vector<int> rcs((size_t)n_devices, AGX_OK), slot((size_t)n_devices, 0);
-    for (int k = 0; k < n_devices; ++k) // shards sharing a device get contexts of their own
-        for (int j = 0; j < k; ++j) slot[(size_t)k] += devices[j] == devices[k];
-    std::vector<std::string> errs((size_t)n_devices);
-    auto shard = [&](int k) {
-        const int64_t lo = cut[(size_t)k], hi = cut[(size_t)k + 1];
-        if (hi <= lo) return;
-        int r;
-        try {
-            agx_ctx *c = nullptr;
-            std::mutex *busy = nullptr;
-            r = agx_shared_ctx(devices[k], slot[(size_t)k], &c, &busy); // created once per process: pools stay warm
-            if (!r) {
-                std::lock_guard<std::mutex> turn(*busy); // concurrent callers take turns on this (device, slot)
-                r = agx_sw_score(c, bases, off + 2 * lo, len + 2 * lo, hi - lo, scores + lo);
-            }
-        } catch (const std::exception &ex) {
-            agx_set_error("shard %d: %s", k, ex.what());
-            r = AGX_E_NOMEM;
-        }
-        if (r) errs[(size_t)k] = agx_last_error();
-        rcs[(size_t)k] = r;
-    };
-    agx_fan_out(n_devices, shard);
-    for (int k = 0; k < n_devices; ++k)
-        if (rcs[(size_t)k]) {
-            agx_set_error("device %d: %s", devices[k], errs[(size_t)k].c_str());
-            return rcs[(size_t)k];
-        }
-    return AGX_OK;
+    return agx_run_shards(
+        "agx_sw_score_devices", devices, n_devices, n_pairs >= 0 && (n_pairs == 0 || (off && len && scores)),
+        [&](int64_t *cut) { return agx_sw_shard_cuts(len, n_pairs, n_devices, cut); },
+        [&](agx_ctx *c, int64_t lo, int64_t hi) { return agx_sw_score(c, bases, off + 2 * lo, len + 2 * lo, hi - lo, scores + lo); });
     AGX_GUARD_END("agx_sw_score_devices")
 }
 
 int agx_sw_score_multi(int n_devices, const uint8_t *bases, const uint64_t *off, const uint32_t *len, int64_t n_pairs,
                        int32_t *scores)
 {
-    const int avail = agx_device_count();
-    if (avail <= 0) {
-        agx_set_error("no HIP device is visible (this library has no CPU fallback)");
-        return AGX_E_NODEVICE;
-    }
-    if (n_devices <= 0 || n_devices > avail) n_devices = avail;
-    n_devices = std::min(n_devices, 1024);
     int devs[1024];
-    for (int k = 0; k < n_devices; ++k) devs[k] = k;
-    return agx_sw_score_devices(devs, n_devices, bases, off, len, n_pairs, scores);
+    n_devices = agx_first_devices(n_devices, devs);
+    return n_devices ? agx_sw_score_devices(devs, n_devices, bases, off, len, n_pairs, scores) : AGX_E_NODEVICE;
 }
 
 } // extern "C"
