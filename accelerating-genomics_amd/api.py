@@ -17,7 +17,11 @@ TUNING_KNOBS = ("AGX_SW_KERNEL", "AGX_SW_TAIL_BETA", "AGX_SW_MAX_C", "AGX_SW_FOR
 _DEFAULT_LIB = "libagx_tuning.so" if any(k in os.environ for k in TUNING_KNOBS) else "libagx.so"
 LIB_PATH = os.environ.get("AGX_LIB_PATH", os.path.join(_HERE, _DEFAULT_LIB))  # override: kernel experiments only
 
-OK, E_ARG, E_NODEVICE, E_HIP, E_NOMEM, E_SYMBOL, E_LIMIT, E_IO = 0, -1, -2, -3, -4, -5, -6, -7
+OK, E_ARG, E_NODEVICE, E_HIP, E_NOMEM, E_SYMBOL, E_LIMIT, E_IO, E_INTERNAL = 0, -1, -2, -3, -4, -5, -6, -7, -8
+SW_ALIGN_ENDS, SW_ALIGN_SPANS = 1, 2
+SW_ALIGN_MAX_QUERY_LEN, SW_ALIGN_MAX_TARGET_LEN = 2560, 65535
+# agx_sw_hit as a numpy record: one per pair, positions 0-based and inclusive, -1 where the score is 0
+SwHit = np.dtype([("score", np.int32), ("a_begin", np.int32), ("a_end", np.int32), ("b_begin", np.int32), ("b_end", np.int32)])
 OPT_SW_KERNEL = 1
 OPT_SW_PLANNER = 2
 SW_PLANNER_AUTO, SW_PLANNER_HOST, SW_PLANNER_DEVICE = 0, 1, 2
@@ -33,6 +37,7 @@ SYMBOLS = [
     "agx_ctx_stream", "agx_ctx_set_stream", "agx_ctx_sync", "agx_ctx_set_option", "agx_warmup_devices", "agx_host_alloc", "agx_host_free",
     "agx_ctx_timer_start", "agx_ctx_timer_stop", "agx_ctx_timer_mark", "agx_ctx_timer_elapsed",
     "agx_sw_batch_create", "agx_sw_batch_create_scored", "agx_sw_batch_create_matrix", "agx_sw_batch_launch", "agx_sw_batch_scores", "agx_sw_batch_bind_scores", "agx_sw_batch_info", "agx_sw_batch_destroy",
+    "agx_sw_batch_create_align", "agx_sw_batch_hits", "agx_sw_align",
     "agx_sw_score", "agx_sw_score_multi", "agx_sw_score_devices", "agx_sw_shard_cuts",
     "agx_phmm_batch_create", "agx_phmm_batch_launch", "agx_phmm_batch_results", "agx_phmm_batch_bind_results", "agx_phmm_batch_info",
     "agx_phmm_batch_destroy", "agx_phmm_forward", "agx_phmm_forward_multi", "agx_phmm_forward_devices", "agx_phmm_shard_cuts",
@@ -147,6 +152,10 @@ def lib():
         l.agx_sw_batch_info.argtypes = [C.c_void_p, C.POINTER(SwInfo)]
         l.agx_sw_batch_destroy.argtypes = [C.c_void_p]
         l.agx_sw_batch_destroy.restype = None
+        l.agx_sw_batch_create_align.argtypes = [C.c_void_p, C.POINTER(SwScoring), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_int64, C.POINTER(C.c_void_p)]
+        l.agx_sw_batch_hits.argtypes = [C.c_void_p, C.c_void_p]
+        l.agx_sw_align.argtypes = [C.c_void_p, C.POINTER(SwScoring), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
         l.agx_sw_score.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
         l.agx_sw_score_multi.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
         l.agx_sw_score_devices.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
@@ -250,8 +259,15 @@ class Context:
         return ms.value
 
     # ---- Smith-Waterman
-    def sw_batch(self, b, scoring=None, matrix=None) -> "SwBatch":
-        return SwBatch(self, b, scoring, matrix)
+    def sw_batch(self, b, scoring=None, matrix=None, align=0) -> "SwBatch":
+        return SwBatch(self, b, scoring, matrix, align)
+
+    def sw_align(self, b, what=SW_ALIGN_SPANS, scoring=None) -> np.ndarray:
+        """b: synth.SWBatch -> SwHit records (score, end cell, and with SW_ALIGN_SPANS the begin cell), one-shot."""
+        out = np.empty(b.n_pairs, SwHit)
+        sc = C.byref(SwScoring(*scoring)) if scoring is not None else None
+        _check(lib().agx_sw_align(self._h, sc, what, _ptr(b.bases), _ptr(b.off), _ptr(b.len), b.n_pairs, _ptr(out)))
+        return out
 
     def sw_score(self, b) -> np.ndarray:
         """b: synth.SWBatch (bases/off/len) -> int32 scores, one-shot."""
@@ -273,12 +289,19 @@ class Context:
 class SwBatch:
     """agx_sw_batch: a scheduled batch resident in HBM (ctx=None: planned on the host only)."""
 
-    def __init__(self, ctx, b, scoring=None, matrix=None):
+    def __init__(self, ctx, b, scoring=None, matrix=None, align=0):
         """scoring: None (the reference's +1/-1/-3/-1) or (match, mismatch, gap_open, gap_extend);
-        matrix: an SwMatrix instead."""
+        matrix: an SwMatrix instead; align: SW_ALIGN_ENDS / SW_ALIGN_SPANS for a batch that also answers hits()."""
         self.ctx = ctx
         self.n_pairs = b.n_pairs
         self._h = C.c_void_p()
+        if align:
+            if matrix is not None:
+                raise AgxError(E_ARG, "align batches take match/mismatch scoring, not a substitution matrix")
+            sc = C.byref(SwScoring(*scoring)) if scoring is not None else None
+            _check(lib().agx_sw_batch_create_align(ctx._h if ctx else None, sc, align, _ptr(b.bases), _ptr(b.off), _ptr(b.len),
+                                                   b.n_pairs, C.byref(self._h)))
+            return
         if matrix is not None:
             _check(lib().agx_sw_batch_create_matrix(ctx._h if ctx else None, C.byref(matrix), _ptr(b.bases), _ptr(b.off),
                                                     _ptr(b.len), b.n_pairs, C.byref(self._h)))
@@ -294,6 +317,13 @@ class SwBatch:
         if out is None:
             out = np.empty(self.n_pairs, np.int32)
         _check(lib().agx_sw_batch_scores(self._h, _ptr(out)))
+        return out
+
+    def hits(self, out=None) -> np.ndarray:
+        """agx_sw_batch_hits: SwHit records in the caller's pair order (align batches only)."""
+        if out is None:
+            out = np.empty(self.n_pairs, SwHit)
+        _check(lib().agx_sw_batch_hits(self._h, _ptr(out)))
         return out
 
     def bind_scores(self, out):

@@ -49,9 +49,10 @@ int tuned_kernel() // 0 = no override
 }
 
 // per-class cost table of the kernel family a batch runs (relative lane time per padded cell)
-inline const double *class_costs(int family) // 0 int32, 1 packed signed, 2 packed biased, 3 int32 on the packed plan's coded image
+inline const double *class_costs(int family) // 0 int32, 1 packed signed, 2 packed biased, 3 int32 on the packed plan's coded image, 4 locating int32
 {
-    return family == 0 ? kSwClassCost : family == 1 ? kSwPkClassCost : family == 3 ? kSwI32dClassCost : kSwPk2ClassCost;
+    // (the locating fill is the int32 cell plus a per-step scan: the int32 kernel's relative costs, no wide classes)
+    return family == 0 ? kSwClassCost : family == 1 ? kSwPkClassCost : family == 3 || family == 4 ? kSwI32dClassCost : kSwPk2ClassCost;
 }
 
 // Lane time a pair costs under tiling (class ci, G): steps * C * 64 / floor(64 / G) padded cells (the
@@ -208,7 +209,16 @@ struct Bucket {
 
 struct agx_sw_batch {
     agx_ctx *ctx = nullptr; // retained
-    int family = 0;         // 0 int32, 1 packed signed, 2 packed biased, 3 int32 on the packed plan's coded image
+    int family = 0;         // 0 int32, 1 packed signed, 2 packed biased, 3 int32 on the packed plan's coded image, 4 locating int32
+    // align batches (agx_sw_batch_create_align): 0 = a score-only batch, else AGX_SW_ALIGN_ENDS / _SPANS
+    int align = 0;
+    agx_sw_scoring scoring{};
+    DevBuf ends;        // per pair: row << kSwLocColBits | column of the end cell, written by the locating fill
+    PinBuf ends_stage;  // its page-locked landing block
+    // SPANS: the sequences, dense, for the begin pass (the caller's arrays need not outlive the create)
+    std::vector<uint8_t> seq;
+    std::vector<uint64_t> seq_off;
+    std::vector<uint32_t> seq_len;
     SwParams prm{};
     int64_t n_pairs = 0;
     DevBuf img, groups, waves, scores;
@@ -231,7 +241,7 @@ struct agx_sw_batch {
 
 namespace {
 int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matrix *matrix, const uint8_t *bases,
-                 const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_batch **out, bool defer = false);
+                 const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_batch **out, bool defer = false, int align = 0);
 int finish_create(agx_sw_batch *b);
 void drop_pending(agx_sw_batch *b);
 }
@@ -249,6 +259,8 @@ void agx_sw_batch_destroy(agx_sw_batch *b)
     b->scores.release();
     b->table.release();
     b->out_stage.release();
+    b->ends.release();
+    b->ends_stage.release();
     agx_ctx_release(b->ctx); // the batch's own reference: a context outlives its batches
     delete b;
 }
@@ -468,7 +480,7 @@ int launch_device_plan(agx_ctx *ctx, DevPlan &dp, agx_sw_batch *b, uint32_t n_pa
 }
 
 int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matrix *matrix, const uint8_t *bases,
-                 const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_batch **out, bool defer)
+                 const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_batch **out, bool defer, int align)
 {
     if (!out) {
         agx_set_error("agx_sw_batch_create: out is NULL");
@@ -560,7 +572,7 @@ int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matri
     // regime or with a dominant shape is planned on the host as before).
     const int want = tuned_kernel() ? tuned_kernel() : ctx ? ctx->opt_sw_kernel : AGX_SW_KERNEL_AUTO;
     const int planner_opt = ctx ? ctx->opt_sw_planner : AGX_SW_PLANNER_HOST;
-    bool dev_candidate = ctx && !matrix && planner_opt != AGX_SW_PLANNER_HOST && n_pairs > 0 &&
+    bool dev_candidate = ctx && !matrix && !align && planner_opt != AGX_SW_PLANNER_HOST && n_pairs > 0 &&
                          (planner_opt == AGX_SW_PLANNER_DEVICE || n_pairs >= kDevPlanMinPairs) &&
                          (want == AGX_SW_KERNEL_AUTO || want == AGX_SW_KERNEL_PACKED_BIASED) && tail_beta_override() < 0 &&
                          !max_classes_override() && !agx_tune("AGX_SW_SORT_WAVES") && !agx_tune("AGX_SW_ONE_LAUNCH") &&
@@ -570,7 +582,8 @@ int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matri
     std::vector<PairPlan> all;
     if (!dev_candidate) all.resize((size_t)n_pairs);
     PairPlan *allp = dev_candidate ? nullptr : all.data();
-    const uint32_t hard_max_short = matrix ? (uint32_t)kSwPackedMaxShort : AGX_SW_MAX_SHORT_LEN; // no wide classes in matrix mode
+    // no wide classes in matrix mode; an align batch lays the FIRST sequence across the lanes (agx_sw_loc_kernel.hip), its limit is on that one
+    const uint32_t hard_max_short = matrix ? (uint32_t)kSwPackedMaxShort : align ? (uint32_t)AGX_SW_ALIGN_MAX_QUERY_LEN : AGX_SW_MAX_SHORT_LEN;
     struct Worker {
         int rc = AGX_OK;
         int64_t bad_pair = -1;
@@ -606,7 +619,7 @@ int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matri
                 me.hi = std::max(me.hi, off[2 * p + 1] + lb);
             }
             if (la == 0 || lb == 0) continue; // no interior cell: score stays 0
-            const bool second_short = lb < la; // ties keep file order (antidiagonalSmithWaterman.c:229-244)
+            const bool second_short = !align && lb < la; // ties keep file order (antidiagonalSmithWaterman.c:229-244)
             const uint32_t lx = second_short ? lb : la, ly = second_short ? la : lb;
             if (lx > hard_max_short || ly > 0xffffu) {
                 if (me.rc == AGX_OK) {
@@ -641,8 +654,8 @@ int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matri
     for (const Worker &w : wk)
         if (w.rc != AGX_OK) {
             const int64_t p = w.bad_pair;
-            agx_set_error("pair %lld: lengths %u x %u exceed the supported %u x 65535 (shorter x longer)", (long long)p,
-                          len[2 * p], len[2 * p + 1], hard_max_short);
+            agx_set_error("pair %lld: lengths %u x %u exceed the supported %u x 65535 (%s)", (long long)p,
+                          len[2 * p], len[2 * p + 1], hard_max_short, align ? "query x target of an align batch" : "shorter x longer");
             return w.rc;
         }
     if (ext_hi < ext_lo) ext_lo = ext_hi = 0; // no byte at all
@@ -661,6 +674,7 @@ int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matri
     // one pair of a lane group at a time (agx_sw_i32d_kernel.hip: 7.5 instead of 8.5 instructions per cell), wherever the
     // coded match exists: delta and mismatch + |gf| must be bytes, the shorter sides within the packed plan's 2560 columns.
     if (family == 0 && !matrix && longest_short <= (uint32_t)kSwPackedMaxShort && prm.delta < 128 && prm.hd >= prm.delta && !agx_tune("AGX_SW_I32_CLASSIC")) family = 3;
+    if (align) family = 4; // the locating fill: int32 state on the byte image, one pair per lane group
     if (family == 2 && !((int64_t)bias + ((int64_t)longest_short + 1) * sc.match - prm.gf < 0x7c00)) family = 1;
     // ... and its rising-offset variant adds (steps + 2) |ge| on top, steps <= longest longer side + 63
     int rising = family == 2 &&
@@ -668,7 +682,8 @@ int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matri
     // ... with column classes when the wrapping column's diagonal constant, mismatch + |gf| - 3 |ge|, is not negative
     if (rising && prm.hd - prm.delta + 3 * prm.ge >= 0) rising = 4;
     if (const char *e = agx_tune("AGX_SW_RISE")) rising = e[0] == '0' ? 0 : e[0] == '1' && rising ? 1 : rising;
-    const bool packed = family != 0;
+    const bool packed = family >= 1 && family <= 3;
+    const bool coded_plan = family == 2 || family == 3; // the packed plan of the biased fill (one launch for all classes)
     const double *costs = class_costs(family);
     const int slots = packed ? 2 : 1;
 
@@ -715,8 +730,11 @@ int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matri
         if (family == 2) agx_sw_pk2_preload();
         if (family == 3) agx_sw_i32d_preload();
         if (family == 0 && !matrix) agx_sw_i32_preload();
+        if (family == 4) agx_sw_loc_preload();
     }
     b->matrix = matrix != nullptr;
+    b->align = align;
+    b->scoring = sc;
     b->prm = prm;
     b->prm.n_out = (uint32_t)n_pairs + 1u;
 
@@ -1019,7 +1037,7 @@ int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matri
         // (the biased packed fill runs two waves per SIMD, and with its round-2b cell the term pays up to 1.2 of ITS
         // fillings = 0.48 of these: 45 056 mixed pairs 6.5 -> 7.2 TCUPS, 49 152 7.15 -> 7.26, but 57 344 7.74 -> 7.55 and
         // 65 536 8.07 -> 7.71 -- tools/sw_tail_rule_check.py)
-        if (fill < (family >= 2 ? 0.48 : 1.6)) {
+        if (fill < (coded_plan ? 0.48 : 1.6)) {
             beta_used = fill < 0.1 ? 10.0 : fill < 0.4 ? 6.0 : 3.0;
             tile_all(~0u, beta_used, false);
         }
@@ -1042,7 +1060,7 @@ int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matri
         // 5.48 -> 5.81.  Smaller batches are in the tail regime, where the launch lasts as long as its longest
         // waves and the few-classes rule still wins (16 384 pairs: 3.58 against 3.02 TCUPS; tools/sw_mixed_check.py).
         const int k_max = max_classes_override()                  ? std::min(max_classes_override(), 1 + (int)(waves_est / per_class))
-                          : family >= 2 && waves_est >= 2048.0 ? kSwNumClasses
+                          : coded_plan && waves_est >= 2048.0 ? kSwNumClasses
                                                                   : std::min(6, 1 + (int)(waves_est / per_class));
         int used = 0;
         for (int c = 0; c < kSwNumClasses; ++c) used += work[c] > 0;
@@ -1224,7 +1242,7 @@ int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matri
         const char *e = agx_tune("AGX_SW_ONE_LAUNCH");
         return !(e && e[0] == '0');
     }();
-    if (family >= 2 && launches.size() > 1 && one_launch_ok) {
+    if (coded_plan && launches.size() > 1 && one_launch_ok) {
         if (sort_waves)
             std::stable_sort(waves.begin(), waves.end(), [](const SwWave &a, const SwWave &b) {
                 return (uint64_t)a.steps * a.reserved > (uint64_t)b.steps * b.reserved;
@@ -1349,6 +1367,8 @@ int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matri
     if (!rc && matrix) rc = b->table.alloc(ctx, table.size() * sizeof(int16_t));
     if (!rc) rc = b->scores.alloc(ctx, ((size_t)n_pairs + 1) * sizeof(int32_t)); // +1: spare slot of vacant packed halves
     if (!rc) rc = b->out_stage.alloc(ctx, ((size_t)n_pairs + 1) * sizeof(int32_t));
+    if (!rc && align) rc = b->ends.alloc(ctx, ((size_t)n_pairs + 1) * sizeof(uint32_t));
+    if (!rc && align) rc = b->ends_stage.alloc(ctx, ((size_t)n_pairs + 1) * sizeof(uint32_t));
     if (!rc && launches.size() > 1) rc = agx_ctx_prepare_fanout(ctx);
     if (rc) return rc;
     hipStream_t cs = ctx->copy;
@@ -1367,6 +1387,7 @@ int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matri
         e = hipMemcpyAsync(b->table.p, table.data(), table.size() * sizeof(int16_t), hipMemcpyHostToDevice, ts);
     // pairs with an empty side are never touched by a kernel: their score is this zero
     if (e == hipSuccess) e = hipMemsetAsync(b->scores.p, 0, b->scores.bytes, ts);
+    if (e == hipSuccess && align) e = hipMemsetAsync(b->ends.p, 0xff, b->ends.bytes, ts); // ... and their end cell is "none"
     if (e == hipSuccess && packed) e = hipMemsetAsync(b->img.p, 0, (size_t)kSwPackedMaxShort + 4, ts);
     uint32_t *flag = (uint32_t *)h_flag.p;
     flag[0] = 0;
@@ -1374,7 +1395,7 @@ int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matri
     if (e == hipSuccess && n_groups) {
         const char *dna_knob = agx_tune("AGX_SW_DNA");
         // the DNA-coded cell adds (mismatch + |gf|) and a table byte: both must be non-negative bytes
-        const bool dna = family >= 2 && prm.delta < 128 && prm.hd >= prm.delta && !(dna_knob && dna_knob[0] == '0');
+        const bool dna = coded_plan && prm.delta < 128 && prm.hd >= prm.delta && !(dna_knob && dna_knob[0] == '0');
         const int pr = dna // the biased packed fill has a DNA-coded cell: its pack kernel decides per wavefront
                            ? agx_sw_pack_dna_launch((const uint8_t *)d_raw.p + kRawPad, (const uint64_t *)d_off.p, raw_base, b->groups.p, b->waves.p,
                                                     (uint32_t)n_waves_total, (uint32_t)n_pairs, (uint32_t *)b->img.p, (uint32_t *)d_flag.p,
@@ -1458,7 +1479,9 @@ int agx_sw_batch_launch(agx_sw_batch *b)
         const SwWave *wv = (const SwWave *)b->waves.p + cl.first_wave;
         int32_t *scores = b->bound ? b->bound : (int32_t *)b->scores.p;
         int r;
-        if (b->matrix)
+        if (b->align)
+            r = agx_sw_loc_launch_class(cl.C, prm, img, (const SwGroup *)b->groups.p, wv, cl.n_waves, scores, (uint32_t *)b->ends.p, st);
+        else if (b->matrix)
             r = agx_sw_mat_launch_class(cl.C, prm, img, (const SwGroup *)b->groups.p, wv, cl.n_waves, scores,
                                         (const int16_t *)b->table.p, st);
         else if (b->family == 3)
@@ -1542,7 +1565,7 @@ int agx_sw_batch_bind_scores(agx_sw_batch *b, int32_t *scores)
     AGX_HIP(hipStreamSynchronize(b->ctx->stream)); // launches in flight still write the old destination
     // only a batch whose records are in file order takes the binding (a sorted batch's waves would scatter 4-byte
     // writes over PCIe: measured slower than the copy kernel behind the fill); the call is a hint otherwise
-    b->bound = (scores && b->file_order && b->n_pairs > 0 && !b->matrix) ? scores : nullptr;
+    b->bound = (scores && b->file_order && b->n_pairs > 0 && !b->matrix && !b->align) ? scores : nullptr;
     return AGX_OK;
 }
 
@@ -1633,6 +1656,171 @@ int agx_sw_score(agx_ctx *ctx, const uint8_t *bases, const uint64_t *off, const 
     }
     return AGX_OK;
     AGX_GUARD_END("agx_sw_score")
+}
+
+int agx_sw_batch_create_align(agx_ctx *ctx, const agx_sw_scoring *scoring, int what, const uint8_t *bases, const uint64_t *off,
+                              const uint32_t *len, int64_t n_pairs, agx_sw_batch **out)
+{
+    if (what != AGX_SW_ALIGN_ENDS && what != AGX_SW_ALIGN_SPANS) {
+        if (out) *out = nullptr;
+        agx_set_error("agx_sw_batch_create_align: what = %d is neither AGX_SW_ALIGN_ENDS nor AGX_SW_ALIGN_SPANS", what);
+        return AGX_E_ARG;
+    }
+    AGX_GUARD_BEGIN
+    agx_sw_batch *b = nullptr;
+    int rc = create_batch(ctx, scoring, nullptr, bases, off, len, n_pairs, &b, false, what);
+    if (rc) return rc;
+    struct Drop {
+        agx_sw_batch *b;
+        ~Drop() { agx_sw_batch_destroy(b); } // (create_batch has waited for everything it queued)
+    } drop{b};
+    if (ctx && n_pairs > 0) b->seq_len.assign(len, len + 2 * n_pairs); // agx_sw_batch_hits checks every end cell against them
+    if (ctx && what == AGX_SW_ALIGN_SPANS && n_pairs > 0) {
+        // the begin pass reads the sequences again, long after this call: a dense copy of the batch's own
+        b->seq_off.resize((size_t)n_pairs * 2);
+        uint64_t at = 0;
+        for (int64_t k = 0; k < 2 * n_pairs; ++k) {
+            b->seq_off[(size_t)k] = at;
+            at += len[k];
+        }
+        b->seq.resize((size_t)at);
+        agx_parallel_for(2 * n_pairs, 8192, [&](int64_t lo, int64_t hi, int) {
+            for (int64_t k = lo; k < hi; ++k)
+                if (len[k]) memcpy(b->seq.data() + b->seq_off[(size_t)k], bases + off[k], len[k]);
+        });
+    }
+    drop.b = nullptr;
+    *out = b;
+    return AGX_OK;
+    AGX_GUARD_END("agx_sw_batch_create_align")
+}
+
+int agx_sw_batch_hits(agx_sw_batch *b, agx_sw_hit *hits)
+{
+    if (!b || (!hits && b->n_pairs)) {
+        agx_set_error("agx_sw_batch_hits: null argument");
+        return AGX_E_ARG;
+    }
+    if (!b->align) {
+        agx_set_error("agx_sw_batch_hits: a score-only batch has no hits (create it with agx_sw_batch_create_align)");
+        return AGX_E_ARG;
+    }
+    if (!b->ctx) {
+        agx_set_error("this batch was planned without a context (no device): it has no hits");
+        return AGX_E_NODEVICE;
+    }
+    AGX_GUARD_BEGIN
+    int rc = agx_bind(b->ctx);
+    if (rc) return rc;
+    hipStream_t st = b->ctx->stream;
+    const int64_t n = b->n_pairs;
+    if (n == 0) {
+        AGX_HIP(hipStreamSynchronize(st));
+        return AGX_OK;
+    }
+    const int32_t *sc = (const int32_t *)b->out_stage.p;
+    const uint32_t *en = (const uint32_t *)b->ends_stage.p;
+    AGX_HIP(hipMemcpyAsync(b->out_stage.p, b->scores.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    AGX_HIP(hipMemcpyAsync(b->ends_stage.p, b->ends.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    AGX_HIP(hipStreamSynchronize(st));
+    // end cells, checked against the caller's lengths: a padding cell must never be reported
+    const uint32_t *len = b->seq_len.empty() ? nullptr : b->seq_len.data(); // (the begin pass's own batch has none: checked against the end cell below)
+    std::vector<int64_t> bad((size_t)agx_host_threads(), -1);
+    agx_parallel_for(n, 16384, [&](int64_t lo, int64_t hi, int tid) {
+        for (int64_t p = lo; p < hi; ++p) {
+            agx_sw_hit h{sc[p], -1, -1, -1, -1};
+            if (en[p] != 0xffffffffu) {
+                h.a_end = (int32_t)(en[p] & ((1u << kSwLocColBits) - 1u));
+                h.b_end = (int32_t)(en[p] >> kSwLocColBits);
+            }
+            const bool located = en[p] != 0xffffffffu;
+            bool ok = sc[p] >= 0 && located == (sc[p] > 0);
+            if (ok && located && len) ok = (uint32_t)h.a_end < len[2 * p] && (uint32_t)h.b_end < len[2 * p + 1];
+            if (!ok && bad[(size_t)tid] < 0) bad[(size_t)tid] = p;
+            hits[p] = h;
+        }
+    });
+    for (int64_t p : bad)
+        if (p >= 0) {
+            agx_set_error("agx_sw_batch_hits: pair %lld: score %d with end cell word 0x%08x is not a cell of its matrix", (long long)p, sc[p], en[p]);
+            return AGX_E_INTERNAL;
+        }
+    if (b->align != AGX_SW_ALIGN_SPANS) return AGX_OK;
+
+    // ---- begin pass: the same fill over the reversed prefixes a[a_end..0], b[b_end..0] of the pairs with a score.  Its end
+    // cell, by the same rule, is the latest begin in b, then in a, of an alignment of that score ending in the end cell
+    // (DESIGN.md has the argument).
+    std::vector<int64_t> pick;
+    pick.reserve((size_t)n);
+    for (int64_t p = 0; p < n; ++p)
+        if (hits[p].score > 0) pick.push_back(p);
+    const int64_t m = (int64_t)pick.size();
+    if (m == 0) return AGX_OK;
+    std::vector<uint64_t> roff((size_t)m * 2);
+    std::vector<uint32_t> rlen((size_t)m * 2);
+    uint64_t at = 0;
+    for (int64_t k = 0; k < m; ++k) {
+        const agx_sw_hit &h = hits[pick[(size_t)k]];
+        roff[(size_t)(2 * k)] = at;
+        rlen[(size_t)(2 * k)] = (uint32_t)h.a_end + 1u;
+        at += (uint64_t)h.a_end + 1u;
+        roff[(size_t)(2 * k + 1)] = at;
+        rlen[(size_t)(2 * k + 1)] = (uint32_t)h.b_end + 1u;
+        at += (uint64_t)h.b_end + 1u;
+    }
+    std::vector<uint8_t> rev((size_t)at);
+    agx_parallel_for(m, 4096, [&](int64_t lo, int64_t hi, int) {
+        for (int64_t k = lo; k < hi; ++k) {
+            const int64_t p = pick[(size_t)k];
+            for (int side = 0; side < 2; ++side) {
+                const uint8_t *src = b->seq.data() + b->seq_off[(size_t)(2 * p + side)];
+                uint8_t *dst = rev.data() + roff[(size_t)(2 * k + side)];
+                const uint32_t l = rlen[(size_t)(2 * k + side)];
+                for (uint32_t i = 0; i < l; ++i) dst[i] = src[l - 1u - i];
+            }
+        }
+    });
+    agx_sw_batch *rb = nullptr;
+    rc = create_batch(b->ctx, &b->scoring, nullptr, rev.data(), roff.data(), rlen.data(), m, &rb, false, AGX_SW_ALIGN_ENDS);
+    if (rc) return rc;
+    struct Drop {
+        agx_sw_batch *b;
+        ~Drop()
+        {
+            (void)hipStreamSynchronize(b->ctx->stream); // an error exit may leave its fill running
+            agx_sw_batch_destroy(b);
+        }
+    } drop{rb};
+    std::vector<agx_sw_hit> rh((size_t)m);
+    rc = agx_sw_batch_launch(rb);
+    if (!rc) rc = agx_sw_batch_hits(rb, rh.data());
+    if (rc) return rc;
+    for (int64_t k = 0; k < m; ++k) {
+        agx_sw_hit &h = hits[pick[(size_t)k]];
+        const agx_sw_hit &r = rh[(size_t)k];
+        if (r.score != h.score || r.a_end < 0 || r.a_end > h.a_end || r.b_end < 0 || r.b_end > h.b_end) {
+            agx_set_error("agx_sw_batch_hits: pair %lld: the reverse fill from its end cell (a %d, b %d) gives score %d at (a %d, b %d), the forward fill %d",
+                          (long long)pick[(size_t)k], h.a_end, h.b_end, r.score, r.a_end, r.b_end, h.score);
+            return AGX_E_INTERNAL;
+        }
+        h.a_begin = h.a_end - r.a_end;
+        h.b_begin = h.b_end - r.b_end;
+    }
+    return AGX_OK;
+    AGX_GUARD_END("agx_sw_batch_hits")
+}
+
+int agx_sw_align(agx_ctx *ctx, const agx_sw_scoring *scoring, int what, const uint8_t *bases, const uint64_t *off,
+                 const uint32_t *len, int64_t n_pairs, agx_sw_hit *hits)
+{
+    agx_sw_batch *b = nullptr;
+    int rc = agx_sw_batch_create_align(ctx, scoring, what, bases, off, len, n_pairs, &b);
+    if (rc) return rc;
+    rc = agx_sw_batch_launch(b);
+    if (!rc) rc = agx_sw_batch_hits(b, hits);
+    if (rc && b->ctx) (void)hipStreamSynchronize(b->ctx->stream); // the blocks go back to the pools: nothing may still run on them
+    agx_sw_batch_destroy(b);
+    return rc;
 }
 
 int agx_sw_shard_cuts(const uint32_t *len, int64_t n_pairs, int n_shards, int64_t *cut)

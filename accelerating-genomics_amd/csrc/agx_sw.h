@@ -111,6 +111,13 @@ int agx_sw_launch_class(int cols_per_lane, const SwParams &prm, const uint32_t *
                         const SwWave *waves, uint32_t n_waves, int32_t *scores, hipStream_t s);
 int agx_sw_wide_launch_class(int cols_per_lane, const SwParams &prm, const uint32_t *img, const SwGroup *groups,
                              const SwWave *waves, uint32_t n_waves, int32_t *scores, hipStream_t s);
+// the locating fill of align batches (agx_sw_loc_kernel.hip): the int32 kernel's records and byte image with the pair's FIRST
+// sequence across the lanes; besides scores[out] it writes ends[out] = row (position in the second sequence) << 12 | column
+// (position in the first) of the first cell in (row, column) order that holds the maximum, 0xffffffff when the score is 0
+constexpr int kSwLocColBits = 12;
+int agx_sw_loc_launch_class(int cols_per_lane, const SwParams &prm, const uint32_t *img, const SwGroup *groups, const SwWave *waves,
+                            uint32_t n_waves, int32_t *scores, uint32_t *ends, hipStream_t s);
+void agx_sw_loc_preload();
 
 // ---- device-side planning (agx_sw_plan_kernel.hip): the O(pairs) passes of the planner as kernels
 constexpr uint32_t kSwPlanEmptyKey = 1u << 27;           // sort key of a pair with an empty side: behind every bucket

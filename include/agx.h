@@ -38,6 +38,7 @@ extern "C" {
 #define AGX_E_SYMBOL (-5)   /* a sequence contains byte 0x00, reserved as the padding symbol */
 #define AGX_E_LIMIT (-6)    /* a length exceeds what the kernels support (see AGX_*_MAX_*) */
 #define AGX_E_IO (-7)       /* parser: file cannot be opened / is malformed */
+#define AGX_E_INTERNAL (-8) /* a result failed the library's own cross-check (agx_sw_batch_hits); agx_last_error() says which */
 
 /* Smith-Waterman: the shorter sequence of a pair is laid across lanes, at most
  * 64 lanes x AGX_SW_MAX_COLS_PER_LANE columns; the longer one streams.  (The
@@ -178,6 +179,41 @@ int agx_sw_batch_scores(agx_sw_batch *b, int32_t *scores);
 int agx_sw_batch_bind_scores(agx_sw_batch *b, int32_t *scores);
 int agx_sw_batch_info(const agx_sw_batch *b, agx_sw_info *info);
 void agx_sw_batch_destroy(agx_sw_batch *b);
+
+/*
+ * Alignment coordinates: where the best local alignment ends and begins (no traceback: the span is what bounds one).
+ * For pair p, a = sequence 2p (the query), b = sequence 2p+1 (the target), raw bytes as given, a trailing '\n'
+ * included if the caller passed one.  H[i][j] is the local-alignment matrix with i a 0-based position in b and j a
+ * 0-based position in a.  All positions are inclusive and in the caller's coordinates.
+ *   score            = max over H, what agx_sw_batch_scores returns
+ *   (b_end, a_end)   = among the cells with H == score the one with the smallest b_end, among those the smallest a_end
+ *   (b_begin, a_begin) = among the alignments of that score ending in the end cell the one that begins latest in b,
+ *                      among those latest in a; equally: the end cell, by the rule above, of a[a_end..0] against
+ *                      b[b_end..0] (both prefixes reversed), mapped back
+ *   score == 0 (no matching symbol, or an empty sequence): all four positions are -1.
+ * An align batch lays a across the lanes whichever sequence is shorter, so its limits are on the roles, not on
+ * "shorter/longer": len(a) <= AGX_SW_ALIGN_MAX_QUERY_LEN (64 lanes x 40 columns), len(b) <= AGX_SW_ALIGN_MAX_TARGET_LEN;
+ * a longer sequence fails the create with AGX_E_LIMIT.  scoring == NULL: the reference's constants.
+ */
+typedef struct agx_sw_hit {
+    int32_t score, a_begin, a_end, b_begin, b_end;
+} agx_sw_hit;
+#define AGX_SW_ALIGN_ENDS 1  /* score + end cell; begins are -1 */
+#define AGX_SW_ALIGN_SPANS 2 /* score + end cell + begin cell (a second fill over the reversed prefixes) */
+#define AGX_SW_ALIGN_MAX_QUERY_LEN 2560
+#define AGX_SW_ALIGN_MAX_TARGET_LEN 65535
+/* Resident batch like agx_sw_batch_create_scored; agx_sw_batch_launch (re)launches its fill, agx_sw_batch_scores returns
+ * its scores, agx_sw_batch_bind_scores is accepted and ignored.  A SPANS batch keeps a host copy of the sequences.
+ * ctx may be NULL: plan only. */
+int agx_sw_batch_create_align(agx_ctx *ctx, const agx_sw_scoring *scoring, int what, const uint8_t *bases, const uint64_t *off,
+                              const uint32_t *len, int64_t n_pairs, agx_sw_batch **out);
+/* Waits for the launched fill and writes one hit per pair in the caller's pair order.  A SPANS batch runs its begin pass
+ * here and checks that the reverse fill reproduces every forward score (AGX_E_INTERNAL otherwise: no span is returned that
+ * the library cannot vouch for).  AGX_E_ARG on a batch that was not created by agx_sw_batch_create_align. */
+int agx_sw_batch_hits(agx_sw_batch *b, agx_sw_hit *hits);
+/* One-shot: create_align + launch + hits + destroy. */
+int agx_sw_align(agx_ctx *ctx, const agx_sw_scoring *scoring, int what, const uint8_t *bases, const uint64_t *off,
+                 const uint32_t *len, int64_t n_pairs, agx_sw_hit *hits);
 
 /* One-shot: create + launch + scores + destroy. */
 int agx_sw_score(agx_ctx *ctx, const uint8_t *bases, const uint64_t *off, const uint32_t *len, int64_t n_pairs,
