@@ -20,6 +20,8 @@ LIB_PATH = os.environ.get("AGX_LIB_PATH", os.path.join(_HERE, _DEFAULT_LIB))  # 
 OK, E_ARG, E_NODEVICE, E_HIP, E_NOMEM, E_SYMBOL, E_LIMIT, E_IO, E_INTERNAL = 0, -1, -2, -3, -4, -5, -6, -7, -8
 SW_ALIGN_ENDS, SW_ALIGN_SPANS = 1, 2
 SW_ALIGN_MAX_QUERY_LEN, SW_ALIGN_MAX_TARGET_LEN = 2560, 65535
+# alignment modes of align batches (include/agx.h, "Alignment modes"): the boundaries of the fill
+SW_MODE_LOCAL, SW_MODE_GLOBAL, SW_MODE_FIT, SW_MODE_EXTEND, SW_MODE_EXTEND_QUERY = 0, 1, 2, 3, 4
 # agx_sw_hit as a numpy record: one per pair, positions 0-based and inclusive, -1 where the score is 0
 SwHit = np.dtype([("score", np.int32), ("a_begin", np.int32), ("a_end", np.int32), ("b_begin", np.int32), ("b_end", np.int32)])
 OPT_SW_KERNEL = 1
@@ -37,7 +39,7 @@ SYMBOLS = [
     "agx_ctx_stream", "agx_ctx_set_stream", "agx_ctx_sync", "agx_ctx_set_option", "agx_warmup_devices", "agx_host_alloc", "agx_host_free",
     "agx_ctx_timer_start", "agx_ctx_timer_stop", "agx_ctx_timer_mark", "agx_ctx_timer_elapsed",
     "agx_sw_batch_create", "agx_sw_batch_create_scored", "agx_sw_batch_create_matrix", "agx_sw_batch_launch", "agx_sw_batch_scores", "agx_sw_batch_bind_scores", "agx_sw_batch_info", "agx_sw_batch_destroy",
-    "agx_sw_batch_create_align", "agx_sw_batch_hits", "agx_sw_align",
+    "agx_sw_batch_create_align", "agx_sw_batch_hits", "agx_sw_align", "agx_sw_batch_create_align_mode", "agx_sw_align_mode",
     "agx_sw_score", "agx_sw_score_multi", "agx_sw_score_devices", "agx_sw_shard_cuts",
     "agx_phmm_batch_create", "agx_phmm_batch_launch", "agx_phmm_batch_results", "agx_phmm_batch_bind_results", "agx_phmm_batch_info",
     "agx_phmm_batch_destroy", "agx_phmm_forward", "agx_phmm_forward_multi", "agx_phmm_forward_devices", "agx_phmm_shard_cuts",
@@ -156,6 +158,9 @@ def lib():
                                                 C.c_int64, C.POINTER(C.c_void_p)]
         l.agx_sw_batch_hits.argtypes = [C.c_void_p, C.c_void_p]
         l.agx_sw_align.argtypes = [C.c_void_p, C.POINTER(SwScoring), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        l.agx_sw_batch_create_align_mode.argtypes = [C.c_void_p, C.POINTER(SwScoring), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                     C.c_int64, C.POINTER(C.c_void_p)]
+        l.agx_sw_align_mode.argtypes = [C.c_void_p, C.POINTER(SwScoring), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
         l.agx_sw_score.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
         l.agx_sw_score_multi.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
         l.agx_sw_score_devices.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
@@ -259,14 +264,18 @@ class Context:
         return ms.value
 
     # ---- Smith-Waterman
-    def sw_batch(self, b, scoring=None, matrix=None, align=0) -> "SwBatch":
-        return SwBatch(self, b, scoring, matrix, align)
+    def sw_batch(self, b, scoring=None, matrix=None, align=0, mode=SW_MODE_LOCAL) -> "SwBatch":
+        return SwBatch(self, b, scoring, matrix, align, mode)
 
-    def sw_align(self, b, what=SW_ALIGN_SPANS, scoring=None) -> np.ndarray:
-        """b: synth.SWBatch -> SwHit records (score, end cell, and with SW_ALIGN_SPANS the begin cell), one-shot."""
+    def sw_align(self, b, what=SW_ALIGN_SPANS, scoring=None, mode=SW_MODE_LOCAL) -> np.ndarray:
+        """b: synth.SWBatch -> SwHit records (score, end cell, and with SW_ALIGN_SPANS the begin cell), one-shot.
+        mode: SW_MODE_LOCAL / _GLOBAL / _FIT / _EXTEND / _EXTEND_QUERY."""
         out = np.empty(b.n_pairs, SwHit)
         sc = C.byref(SwScoring(*scoring)) if scoring is not None else None
-        _check(lib().agx_sw_align(self._h, sc, what, _ptr(b.bases), _ptr(b.off), _ptr(b.len), b.n_pairs, _ptr(out)))
+        if mode == SW_MODE_LOCAL:
+            _check(lib().agx_sw_align(self._h, sc, what, _ptr(b.bases), _ptr(b.off), _ptr(b.len), b.n_pairs, _ptr(out)))
+        else:
+            _check(lib().agx_sw_align_mode(self._h, sc, mode, what, _ptr(b.bases), _ptr(b.off), _ptr(b.len), b.n_pairs, _ptr(out)))
         return out
 
     def sw_score(self, b) -> np.ndarray:
@@ -289,18 +298,25 @@ class Context:
 class SwBatch:
     """agx_sw_batch: a scheduled batch resident in HBM (ctx=None: planned on the host only)."""
 
-    def __init__(self, ctx, b, scoring=None, matrix=None, align=0):
+    def __init__(self, ctx, b, scoring=None, matrix=None, align=0, mode=SW_MODE_LOCAL):
         """scoring: None (the reference's +1/-1/-3/-1) or (match, mismatch, gap_open, gap_extend);
-        matrix: an SwMatrix instead; align: SW_ALIGN_ENDS / SW_ALIGN_SPANS for a batch that also answers hits()."""
+        matrix: an SwMatrix instead; align: SW_ALIGN_ENDS / SW_ALIGN_SPANS for a batch that also answers hits();
+        mode: SW_MODE_* of an align batch (local, global, fit, extension)."""
         self.ctx = ctx
         self.n_pairs = b.n_pairs
         self._h = C.c_void_p()
+        if mode != SW_MODE_LOCAL and not align:
+            raise AgxError(E_ARG, "mode= applies to align batches: pass align=SW_ALIGN_ENDS or SW_ALIGN_SPANS")
         if align:
             if matrix is not None:
                 raise AgxError(E_ARG, "align batches take match/mismatch scoring, not a substitution matrix")
             sc = C.byref(SwScoring(*scoring)) if scoring is not None else None
-            _check(lib().agx_sw_batch_create_align(ctx._h if ctx else None, sc, align, _ptr(b.bases), _ptr(b.off), _ptr(b.len),
-                                                   b.n_pairs, C.byref(self._h)))
+            if mode == SW_MODE_LOCAL:
+                _check(lib().agx_sw_batch_create_align(ctx._h if ctx else None, sc, align, _ptr(b.bases), _ptr(b.off), _ptr(b.len),
+                                                       b.n_pairs, C.byref(self._h)))
+            else:
+                _check(lib().agx_sw_batch_create_align_mode(ctx._h if ctx else None, sc, mode, align, _ptr(b.bases), _ptr(b.off), _ptr(b.len),
+                                                            b.n_pairs, C.byref(self._h)))
             return
         if matrix is not None:
             _check(lib().agx_sw_batch_create_matrix(ctx._h if ctx else None, C.byref(matrix), _ptr(b.bases), _ptr(b.off),

@@ -49,10 +49,10 @@ int tuned_kernel() // 0 = no override
 }
 
 // per-class cost table of the kernel family a batch runs (relative lane time per padded cell)
-inline const double *class_costs(int family) // 0 int32, 1 packed signed, 2 packed biased, 3 int32 on the packed plan's coded image, 4 locating int32
+inline const double *class_costs(int family) // 0 int32, 1 packed signed, 2 packed biased, 3 int32 on the packed plan's coded image, 4 locating int32, 5 anchored int32
 {
     // (the locating fill is the int32 cell plus a per-step scan: the int32 kernel's relative costs, no wide classes)
-    return family == 0 ? kSwClassCost : family == 1 ? kSwPkClassCost : family == 3 || family == 4 ? kSwI32dClassCost : kSwPk2ClassCost;
+    return family == 0 ? kSwClassCost : family == 1 ? kSwPkClassCost : family >= 3 ? kSwI32dClassCost : kSwPk2ClassCost;
 }
 
 // Lane time a pair costs under tiling (class ci, G): steps * C * 64 / floor(64 / G) padded cells (the
@@ -209,9 +209,13 @@ struct Bucket {
 
 struct agx_sw_batch {
     agx_ctx *ctx = nullptr; // retained
-    int family = 0;         // 0 int32, 1 packed signed, 2 packed biased, 3 int32 on the packed plan's coded image, 4 locating int32
+    int family = 0;         // 0 int32, 1 packed signed, 2 packed biased, 3 int32 on the packed plan's coded image, 4 locating int32, 5 anchored int32
     // align batches (agx_sw_batch_create_align): 0 = a score-only batch, else AGX_SW_ALIGN_ENDS / _SPANS
     int align = 0;
+    int mode = 0; // AGX_SW_MODE_*: anything but LOCAL runs the anchored fill (agx_sw_anch_kernel.hip)
+    // modes other than LOCAL: pairs with an empty side whose score is not the zero the device array holds for them
+    std::vector<int64_t> fix_pair;
+    std::vector<int32_t> fix_score;
     agx_sw_scoring scoring{};
     DevBuf ends;        // per pair: row << kSwLocColBits | column of the end cell, written by the locating fill
     PinBuf ends_stage;  // its page-locked landing block
@@ -241,7 +245,7 @@ struct agx_sw_batch {
 
 namespace {
 int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matrix *matrix, const uint8_t *bases,
-                 const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_batch **out, bool defer = false, int align = 0);
+                 const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_batch **out, bool defer = false, int align = 0, int mode = 0);
 int finish_create(agx_sw_batch *b);
 void drop_pending(agx_sw_batch *b);
 }
@@ -480,7 +484,7 @@ int launch_device_plan(agx_ctx *ctx, DevPlan &dp, agx_sw_batch *b, uint32_t n_pa
 }
 
 int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matrix *matrix, const uint8_t *bases,
-                 const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_batch **out, bool defer, int align)
+                 const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_batch **out, bool defer, int align, int mode)
 {
     if (!out) {
         agx_set_error("agx_sw_batch_create: out is NULL");
@@ -674,7 +678,7 @@ int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matri
     // one pair of a lane group at a time (agx_sw_i32d_kernel.hip: 7.5 instead of 8.5 instructions per cell), wherever the
     // coded match exists: delta and mismatch + |gf| must be bytes, the shorter sides within the packed plan's 2560 columns.
     if (family == 0 && !matrix && longest_short <= (uint32_t)kSwPackedMaxShort && prm.delta < 128 && prm.hd >= prm.delta && !agx_tune("AGX_SW_I32_CLASSIC")) family = 3;
-    if (align) family = 4; // the locating fill: int32 state on the byte image, one pair per lane group
+    if (align) family = mode ? 5 : 4; // the locating / anchored fill: int32 state on the byte image, one pair per lane group
     if (family == 2 && !((int64_t)bias + ((int64_t)longest_short + 1) * sc.match - prm.gf < 0x7c00)) family = 1;
     // ... and its rising-offset variant adds (steps + 2) |ge| on top, steps <= longest longer side + 63
     int rising = family == 2 &&
@@ -731,9 +735,11 @@ int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matri
         if (family == 3) agx_sw_i32d_preload();
         if (family == 0 && !matrix) agx_sw_i32_preload();
         if (family == 4) agx_sw_loc_preload();
+        if (family == 5) agx_sw_anch_preload();
     }
     b->matrix = matrix != nullptr;
     b->align = align;
+    b->mode = mode;
     b->scoring = sc;
     b->prm = prm;
     b->prm.n_out = (uint32_t)n_pairs + 1u;
@@ -1479,7 +1485,10 @@ int agx_sw_batch_launch(agx_sw_batch *b)
         const SwWave *wv = (const SwWave *)b->waves.p + cl.first_wave;
         int32_t *scores = b->bound ? b->bound : (int32_t *)b->scores.p;
         int r;
-        if (b->align)
+        if (b->family == 5)
+            r = agx_sw_anch_launch_class(cl.C, b->mode != AGX_SW_MODE_EXTEND, b->mode == AGX_SW_MODE_FIT ? 1 : b->mode == AGX_SW_MODE_GLOBAL ? 2 : 0, prm,
+                                         img, (const SwGroup *)b->groups.p, wv, cl.n_waves, scores, (uint32_t *)b->ends.p, st);
+        else if (b->align)
             r = agx_sw_loc_launch_class(cl.C, prm, img, (const SwGroup *)b->groups.p, wv, cl.n_waves, scores, (uint32_t *)b->ends.p, st);
         else if (b->matrix)
             r = agx_sw_mat_launch_class(cl.C, prm, img, (const SwGroup *)b->groups.p, wv, cl.n_waves, scores,
@@ -1543,6 +1552,7 @@ int agx_sw_batch_scores(agx_sw_batch *b, int32_t *scores)
     }
     AGX_HIP(hipStreamSynchronize(b->ctx->stream));
     if (dst != scores) memcpy(scores, dst, bytes);
+    for (size_t k = 0; k < b->fix_pair.size(); ++k) scores[b->fix_pair[k]] = b->fix_score[k];
     return AGX_OK;
 }
 
@@ -1661,6 +1671,41 @@ int agx_sw_score(agx_ctx *ctx, const uint8_t *bases, const uint64_t *off, const 
 int agx_sw_batch_create_align(agx_ctx *ctx, const agx_sw_scoring *scoring, int what, const uint8_t *bases, const uint64_t *off,
                               const uint32_t *len, int64_t n_pairs, agx_sw_batch **out)
 {
+    return agx_sw_batch_create_align_mode(ctx, scoring, AGX_SW_MODE_LOCAL, what, bases, off, len, n_pairs, out);
+}
+
+} // extern "C"
+
+namespace {
+// What a pair with an empty side answers in the modes other than LOCAL (include/agx.h, "Alignment modes"): no cell is
+// filled, the boundary formulas are the answer.  D[0][la] = all of a in one gap; GLOBAL with la = 0 the same for b.
+agx_sw_hit empty_side_hit(int mode, int what, const agx_sw_scoring &sc, uint32_t la, uint32_t lb)
+{
+    agx_sw_hit h{0, -1, -1, -1, -1};
+    const int gap_a = la ? sc.gap_open + (int)la * sc.gap_extend : 0;
+    const int gap_b = lb ? sc.gap_open + (int)lb * sc.gap_extend : 0;
+    if (mode == AGX_SW_MODE_EXTEND) return h; // D[0][0] = 0 is the maximum: nothing consumed, all four stay -1
+    h.a_end = (int32_t)la - 1;
+    if (mode == AGX_SW_MODE_GLOBAL) {
+        h.score = gap_a + gap_b; // (one of them is 0)
+        h.b_end = (int32_t)lb - 1;
+    } else
+        h.score = gap_a; // FIT, EXTEND_QUERY: max_i D[i][la] stands at i = 0 (la = 0: D[i][0] <= 0 = D[0][0]; lb = 0: i = 0 only)
+    if (what == AGX_SW_ALIGN_SPANS) h.a_begin = h.b_begin = 0;
+    return h;
+}
+} // namespace
+
+extern "C" {
+
+int agx_sw_batch_create_align_mode(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int what, const uint8_t *bases,
+                                   const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_batch **out)
+{
+    if (mode < AGX_SW_MODE_LOCAL || mode > AGX_SW_MODE_EXTEND_QUERY) {
+        if (out) *out = nullptr;
+        agx_set_error("agx_sw_batch_create_align_mode: mode = %d is not one of AGX_SW_MODE_LOCAL .. AGX_SW_MODE_EXTEND_QUERY (0..4)", mode);
+        return AGX_E_ARG;
+    }
     if (what != AGX_SW_ALIGN_ENDS && what != AGX_SW_ALIGN_SPANS) {
         if (out) *out = nullptr;
         agx_set_error("agx_sw_batch_create_align: what = %d is neither AGX_SW_ALIGN_ENDS nor AGX_SW_ALIGN_SPANS", what);
@@ -1668,14 +1713,29 @@ int agx_sw_batch_create_align(agx_ctx *ctx, const agx_sw_scoring *scoring, int w
     }
     AGX_GUARD_BEGIN
     agx_sw_batch *b = nullptr;
-    int rc = create_batch(ctx, scoring, nullptr, bases, off, len, n_pairs, &b, false, what);
+    int rc = create_batch(ctx, scoring, nullptr, bases, off, len, n_pairs, &b, false, what, mode);
     if (rc) return rc;
     struct Drop {
         agx_sw_batch *b;
         ~Drop() { agx_sw_batch_destroy(b); } // (create_batch has waited for everything it queued)
     } drop{b};
+    if (mode != AGX_SW_MODE_LOCAL)
+        for (int64_t p = 0; p < n_pairs; ++p) { // the planner skips pairs with an empty side: their answers come from the formulas
+            const uint32_t la = len[2 * p], lb = len[2 * p + 1];
+            if (la && lb) continue;
+            if (la > (uint32_t)AGX_SW_ALIGN_MAX_QUERY_LEN || lb > (uint32_t)AGX_SW_ALIGN_MAX_TARGET_LEN) {
+                agx_set_error("pair %lld: lengths %u x %u exceed the supported %d x %d (query x target of an align batch)", (long long)p, la, lb,
+                              AGX_SW_ALIGN_MAX_QUERY_LEN, AGX_SW_ALIGN_MAX_TARGET_LEN);
+                return AGX_E_LIMIT;
+            }
+            const int32_t v = empty_side_hit(mode, what, b->scoring, la, lb).score;
+            if (ctx && v) {
+                b->fix_pair.push_back(p);
+                b->fix_score.push_back(v);
+            }
+        }
     if (ctx && n_pairs > 0) b->seq_len.assign(len, len + 2 * n_pairs); // agx_sw_batch_hits checks every end cell against them
-    if (ctx && what == AGX_SW_ALIGN_SPANS && n_pairs > 0) {
+    if (ctx && what == AGX_SW_ALIGN_SPANS && n_pairs > 0 && (mode == AGX_SW_MODE_LOCAL || mode == AGX_SW_MODE_FIT)) {
         // the begin pass reads the sequences again, long after this call: a dense copy of the batch's own
         b->seq_off.resize((size_t)n_pairs * 2);
         uint64_t at = 0;
@@ -1724,36 +1784,60 @@ int agx_sw_batch_hits(agx_sw_batch *b, agx_sw_hit *hits)
     AGX_HIP(hipMemcpyAsync(b->ends_stage.p, b->ends.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     AGX_HIP(hipStreamSynchronize(st));
     // end cells, checked against the caller's lengths: a padding cell must never be reported
-    const uint32_t *len = b->seq_len.empty() ? nullptr : b->seq_len.data(); // (the begin pass's own batch has none: checked against the end cell below)
+    const uint32_t *len = b->seq_len.empty() ? nullptr : b->seq_len.data(); // (the begin passes' own batches have none: checked against the end cell below)
+    const int mode = b->mode;
+    const bool spans = b->align == AGX_SW_ALIGN_SPANS;
     std::vector<int64_t> bad((size_t)agx_host_threads(), -1);
     agx_parallel_for(n, 16384, [&](int64_t lo, int64_t hi, int tid) {
         for (int64_t p = lo; p < hi; ++p) {
             agx_sw_hit h{sc[p], -1, -1, -1, -1};
-            if (en[p] != 0xffffffffu) {
-                h.a_end = (int32_t)(en[p] & ((1u << kSwLocColBits) - 1u));
-                h.b_end = (int32_t)(en[p] >> kSwLocColBits);
+            bool ok;
+            if (mode == AGX_SW_MODE_LOCAL) {
+                if (en[p] != 0xffffffffu) {
+                    h.a_end = (int32_t)(en[p] & ((1u << kSwLocColBits) - 1u));
+                    h.b_end = (int32_t)(en[p] >> kSwLocColBits);
+                }
+                const bool located = en[p] != 0xffffffffu;
+                ok = sc[p] >= 0 && located == (sc[p] > 0);
+                if (ok && located && len) ok = (uint32_t)h.a_end < len[2 * p] && (uint32_t)h.b_end < len[2 * p + 1];
+            } else if (len && (len[2 * p] == 0 || len[2 * p + 1] == 0)) {
+                h = empty_side_hit(mode, b->align, b->scoring, len[2 * p], len[2 * p + 1]);
+                ok = sc[p] == 0 && en[p] == 0xffffffffu; // no kernel wrote there
+            } else {
+                // the anchored fill's word: (row + 1) << 12 | (column + 1); 0xffffffff = no kernel wrote the slot
+                h.a_end = (int32_t)(en[p] & ((1u << kSwLocColBits) - 1u)) - 1;
+                h.b_end = (int32_t)(en[p] >> kSwLocColBits) - 1;
+                ok = en[p] != 0xffffffffu;
+                const int64_t la = len ? (int64_t)len[2 * p] : -1, lb = len ? (int64_t)len[2 * p + 1] : -1;
+                if (mode == AGX_SW_MODE_EXTEND) {
+                    ok = ok && sc[p] >= 0 && (sc[p] > 0 ? h.a_end >= 0 && h.b_end >= 0 : h.a_end == -1 && h.b_end == -1);
+                    if (ok && len) ok = h.a_end < la && h.b_end < lb;
+                } else {
+                    ok = ok && h.a_end >= 0 && h.b_end >= -1; // all of a, whatever of b
+                    if (ok && len) ok = h.a_end == la - 1 && (mode == AGX_SW_MODE_GLOBAL ? h.b_end == lb - 1 : h.b_end < lb);
+                }
+                if (ok && spans && !(mode == AGX_SW_MODE_EXTEND && sc[p] == 0)) h.a_begin = h.b_begin = 0; // (FIT: b_begin follows below)
             }
-            const bool located = en[p] != 0xffffffffu;
-            bool ok = sc[p] >= 0 && located == (sc[p] > 0);
-            if (ok && located && len) ok = (uint32_t)h.a_end < len[2 * p] && (uint32_t)h.b_end < len[2 * p + 1];
             if (!ok && bad[(size_t)tid] < 0) bad[(size_t)tid] = p;
             hits[p] = h;
         }
     });
     for (int64_t p : bad)
         if (p >= 0) {
-            agx_set_error("agx_sw_batch_hits: pair %lld: score %d with end cell word 0x%08x is not a cell of its matrix", (long long)p, sc[p], en[p]);
+            agx_set_error("agx_sw_batch_hits: pair %lld (mode %d): score %d with end cell word 0x%08x is not a cell of its matrix", (long long)p, mode, sc[p], en[p]);
             return AGX_E_INTERNAL;
         }
-    if (b->align != AGX_SW_ALIGN_SPANS) return AGX_OK;
+    if (!spans || (mode != AGX_SW_MODE_LOCAL && mode != AGX_SW_MODE_FIT)) return AGX_OK;
+    const bool fit = mode == AGX_SW_MODE_FIT;
 
-    // ---- begin pass: the same fill over the reversed prefixes a[a_end..0], b[b_end..0] of the pairs with a score.  Its end
-    // cell, by the same rule, is the latest begin in b, then in a, of an alignment of that score ending in the end cell
-    // (DESIGN.md has the argument).
+    // ---- begin pass.  LOCAL: the same fill over the reversed prefixes a[a_end..0], b[b_end..0] of the pairs with a score.
+    // Its end cell, by the same rule, is the latest begin in b, then in a, of an alignment of that score ending in the end
+    // cell.  FIT: all of a reversed against b[b_end..0] in mode EXTEND_QUERY -- the smallest reversed end is the latest
+    // begin in b (DESIGN.md has both arguments).
     std::vector<int64_t> pick;
     pick.reserve((size_t)n);
     for (int64_t p = 0; p < n; ++p)
-        if (hits[p].score > 0) pick.push_back(p);
+        if (fit ? hits[p].b_end >= 0 : hits[p].score > 0) pick.push_back(p);
     const int64_t m = (int64_t)pick.size();
     if (m == 0) return AGX_OK;
     std::vector<uint64_t> roff((size_t)m * 2);
@@ -1781,7 +1865,8 @@ int agx_sw_batch_hits(agx_sw_batch *b, agx_sw_hit *hits)
         }
     });
     agx_sw_batch *rb = nullptr;
-    rc = create_batch(b->ctx, &b->scoring, nullptr, rev.data(), roff.data(), rlen.data(), m, &rb, false, AGX_SW_ALIGN_ENDS);
+    rc = create_batch(b->ctx, &b->scoring, nullptr, rev.data(), roff.data(), rlen.data(), m, &rb, false, AGX_SW_ALIGN_ENDS,
+                      fit ? AGX_SW_MODE_EXTEND_QUERY : AGX_SW_MODE_LOCAL);
     if (rc) return rc;
     struct Drop {
         agx_sw_batch *b;
@@ -1798,12 +1883,12 @@ int agx_sw_batch_hits(agx_sw_batch *b, agx_sw_hit *hits)
     for (int64_t k = 0; k < m; ++k) {
         agx_sw_hit &h = hits[pick[(size_t)k]];
         const agx_sw_hit &r = rh[(size_t)k];
-        if (r.score != h.score || r.a_end < 0 || r.a_end > h.a_end || r.b_end < 0 || r.b_end > h.b_end) {
+        if (r.score != h.score || r.a_end < 0 || r.a_end > h.a_end || r.b_end < 0 || r.b_end > h.b_end || (fit && r.a_end != h.a_end)) {
             agx_set_error("agx_sw_batch_hits: pair %lld: the reverse fill from its end cell (a %d, b %d) gives score %d at (a %d, b %d), the forward fill %d",
                           (long long)pick[(size_t)k], h.a_end, h.b_end, r.score, r.a_end, r.b_end, h.score);
             return AGX_E_INTERNAL;
         }
-        h.a_begin = h.a_end - r.a_end;
+        if (!fit) h.a_begin = h.a_end - r.a_end;
         h.b_begin = h.b_end - r.b_end;
     }
     return AGX_OK;
@@ -1813,8 +1898,14 @@ int agx_sw_batch_hits(agx_sw_batch *b, agx_sw_hit *hits)
 int agx_sw_align(agx_ctx *ctx, const agx_sw_scoring *scoring, int what, const uint8_t *bases, const uint64_t *off,
                  const uint32_t *len, int64_t n_pairs, agx_sw_hit *hits)
 {
+    return agx_sw_align_mode(ctx, scoring, AGX_SW_MODE_LOCAL, what, bases, off, len, n_pairs, hits);
+}
+
+int agx_sw_align_mode(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int what, const uint8_t *bases, const uint64_t *off,
+                      const uint32_t *len, int64_t n_pairs, agx_sw_hit *hits)
+{
     agx_sw_batch *b = nullptr;
-    int rc = agx_sw_batch_create_align(ctx, scoring, what, bases, off, len, n_pairs, &b);
+    int rc = agx_sw_batch_create_align_mode(ctx, scoring, mode, what, bases, off, len, n_pairs, &b);
     if (rc) return rc;
     rc = agx_sw_batch_launch(b);
     if (!rc) rc = agx_sw_batch_hits(b, hits);

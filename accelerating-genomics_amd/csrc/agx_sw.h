@@ -118,6 +118,12 @@ constexpr int kSwLocColBits = 12;
 int agx_sw_loc_launch_class(int cols_per_lane, const SwParams &prm, const uint32_t *img, const SwGroup *groups, const SwWave *waves,
                             uint32_t n_waves, int32_t *scores, uint32_t *ends, hipStream_t s);
 void agx_sw_loc_preload();
+// the anchored fill of the align modes GLOBAL / FIT / EXTEND / EXTEND_QUERY (agx_sw_anch_kernel.hip): the locating fill's plan,
+// no zero floor, gap-initialised boundaries.  capture 0 = the first maximum anywhere (EXTEND), 1 = in the query's last column;
+// flags: 1 = free target start (FIT), 2 = report the corner cell (GLOBAL).  ends[out] = (row + 1) << 12 | (column + 1).
+int agx_sw_anch_launch_class(int cols_per_lane, int capture, int flags, const SwParams &prm, const uint32_t *img, const SwGroup *groups,
+                             const SwWave *waves, uint32_t n_waves, int32_t *scores, uint32_t *ends, hipStream_t s);
+void agx_sw_anch_preload();
 
 // ---- device-side planning (agx_sw_plan_kernel.hip): the O(pairs) passes of the planner as kernels
 constexpr uint32_t kSwPlanEmptyKey = 1u << 27;           // sort key of a pair with an empty side: behind every bucket

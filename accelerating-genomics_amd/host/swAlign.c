@@ -1,5 +1,6 @@
 /*
- * swAlign <file_path>: where the best local alignment of every pair ends and begins.
+ * swAlign <file_path> [local|global|fit|extend|extend-query]: where the best alignment of every pair ends and begins
+ * (default: local; the other modes are include/agx.h's "Alignment modes").
  * Reads the Smith-Waterman input format of `antidiagonalSmithWaterman` (header = number of sequence lines, pair p =
  * lines 2p and 2p+1, the newline kept as a symbol) through agx_sw_reader_* and prints one line per pair, in file order:
  *     score a_begin a_end b_begin b_end
@@ -16,8 +17,12 @@
 
 int main(int argc, char *argv[])
 {
-    if (argc != 2) {
-        fprintf(stderr, "Usage: %s <file_path>\n", argv[0]);
+    static const char *const words[] = {"local", "global", "fit", "extend", "extend-query"}; /* AGX_SW_MODE_* 0..4 */
+    int mode = argc == 2 ? AGX_SW_MODE_LOCAL : -1;
+    for (int k = 0; argc == 3 && k < 5; k++)
+        if (!strcmp(argv[2], words[k])) mode = k;
+    if (mode < 0) {
+        fprintf(stderr, "Usage: %s <file_path> [local|global|fit|extend|extend-query]\n", argv[0]);
         return 1;
     }
     const char *cp = getenv("AGX_CLI_CHUNK_PAIRS");
@@ -46,7 +51,7 @@ int main(int argc, char *argv[])
                 fprintf(stderr, "swAlign: %s\n", agx_last_error());
                 status = EXIT_FAILURE;
             }
-            if (!status && agx_sw_align(ctx, NULL, AGX_SW_ALIGN_SPANS, t->bases, t->off, t->len, t->n_pairs, hits) != AGX_OK) {
+            if (!status && agx_sw_align_mode(ctx, NULL, mode, AGX_SW_ALIGN_SPANS, t->bases, t->off, t->len, t->n_pairs, hits) != AGX_OK) {
                 fprintf(stderr, "swAlign: %s\n", agx_last_error());
                 status = EXIT_FAILURE;
             }

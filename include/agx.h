@@ -215,6 +215,42 @@ int agx_sw_batch_hits(agx_sw_batch *b, agx_sw_hit *hits);
 int agx_sw_align(agx_ctx *ctx, const agx_sw_scoring *scoring, int what, const uint8_t *bases, const uint64_t *off,
                  const uint32_t *len, int64_t n_pairs, agx_sw_hit *hits);
 
+/*
+ * Alignment modes: the same fill with other boundaries -- global, fit and extension alignment, score and coordinates,
+ * still without a traceback.  a = sequence 2p (query), la = len(a); b = sequence 2p+1 (target), lb = len(b); the first
+ * cell of a gap costs gap_open + gap_extend, every further cell gap_extend.
+ * D[i][j], 0 <= i <= lb, 0 <= j <= la, is the best score of an alignment of a[0..j) with b[s..i); it may end in any
+ * state (match, gap in a, gap in b).  D[0][0] = 0; D[0][j] = gap_open + j gap_extend for j > 0; the left column D[i][0],
+ * i > 0, is gap_open + i gap_extend when the start is pinned (s = 0) and 0 when the target start is free (any s <= i).
+ * There is NO zero floor: scores may be negative.
+ * Results are the caller's 0-based inclusive coordinates, a_end = j - 1, b_end = i - 1; -1 = nothing of that sequence
+ * consumed; an empty range is begin 0, end -1.
+ *   mode                  start              score                             end cell
+ *   AGX_SW_MODE_LOCAL     --                 exactly agx_sw_batch_create_align's
+ *   AGX_SW_MODE_GLOBAL    pinned             D[lb][la]                         (lb-1, la-1)
+ *   AGX_SW_MODE_FIT       target start free  max_i D[i][la], i = 0..lb         a_end = la-1, b_end = smallest such i, minus 1
+ *   AGX_SW_MODE_EXTEND    pinned             max_{i,j} D[i][j] incl. D[0][0],  smallest i, then smallest j among the maxima;
+ *                                            so >= 0                           score 0: a_end = b_end = -1
+ *   AGX_SW_MODE_EXTEND_QUERY pinned          max_i D[i][la]                    a_end = la-1, b_end = smallest such i, minus 1
+ * AGX_SW_ALIGN_ENDS leaves the begins at -1.  AGX_SW_ALIGN_SPANS fills them: GLOBAL, EXTEND, EXTEND_QUERY begin at
+ * a_begin = b_begin = 0 (EXTEND with score 0 keeps -1 for all four, as in the local rule; no second fill).  FIT:
+ * a_begin = 0 and b_begin = the LATEST start s among the alignments of that score that consume b through b_end (0 when
+ * b_end = -1), found by a second fill -- reversed a against reversed b[0..b_end] in mode EXTEND_QUERY, whose score must
+ * equal the forward one (AGX_E_INTERNAL naming the pair otherwise).
+ * Pairs with an empty side have their answers from the formulas above (GLOBAL with la = 0: gap_open + lb gap_extend).
+ * Limits are those of align batches; agx_sw_batch_scores returns the mode's score.  A mode outside 0..4: AGX_E_ARG.
+ */
+#define AGX_SW_MODE_LOCAL 0
+#define AGX_SW_MODE_GLOBAL 1
+#define AGX_SW_MODE_FIT 2
+#define AGX_SW_MODE_EXTEND 3
+#define AGX_SW_MODE_EXTEND_QUERY 4
+/* agx_sw_batch_create_align / agx_sw_align with a mode (those two mean AGX_SW_MODE_LOCAL).  ctx may be NULL: plan only. */
+int agx_sw_batch_create_align_mode(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int what, const uint8_t *bases,
+                                   const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_batch **out);
+int agx_sw_align_mode(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int what, const uint8_t *bases, const uint64_t *off,
+                      const uint32_t *len, int64_t n_pairs, agx_sw_hit *hits);
+
 /* One-shot: create + launch + scores + destroy. */
 int agx_sw_score(agx_ctx *ctx, const uint8_t *bases, const uint64_t *off, const uint32_t *len, int64_t n_pairs,
                  int32_t *scores);
