@@ -40,6 +40,7 @@ SYMBOLS = [
     "agx_ctx_timer_start", "agx_ctx_timer_stop", "agx_ctx_timer_mark", "agx_ctx_timer_elapsed",
     "agx_sw_batch_create", "agx_sw_batch_create_scored", "agx_sw_batch_create_matrix", "agx_sw_batch_launch", "agx_sw_batch_scores", "agx_sw_batch_bind_scores", "agx_sw_batch_info", "agx_sw_batch_destroy",
     "agx_sw_batch_create_align", "agx_sw_batch_hits", "agx_sw_align", "agx_sw_batch_create_align_mode", "agx_sw_align_mode",
+    "agx_sw_batch_create_align_matrix", "agx_sw_align_matrix",
     "agx_sw_score", "agx_sw_score_multi", "agx_sw_score_devices", "agx_sw_shard_cuts",
     "agx_phmm_batch_create", "agx_phmm_batch_launch", "agx_phmm_batch_results", "agx_phmm_batch_bind_results", "agx_phmm_batch_info",
     "agx_phmm_batch_destroy", "agx_phmm_forward", "agx_phmm_forward_multi", "agx_phmm_forward_devices", "agx_phmm_shard_cuts",
@@ -161,6 +162,9 @@ def lib():
         l.agx_sw_batch_create_align_mode.argtypes = [C.c_void_p, C.POINTER(SwScoring), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                                      C.c_int64, C.POINTER(C.c_void_p)]
         l.agx_sw_align_mode.argtypes = [C.c_void_p, C.POINTER(SwScoring), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        l.agx_sw_batch_create_align_matrix.argtypes = [C.c_void_p, C.POINTER(SwMatrix), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                       C.c_int64, C.POINTER(C.c_void_p)]
+        l.agx_sw_align_matrix.argtypes = [C.c_void_p, C.POINTER(SwMatrix), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
         l.agx_sw_score.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
         l.agx_sw_score_multi.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
         l.agx_sw_score_devices.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
@@ -267,10 +271,15 @@ class Context:
     def sw_batch(self, b, scoring=None, matrix=None, align=0, mode=SW_MODE_LOCAL) -> "SwBatch":
         return SwBatch(self, b, scoring, matrix, align, mode)
 
-    def sw_align(self, b, what=SW_ALIGN_SPANS, scoring=None, mode=SW_MODE_LOCAL) -> np.ndarray:
+    def sw_align(self, b, what=SW_ALIGN_SPANS, scoring=None, mode=SW_MODE_LOCAL, matrix=None) -> np.ndarray:
         """b: synth.SWBatch -> SwHit records (score, end cell, and with SW_ALIGN_SPANS the begin cell), one-shot.
-        mode: SW_MODE_LOCAL / _GLOBAL / _FIT / _EXTEND / _EXTEND_QUERY."""
+        mode: SW_MODE_LOCAL / _GLOBAL / _FIT / _EXTEND / _EXTEND_QUERY; matrix: an SwMatrix instead of scoring."""
         out = np.empty(b.n_pairs, SwHit)
+        if matrix is not None:
+            if scoring is not None:
+                raise AgxError(E_ARG, "pass either scoring= or matrix=, not both")
+            _check(lib().agx_sw_align_matrix(self._h, C.byref(matrix), mode, what, _ptr(b.bases), _ptr(b.off), _ptr(b.len), b.n_pairs, _ptr(out)))
+            return out
         sc = C.byref(SwScoring(*scoring)) if scoring is not None else None
         if mode == SW_MODE_LOCAL:
             _check(lib().agx_sw_align(self._h, sc, what, _ptr(b.bases), _ptr(b.off), _ptr(b.len), b.n_pairs, _ptr(out)))
@@ -300,16 +309,20 @@ class SwBatch:
 
     def __init__(self, ctx, b, scoring=None, matrix=None, align=0, mode=SW_MODE_LOCAL):
         """scoring: None (the reference's +1/-1/-3/-1) or (match, mismatch, gap_open, gap_extend);
-        matrix: an SwMatrix instead; align: SW_ALIGN_ENDS / SW_ALIGN_SPANS for a batch that also answers hits();
+        matrix: an SwMatrix instead (score-only and align batches alike); align: SW_ALIGN_ENDS / SW_ALIGN_SPANS for a batch that also answers hits();
         mode: SW_MODE_* of an align batch (local, global, fit, extension)."""
         self.ctx = ctx
         self.n_pairs = b.n_pairs
         self._h = C.c_void_p()
         if mode != SW_MODE_LOCAL and not align:
             raise AgxError(E_ARG, "mode= applies to align batches: pass align=SW_ALIGN_ENDS or SW_ALIGN_SPANS")
+        if align and matrix is not None:
+            if scoring is not None:
+                raise AgxError(E_ARG, "an align batch takes either scoring= or matrix=, not both")
+            _check(lib().agx_sw_batch_create_align_matrix(ctx._h if ctx else None, C.byref(matrix), mode, align, _ptr(b.bases), _ptr(b.off),
+                                                          _ptr(b.len), b.n_pairs, C.byref(self._h)))
+            return
         if align:
-            if matrix is not None:
-                raise AgxError(E_ARG, "align batches take match/mismatch scoring, not a substitution matrix")
             sc = C.byref(SwScoring(*scoring)) if scoring is not None else None
             if mode == SW_MODE_LOCAL:
                 _check(lib().agx_sw_batch_create_align(ctx._h if ctx else None, sc, align, _ptr(b.bases), _ptr(b.off), _ptr(b.len),

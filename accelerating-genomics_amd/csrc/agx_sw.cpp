@@ -231,6 +231,7 @@ struct agx_sw_batch {
     PinBuf out_stage; // page-locked landing block of the scores, taken at create: agx_sw_batch_scores allocates nothing
                       // (a first hipHostMalloc costs milliseconds, and hipvers' timed window is launch -> scores)
     bool matrix = false;
+    agx_sw_matrix mat{}; // ... and the caller's matrix itself: an align batch's begin pass creates its own batch from it
     std::vector<ClassLaunch> launches;
     agx_sw_info info{};
     // A batch created without the closing wait (the pieces of agx_sw_score): its upload, planning and pack kernels may
@@ -734,10 +735,11 @@ int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matri
         if (family == 2) agx_sw_pk2_preload();
         if (family == 3) agx_sw_i32d_preload();
         if (family == 0 && !matrix) agx_sw_i32_preload();
-        if (family == 4) agx_sw_loc_preload();
-        if (family == 5) agx_sw_anch_preload();
+        if (family == 4) (matrix ? agx_sw_loc_mat_preload : agx_sw_loc_preload)();
+        if (family == 5) (matrix ? agx_sw_anch_mat_preload : agx_sw_anch_preload)();
     }
     b->matrix = matrix != nullptr;
+    if (matrix) b->mat = *matrix;
     b->align = align;
     b->mode = mode;
     b->scoring = sc;
@@ -1484,10 +1486,17 @@ int agx_sw_batch_launch(agx_sw_batch *b)
         const uint32_t *img = (const uint32_t *)b->img.p;
         const SwWave *wv = (const SwWave *)b->waves.p + cl.first_wave;
         int32_t *scores = b->bound ? b->bound : (int32_t *)b->scores.p;
+        const int anch_capture = b->mode != AGX_SW_MODE_EXTEND, anch_flags = b->mode == AGX_SW_MODE_FIT ? 1 : b->mode == AGX_SW_MODE_GLOBAL ? 2 : 0;
         int r;
-        if (b->family == 5)
-            r = agx_sw_anch_launch_class(cl.C, b->mode != AGX_SW_MODE_EXTEND, b->mode == AGX_SW_MODE_FIT ? 1 : b->mode == AGX_SW_MODE_GLOBAL ? 2 : 0, prm,
-                                         img, (const SwGroup *)b->groups.p, wv, cl.n_waves, scores, (uint32_t *)b->ends.p, st);
+        if (b->family == 5 && b->matrix)
+            r = agx_sw_anch_mat_launch_class(cl.C, anch_capture, anch_flags, prm, img, (const SwGroup *)b->groups.p, wv, cl.n_waves, scores,
+                                             (uint32_t *)b->ends.p, (const int16_t *)b->table.p, st);
+        else if (b->family == 5)
+            r = agx_sw_anch_launch_class(cl.C, anch_capture, anch_flags, prm, img, (const SwGroup *)b->groups.p, wv, cl.n_waves, scores,
+                                         (uint32_t *)b->ends.p, st);
+        else if (b->align && b->matrix)
+            r = agx_sw_loc_mat_launch_class(cl.C, prm, img, (const SwGroup *)b->groups.p, wv, cl.n_waves, scores, (uint32_t *)b->ends.p,
+                                            (const int16_t *)b->table.p, st);
         else if (b->align)
             r = agx_sw_loc_launch_class(cl.C, prm, img, (const SwGroup *)b->groups.p, wv, cl.n_waves, scores, (uint32_t *)b->ends.p, st);
         else if (b->matrix)
@@ -1694,26 +1703,24 @@ agx_sw_hit empty_side_hit(int mode, int what, const agx_sw_scoring &sc, uint32_t
     if (what == AGX_SW_ALIGN_SPANS) h.a_begin = h.b_begin = 0;
     return h;
 }
-} // namespace
 
-extern "C" {
-
-int agx_sw_batch_create_align_mode(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int what, const uint8_t *bases,
-                                   const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_batch **out)
+// an align batch under match/mismatch scoring (matrix == NULL) or under a substitution matrix (scoring unused)
+int create_align(const char *who, agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matrix *matrix, int mode, int what,
+                 const uint8_t *bases, const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_batch **out)
 {
     if (mode < AGX_SW_MODE_LOCAL || mode > AGX_SW_MODE_EXTEND_QUERY) {
         if (out) *out = nullptr;
-        agx_set_error("agx_sw_batch_create_align_mode: mode = %d is not one of AGX_SW_MODE_LOCAL .. AGX_SW_MODE_EXTEND_QUERY (0..4)", mode);
+        agx_set_error("%s%s: mode = %d is not one of AGX_SW_MODE_LOCAL .. AGX_SW_MODE_EXTEND_QUERY (0..4)", who, matrix ? "" : "_mode", mode);
         return AGX_E_ARG;
     }
     if (what != AGX_SW_ALIGN_ENDS && what != AGX_SW_ALIGN_SPANS) {
         if (out) *out = nullptr;
-        agx_set_error("agx_sw_batch_create_align: what = %d is neither AGX_SW_ALIGN_ENDS nor AGX_SW_ALIGN_SPANS", what);
+        agx_set_error("%s: what = %d is neither AGX_SW_ALIGN_ENDS nor AGX_SW_ALIGN_SPANS", who, what);
         return AGX_E_ARG;
     }
     AGX_GUARD_BEGIN
     agx_sw_batch *b = nullptr;
-    int rc = create_batch(ctx, scoring, nullptr, bases, off, len, n_pairs, &b, false, what, mode);
+    int rc = create_batch(ctx, scoring, matrix, bases, off, len, n_pairs, &b, false, what, mode);
     if (rc) return rc;
     struct Drop {
         agx_sw_batch *b;
@@ -1752,7 +1759,27 @@ int agx_sw_batch_create_align_mode(agx_ctx *ctx, const agx_sw_scoring *scoring, 
     drop.b = nullptr;
     *out = b;
     return AGX_OK;
-    AGX_GUARD_END("agx_sw_batch_create_align")
+    AGX_GUARD_END(who)
+}
+} // namespace
+
+extern "C" {
+
+int agx_sw_batch_create_align_mode(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int what, const uint8_t *bases,
+                                   const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_batch **out)
+{
+    return create_align("agx_sw_batch_create_align", ctx, scoring, nullptr, mode, what, bases, off, len, n_pairs, out);
+}
+
+int agx_sw_batch_create_align_matrix(agx_ctx *ctx, const agx_sw_matrix *matrix, int mode, int what, const uint8_t *bases,
+                                     const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_batch **out)
+{
+    if (!matrix) {
+        if (out) *out = nullptr;
+        agx_set_error("agx_sw_batch_create_align_matrix: matrix is NULL");
+        return AGX_E_ARG;
+    }
+    return create_align("agx_sw_batch_create_align_matrix", ctx, nullptr, matrix, mode, what, bases, off, len, n_pairs, out);
 }
 
 int agx_sw_batch_hits(agx_sw_batch *b, agx_sw_hit *hits)
@@ -1865,7 +1892,8 @@ int agx_sw_batch_hits(agx_sw_batch *b, agx_sw_hit *hits)
         }
     });
     agx_sw_batch *rb = nullptr;
-    rc = create_batch(b->ctx, &b->scoring, nullptr, rev.data(), roff.data(), rlen.data(), m, &rb, false, AGX_SW_ALIGN_ENDS,
+    // (a substitution matrix is symmetric and a stays across the lanes: the reversed problem runs under the same matrix)
+    rc = create_batch(b->ctx, &b->scoring, b->matrix ? &b->mat : nullptr, rev.data(), roff.data(), rlen.data(), m, &rb, false, AGX_SW_ALIGN_ENDS,
                       fit ? AGX_SW_MODE_EXTEND_QUERY : AGX_SW_MODE_LOCAL);
     if (rc) return rc;
     struct Drop {
@@ -1901,17 +1929,35 @@ int agx_sw_align(agx_ctx *ctx, const agx_sw_scoring *scoring, int what, const ui
     return agx_sw_align_mode(ctx, scoring, AGX_SW_MODE_LOCAL, what, bases, off, len, n_pairs, hits);
 }
 
-int agx_sw_align_mode(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int what, const uint8_t *bases, const uint64_t *off,
-                      const uint32_t *len, int64_t n_pairs, agx_sw_hit *hits)
+} // extern "C"
+
+namespace {
+int align_once(agx_sw_batch *b, agx_sw_hit *hits) // launch + hits + destroy
 {
-    agx_sw_batch *b = nullptr;
-    int rc = agx_sw_batch_create_align_mode(ctx, scoring, mode, what, bases, off, len, n_pairs, &b);
-    if (rc) return rc;
-    rc = agx_sw_batch_launch(b);
+    int rc = agx_sw_batch_launch(b);
     if (!rc) rc = agx_sw_batch_hits(b, hits);
     if (rc && b->ctx) (void)hipStreamSynchronize(b->ctx->stream); // the blocks go back to the pools: nothing may still run on them
     agx_sw_batch_destroy(b);
     return rc;
+}
+} // namespace
+
+extern "C" {
+
+int agx_sw_align_mode(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int what, const uint8_t *bases, const uint64_t *off,
+                      const uint32_t *len, int64_t n_pairs, agx_sw_hit *hits)
+{
+    agx_sw_batch *b = nullptr;
+    const int rc = agx_sw_batch_create_align_mode(ctx, scoring, mode, what, bases, off, len, n_pairs, &b);
+    return rc ? rc : align_once(b, hits);
+}
+
+int agx_sw_align_matrix(agx_ctx *ctx, const agx_sw_matrix *matrix, int mode, int what, const uint8_t *bases, const uint64_t *off,
+                        const uint32_t *len, int64_t n_pairs, agx_sw_hit *hits)
+{
+    agx_sw_batch *b = nullptr;
+    const int rc = agx_sw_batch_create_align_matrix(ctx, matrix, mode, what, bases, off, len, n_pairs, &b);
+    return rc ? rc : align_once(b, hits);
 }
 
 int agx_sw_shard_cuts(const uint32_t *len, int64_t n_pairs, int n_shards, int64_t *cut)

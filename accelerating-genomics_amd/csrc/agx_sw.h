@@ -124,6 +124,14 @@ void agx_sw_loc_preload();
 int agx_sw_anch_launch_class(int cols_per_lane, int capture, int flags, const SwParams &prm, const uint32_t *img, const SwGroup *groups,
                              const SwWave *waves, uint32_t n_waves, int32_t *scores, uint32_t *ends, hipStream_t s);
 void agx_sw_anch_preload();
+// the two align fills under a substitution matrix (agx_sw_loc_mat_kernel.hip, agx_sw_anch_mat_kernel.hip): the
+// same records, plans and ends[] words on the matrix image of agx_sw_mat_launch_class (symbol numbers, 0 = padding) with its table
+int agx_sw_loc_mat_launch_class(int cols_per_lane, const SwParams &prm, const uint32_t *img, const SwGroup *groups, const SwWave *waves,
+                                uint32_t n_waves, int32_t *scores, uint32_t *ends, const int16_t *table, hipStream_t s);
+void agx_sw_loc_mat_preload();
+int agx_sw_anch_mat_launch_class(int cols_per_lane, int capture, int flags, const SwParams &prm, const uint32_t *img, const SwGroup *groups,
+                                 const SwWave *waves, uint32_t n_waves, int32_t *scores, uint32_t *ends, const int16_t *table, hipStream_t s);
+void agx_sw_anch_mat_preload();
 
 // ---- device-side planning (agx_sw_plan_kernel.hip): the O(pairs) passes of the planner as kernels
 constexpr uint32_t kSwPlanEmptyKey = 1u << 27;           // sort key of a pair with an empty side: behind every bucket

@@ -1,0 +1,46 @@
+// Substitution-matrix build of the anchored fill (agx_sw_batch_create_align_matrix, modes GLOBAL / FIT / EXTEND /
+// EXTEND_QUERY): the body of agx_sw_anch_kernel.inc with its MAT flag, the table in LDS.  A translation
+// unit of its own, so the match/mismatch code object is the one it was.
+#include "agx_sw_anch_kernel.inc"
+
+template <int C, bool COL>
+__global__ void __launch_bounds__(256) sw_fill_anch_mat(const SwParams prm, const int flags, const uint32_t *__restrict__ img,
+                                                        const SwGroup *__restrict__ groups, const SwWave *__restrict__ waves, uint32_t n_waves,
+                                                        int32_t *__restrict__ scores, uint32_t *__restrict__ ends,
+                                                        const int16_t *__restrict__ table)
+{
+    __shared__ int16_t sub[kSwMatDim * kSwMatDim];
+    for (int k = threadIdx.x; k < kSwMatDim * kSwMatDim; k += 256) sub[k] = table[k];
+    __syncthreads();
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * 4u + (threadIdx.x >> 6));
+    if (wave >= n_waves) return;
+    anch_body<C, COL, true>(prm, flags, img, groups, waves[wave], scores, ends, sub);
+}
+
+} // namespace
+
+// capture: 0 = ANY (EXTEND), 1 = COL; flags: 1 = free target start (FIT), 2 = report the corner (GLOBAL)
+int agx_sw_anch_mat_launch_class(int cols_per_lane, int capture, int flags, const SwParams &prm, const uint32_t *img, const SwGroup *groups,
+                                 const SwWave *waves, uint32_t n_waves, int32_t *scores, uint32_t *ends, const int16_t *table, hipStream_t s)
+{
+    if (n_waves == 0) return 0;
+    const uint32_t blocks = (n_waves + 3) / 4;
+    switch (cols_per_lane) {
+#define AGX_SW_CASE(CC)                                                                                                                                     \
+    case CC:                                                                                                                                                \
+        if (capture)                                                                                                                                        \
+            hipLaunchKernelGGL((sw_fill_anch_mat<CC, true>), dim3(blocks), dim3(256), 0, s, prm, flags, img, groups, waves, n_waves, scores, ends, table);  \
+        else                                                                                                                                                \
+            hipLaunchKernelGGL((sw_fill_anch_mat<CC, false>), dim3(blocks), dim3(256), 0, s, prm, flags, img, groups, waves, n_waves, scores, ends, table); \
+        return hipGetLastError() == hipSuccess ? 0 : -1;
+        AGX_SW_FOR_EACH_CLASS(AGX_SW_CASE)
+#undef AGX_SW_CASE
+    default: return -2;
+    }
+}
+
+void agx_sw_anch_mat_preload()
+{
+    hipFuncAttributes a;
+    (void)hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&sw_fill_anch_mat<38, true>));
+}

@@ -1,6 +1,10 @@
 /*
  * swAlign <file_path> [local|global|fit|extend|extend-query]: where the best alignment of every pair ends and begins
  * (default: local; the other modes are include/agx.h's "Alignment modes").
+ * swAlign <file_path> <mode> <matrix_file> [gap_open gap_extend]: the same under a substitution matrix (gaps default to
+ * -11 -1).  The matrix file is the usual text layout: '#' comment lines, one line of symbols, then one row per symbol
+ * holding the symbol followed by its integers; at most 32 symbols, letters in either case, the matrix symmetric.  With a
+ * matrix the trailing "\n" or "\r\n" of every line is stripped before aligning: a newline is not a residue.
  * Reads the Smith-Waterman input format of `antidiagonalSmithWaterman` (header = number of sequence lines, pair p =
  * lines 2p and 2p+1, the newline kept as a symbol) through agx_sw_reader_* and prints one line per pair, in file order:
  *     score a_begin a_end b_begin b_end
@@ -13,17 +17,123 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <ctype.h>
+
 #include "agx.h"
+
+/* Reads a substitution matrix in the usual text layout into m (gaps are the caller's).  Returns 0, or -1 with a message in err. */
+static int read_matrix(const char *path, agx_sw_matrix *m, char *err, size_t err_len)
+{
+    FILE *f = fopen(path, "r");
+    if (!f) {
+        snprintf(err, err_len, "cannot open matrix file %s", path);
+        return -1;
+    }
+    char line[4096];
+    int n = 0, rows = 0, line_no = 0, rc = 0;
+    unsigned char seen[AGX_SW_MATRIX_MAX_SYMBOLS] = {0};
+    memset(m->code, 0xff, sizeof m->code);
+    memset(m->score, 0, sizeof m->score);
+    while (!rc && fgets(line, sizeof line, f)) {
+        line_no++;
+        char *p = line;
+        while (isspace((unsigned char)*p)) p++;
+        if (*p == '#' || *p == 0) continue;
+        if (n == 0) { /* the line of symbols: single characters separated by blanks */
+            while (*p && !rc) {
+                if (p[1] && !isspace((unsigned char)p[1])) {
+                    snprintf(err, err_len, "%s:%d: the line of symbols holds a word of more than one character", path, line_no);
+                    rc = -1;
+                } else if (n == AGX_SW_MATRIX_MAX_SYMBOLS) {
+                    snprintf(err, err_len, "%s:%d: more than %d symbols", path, line_no, AGX_SW_MATRIX_MAX_SYMBOLS);
+                    rc = -1;
+                } else if (m->code[(unsigned char)*p] != 0xff) {
+                    snprintf(err, err_len, "%s:%d: symbol '%c' appears twice", path, line_no, *p);
+                    rc = -1;
+                } else {
+                    m->code[tolower((unsigned char)*p)] = m->code[toupper((unsigned char)*p)] = (uint8_t)n;
+                    n++;
+                    p++;
+                    while (isspace((unsigned char)*p)) p++;
+                }
+            }
+            continue;
+        }
+        /* a row: its symbol, then n integers */
+        const int a = (p[1] == 0 || isspace((unsigned char)p[1])) ? m->code[(unsigned char)*p] : 0xff;
+        if (a == 0xff || seen[a]) {
+            snprintf(err, err_len, "%s:%d: the row does not begin with a symbol of the first line that has no row yet", path, line_no);
+            rc = -1;
+            break;
+        }
+        seen[a] = 1;
+        rows++;
+        p++;
+        for (int c = 0; c < n && !rc; c++) {
+            char *end;
+            const long v = strtol(p, &end, 10);
+            if (end == p || v < -128 || v > 127) {
+                snprintf(err, err_len, "%s:%d: row '%c' needs %d integers in -128..127", path, line_no, line[0], n);
+                rc = -1;
+            }
+            m->score[a][c] = (int8_t)v;
+            p = end;
+        }
+        while (!rc && isspace((unsigned char)*p)) p++;
+        if (!rc && *p) {
+            snprintf(err, err_len, "%s:%d: more than %d entries in the row", path, line_no, n);
+            rc = -1;
+        }
+    }
+    fclose(f);
+    if (!rc && (n == 0 || rows != n)) {
+        snprintf(err, err_len, "%s: %d symbols but %d rows", path, n, rows);
+        rc = -1;
+    }
+    for (int a = 0; !rc && a < n; a++)
+        for (int c = 0; !rc && c < a; c++)
+            if (m->score[a][c] != m->score[c][a]) {
+                snprintf(err, err_len, "%s: the matrix is not symmetric at (%d, %d): %d against %d", path, a, c, m->score[a][c], m->score[c][a]);
+                rc = -1;
+            }
+    m->n_symbols = n;
+    return rc;
+}
 
 int main(int argc, char *argv[])
 {
     static const char *const words[] = {"local", "global", "fit", "extend", "extend-query"}; /* AGX_SW_MODE_* 0..4 */
     int mode = argc == 2 ? AGX_SW_MODE_LOCAL : -1;
-    for (int k = 0; argc == 3 && k < 5; k++)
+    for (int k = 0; (argc == 3 || argc == 4 || argc == 6) && k < 5; k++)
         if (!strcmp(argv[2], words[k])) mode = k;
     if (mode < 0) {
-        fprintf(stderr, "Usage: %s <file_path> [local|global|fit|extend|extend-query]\n", argv[0]);
+        fprintf(stderr,
+                "Usage: %s <file_path> [local|global|fit|extend|extend-query]\n"
+                "       %s <file_path> <mode> <matrix_file> [gap_open gap_extend]\n"
+                "With a matrix file ('#' comments, a line of symbols, a row per symbol: the symbol and its integers; symmetric,\n"
+                "letters in either case) gaps default to -11 -1 and the line ends (\\n, \\r\\n) are stripped, not aligned.\n",
+                argv[0], argv[0]);
         return 1;
+    }
+    static agx_sw_matrix matrix;
+    const int with_matrix = argc >= 4;
+    if (with_matrix) {
+        char err[512];
+        if (read_matrix(argv[3], &matrix, err, sizeof err)) {
+            fprintf(stderr, "swAlign: %s\n", err);
+            return EXIT_FAILURE;
+        }
+        matrix.gap_open = -11;
+        matrix.gap_extend = -1;
+        if (argc == 6) {
+            char *e1, *e2;
+            matrix.gap_open = (int32_t)strtol(argv[4], &e1, 10);
+            matrix.gap_extend = (int32_t)strtol(argv[5], &e2, 10);
+            if (e1 == argv[4] || *e1 || e2 == argv[5] || *e2) {
+                fprintf(stderr, "swAlign: gap_open and gap_extend must be integers (got '%s' '%s')\n", argv[4], argv[5]);
+                return EXIT_FAILURE;
+            }
+        }
     }
     const char *cp = getenv("AGX_CLI_CHUNK_PAIRS");
     const int64_t chunk_pairs = cp && atoll(cp) > 0 ? atoll(cp) : 262144;
@@ -51,7 +161,13 @@ int main(int argc, char *argv[])
                 fprintf(stderr, "swAlign: %s\n", agx_last_error());
                 status = EXIT_FAILURE;
             }
-            if (!status && agx_sw_align_mode(ctx, NULL, mode, AGX_SW_ALIGN_SPANS, t->bases, t->off, t->len, t->n_pairs, hits) != AGX_OK) {
+            if (with_matrix) /* a line's end is not a residue */
+                for (int64_t k = 0; k < 2 * t->n_pairs; k++) {
+                    if (t->len[k] && t->bases[t->off[k] + t->len[k] - 1] == '\n') t->len[k]--;
+                    if (t->len[k] && t->bases[t->off[k] + t->len[k] - 1] == '\r') t->len[k]--;
+                }
+            if (!status && (with_matrix ? agx_sw_align_matrix(ctx, &matrix, mode, AGX_SW_ALIGN_SPANS, t->bases, t->off, t->len, t->n_pairs, hits)
+                                        : agx_sw_align_mode(ctx, NULL, mode, AGX_SW_ALIGN_SPANS, t->bases, t->off, t->len, t->n_pairs, hits)) != AGX_OK) {
                 fprintf(stderr, "swAlign: %s\n", agx_last_error());
                 status = EXIT_FAILURE;
             }

@@ -251,6 +251,18 @@ int agx_sw_batch_create_align_mode(agx_ctx *ctx, const agx_sw_scoring *scoring, 
 int agx_sw_align_mode(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int what, const uint8_t *bases, const uint64_t *off,
                       const uint32_t *len, int64_t n_pairs, agx_sw_hit *hits);
 
+/* Align batches under a substitution matrix (agx_sw_matrix, validated as by agx_sw_batch_create_matrix; NULL: AGX_E_ARG).
+ * The contract is that of "Alignment coordinates" and "Alignment modes" above in every mode, with the diagonal move adding
+ * score[code[a_j]][code[b_i]] in place of match / mismatch; a byte outside the alphabet fails with AGX_E_SYMBOL naming the pair.
+ * A diagonal score may be <= 0 even for identical symbols, so: a LOCAL or EXTEND score of 0 means "nothing consumed" (all four
+ * positions -1), whatever the sequences hold; GLOBAL, FIT and EXTEND_QUERY scores may be negative.  The batch behaves as
+ * agx_sw_batch_create_align_mode's does (launch, scores, hits, bind_scores ignored, limits; ctx may be NULL: plan only). */
+int agx_sw_batch_create_align_matrix(agx_ctx *ctx, const agx_sw_matrix *matrix, int mode, int what, const uint8_t *bases,
+                                     const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_batch **out);
+/* One-shot: create_align_matrix + launch + hits + destroy. */
+int agx_sw_align_matrix(agx_ctx *ctx, const agx_sw_matrix *matrix, int mode, int what, const uint8_t *bases, const uint64_t *off,
+                        const uint32_t *len, int64_t n_pairs, agx_sw_hit *hits);
+
 /* One-shot: create + launch + scores + destroy. */
 int agx_sw_score(agx_ctx *ctx, const uint8_t *bases, const uint64_t *off, const uint32_t *len, int64_t n_pairs,
                  int32_t *scores);
