@@ -24,6 +24,9 @@ SW_ALIGN_MAX_QUERY_LEN, SW_ALIGN_MAX_TARGET_LEN = 2560, 65535
 SW_MODE_LOCAL, SW_MODE_GLOBAL, SW_MODE_FIT, SW_MODE_EXTEND, SW_MODE_EXTEND_QUERY = 0, 1, 2, 3, 4
 # agx_sw_hit as a numpy record: one per pair, positions 0-based and inclusive, -1 where the score is 0
 SwHit = np.dtype([("score", np.int32), ("a_begin", np.int32), ("a_end", np.int32), ("b_begin", np.int32), ("b_end", np.int32)])
+# agx_sw_stat as a numpy record: matches and aligned pairs of the reported alignment (include/agx.h, "Alignment statistics")
+SwStat = np.dtype([("matches", np.int32), ("pairs", np.int32)])
+SW_STATS_MAX_QUERY_LEN = 1792
 OPT_SW_KERNEL = 1
 OPT_SW_PLANNER = 2
 SW_PLANNER_AUTO, SW_PLANNER_HOST, SW_PLANNER_DEVICE = 0, 1, 2
@@ -41,6 +44,7 @@ SYMBOLS = [
     "agx_sw_batch_create", "agx_sw_batch_create_scored", "agx_sw_batch_create_matrix", "agx_sw_batch_launch", "agx_sw_batch_scores", "agx_sw_batch_bind_scores", "agx_sw_batch_info", "agx_sw_batch_destroy",
     "agx_sw_batch_create_align", "agx_sw_batch_hits", "agx_sw_align", "agx_sw_batch_create_align_mode", "agx_sw_align_mode",
     "agx_sw_batch_create_align_matrix", "agx_sw_align_matrix",
+    "agx_sw_batch_create_align_stats", "agx_sw_batch_stats", "agx_sw_align_stats",
     "agx_sw_score", "agx_sw_score_multi", "agx_sw_score_devices", "agx_sw_shard_cuts",
     "agx_phmm_batch_create", "agx_phmm_batch_launch", "agx_phmm_batch_results", "agx_phmm_batch_bind_results", "agx_phmm_batch_info",
     "agx_phmm_batch_destroy", "agx_phmm_forward", "agx_phmm_forward_multi", "agx_phmm_forward_devices", "agx_phmm_shard_cuts",
@@ -165,6 +169,11 @@ def lib():
         l.agx_sw_batch_create_align_matrix.argtypes = [C.c_void_p, C.POINTER(SwMatrix), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                                        C.c_int64, C.POINTER(C.c_void_p)]
         l.agx_sw_align_matrix.argtypes = [C.c_void_p, C.POINTER(SwMatrix), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        l.agx_sw_batch_create_align_stats.argtypes = [C.c_void_p, C.POINTER(SwScoring), C.POINTER(SwMatrix), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                      C.c_int64, C.POINTER(C.c_void_p)]
+        l.agx_sw_batch_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        l.agx_sw_align_stats.argtypes = [C.c_void_p, C.POINTER(SwScoring), C.POINTER(SwMatrix), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                         C.c_void_p, C.c_void_p]
         l.agx_sw_score.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
         l.agx_sw_score_multi.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
         l.agx_sw_score_devices.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
@@ -268,8 +277,16 @@ class Context:
         return ms.value
 
     # ---- Smith-Waterman
-    def sw_batch(self, b, scoring=None, matrix=None, align=0, mode=SW_MODE_LOCAL) -> "SwBatch":
-        return SwBatch(self, b, scoring, matrix, align, mode)
+    def sw_batch(self, b, scoring=None, matrix=None, align=0, mode=SW_MODE_LOCAL, stats=False) -> "SwBatch":
+        return SwBatch(self, b, scoring, matrix, align, mode, stats)
+
+    def sw_align_stats(self, b, scoring=None, mode=SW_MODE_LOCAL, matrix=None):
+        """b: synth.SWBatch -> (SwHit records as SW_ALIGN_SPANS gives them, SwStat records: matches and pairs), one-shot."""
+        hits, stats = np.empty(b.n_pairs, SwHit), np.empty(b.n_pairs, SwStat)
+        sc = C.byref(SwScoring(*scoring)) if scoring is not None else None
+        mx = C.byref(matrix) if matrix is not None else None
+        _check(lib().agx_sw_align_stats(self._h, sc, mx, mode, _ptr(b.bases), _ptr(b.off), _ptr(b.len), b.n_pairs, _ptr(hits), _ptr(stats)))
+        return hits, stats
 
     def sw_align(self, b, what=SW_ALIGN_SPANS, scoring=None, mode=SW_MODE_LOCAL, matrix=None) -> np.ndarray:
         """b: synth.SWBatch -> SwHit records (score, end cell, and with SW_ALIGN_SPANS the begin cell), one-shot.
@@ -307,13 +324,21 @@ class Context:
 class SwBatch:
     """agx_sw_batch: a scheduled batch resident in HBM (ctx=None: planned on the host only)."""
 
-    def __init__(self, ctx, b, scoring=None, matrix=None, align=0, mode=SW_MODE_LOCAL):
+    def __init__(self, ctx, b, scoring=None, matrix=None, align=0, mode=SW_MODE_LOCAL, stats=False):
         """scoring: None (the reference's +1/-1/-3/-1) or (match, mismatch, gap_open, gap_extend);
         matrix: an SwMatrix instead (score-only and align batches alike); align: SW_ALIGN_ENDS / SW_ALIGN_SPANS for a batch that also answers hits();
-        mode: SW_MODE_* of an align batch (local, global, fit, extension)."""
+        mode: SW_MODE_* of an align batch (local, global, fit, extension); stats=True: a SPANS batch that also answers stats()."""
         self.ctx = ctx
         self.n_pairs = b.n_pairs
         self._h = C.c_void_p()
+        if stats:
+            if align not in (0, SW_ALIGN_SPANS):
+                raise AgxError(E_ARG, "a stats batch is a SW_ALIGN_SPANS batch")
+            sc = C.byref(SwScoring(*scoring)) if scoring is not None else None
+            mx = C.byref(matrix) if matrix is not None else None
+            _check(lib().agx_sw_batch_create_align_stats(ctx._h if ctx else None, sc, mx, mode, _ptr(b.bases), _ptr(b.off), _ptr(b.len),
+                                                         b.n_pairs, C.byref(self._h)))
+            return
         if mode != SW_MODE_LOCAL and not align:
             raise AgxError(E_ARG, "mode= applies to align batches: pass align=SW_ALIGN_ENDS or SW_ALIGN_SPANS")
         if align and matrix is not None:
@@ -354,6 +379,12 @@ class SwBatch:
             out = np.empty(self.n_pairs, SwHit)
         _check(lib().agx_sw_batch_hits(self._h, _ptr(out)))
         return out
+
+    def stats(self):
+        """agx_sw_batch_stats: (SwHit records, SwStat records) in the caller's pair order (stats batches only)."""
+        hits, stats = np.empty(self.n_pairs, SwHit), np.empty(self.n_pairs, SwStat)
+        _check(lib().agx_sw_batch_stats(self._h, _ptr(hits), _ptr(stats)))
+        return hits, stats
 
     def bind_scores(self, out):
         """agx_sw_batch_bind_scores: out = a page-locked int32 array (host_array) or None."""

@@ -213,6 +213,11 @@ struct agx_sw_batch {
     // align batches (agx_sw_batch_create_align): 0 = a score-only batch, else AGX_SW_ALIGN_ENDS / _SPANS
     int align = 0;
     int mode = 0; // AGX_SW_MODE_*: anything but LOCAL runs the anchored fill (agx_sw_anch_kernel.hip)
+    // agx_sw_batch_create_align_stats: 0 = no statistics; 1 = a stats batch whose own fill is the plain one (LOCAL,
+    // FIT: the begin pass carries L); 2 = this batch's fill is the stats build and writes L = matches << 12 | pairs per pair
+    int stats = 0;
+    DevBuf lstat;       // stats == 2: L of every pair's captured cell
+    PinBuf lstat_stage; // its page-locked landing block
     // modes other than LOCAL: pairs with an empty side whose score is not the zero the device array holds for them
     std::vector<int64_t> fix_pair;
     std::vector<int32_t> fix_score;
@@ -246,7 +251,8 @@ struct agx_sw_batch {
 
 namespace {
 int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matrix *matrix, const uint8_t *bases,
-                 const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_batch **out, bool defer = false, int align = 0, int mode = 0);
+                 const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_batch **out, bool defer = false, int align = 0, int mode = 0,
+                 int stats = 0);
 int finish_create(agx_sw_batch *b);
 void drop_pending(agx_sw_batch *b);
 }
@@ -266,6 +272,8 @@ void agx_sw_batch_destroy(agx_sw_batch *b)
     b->out_stage.release();
     b->ends.release();
     b->ends_stage.release();
+    b->lstat.release();
+    b->lstat_stage.release();
     agx_ctx_release(b->ctx); // the batch's own reference: a context outlives its batches
     delete b;
 }
@@ -485,7 +493,7 @@ int launch_device_plan(agx_ctx *ctx, DevPlan &dp, agx_sw_batch *b, uint32_t n_pa
 }
 
 int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matrix *matrix, const uint8_t *bases,
-                 const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_batch **out, bool defer, int align, int mode)
+                 const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_batch **out, bool defer, int align, int mode, int stats)
 {
     if (!out) {
         agx_set_error("agx_sw_batch_create: out is NULL");
@@ -588,7 +596,12 @@ int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matri
     if (!dev_candidate) all.resize((size_t)n_pairs);
     PairPlan *allp = dev_candidate ? nullptr : all.data();
     // no wide classes in matrix mode; an align batch lays the FIRST sequence across the lanes (agx_sw_loc_kernel.hip), its limit is on that one
-    const uint32_t hard_max_short = matrix ? (uint32_t)kSwPackedMaxShort : align ? (uint32_t)AGX_SW_ALIGN_MAX_QUERY_LEN : AGX_SW_MAX_SHORT_LEN;
+    // (a stats batch: the classes the stats builds exist for bound the query, also where the batch's own fill is the plain one --
+    // its begin pass is not)
+    const uint32_t hard_max_short = stats    ? (uint32_t)AGX_SW_STATS_MAX_QUERY_LEN
+                                    : matrix ? (uint32_t)kSwPackedMaxShort
+                                    : align  ? (uint32_t)AGX_SW_ALIGN_MAX_QUERY_LEN
+                                             : AGX_SW_MAX_SHORT_LEN;
     struct Worker {
         int rc = AGX_OK;
         int64_t bad_pair = -1;
@@ -689,7 +702,7 @@ int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matri
     if (const char *e = agx_tune("AGX_SW_RISE")) rising = e[0] == '0' ? 0 : e[0] == '1' && rising ? 1 : rising;
     const bool packed = family >= 1 && family <= 3;
     const bool coded_plan = family == 2 || family == 3; // the packed plan of the biased fill (one launch for all classes)
-    const double *costs = class_costs(family);
+    const double *costs = stats == 2 ? kSwStatsClassCost : class_costs(family); // (the stats builds: fewer classes)
     const int slots = packed ? 2 : 1;
 
     // plan-only batches check the symbols on the host; with a device the pack kernel does it
@@ -735,13 +748,16 @@ int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matri
         if (family == 2) agx_sw_pk2_preload();
         if (family == 3) agx_sw_i32d_preload();
         if (family == 0 && !matrix) agx_sw_i32_preload();
-        if (family == 4) (matrix ? agx_sw_loc_mat_preload : agx_sw_loc_preload)();
-        if (family == 5) (matrix ? agx_sw_anch_mat_preload : agx_sw_anch_preload)();
+        if (family == 4 && stats != 2) (matrix ? agx_sw_loc_mat_preload : agx_sw_loc_preload)();
+        if (family == 5 && stats != 2) (matrix ? agx_sw_anch_mat_preload : agx_sw_anch_preload)();
+        if (family == 4 && stats == 2) (matrix ? agx_sw_loc_mat_stats_preload : agx_sw_loc_stats_preload)();
+        if (family == 5 && stats == 2) (matrix ? agx_sw_anch_mat_stats_preload : agx_sw_anch_stats_preload)();
     }
     b->matrix = matrix != nullptr;
     if (matrix) b->mat = *matrix;
     b->align = align;
     b->mode = mode;
+    b->stats = stats;
     b->scoring = sc;
     b->prm = prm;
     b->prm.n_out = (uint32_t)n_pairs + 1u;
@@ -1377,6 +1393,8 @@ int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matri
     if (!rc) rc = b->out_stage.alloc(ctx, ((size_t)n_pairs + 1) * sizeof(int32_t));
     if (!rc && align) rc = b->ends.alloc(ctx, ((size_t)n_pairs + 1) * sizeof(uint32_t));
     if (!rc && align) rc = b->ends_stage.alloc(ctx, ((size_t)n_pairs + 1) * sizeof(uint32_t));
+    if (!rc && stats == 2) rc = b->lstat.alloc(ctx, ((size_t)n_pairs + 1) * sizeof(uint32_t));
+    if (!rc && stats == 2) rc = b->lstat_stage.alloc(ctx, ((size_t)n_pairs + 1) * sizeof(uint32_t));
     if (!rc && launches.size() > 1) rc = agx_ctx_prepare_fanout(ctx);
     if (rc) return rc;
     hipStream_t cs = ctx->copy;
@@ -1396,6 +1414,7 @@ int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matri
     // pairs with an empty side are never touched by a kernel: their score is this zero
     if (e == hipSuccess) e = hipMemsetAsync(b->scores.p, 0, b->scores.bytes, ts);
     if (e == hipSuccess && align) e = hipMemsetAsync(b->ends.p, 0xff, b->ends.bytes, ts); // ... and their end cell is "none"
+    if (e == hipSuccess && stats == 2) e = hipMemsetAsync(b->lstat.p, 0, b->lstat.bytes, ts); // ... and they paired nothing
     if (e == hipSuccess && packed) e = hipMemsetAsync(b->img.p, 0, (size_t)kSwPackedMaxShort + 4, ts);
     uint32_t *flag = (uint32_t *)h_flag.p;
     flag[0] = 0;
@@ -1488,7 +1507,19 @@ int agx_sw_batch_launch(agx_sw_batch *b)
         int32_t *scores = b->bound ? b->bound : (int32_t *)b->scores.p;
         const int anch_capture = b->mode != AGX_SW_MODE_EXTEND, anch_flags = b->mode == AGX_SW_MODE_FIT ? 1 : b->mode == AGX_SW_MODE_GLOBAL ? 2 : 0;
         int r;
-        if (b->family == 5 && b->matrix)
+        uint32_t *lstat = (uint32_t *)b->lstat.p;
+        if (b->stats == 2 && b->family == 5 && b->matrix)
+            r = agx_sw_anch_mat_stats_launch_class(cl.C, anch_capture, anch_flags, prm, img, (const SwGroup *)b->groups.p, wv, cl.n_waves, scores,
+                                                   (uint32_t *)b->ends.p, lstat, (const int16_t *)b->table.p, st);
+        else if (b->stats == 2 && b->family == 5)
+            r = agx_sw_anch_stats_launch_class(cl.C, anch_capture, anch_flags, prm, img, (const SwGroup *)b->groups.p, wv, cl.n_waves, scores,
+                                               (uint32_t *)b->ends.p, lstat, st);
+        else if (b->stats == 2 && b->matrix)
+            r = agx_sw_loc_mat_stats_launch_class(cl.C, prm, img, (const SwGroup *)b->groups.p, wv, cl.n_waves, scores, (uint32_t *)b->ends.p, lstat,
+                                                  (const int16_t *)b->table.p, st);
+        else if (b->stats == 2)
+            r = agx_sw_loc_stats_launch_class(cl.C, prm, img, (const SwGroup *)b->groups.p, wv, cl.n_waves, scores, (uint32_t *)b->ends.p, lstat, st);
+        else if (b->family == 5 && b->matrix)
             r = agx_sw_anch_mat_launch_class(cl.C, anch_capture, anch_flags, prm, img, (const SwGroup *)b->groups.p, wv, cl.n_waves, scores,
                                              (uint32_t *)b->ends.p, (const int16_t *)b->table.p, st);
         else if (b->family == 5)
@@ -1706,11 +1737,11 @@ agx_sw_hit empty_side_hit(int mode, int what, const agx_sw_scoring &sc, uint32_t
 
 // an align batch under match/mismatch scoring (matrix == NULL) or under a substitution matrix (scoring unused)
 int create_align(const char *who, agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matrix *matrix, int mode, int what,
-                 const uint8_t *bases, const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_batch **out)
+                 const uint8_t *bases, const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_batch **out, bool stats = false)
 {
     if (mode < AGX_SW_MODE_LOCAL || mode > AGX_SW_MODE_EXTEND_QUERY) {
         if (out) *out = nullptr;
-        agx_set_error("%s%s: mode = %d is not one of AGX_SW_MODE_LOCAL .. AGX_SW_MODE_EXTEND_QUERY (0..4)", who, matrix ? "" : "_mode", mode);
+        agx_set_error("%s%s: mode = %d is not one of AGX_SW_MODE_LOCAL .. AGX_SW_MODE_EXTEND_QUERY (0..4)", who, matrix || stats ? "" : "_mode", mode);
         return AGX_E_ARG;
     }
     if (what != AGX_SW_ALIGN_ENDS && what != AGX_SW_ALIGN_SPANS) {
@@ -1720,7 +1751,10 @@ int create_align(const char *who, agx_ctx *ctx, const agx_sw_scoring *scoring, c
     }
     AGX_GUARD_BEGIN
     agx_sw_batch *b = nullptr;
-    int rc = create_batch(ctx, scoring, matrix, bases, off, len, n_pairs, &b, false, what, mode);
+    // a stats batch: LOCAL and FIT keep the plain forward fill (their begin pass carries L), the pinned modes' only fill carries it
+    const int stats_kind = !stats ? 0 : (mode == AGX_SW_MODE_LOCAL || mode == AGX_SW_MODE_FIT) ? 1 : 2;
+    const int max_query = stats ? AGX_SW_STATS_MAX_QUERY_LEN : AGX_SW_ALIGN_MAX_QUERY_LEN;
+    int rc = create_batch(ctx, scoring, matrix, bases, off, len, n_pairs, &b, false, what, mode, stats_kind);
     if (rc) return rc;
     struct Drop {
         agx_sw_batch *b;
@@ -1730,9 +1764,9 @@ int create_align(const char *who, agx_ctx *ctx, const agx_sw_scoring *scoring, c
         for (int64_t p = 0; p < n_pairs; ++p) { // the planner skips pairs with an empty side: their answers come from the formulas
             const uint32_t la = len[2 * p], lb = len[2 * p + 1];
             if (la && lb) continue;
-            if (la > (uint32_t)AGX_SW_ALIGN_MAX_QUERY_LEN || lb > (uint32_t)AGX_SW_ALIGN_MAX_TARGET_LEN) {
+            if (la > (uint32_t)max_query || lb > (uint32_t)AGX_SW_ALIGN_MAX_TARGET_LEN) {
                 agx_set_error("pair %lld: lengths %u x %u exceed the supported %d x %d (query x target of an align batch)", (long long)p, la, lb,
-                              AGX_SW_ALIGN_MAX_QUERY_LEN, AGX_SW_ALIGN_MAX_TARGET_LEN);
+                              max_query, AGX_SW_ALIGN_MAX_TARGET_LEN);
                 return AGX_E_LIMIT;
             }
             const int32_t v = empty_side_hit(mode, what, b->scoring, la, lb).score;
@@ -1782,21 +1816,13 @@ int agx_sw_batch_create_align_matrix(agx_ctx *ctx, const agx_sw_matrix *matrix, 
     return create_align("agx_sw_batch_create_align_matrix", ctx, nullptr, matrix, mode, what, bases, off, len, n_pairs, out);
 }
 
-int agx_sw_batch_hits(agx_sw_batch *b, agx_sw_hit *hits)
+} // extern "C"
+
+namespace {
+// agx_sw_batch_hits; with L (agx_sw_batch_stats) also the word matches << 12 | pairs of every pair, 0 where no fill says
+// otherwise: from this batch's own fill (stats == 2), else from the begin pass, which then runs the stats build
+int hits_impl(agx_sw_batch *b, agx_sw_hit *hits, std::vector<uint32_t> *L)
 {
-    if (!b || (!hits && b->n_pairs)) {
-        agx_set_error("agx_sw_batch_hits: null argument");
-        return AGX_E_ARG;
-    }
-    if (!b->align) {
-        agx_set_error("agx_sw_batch_hits: a score-only batch has no hits (create it with agx_sw_batch_create_align)");
-        return AGX_E_ARG;
-    }
-    if (!b->ctx) {
-        agx_set_error("this batch was planned without a context (no device): it has no hits");
-        return AGX_E_NODEVICE;
-    }
-    AGX_GUARD_BEGIN
     int rc = agx_bind(b->ctx);
     if (rc) return rc;
     hipStream_t st = b->ctx->stream;
@@ -1807,9 +1833,13 @@ int agx_sw_batch_hits(agx_sw_batch *b, agx_sw_hit *hits)
     }
     const int32_t *sc = (const int32_t *)b->out_stage.p;
     const uint32_t *en = (const uint32_t *)b->ends_stage.p;
+    const bool own_l = L && b->stats == 2;
     AGX_HIP(hipMemcpyAsync(b->out_stage.p, b->scores.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     AGX_HIP(hipMemcpyAsync(b->ends_stage.p, b->ends.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    if (own_l) AGX_HIP(hipMemcpyAsync(b->lstat_stage.p, b->lstat.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     AGX_HIP(hipStreamSynchronize(st));
+    if (own_l) L->assign((const uint32_t *)b->lstat_stage.p, (const uint32_t *)b->lstat_stage.p + n);
+    else if (L) L->assign((size_t)n, 0u);
     // end cells, checked against the caller's lengths: a padding cell must never be reported
     const uint32_t *len = b->seq_len.empty() ? nullptr : b->seq_len.data(); // (the begin passes' own batches have none: checked against the end cell below)
     const int mode = b->mode;
@@ -1894,7 +1924,7 @@ int agx_sw_batch_hits(agx_sw_batch *b, agx_sw_hit *hits)
     agx_sw_batch *rb = nullptr;
     // (a substitution matrix is symmetric and a stays across the lanes: the reversed problem runs under the same matrix)
     rc = create_batch(b->ctx, &b->scoring, b->matrix ? &b->mat : nullptr, rev.data(), roff.data(), rlen.data(), m, &rb, false, AGX_SW_ALIGN_ENDS,
-                      fit ? AGX_SW_MODE_EXTEND_QUERY : AGX_SW_MODE_LOCAL);
+                      fit ? AGX_SW_MODE_EXTEND_QUERY : AGX_SW_MODE_LOCAL, L ? 2 : 0);
     if (rc) return rc;
     struct Drop {
         agx_sw_batch *b;
@@ -1905,8 +1935,9 @@ int agx_sw_batch_hits(agx_sw_batch *b, agx_sw_hit *hits)
         }
     } drop{rb};
     std::vector<agx_sw_hit> rh((size_t)m);
+    std::vector<uint32_t> rl;
     rc = agx_sw_batch_launch(rb);
-    if (!rc) rc = agx_sw_batch_hits(rb, rh.data());
+    if (!rc) rc = hits_impl(rb, rh.data(), L ? &rl : nullptr);
     if (rc) return rc;
     for (int64_t k = 0; k < m; ++k) {
         agx_sw_hit &h = hits[pick[(size_t)k]];
@@ -1918,9 +1949,92 @@ int agx_sw_batch_hits(agx_sw_batch *b, agx_sw_hit *hits)
         }
         if (!fit) h.a_begin = h.a_end - r.a_end;
         h.b_begin = h.b_end - r.b_end;
+        if (L) (*L)[(size_t)pick[(size_t)k]] = rl[(size_t)k];
     }
     return AGX_OK;
+}
+} // namespace
+
+extern "C" {
+
+int agx_sw_batch_hits(agx_sw_batch *b, agx_sw_hit *hits)
+{
+    if (!b || (!hits && b->n_pairs)) {
+        agx_set_error("agx_sw_batch_hits: null argument");
+        return AGX_E_ARG;
+    }
+    if (!b->align) {
+        agx_set_error("agx_sw_batch_hits: a score-only batch has no hits (create it with agx_sw_batch_create_align)");
+        return AGX_E_ARG;
+    }
+    if (!b->ctx) {
+        agx_set_error("this batch was planned without a context (no device): it has no hits");
+        return AGX_E_NODEVICE;
+    }
+    AGX_GUARD_BEGIN
+    return hits_impl(b, hits, nullptr);
     AGX_GUARD_END("agx_sw_batch_hits")
+}
+
+int agx_sw_batch_stats(agx_sw_batch *b, agx_sw_hit *hits, agx_sw_stat *stats)
+{
+    if (!b || (!stats && b->n_pairs)) {
+        agx_set_error("agx_sw_batch_stats: null argument");
+        return AGX_E_ARG;
+    }
+    if (!b->stats || b->align != AGX_SW_ALIGN_SPANS) {
+        agx_set_error("agx_sw_batch_stats: not a stats batch (create it with agx_sw_batch_create_align_stats)");
+        return AGX_E_ARG;
+    }
+    if (!b->ctx) {
+        agx_set_error("this batch was planned without a context (no device): it has no stats");
+        return AGX_E_NODEVICE;
+    }
+    AGX_GUARD_BEGIN
+    const int64_t n = b->n_pairs;
+    std::vector<agx_sw_hit> own;
+    if (!hits && n) {
+        own.resize((size_t)n);
+        hits = own.data();
+    }
+    std::vector<uint32_t> L;
+    const int rc = hits_impl(b, hits, &L);
+    if (rc || n == 0) return rc;
+    // Every stat is checked before it leaves: 0 <= matches <= pairs <= min(columns of a, of b); under match/mismatch scoring
+    // what the score leaves after matches, mismatches and gap cells must be a whole number of gap opens, between "one if
+    // there is a gap cell" and "one per gap cell".
+    const agx_sw_scoring s = b->scoring;
+    const bool mm = !b->matrix;
+    std::vector<int64_t> bad((size_t)agx_host_threads(), -1);
+    agx_parallel_for(n, 16384, [&](int64_t lo, int64_t hi, int tid) {
+        for (int64_t p = lo; p < hi; ++p) {
+            const agx_sw_hit &h = hits[p];
+            const int64_t ca = h.a_begin >= 0 && h.a_end >= h.a_begin ? (int64_t)h.a_end - h.a_begin + 1 : 0;
+            const int64_t cb = h.b_begin >= 0 && h.b_end >= h.b_begin ? (int64_t)h.b_end - h.b_begin + 1 : 0;
+            const int64_t matches = L[(size_t)p] >> kSwStatColBits, pairs = L[(size_t)p] & ((1u << kSwStatColBits) - 1u);
+            bool ok = matches <= pairs && pairs <= std::min(ca, cb);
+            if (ok && mm && ca + cb > 0) {
+                const int64_t gaps = ca + cb - 2 * pairs;
+                const int64_t r = (int64_t)h.score - matches * s.match - (pairs - matches) * s.mismatch - gaps * s.gap_extend;
+                if (s.gap_open == 0) ok = r == 0;
+                else {
+                    const int64_t opens = r / s.gap_open;
+                    ok = r % s.gap_open == 0 && opens >= (gaps ? 1 : 0) && opens <= gaps;
+                }
+            }
+            if (!ok && bad[(size_t)tid] < 0) bad[(size_t)tid] = p;
+            stats[p] = agx_sw_stat{(int32_t)matches, (int32_t)pairs};
+        }
+    });
+    for (int64_t p : bad)
+        if (p >= 0) {
+            agx_set_error("agx_sw_batch_stats: pair %lld (mode %d): matches %u, pairs %u do not fit its score %d over the span a %d..%d, b %d..%d",
+                          (long long)p, b->mode, L[(size_t)p] >> kSwStatColBits, L[(size_t)p] & ((1u << kSwStatColBits) - 1u), hits[p].score,
+                          hits[p].a_begin, hits[p].a_end, hits[p].b_begin, hits[p].b_end);
+            return AGX_E_INTERNAL;
+        }
+    return AGX_OK;
+    AGX_GUARD_END("agx_sw_batch_stats")
 }
 
 int agx_sw_align(agx_ctx *ctx, const agx_sw_scoring *scoring, int what, const uint8_t *bases, const uint64_t *off,
@@ -1958,6 +2072,30 @@ int agx_sw_align_matrix(agx_ctx *ctx, const agx_sw_matrix *matrix, int mode, int
     agx_sw_batch *b = nullptr;
     const int rc = agx_sw_batch_create_align_matrix(ctx, matrix, mode, what, bases, off, len, n_pairs, &b);
     return rc ? rc : align_once(b, hits);
+}
+
+int agx_sw_batch_create_align_stats(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matrix *matrix, int mode, const uint8_t *bases,
+                                    const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_batch **out)
+{
+    if (scoring && matrix) {
+        if (out) *out = nullptr;
+        agx_set_error("agx_sw_batch_create_align_stats: both scoring and matrix given; exactly one way of scoring");
+        return AGX_E_ARG;
+    }
+    return create_align("agx_sw_batch_create_align_stats", ctx, scoring, matrix, mode, AGX_SW_ALIGN_SPANS, bases, off, len, n_pairs, out, true);
+}
+
+int agx_sw_align_stats(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matrix *matrix, int mode, const uint8_t *bases,
+                       const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_hit *hits, agx_sw_stat *stats)
+{
+    agx_sw_batch *b = nullptr;
+    int rc = agx_sw_batch_create_align_stats(ctx, scoring, matrix, mode, bases, off, len, n_pairs, &b);
+    if (rc) return rc;
+    rc = agx_sw_batch_launch(b);
+    if (!rc) rc = agx_sw_batch_stats(b, hits, stats);
+    if (rc && b->ctx) (void)hipStreamSynchronize(b->ctx->stream); // the blocks go back to the pools: nothing may still run on them
+    agx_sw_batch_destroy(b);
+    return rc;
 }
 
 int agx_sw_shard_cuts(const uint32_t *len, int64_t n_pairs, int n_shards, int64_t *cut)

@@ -132,6 +132,27 @@ void agx_sw_loc_mat_preload();
 int agx_sw_anch_mat_launch_class(int cols_per_lane, int capture, int flags, const SwParams &prm, const uint32_t *img, const SwGroup *groups,
                                  const SwWave *waves, uint32_t n_waves, int32_t *scores, uint32_t *ends, const int16_t *table, hipStream_t s);
 void agx_sw_anch_mat_preload();
+// the align fills WITH alignment statistics (agx_sw_*_stats_kernel.hip): the same records, plans, images and
+// ends[] words; every state carries L = matches << 12 | pairs of its best path beside the score, and lstat[out] receives L of
+// the captured cell.  Built for the classes below only (see DESIGN.md 4.1e for the ones left out).
+#define AGX_SW_FOR_EACH_STATS_CLASS(X) X(4) X(6) X(8) X(10) X(12) X(14) X(16) X(18) X(20) X(22) X(24) X(26) X(28)
+constexpr int kSwStatsTopClass = 28; // 64 x 28 = AGX_SW_STATS_MAX_QUERY_LEN
+// the int32 kernel's relative costs for the classes that are built (unmeasured for these kernels), 0 = not built
+static const double kSwStatsClassCost[] = {1.373, 1.250, 1.178, 1.138, 1.112, 1.080, 1.051, 1.033, 1.025, 1.022, 1.014, 1.014, 1.011, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+constexpr int kSwStatColBits = 12; // L = matches << 12 | pairs
+int agx_sw_loc_stats_launch_class(int cols_per_lane, const SwParams &prm, const uint32_t *img, const SwGroup *groups, const SwWave *waves,
+                                  uint32_t n_waves, int32_t *scores, uint32_t *ends, uint32_t *lstat, hipStream_t s);
+int agx_sw_loc_mat_stats_launch_class(int cols_per_lane, const SwParams &prm, const uint32_t *img, const SwGroup *groups, const SwWave *waves,
+                                      uint32_t n_waves, int32_t *scores, uint32_t *ends, uint32_t *lstat, const int16_t *table, hipStream_t s);
+int agx_sw_anch_stats_launch_class(int cols_per_lane, int capture, int flags, const SwParams &prm, const uint32_t *img, const SwGroup *groups,
+                                   const SwWave *waves, uint32_t n_waves, int32_t *scores, uint32_t *ends, uint32_t *lstat, hipStream_t s);
+int agx_sw_anch_mat_stats_launch_class(int cols_per_lane, int capture, int flags, const SwParams &prm, const uint32_t *img, const SwGroup *groups,
+                                       const SwWave *waves, uint32_t n_waves, int32_t *scores, uint32_t *ends, uint32_t *lstat,
+                                       const int16_t *table, hipStream_t s);
+void agx_sw_loc_stats_preload();
+void agx_sw_loc_mat_stats_preload();
+void agx_sw_anch_stats_preload();
+void agx_sw_anch_mat_stats_preload();
 
 // ---- device-side planning (agx_sw_plan_kernel.hip): the O(pairs) passes of the planner as kernels
 constexpr uint32_t kSwPlanEmptyKey = 1u << 27;           // sort key of a pair with an empty side: behind every bucket

@@ -35,9 +35,19 @@
 // real cell has a padding cell above, left or upper-left of it (pre-rows are wiped by the top reset), so it does not
 // depend on what padding scores at all.  The diagonal adds at most 128 * 2560 to the range either way: within 1.35e8.
 //
-// (shared by agx_sw_anch_kernel.hip and agx_sw_anch_mat_kernel.hip; opens an anonymous namespace that the including file
-// closes after its launch helper)
+// STATS (agx_sw_anch_stats_kernel.hip, agx_sw_anch_mat_stats_kernel.hip; DESIGN.md 4.1e): as in agx_sw_loc_kernel.inc every
+// state is the tuple (score, L), L = matches << 12 | pairs, one int64 = score << 32 | L; the top reset and both kinds of left
+// boundary load L = 0, minus infinity is the tuple (-2^30, 0) and never wins whatever it meets.  The start is pinned in the
+// modes that run this build (GLOBAL, EXTEND, EXTEND_QUERY, and EXTEND_QUERY as FIT's begin pass), so every path into the
+// captured cell starts at the origin and the tuple maximum there is over exactly the alignments of the reported span.
+// Capture reads the score word only: ANY as the locating fill does, COL by strict improvement of the selected column's
+// score; L is what the chosen cell holds.
+//
+// (shared by agx_sw_anch_kernel.hip, agx_sw_anch_mat_kernel.hip and their _stats builds; opens an anonymous namespace that
+// the including file closes after its launch helper)
 #include "agx_sw.h"
+
+#include <type_traits>
 
 namespace {
 
@@ -50,11 +60,29 @@ __device__ __forceinline__ int anch_shr1(int old, int v)
     return __builtin_amdgcn_update_dpp(old, v, 0x138, 0xf, 0xf, false);
 }
 
-template <int C, bool COL, bool MAT>
+__device__ __forceinline__ long long anch_shr1(long long old, long long v) // STATS: both words of the tuple
+{
+    const uint32_t lo = (uint32_t)anch_shr1((int)old, (int)v);
+    const int hi = anch_shr1((int)(old >> 32), (int)(v >> 32));
+    return (long long)(((unsigned long long)(uint32_t)hi << 32) | lo);
+}
+// a score as a state: itself, or the tuple (score, 0)
+template <typename S>
+__device__ __forceinline__ S anch_lift(int v)
+{
+    if constexpr (sizeof(S) == 8) return (S)((unsigned long long)(long long)v << 32);
+    else return v;
+}
+__device__ __forceinline__ int anch_score(int v) { return v; }
+__device__ __forceinline__ int anch_score(long long v) { return (int)(v >> 32); }
+
+template <int C, bool COL, bool MAT, bool STATS = false>
 __device__ __forceinline__ void anch_body(const SwParams &prm, const int flags, const uint32_t *__restrict__ img,
                                           const SwGroup *__restrict__ groups, const SwWave w, int32_t *__restrict__ scores,
-                                          uint32_t *__restrict__ ends, const int16_t *sub)
+                                          uint32_t *__restrict__ ends, const int16_t *sub, uint32_t *__restrict__ lstat = nullptr)
 {
+    using S = typename std::conditional<STATS, long long, int>::type;
+    using U = typename std::conditional<STATS, unsigned long long, uint32_t>::type;
     constexpr int XW = (C + 3) / 4; // dwords holding this lane's C symbols
     const int ge = prm.ge, gf = prm.gf, s_match = prm.hd, s_mis = prm.hd - prm.delta;
     const int lane = threadIdx.x & 63;
@@ -88,8 +116,8 @@ __device__ __forceinline__ void anch_body(const SwParams &prm, const int flags, 
     // state as in the locating fill: z = H + gf at offset r(t) = t |ge|, e = E at offset r(t - 1); no floor
     const int age = -ge;
     const bool free_start = (flags & 1) != 0;
-    int zb = free_start ? gf - age : 2 * gf - age; // Z[r][-1] at r(t - 1)
-    const int zb_inc = free_start ? age : 0;
+    S zb = anch_lift<S>(free_start ? gf - age : 2 * gf - age); // Z[r][-1] at r(t - 1)
+    const S zb_inc = anch_lift<S>(free_start ? age : 0);
     const int ztop = 2 * gf - gl * C * age + (gl - 1) * age; // Z[-1][gl C] at r(gl - 1)
     const int last_lane = la > 0 ? (la - 1) / C : 0;
     const int kcol = (active && gl == last_lane && la > 0) ? la - 1 - last_lane * C : 0;
@@ -102,13 +130,15 @@ __device__ __forceinline__ void anch_body(const SwParams &prm, const int flags, 
         kmask[n] = (kcol >> n) & 1 ? 0xffffffffu : 0u;
         asm volatile("" : "+v"(kmask[n]));
     }
-    int z[C], e[C];
+    S z[C], e[C];
 #pragma unroll
     for (int j = 0; j < C; ++j) {
         z[j] = 0;
-        e[j] = kNegInf;
+        e[j] = anch_lift<S>(kNegInf);
     }
-    int z_last = 0, f_last = 0, diag_in = 0, best = 0, zcorner = 0;
+    S z_last = 0, f_last = 0, diag_in = 0, zcorner = 0;
+    int best = 0;
+    uint32_t best_l = 0; // STATS: L of the cell `best` was first reached in
     constexpr int kPadRow = MAT ? 0 : (int)kAnchRowPad;
     int yc_prev = kPadRow;
     int hit_t = -1, hit_j = 0;
@@ -127,8 +157,8 @@ __device__ __forceinline__ void anch_body(const SwParams &prm, const int flags, 
     auto step = [&]() __attribute__((always_inline)) {
         const int fresh = (t < ly) ? (int)(rows & 0xffu) : kPadRow;
         rows >>= 8;
-        int zl = anch_shr1(zb, z_last);
-        int fl = anch_shr1(zb, f_last);
+        S zl = anch_shr1(zb, z_last);
+        S fl = anch_shr1(zb, f_last);
         int yc = anch_shr1(fresh, yc_prev);
         if (start) {
             zl = zb;
@@ -136,14 +166,14 @@ __device__ __forceinline__ void anch_body(const SwParams &prm, const int flags, 
             yc = fresh;
         }
         if (t == gl) { // row 0 of this lane: row -1 above it, nothing captured yet
-            int v = ztop;
+            S v = anch_lift<S>(ztop);
 #pragma unroll
             for (int j = 0; j < C; ++j) {
                 z[j] = v;
-                e[j] = kNegInf;
-                v += ge;
+                e[j] = anch_lift<S>(kNegInf);
+                v += anch_lift<S>(ge);
             }
-            diag_in = start ? gf - 2 * age : ztop;
+            diag_in = anch_lift<S>(start ? gf - 2 * age : ztop);
             if (COL) {
                 best = ztop + kcol * ge; // H[-1][la-1], found in row -1
                 hit_t = gl - 1;
@@ -151,57 +181,71 @@ __device__ __forceinline__ void anch_body(const SwParams &prm, const int flags, 
                 best = gf + (gl - 1) * age; // H[-1][-1] = 0
                 hit_t = -1;
             }
+            best_l = 0;
         }
         best += age;
-        int zd = diag_in;
+        S zd = diag_in;
         diag_in = zl;
-        int zleft = zl, f = fl;
+        S zleft = zl, f = fl;
         const int ycol = yc * 2; // MAT: byte offset inside a matrix row
+        // STATS: a pair counts in the rows of b only; MAT: identical symbols = this column's row offset equals the step's
+        const uint32_t row_inc = yc != kPadRow ? 1u : 0u;
+        const int yrow = yc != kPadRow ? yc * (kSwMatDim * 2) : -1;
 #pragma unroll
         for (int j = 0; j < C; ++j) {
             const int xs = (int)((xw[j >> 2] >> (8 * (j & 3))) & 0xffu);
-            const int up = z[j];
-            const int ev = max(up, e[j]);
+            const S up = z[j];
+            const S ev = max(up, e[j]);
             f = max(zleft, f);
-            if (j) f += ge;
+            if (j) f += anch_lift<S>(ge);
             const int lag = j ? 0 : age;
-            int s;
-            if constexpr (MAT)
+            S s;
+            if constexpr (MAT && STATS)
+                s = zd + (anch_lift<S>(lag + *reinterpret_cast<const int16_t *>(reinterpret_cast<const char *>(sub) + (xrow[j] + ycol))) +
+                          (S)(xrow[j] == yrow ? 0x1001u : row_inc));
+            else if constexpr (MAT)
                 s = zd + lag + *reinterpret_cast<const int16_t *>(reinterpret_cast<const char *>(sub) + (xrow[j] + ycol));
+            else if constexpr (STATS)
+                s = zd + (anch_lift<S>(xs == yc ? s_match + lag : s_mis + lag) + (S)(xs == yc ? 0x1001u : row_inc));
             else
                 s = zd + (xs == yc ? s_match + lag : s_mis + lag);
-            const int v = max(max(ev, f), s);
-            const int zn = v + (gf + age);
+            const S v = max(max(ev, f), s);
+            const S zn = v + anch_lift<S>(gf + age);
             e[j] = ev;
             z[j] = zn;
             zd = up;
             zleft = zn;
         }
         if (COL) {
-            uint32_t sel[C];
+            U sel[C];
 #pragma unroll
-            for (int j = 0; j < C; ++j) sel[j] = (uint32_t)z[j];
+            for (int j = 0; j < C; ++j) sel[j] = (U)z[j];
 #pragma unroll
             for (int bit = 1, n = 0; bit < C; bit <<= 1, ++n) {
-                const uint32_t on = kmask[n];
+                const U on = (U)(S)(int)kmask[n]; // (STATS: the mask over both words)
 #pragma unroll
                 for (int j = 0; j + bit < C; j += 2 * bit) sel[j] = (on & sel[j + bit]) | (~on & sel[j]);
             }
-            const int zk = (int)sel[0];
+            const S zk = (S)sel[0];
             const bool in_b = t <= t_last; // rows beyond b do not count
-            const bool better = in_b && zk > best;
-            best = better ? zk : best;
+            const bool better = in_b && anch_score(zk) > best;
+            best = better ? anch_score(zk) : best;
+            if constexpr (STATS) best_l = better ? (uint32_t)zk : best_l;
             hit_t = better ? t : hit_t;
             zcorner = in_b ? zk : zcorner;
         } else {
-            int m = z[0];
+            int m = anch_score(z[0]);
 #pragma unroll
-            for (int j = 1; j < C; j += 2) m = j + 1 < C ? max(max(m, z[j]), z[j + 1]) : max(m, z[j]);
+            for (int j = 1; j < C; j += 2) m = j + 1 < C ? max(max(m, anch_score(z[j])), anch_score(z[j + 1])) : max(m, anch_score(z[j]));
             if (m > best) { // a higher score than in any earlier row of this lane's columns
                 int col = 0;
 #pragma unroll
-                for (int j = C - 1; j > 0; --j) col = z[j] == m ? j : col;
-                col = z[0] == m ? 0 : col; // leftmost column of the row that holds it
+                for (int j = C - 1; j > 0; --j) col = anch_score(z[j]) == m ? j : col;
+                col = anch_score(z[0]) == m ? 0 : col; // leftmost column of the row that holds it
+                if constexpr (STATS) { // L of that very cell
+#pragma unroll
+                    for (int j = C - 1; j >= 0; --j) best_l = anch_score(z[j]) == m ? (uint32_t)z[j] : best_l;
+                }
                 best = m;
                 hit_t = t;
                 hit_j = col;
@@ -231,28 +275,34 @@ __device__ __forceinline__ void anch_body(const SwParams &prm, const int flags, 
     uint32_t key;
     if (COL) {
         if (flags & 2) { // GLOBAL: the corner, whatever the column's maximum
-            best = zcorner - gf - t_last * age;
+            best = anch_score(zcorner) - gf - t_last * age;
+            if constexpr (STATS) best_l = (uint32_t)zcorner;
             hit_t = t_last;
         }
         key = ((uint32_t)(hit_t - gl + 1) << kSwLocColBits) | (uint32_t)la;
         const int src = grp * G + last_lane; // the lane that owns the query's last column
         best = __shfl(best, src);
         key = (uint32_t)__shfl((int)key, src);
+        if constexpr (STATS) best_l = (uint32_t)__shfl((int)best_l, src);
     } else {
         key = hit_t < 0 ? 0u : ((uint32_t)(hit_t - gl + 1) << kSwLocColBits) | (uint32_t)(gl * C + hit_j + 1);
         // over the group's lanes by the rule: score, then row, then column (G need not be a power of two)
         for (int o = 1; o < G; o <<= 1) {
             const int ob = __shfl_down(best, o);
             const uint32_t ok = (uint32_t)__shfl_down((int)key, o);
+            uint32_t ol = 0;
+            if constexpr (STATS) ol = (uint32_t)__shfl_down((int)best_l, o);
             if (gl + o < G && (ob > best || (ob == best && ok < key))) {
                 best = ob;
                 key = ok;
+                best_l = ol;
             }
         }
     }
     if (feeder) {
         scores[g.out] = best;
         ends[g.out] = key;
+        if constexpr (STATS) lstat[g.out] = best_l;
     }
 }
 

@@ -27,9 +27,22 @@
 // compare + select.  Every entry of row 0 and column 0 is <= 0 (the create path fills them with min(0, lowest entry)), so
 // the diagonal move into a padding cell is still "without a gain" and the argument above stands word for word.
 //
-// (shared by agx_sw_loc_kernel.hip and agx_sw_loc_mat_kernel.hip; opens an anonymous namespace that the including file
-// closes after its launch helper)
+// STATS (agx_sw_loc_stats_kernel.hip, agx_sw_loc_mat_stats_kernel.hip; DESIGN.md 4.1e): every state is the tuple (score, L),
+// L = matches << 12 | pairs of the best path into it, compared lexicographically and held as ONE int64, score << 32 | L.  L is
+// non-negative and below 2^24 (pairs <= 2560), so the signed 64-bit order is the tuple order, the high word is the score word
+// of the plain build -- rising offset, floor and all -- and a 64-bit add never carries from L into the score.  A diagonal move
+// adds 0x1001 for identical symbols and 1 otherwise, but nothing in a row before or beyond b: the pre-rows of the skew must
+// stay at the floor tuple (0, 0), which a mismatch of 0 or a padding entry of 0 would otherwise beat.  Capture is by the score
+// word alone, exactly as above; L is read at the cell so chosen (the leftmost column of the row that holds the score, whatever
+// L the columns further right hold) and leaves by a vector store to lstat[out].  This build runs the BEGIN pass of a stats
+// batch: there every alignment of the reported score begins in the first cell (DESIGN.md 4.1b), so the tuple maximum at the
+// end cell is over exactly the alignments of the reported span.
+//
+// (shared by agx_sw_loc_kernel.hip, agx_sw_loc_mat_kernel.hip and their _stats builds; opens an anonymous namespace that the
+// including file closes after its launch helper)
 #include "agx_sw.h"
+
+#include <type_traits>
 
 namespace {
 
@@ -40,11 +53,28 @@ __device__ __forceinline__ int loc_shr1(int old, int v)
     // DPP wave_shr:1 -- lane i receives lane i-1's v (a group's first lane substitutes the boundary)
     return __builtin_amdgcn_update_dpp(old, v, 0x138, 0xf, 0xf, false);
 }
-
-template <int C, bool MAT>
-__device__ __forceinline__ void loc_body(const SwParams &prm, const uint32_t *__restrict__ img, const SwGroup *__restrict__ groups,
-                                         const SwWave w, int32_t *__restrict__ scores, uint32_t *__restrict__ ends, const int16_t *sub)
+__device__ __forceinline__ long long loc_shr1(long long old, long long v) // STATS: both words of the tuple
 {
+    const uint32_t lo = (uint32_t)loc_shr1((int)old, (int)v);
+    const int hi = loc_shr1((int)(old >> 32), (int)(v >> 32));
+    return (long long)(((unsigned long long)(uint32_t)hi << 32) | lo);
+}
+// a score as a state: itself, or the tuple (score, 0)
+template <typename S>
+__device__ __forceinline__ S loc_lift(int v)
+{
+    if constexpr (sizeof(S) == 8) return (S)((unsigned long long)(long long)v << 32);
+    else return v;
+}
+__device__ __forceinline__ int loc_score(int v) { return v; }
+__device__ __forceinline__ int loc_score(long long v) { return (int)(v >> 32); }
+
+template <int C, bool MAT, bool STATS = false>
+__device__ __forceinline__ void loc_body(const SwParams &prm, const uint32_t *__restrict__ img, const SwGroup *__restrict__ groups,
+                                         const SwWave w, int32_t *__restrict__ scores, uint32_t *__restrict__ ends, const int16_t *sub,
+                                         uint32_t *__restrict__ lstat = nullptr)
+{
+    using S = typename std::conditional<STATS, long long, int>::type;
     constexpr int XW = (C + 3) / 4; // dwords holding this lane's C symbols
     const int ge = prm.ge, gf = prm.gf, s_match = prm.hd, s_mis = prm.hd - prm.delta;
     const int lane = threadIdx.x & 63;
@@ -76,15 +106,17 @@ __device__ __forceinline__ void loc_body(const SwParams &prm, const uint32_t *__
 
     // state as in agx_sw_kernel.inc: z = H + gf and e = max(P, 0), both with the rising offset r(t) = t |ge|
     const int age = -ge;
-    int floor_t = -age;
-    int zb = gf - age;
-    int z[C], e[C];
+    S floor_t = loc_lift<S>(-age);
+    S zb = loc_lift<S>(gf - age);
+    S z[C], e[C];
 #pragma unroll
     for (int j = 0; j < C; ++j) {
-        z[j] = gf - age;
-        e[j] = -2 * age;
+        z[j] = loc_lift<S>(gf - age);
+        e[j] = loc_lift<S>(-2 * age);
     }
-    int z_last = gf - age, f_last = gf - age, diag_in = gf - 2 * age, best = gf - age;
+    S z_last = loc_lift<S>(gf - age), f_last = loc_lift<S>(gf - age), diag_in = loc_lift<S>(gf - 2 * age);
+    int best = gf - age;
+    uint32_t best_l = 0; // STATS: L of the cell `best` was first reached in
     constexpr int kPadRow = MAT ? 0 : (int)kLocRowPad;
     int yc_prev = kPadRow;
     int hit_t = -1, hit_j = 0; // step and own column at which `best` was first reached
@@ -103,8 +135,8 @@ __device__ __forceinline__ void loc_body(const SwParams &prm, const uint32_t *__
     auto step = [&]() __attribute__((always_inline)) {
         const int fresh = (t < ly) ? (int)(rows & 0xffu) : kPadRow;
         rows >>= 8;
-        int zl = loc_shr1(zb, z_last);
-        int fl = loc_shr1(zb, f_last);
+        S zl = loc_shr1(zb, z_last);
+        S fl = loc_shr1(zb, f_last);
         int yc = loc_shr1(fresh, yc_prev);
         if (start) {
             zl = zb;
@@ -112,38 +144,50 @@ __device__ __forceinline__ void loc_body(const SwParams &prm, const uint32_t *__
             yc = fresh;
         }
         best += age;
-        int zd = diag_in;
+        S zd = diag_in;
         diag_in = zl;
-        int zleft = zl, f = fl;
+        S zleft = zl, f = fl;
         const int ycol = yc * 2; // MAT: byte offset inside a matrix row
+        // STATS: a pair counts in the rows of b only; MAT: identical symbols = this column's row offset equals the step's
+        const uint32_t row_inc = yc != kPadRow ? 1u : 0u;
+        const int yrow = yc != kPadRow ? yc * (kSwMatDim * 2) : -1;
 #pragma unroll
         for (int j = 0; j < C; ++j) {
             const int xs = (int)((xw[j >> 2] >> (8 * (j & 3))) & 0xffu);
-            const int up = z[j];
-            const int ev = max(max(up, e[j]), floor_t);
+            const S up = z[j];
+            const S ev = max(max(up, e[j]), floor_t);
             f = max(zleft, f);
-            if (j) f += ge;
+            if (j) f += loc_lift<S>(ge);
             const int lag = j ? 0 : age;
-            int s;
-            if constexpr (MAT)
+            S s;
+            if constexpr (MAT && STATS)
+                s = zd + (loc_lift<S>(lag + *reinterpret_cast<const int16_t *>(reinterpret_cast<const char *>(sub) + (xrow[j] + ycol))) +
+                          (S)(xrow[j] == yrow ? 0x1001u : row_inc));
+            else if constexpr (MAT)
                 s = zd + lag + *reinterpret_cast<const int16_t *>(reinterpret_cast<const char *>(sub) + (xrow[j] + ycol));
+            else if constexpr (STATS)
+                s = zd + (loc_lift<S>(xs == yc ? s_match + lag : s_mis + lag) + (S)(xs == yc ? 0x1001u : row_inc));
             else
                 s = zd + (xs == yc ? s_match + lag : s_mis + lag);
-            const int v = max(max(ev, f), s);
-            const int zn = v + (gf + age);
+            const S v = max(max(ev, f), s);
+            const S zn = v + loc_lift<S>(gf + age);
             e[j] = ev;
             z[j] = zn;
             zd = up;
             zleft = zn;
         }
-        int m = z[0];
+        int m = loc_score(z[0]);
 #pragma unroll
-        for (int j = 1; j < C; j += 2) m = j + 1 < C ? max(max(m, z[j]), z[j + 1]) : max(m, z[j]);
+        for (int j = 1; j < C; j += 2) m = j + 1 < C ? max(max(m, loc_score(z[j])), loc_score(z[j + 1])) : max(m, loc_score(z[j]));
         if (m > best) { // a higher score than in any earlier row of this lane's columns
             int col = 0;
 #pragma unroll
-            for (int j = C - 1; j > 0; --j) col = z[j] == m ? j : col;
-            col = z[0] == m ? 0 : col; // leftmost column of the row that holds it
+            for (int j = C - 1; j > 0; --j) col = loc_score(z[j]) == m ? j : col;
+            col = loc_score(z[0]) == m ? 0 : col; // leftmost column of the row that holds it
+            if constexpr (STATS) { // L of that very cell
+#pragma unroll
+                for (int j = C - 1; j >= 0; --j) best_l = loc_score(z[j]) == m ? (uint32_t)z[j] : best_l;
+            }
             best = m;
             hit_t = t;
             hit_j = col;
@@ -151,8 +195,8 @@ __device__ __forceinline__ void loc_body(const SwParams &prm, const uint32_t *__
         z_last = zleft;
         f_last = f;
         yc_prev = yc;
-        floor_t += age;
-        zb += age;
+        floor_t += loc_lift<S>(age);
+        zb += loc_lift<S>(age);
         ++t;
     };
 
@@ -178,14 +222,18 @@ __device__ __forceinline__ void loc_body(const SwParams &prm, const uint32_t *__
     for (int o = 1; o < G; o <<= 1) {
         const int ob = __shfl_down(best, o);
         const uint32_t ok = (uint32_t)__shfl_down((int)key, o);
+        uint32_t ol = 0;
+        if constexpr (STATS) ol = (uint32_t)__shfl_down((int)best_l, o);
         if (gl + o < G && (ob > best || (ob == best && ok < key))) {
             best = ob;
             key = ok;
+            best_l = ol;
         }
     }
     if (feeder) {
         scores[g.out] = best;
         ends[g.out] = key;
+        if constexpr (STATS) lstat[g.out] = best_l;
     }
 }
 

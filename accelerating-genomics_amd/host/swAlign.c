@@ -1,5 +1,5 @@
 /*
- * swAlign <file_path> [local|global|fit|extend|extend-query]: where the best alignment of every pair ends and begins
+ * swAlign <file_path> [local|global|fit|extend|extend-query][+stats]: where the best alignment of every pair ends and begins
  * (default: local; the other modes are include/agx.h's "Alignment modes").
  * swAlign <file_path> <mode> <matrix_file> [gap_open gap_extend]: the same under a substitution matrix (gaps default to
  * -11 -1).  The matrix file is the usual text layout: '#' comment lines, one line of symbols, then one row per symbol
@@ -11,6 +11,10 @@
  * a = the pair's first line (the query), b = its second (the target); positions are 0-based and inclusive, all -1 when
  * the score is 0 (include/agx.h, "Alignment coordinates").  The fill and the begin pass run on GPU 0 through libagx;
  * there is no CPU path.
+ * The mode word may carry the suffix "+stats" (local+stats, fit+stats ...): every line then ends in two more numbers,
+ *     score a_begin a_end b_begin b_end matches pairs
+ * the identical symbols and the aligned pairs of that alignment (include/agx.h, "Alignment statistics"; queries up to
+ * AGX_SW_STATS_MAX_QUERY_LEN).  Without the suffix the output is what it was.
  *   AGX_CLI_CHUNK_PAIRS   pairs per agx_sw_align call (default 262144)
  */
 #include <stdio.h>
@@ -104,14 +108,22 @@ int main(int argc, char *argv[])
 {
     static const char *const words[] = {"local", "global", "fit", "extend", "extend-query"}; /* AGX_SW_MODE_* 0..4 */
     int mode = argc == 2 ? AGX_SW_MODE_LOCAL : -1;
-    for (int k = 0; (argc == 3 || argc == 4 || argc == 6) && k < 5; k++)
+    int with_stats = 0;
+    for (int k = 0; (argc == 3 || argc == 4 || argc == 6) && k < 5; k++) {
+        const size_t n = strlen(words[k]);
         if (!strcmp(argv[2], words[k])) mode = k;
+        if (!strncmp(argv[2], words[k], n) && !strcmp(argv[2] + n, "+stats")) {
+            mode = k;
+            with_stats = 1;
+        }
+    }
     if (mode < 0) {
         fprintf(stderr,
                 "Usage: %s <file_path> [local|global|fit|extend|extend-query]\n"
                 "       %s <file_path> <mode> <matrix_file> [gap_open gap_extend]\n"
                 "With a matrix file ('#' comments, a line of symbols, a row per symbol: the symbol and its integers; symmetric,\n"
-                "letters in either case) gaps default to -11 -1 and the line ends (\\n, \\r\\n) are stripped, not aligned.\n",
+                "letters in either case) gaps default to -11 -1 and the line ends (\\n, \\r\\n) are stripped, not aligned.\n"
+                "<mode>+stats (local+stats, fit+stats ...): every line ends in two more numbers, matches and aligned pairs.\n",
                 argv[0], argv[0]);
         return 1;
     }
@@ -153,7 +165,8 @@ int main(int argc, char *argv[])
         }
         if (t->n_pairs > 0) {
             agx_sw_hit *hits = (agx_sw_hit *)malloc(sizeof(agx_sw_hit) * (size_t)t->n_pairs);
-            if (!hits) {
+            agx_sw_stat *stats = with_stats ? (agx_sw_stat *)malloc(sizeof(agx_sw_stat) * (size_t)t->n_pairs) : NULL;
+            if (!hits || (with_stats && !stats)) {
                 fprintf(stderr, "swAlign: out of memory\n");
                 status = EXIT_FAILURE;
             }
@@ -166,15 +179,25 @@ int main(int argc, char *argv[])
                     if (t->len[k] && t->bases[t->off[k] + t->len[k] - 1] == '\n') t->len[k]--;
                     if (t->len[k] && t->bases[t->off[k] + t->len[k] - 1] == '\r') t->len[k]--;
                 }
-            if (!status && (with_matrix ? agx_sw_align_matrix(ctx, &matrix, mode, AGX_SW_ALIGN_SPANS, t->bases, t->off, t->len, t->n_pairs, hits)
+            if (!status && with_stats) {
+                if (agx_sw_align_stats(ctx, NULL, with_matrix ? &matrix : NULL, mode, t->bases, t->off, t->len, t->n_pairs, hits, stats) != AGX_OK) {
+                    fprintf(stderr, "swAlign: %s\n", agx_last_error());
+                    status = EXIT_FAILURE;
+                }
+            } else if (!status && (with_matrix ? agx_sw_align_matrix(ctx, &matrix, mode, AGX_SW_ALIGN_SPANS, t->bases, t->off, t->len, t->n_pairs, hits)
                                         : agx_sw_align_mode(ctx, NULL, mode, AGX_SW_ALIGN_SPANS, t->bases, t->off, t->len, t->n_pairs, hits)) != AGX_OK) {
                 fprintf(stderr, "swAlign: %s\n", agx_last_error());
                 status = EXIT_FAILURE;
             }
-            if (!status)
+            if (!status && with_stats)
+                for (int64_t p = 0; p < t->n_pairs; p++)
+                    printf("%d %d %d %d %d %d %d\n", hits[p].score, hits[p].a_begin, hits[p].a_end, hits[p].b_begin, hits[p].b_end, stats[p].matches,
+                           stats[p].pairs);
+            else if (!status)
                 for (int64_t p = 0; p < t->n_pairs; p++)
                     printf("%d %d %d %d %d\n", hits[p].score, hits[p].a_begin, hits[p].a_end, hits[p].b_begin, hits[p].b_end);
             free(hits);
+            free(stats);
         }
         agx_sw_text_free(t);
     }

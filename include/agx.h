@@ -263,6 +263,43 @@ int agx_sw_batch_create_align_matrix(agx_ctx *ctx, const agx_sw_matrix *matrix, 
 int agx_sw_align_matrix(agx_ctx *ctx, const agx_sw_matrix *matrix, int mode, int what, const uint8_t *bases, const uint64_t *off,
                         const uint32_t *len, int64_t n_pairs, agx_sw_hit *hits);
 
+/*
+ * Alignment statistics: matches and aligned pairs of the reported alignment, still without a traceback.
+ * For a pair, let score, a_begin..a_end, b_begin..b_end be exactly what an AGX_SW_ALIGN_SPANS batch of the same mode and
+ * scoring reports.  Among the alignments that attain `score` and consume exactly a[a_begin..a_end] and b[b_begin..b_end],
+ * take the one with the most matches, among those the one with the most pairs:
+ *   pairs   = its diagonal moves (an a symbol aligned with a b symbol)
+ *   matches = the pairs of identical input bytes; under a matrix, of identical symbol codes, whatever that entry scores
+ * Nothing consumed gives {0, 0}: a LOCAL or EXTEND score of 0, an empty side (GLOBAL included), b_end = -1.
+ * Everything else is the caller's arithmetic.  With ca = a_end - a_begin + 1 and cb = b_end - b_begin + 1:
+ *   alignment columns = ca + cb - pairs   (so "most pairs" is "fewest columns")
+ *   mismatches        = pairs - matches
+ *   gap cells         = ca + cb - 2 pairs
+ *   identity          = matches / columns
+ * The number of gap OPENS is not reported (it is not determined under a matrix or with gap_open = 0).
+ * The query limit of a stats batch is AGX_SW_STATS_MAX_QUERY_LEN (the widest lane classes are not built with statistics);
+ * a longer query fails the create with AGX_E_LIMIT.  The target limit stays AGX_SW_ALIGN_MAX_TARGET_LEN.
+ */
+typedef struct agx_sw_stat {
+    int32_t matches, pairs;
+} agx_sw_stat;
+#define AGX_SW_STATS_MAX_QUERY_LEN 1792 /* 64 lanes x 28 columns */
+/* A stats batch is an AGX_SW_ALIGN_SPANS batch of `mode` that can also answer agx_sw_batch_stats.  Exactly one way of scoring:
+ * matrix != NULL (then scoring must be NULL: AGX_E_ARG otherwise), else scoring, else the reference's constants.
+ * agx_sw_batch_launch (re)launches, agx_sw_batch_scores returns the mode's score, agx_sw_batch_hits what a SPANS batch returns,
+ * agx_sw_batch_bind_scores is accepted and ignored.  ctx may be NULL: plan only. */
+int agx_sw_batch_create_align_stats(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matrix *matrix, int mode, const uint8_t *bases,
+                                    const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_batch **out);
+/* Waits for the launched fill and writes one stat (and, hits != NULL, one hit) per pair in the caller's pair order.  Every stat
+ * is checked before it is returned -- 0 <= matches <= pairs <= min(ca, cb), and under match/mismatch scoring the score minus
+ * matches, mismatches and gap cells must be a whole number of gap opens between "1 if there is a gap cell" and "one per gap
+ * cell" -- AGX_E_INTERNAL naming the pair otherwise: no stat is returned that the library cannot vouch for.
+ * AGX_E_ARG on a batch that was not created by agx_sw_batch_create_align_stats. */
+int agx_sw_batch_stats(agx_sw_batch *b, agx_sw_hit *hits /* may be NULL */, agx_sw_stat *stats);
+/* One-shot: create_align_stats + launch + stats + destroy. */
+int agx_sw_align_stats(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matrix *matrix, int mode, const uint8_t *bases,
+                       const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_hit *hits /* may be NULL */, agx_sw_stat *stats);
+
 /* One-shot: create + launch + scores + destroy. */
 int agx_sw_score(agx_ctx *ctx, const uint8_t *bases, const uint64_t *off, const uint32_t *len, int64_t n_pairs,
                  int32_t *scores);

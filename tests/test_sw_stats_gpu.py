@@ -1,0 +1,350 @@
+"""Alignment statistics on the device (agx_sw_batch_create_align_stats / agx_sw_batch_stats / agx_sw_align_stats): every
+comparison is exact -- all five hit fields and both stat fields of every pair -- against the existing by-definition checkers
+for score and span and tests/sw_stats_ref.py for matches and pairs."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import accelerating_genomics_amd.api as agx
+import accelerating_genomics_amd.synth as synth
+from tests import sw_stats_ref as ref
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ACGT = np.frombuffer(b"ACGT", np.uint8)
+AMINO = b"ARNDCQEGHILKMFPSTWYV"
+HIT_FIELDS = ("score", "a_begin", "a_end", "b_begin", "b_end")
+STAT_FIELDS = ("matches", "pairs")
+MODES = pytest.mark.parametrize("mode", ref.MODES, ids=[ref.MODE_NAMES[m] for m in ref.MODES])
+TIE_SCORINGS = [(1, -1, -3, -1), (1, 0, 0, 0), (1, -2, 0, -1), (2, -3, -5, -2)]
+QMAX = agx.SW_STATS_MAX_QUERY_LEN
+TOP_CLASS = QMAX // 64  # the widest lane class of the stats builds
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    with agx.Context(0) as c:
+        yield c
+
+
+def _same(got, want, fields, what=""):
+    for f in fields:
+        bad = np.nonzero(got[f] != want[f])[0]
+        assert bad.size == 0, "%s %s: %d pairs differ, first %d: got %s, want %s" % (what, f, bad.size, bad[0], got[bad[0]], want[bad[0]])
+
+
+_cache = {}
+
+
+def _shared(name, make):
+    if name not in _cache:
+        _cache[name] = make()
+    return _cache[name]
+
+
+def _expected(name, b, mode, scoring=None, matrix=None):
+    return _shared(("want", name, mode, scoring), lambda: ref.expected(b, mode, scoring, matrix))
+
+
+def _batch(ctx, b, mode, scoring=None, matrix=None, relaunch=False):
+    dev = ctx.sw_batch(b, scoring=scoring, matrix=matrix, mode=mode, stats=True)
+    try:
+        dev.launch()
+        hits, stats = dev.stats()
+        assert np.array_equal(dev.scores(), hits["score"])  # agx_sw_batch_scores returns the mode's score
+        _same(dev.hits(), hits, HIT_FIELDS, "agx_sw_batch_hits of a stats batch")
+        if relaunch:
+            dev.launch()
+            h2, s2 = dev.stats()
+            _same(h2, hits, HIT_FIELDS, "relaunch")
+            _same(s2, stats, STAT_FIELDS, "relaunch")
+        return hits, stats
+    finally:
+        dev.close()
+
+
+def _check(ctx, name, b, mode, scoring=None, matrix=None, oneshot=False):
+    want_hits, smax, smin = _expected(name, b, mode, scoring, matrix)
+    what = "%s %s %s" % (name, ref.MODE_NAMES[mode], scoring)
+    hits, stats = _batch(ctx, b, mode, scoring, matrix)
+    _same(hits, want_hits, HIT_FIELDS, what + " batch")
+    _same(stats, smax, STAT_FIELDS, what + " batch")
+    if oneshot:
+        hits, stats = ctx.sw_align_stats(b, scoring, mode, matrix)
+        _same(hits, want_hits, HIT_FIELDS, what + " one-shot")
+        _same(stats, smax, STAT_FIELDS, what + " one-shot")
+    return want_hits, smax, smin
+
+
+def _rand(rng, n):
+    return ACGT[rng.integers(0, 4, size=n)].tobytes()
+
+
+def _up_to_40():
+    rng = np.random.default_rng(31)
+    seqs = []
+    for la in range(41):
+        for lb in range(41):
+            a = _rand(rng, la)
+            if (la + lb) % 2:
+                t = _rand(rng, lb)
+            else:  # b from copies of a: the maximum is reached many times
+                t = (a * (lb // max(la, 1) + 1))[:lb]
+            seqs += [a, t]
+    return synth.sw_from_seqs(seqs)
+
+
+@MODES
+def test_every_length_pair_up_to_40(ctx, mode):
+    """len(a) x len(b) over 0..40 x 0..40 (the batch of tests/test_sw_modes_gpu.py): empty sides, fewer rows than the skew,
+    every narrow class.  Batch and one-shot."""
+    _check(ctx, "up_to_40", _shared("up_to_40", _up_to_40), mode, oneshot=True)
+
+
+def _last_column():
+    rng = np.random.default_rng(33)
+    seqs = []
+    # (the stats builds stop at TOP_CLASS columns per lane: the lengths either side of one and two lanes of it as well)
+    for la in (38, 39, 40, 41, 76, 77, 150, 151, 152, 300, 512, TOP_CLASS - 1, TOP_CLASS, TOP_CLASS + 1, 2 * TOP_CLASS, 2 * TOP_CLASS + 1):
+        a = _rand(rng, la)
+        for lb in range(1, 61):
+            kind = lb % 3
+            if kind == 0:
+                t = _rand(rng, lb)
+            elif kind == 1:  # the end of a: the last column carries the maximum in the last rows
+                t = a[-lb:]
+            else:  # the end of a, then a tail
+                t = (a[-(lb - lb // 3):] + _rand(rng, lb))[:lb]
+            seqs += [a, t]
+    return synth.sw_from_seqs(seqs)
+
+
+@pytest.mark.parametrize("mode", [ref.GLOBAL, ref.FIT, ref.EXTEND_QUERY, ref.LOCAL], ids=["global", "fit", "extend-query", "local"])
+def test_last_column_in_every_lane_position(ctx, mode):
+    """The query's last column at the end of a lane, at its start, in the group's only lane and in its last one, against
+    targets of 1..60 rows: the COL modes and LOCAL."""
+    _check(ctx, "last_column", _shared("last_column", _last_column), mode)
+
+
+def _tie_heavy():
+    rng = np.random.default_rng(32)
+    seqs = []
+    for k in range(600):
+        la, lb = int(rng.integers(1, 200)), int(rng.integers(1, 200))
+        kind = k % 6
+        if kind == 0:  # homopolymers: every tie at once
+            a, t = b"A" * la, b"A" * lb
+        elif kind == 1:  # tandem repeats of period 2..4
+            unit = _rand(rng, int(rng.integers(2, 5)))
+            a, t = (unit * la)[:la], (unit * lb)[:lb]
+        elif kind == 2:  # the same motif twice in b
+            m = _rand(rng, min(la, 30))
+            a, t = m, _rand(rng, 5) + m + _rand(rng, int(rng.integers(0, 40))) + m + _rand(rng, 3)
+        elif kind == 3:  # ... twice in a
+            m = _rand(rng, min(lb, 30))
+            a, t = _rand(rng, 5) + m + _rand(rng, int(rng.integers(0, 40))) + m + _rand(rng, 3), m
+        elif kind == 4:  # random pairs
+            a, t = _rand(rng, la), _rand(rng, lb)
+        else:
+            # Two optimal alignments of ONE span that differ in matches need more than the kinds above under gap costs such
+            # as -3/-1: between two flanks, k mismatches in a row tie with two gaps of g cells around k - g matches where
+            # k X = (k - g) M + 2 (O + g E).  (1, -1, -3, -1): g = 2, k = 6; (2, -3, -5, -2): g = 5, k = 8.
+            g, w = ((2, b"AACC"), (5, b"ACA"))[(k // 6) % 2]
+            f1, f2 = _rand(rng, int(rng.integers(15, 40))), _rand(rng, int(rng.integers(15, 40)))
+            a, t = f1 + b"G" * g + w + f2, f1 + w + b"T" * g + f2
+        seqs += [a, t]
+    return synth.sw_from_seqs(seqs)
+
+
+@MODES
+@pytest.mark.parametrize("scoring", TIE_SCORINGS, ids=str)
+def test_tie_heavy_inputs(ctx, mode, scoring):
+    """600 pairs of lengths 1..200 (homopolymers, tandem repeats, a motif twice in b, twice in a, random pairs, and flanked
+    regions where a run of mismatches ties with two gaps) under four scorings; under (1, -2, 0, -1) a mismatch ties with two gap cells, so "most
+    pairs" decides.  The cap: in every (mode, scoring) at least one pair has optimal alignments of its span that differ in
+    (matches, pairs) -- otherwise the rule was never exercised."""
+    _, smax, smin = _check(ctx, "tie_heavy", _shared("tie_heavy", _tie_heavy), mode, scoring)
+    differ = int(np.count_nonzero((smax["matches"] != smin["matches"]) | (smax["pairs"] != smin["pairs"])))
+    print("tie rule exercised in %d of %d pairs (%s, %s)" % (differ, smax.size, ref.MODE_NAMES[mode], scoring))
+    assert differ >= 1
+
+
+def _capture():
+    """Equal scores further on with more identical symbols: the end cell must not move."""
+    rng = np.random.default_rng(35)
+    seqs = []
+    for k in range(60):
+        m = _rand(rng, int(rng.integers(6, 30)))
+        junk = b"GGGG" * int(rng.integers(1, 5))
+        # the motif twice in b; around the second copy a match and a mismatch on either side: +1 -1, the same score, more matches
+        seqs += [b"CA" + m + b"AC", b"TT" + m + b"TT" + junk + b"CT" + m + b"TC"]
+        # pinned start: the score of the motif again two pairs further on, one more match
+        seqs += [m + b"AC" + _rand(rng, 3), m + b"TC" + _rand(rng, 5)]
+        # the last column's maximum in several rows: the motif in tandem, and with a unit of it repeated
+        seqs += [m, m * int(rng.integers(2, 5))]
+        seqs += [m, _rand(rng, 4) + m + m[-3:] * 4]
+    return synth.sw_from_seqs(seqs)
+
+
+@MODES
+@pytest.mark.parametrize("scoring", [(1, -1, -3, -1), (1, 0, 0, 0)], ids=str)
+def test_capture_is_by_score_alone(ctx, mode, scoring):
+    """The hits of a stats batch are those of a plain SPANS batch of the same mode on the same input, field for field, where
+    a later cell holds the same score with more matches (LOCAL, EXTEND) and where the query's last column holds its maximum in
+    several rows (FIT, EXTEND_QUERY); the stats are the checker's."""
+    b = _shared("capture", _capture)
+    hits, _ = _batch(ctx, b, mode, scoring)
+    plain = ctx.sw_align(b, agx.SW_ALIGN_SPANS, scoring, mode=mode)
+    _same(hits, plain, HIT_FIELDS, "stats batch against a plain SPANS batch")
+    _check(ctx, "capture", b, mode, scoring)
+
+
+@MODES
+def test_field_width_longest_query_against_itself(ctx, mode):
+    """a = b of AGX_SW_STATS_MAX_QUERY_LEN symbols: matches = pairs = that length, the fields' largest values."""
+    b = _shared("self", lambda: synth.sw_from_seqs([_rand(np.random.default_rng(36), QMAX)] * 2))
+    hits, stats = _batch(ctx, b, mode)
+    assert tuple(hits[0]) == (QMAX, 0, QMAX - 1, 0, QMAX - 1) and tuple(stats[0]) == (QMAX, QMAX)
+    _check(ctx, "self", b, mode)
+
+
+@pytest.mark.parametrize("mode", [ref.FIT, ref.LOCAL], ids=["fit", "local"])
+def test_field_width_longest_query_in_the_longest_target(ctx, mode):
+    """The longest query against a target of 65 535 symbols that contains it once."""
+    def make():
+        rng = np.random.default_rng(37)
+        a = _rand(rng, QMAX)
+        return synth.sw_from_seqs([a, _rand(rng, 40000) + a + _rand(rng, 65535 - 40000 - QMAX)])
+
+    b = _shared("in_target", make)
+    assert list(b.len) == [QMAX, 65535]
+    hits, stats = _batch(ctx, b, mode)
+    assert tuple(hits[0]) == (QMAX, 0, QMAX - 1, 40000, 40000 + QMAX - 1) and tuple(stats[0]) == (QMAX, QMAX)
+    _check(ctx, "in_target", b, mode)
+
+
+def _blosum62():
+    path = os.path.join(ROOT, "tests", "golden", "blosum62.mat")
+    rows = [l.split() for l in open(path) if l.strip() and not l.startswith("#")]
+    alphabet = "".join(rows[0]).encode()
+    scores = [[int(v) for v in r[1:]] for r in rows[1:]]
+    assert [r[0] for r in rows[1:]] == rows[0]
+    return agx.SwMatrix.build(alphabet, scores, -11, -1)
+
+
+def _protein_pairs(n, lo, hi, seed):
+    rng = np.random.default_rng(seed)
+    aa = np.frombuffer(AMINO, np.uint8)
+    seqs = []
+    for k in range(n):
+        la, lb = int(rng.integers(lo, hi + 1)), int(rng.integers(lo, hi + 1))
+        a = aa[rng.integers(0, 20, size=la)]
+        if k % 3 == 0:  # a mutated copy: 10 % substitutions, a few indels, cut or padded to its length
+            t = a.copy()
+            sub = rng.random(t.size) < 0.1
+            t[sub] = aa[rng.integers(0, 20, size=int(sub.sum()))]
+            for _ in range(int(rng.integers(0, 4))):
+                at = int(rng.integers(0, t.size + 1))
+                t = np.concatenate([t[:at], aa[rng.integers(0, 20, size=int(rng.integers(1, 6)))], t[at:]]) if rng.random() < 0.5 else np.delete(t, slice(at, at + 3))
+            t = np.concatenate([t, aa[rng.integers(0, 20, size=lb)]])[:lb]
+        else:
+            t = aa[rng.integers(0, 20, size=lb)]
+        seqs += [a.tobytes(), t.tobytes()]
+    return synth.sw_from_seqs(seqs)
+
+
+@MODES
+def test_blosum62(ctx, mode):
+    """2 000 protein pairs of lengths 1..300, a third of them mutated copies, BLOSUM62 with gaps -11 / -1."""
+    b = _shared("protein", lambda: _protein_pairs(2000, 1, 300, 41))
+    _check(ctx, "protein", b, mode, matrix=_shared("blosum62", _blosum62))
+
+
+EDGE_MATRICES = {
+    # every entry positive: padding scores 0 and ties with its diagonal neighbour
+    "all_positive": lambda: agx.SwMatrix.build(b"ACGT", [[3 if a == c else 1 for c in range(4)] for a in range(4)], -2, -1),
+    # identical symbols score 0: a match is identical codes even where the entry is <= 0
+    "zero_diagonal": lambda: agx.SwMatrix.build(b"ACGT", [[0 if a == c else (2 if (a ^ c) == 1 else -3) for c in range(4)] for a in range(4)], -4, -1),
+}
+
+
+@MODES
+@pytest.mark.parametrize("which", sorted(EDGE_MATRICES))
+def test_edge_matrices(ctx, mode, which):
+    b = _shared("edge", lambda: synth.sw_pairs(600, 1, 120, seed=42, related_frac=0.5, newline=False))
+    m = _shared(which, EDGE_MATRICES[which])
+    _, smax, _ = _check(ctx, "edge_" + which, b, mode, matrix=m)
+    if which == "zero_diagonal" and mode == ref.GLOBAL:
+        assert int(smax["matches"].max()) > 0
+
+
+def test_relaunch_side_by_side_and_context_lifetime():
+    """Relaunch gives the same answer; a stats batch and a SPANS batch from one context do not disturb each other; the context
+    may be destroyed before the batch."""
+    b = synth.sw_pairs(1500, 1, 300, seed=43, related_frac=0.5)
+    c = agx.Context(0)
+    for mode in ref.MODES:
+        want_hits, smax, _ = ref.expected(b, mode)
+        st = c.sw_batch(b, mode=mode, stats=True)
+        sp = c.sw_batch(b, align=agx.SW_ALIGN_SPANS, mode=mode)
+        try:
+            st.launch()
+            sp.launch()
+            hits, stats = st.stats()
+            _same(sp.hits(), want_hits, HIT_FIELDS, "SPANS beside stats")
+            _same(hits, want_hits, HIT_FIELDS, "stats beside SPANS")
+            _same(stats, smax, STAT_FIELDS, "stats beside SPANS")
+            st.launch()
+            sp.launch()
+            _same(sp.hits(), want_hits, HIT_FIELDS, "SPANS relaunch")
+            h2, s2 = st.stats()
+            _same(h2, want_hits, HIT_FIELDS, "stats relaunch")
+            _same(s2, smax, STAT_FIELDS, "stats relaunch")
+        finally:
+            sp.close()
+            if mode != ref.MODES[-1]:
+                st.close()
+    c.close()  # the last stats batch outlives its context
+    try:
+        st.launch()
+        hits, stats = st.stats()
+        _same(hits, want_hits, HIT_FIELDS, "after the context")
+        _same(stats, smax, STAT_FIELDS, "after the context")
+    finally:
+        st.close()
+
+
+def _write_pairs(path, b):
+    with open(path, "wb") as f:
+        f.write(b"%d\n" % (2 * b.n_pairs))
+        for k in range(2 * b.n_pairs):
+            f.write(b.bases[int(b.off[k]):int(b.off[k]) + int(b.len[k])].tobytes() + b"\n")
+
+
+@pytest.mark.parametrize("word,mode,with_matrix", [("local", ref.LOCAL, False), ("global", ref.GLOBAL, False), ("fit", ref.FIT, True),
+                                                   ("extend", ref.EXTEND, True)])
+def test_swalign_stats_suffix(tmp_path, word, mode, with_matrix):
+    """swAlign <file> <mode>+stats on a 200-pair file: the first five columns are byte for byte what swAlign <file> <mode>
+    prints (with a matrix: swAlign <file> <mode> <matrix_file>), the last two are the checker's."""
+    exe = os.path.join(ROOT, "accelerating-genomics_amd", "bin", "swAlign")
+    path = str(tmp_path / "pairs.in")
+    if with_matrix:
+        b = _protein_pairs(200, 1, 200, 44)
+        extra = [os.path.join(ROOT, "tests", "golden", "blosum62.mat")]
+    else:
+        b = synth.sw_pairs(200, 1, 200, seed=44, related_frac=0.5, newline=False)
+        extra = []
+    _write_pairs(path, b)
+    plain = subprocess.run([exe, path, word] + extra, capture_output=True, timeout=300, check=True).stdout.splitlines()
+    got = subprocess.run([exe, path, word + "+stats"] + extra, capture_output=True, timeout=300, check=True).stdout.splitlines()
+    assert len(plain) == len(got) == 200
+    if with_matrix:  # the command line strips the line ends under a matrix
+        _, smax, _ = ref.expected(b, mode, matrix=_shared("blosum62", _blosum62))
+    else:  # ... and keeps them as symbols otherwise: the batch as the file says it
+        _, fb, _ = agx.read_sw_text(path)
+        _, smax, _ = ref.expected(fb, mode)
+    for p in range(200):
+        assert got[p] == plain[p] + b" %d %d" % (smax[p]["matches"], smax[p]["pairs"]), p
