@@ -700,6 +700,10 @@ int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matri
     // ... with column classes when the wrapping column's diagonal constant, mismatch + |gf| - 3 |ge|, is not negative
     if (rising && prm.hd - prm.delta + 3 * prm.ge >= 0) rising = 4;
     if (const char *e = agx_tune("AGX_SW_RISE")) rising = e[0] == '0' ? 0 : e[0] == '1' && rising ? 1 : rising;
+    // (what tests/test_sw_range_cpu.py reads: that a batch one symbol beyond an edge of the rules above changes its kernel)
+    if (trace)
+        fprintf(stderr, "[agx_sw_batch_create] family %d rising %d: longest shorter side %u, longest longer side %u\n", family, rising,
+                longest_short, longest_long);
     const bool packed = family >= 1 && family <= 3;
     const bool coded_plan = family == 2 || family == 3; // the packed plan of the biased fill (one launch for all classes)
     const double *costs = stats == 2 ? kSwStatsClassCost : class_costs(family); // (the stats builds: fewer classes)
