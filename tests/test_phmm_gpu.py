@@ -134,26 +134,31 @@ def test_striped_and_single_pass_pairs_in_one_batch(ctx, oracle):
         st = int(rng.integers(0, src.size - R))
         q = lambda lo, hi: (rng.integers(lo, hi, size=R) + 33).astype(np.uint8).tobytes()
         reads.append((src[st : st + R].tobytes(), q(6, 42), q(39, 46), q(39, 46), bytes([43]) * R))
-    b = synth.phmm_from_regions([(reads, haps)])
-    b.hap_bases[rng.random(b.hap_bases.size) < 0.01] = ord("N")
-    s_ref, l_ref = oracle.phmm_batch(b, 0)
-    for prec, tol in ((agx.PHMM_F64, 0.0), (agx.PHMM_F64_FMA, 1e-12), (agx.PHMM_F32, 1e-6), (agx.PHMM_F32_FMA, 1e-6)):
-        dev = ctx.phmm_batch(b, prec)
+    plain = synth.phmm_from_regions([(reads, haps)])
+    with_n = synth.phmm_from_regions([(reads, haps)])
+    with_n.hap_bases[rng.random(with_n.hap_bases.size) < 0.01] = ord("N")
+    # with N in the haplotypes the main launch is the selecting fill's (plain packed cell); without, the striped launch runs
+    # beside a looked-up-prior main launch (fast packed cell)
+    for b in (with_n, plain):
+        assert (bytes(b.hap_bases).count(b"N") > 0) == (b is with_n)
+        s_ref, l_ref = oracle.phmm_batch(b, 0)
+        for prec, tol in ((agx.PHMM_F64, 0.0), (agx.PHMM_F64_FMA, 1e-12), (agx.PHMM_F32, 1e-6), (agx.PHMM_F32_FMA, 1e-6)):
+            dev = ctx.phmm_batch(b, prec)
+            dev.launch()
+            dev.launch()  # the boundary scratch is reused
+            l, s = dev.results()
+            assert dev.info().n_launches >= 2
+            dev.close()
+            if prec == agx.PHMM_F64:
+                assert np.array_equal(s, s_ref) and np.array_equal(l, l_ref)
+            else:
+                assert relerr(l, l_ref) <= tol
+        s3, l3 = oracle.phmm_batch(b, 3)
+        dev = ctx.phmm_batch(b, agx.PHMM_F64 | agx.PHMM_GATK_PRIOR)
         dev.launch()
-        dev.launch()  # the boundary scratch is reused
-        l, s = dev.results()
-        assert dev.info().n_launches >= 2
+        _, s = dev.results()
         dev.close()
-        if prec == agx.PHMM_F64:
-            assert np.array_equal(s, s_ref) and np.array_equal(l, l_ref)
-        else:
-            assert relerr(l, l_ref) <= tol
-    s3, l3 = oracle.phmm_batch(b, 3)
-    dev = ctx.phmm_batch(b, agx.PHMM_F64 | agx.PHMM_GATK_PRIOR)
-    dev.launch()
-    _, s = dev.results()
-    dev.close()
-    assert np.array_equal(s, s3)
+        assert np.array_equal(s, s3)
 
 
 def test_striped_gatk_prior_on_the_longest_reads(ctx, oracle):
@@ -681,3 +686,55 @@ def test_bound_results_arrive_in_the_callers_page_locked_array(ctx, oracle):
         dev.results((out, None), want_sums=False)
         assert relerr(out, ref) <= 1e-6
         dev.close()
+
+
+ODD_BYTES = [ord(c) for c in "acgtnRY-*"] + [0x01, 0xff]
+
+
+@pytest.mark.parametrize("byte", ODD_BYTES, ids=lambda v: "0x%02x" % v)
+def test_bytes_outside_the_alphabets(ctx, oracle, byte):
+    """One byte outside ACGTN (reads) / ACGT (haplotypes) -- lower case, IUPAC codes, gap characters, control and high bytes --
+    as the first byte of the first sequence or the last of the last, in a read or in a haplotype, takes the batch off the
+    plain-DNA kernels.  The reference compares bytes (n is not N, a matches only a): every precision at its usual bar."""
+    base = synth.phmm_regions(2, 3, 3, 40, 120, seed=600, jitter=9)
+    for track, at in (("read_bases", 0), ("read_bases", -1), ("hap_bases", 0), ("hap_bases", -1)):
+        b = synth.PhmmBatch(*(getattr(base, f).copy() for f in ("read_bases", "q_base", "q_ins", "q_del", "q_gcp", "roff", "hap_bases", "hoff", "rreg", "hreg")))
+        getattr(b, track)[at] = byte
+        s_ref, l_ref = oracle.phmm_batch(b, 0)
+        assert np.all(np.isfinite(l_ref))
+        dev = ctx.phmm_batch(b, agx.PHMM_F64)
+        dev.launch()
+        l, s = dev.results()
+        dev.close()
+        assert np.array_equal(s, s_ref) and np.array_equal(l, l_ref), (track, at)
+        assert relerr(ctx.phmm_forward(b, agx.PHMM_F64_FMA), l_ref) <= 1e-12, (track, at)
+        for prec in (agx.PHMM_F32, agx.PHMM_F32_FMA):
+            assert relerr(ctx.phmm_forward(b, prec), l_ref) <= 1e-6, (track, at, prec)
+
+
+def test_a_quality_byte_below_the_phred_range_keeps_trains_out(ctx, oracle):
+    """A quality byte below '!' is a "probability" above 1: a first read whose state ran to infinity there would hand NaN to
+    the second read of a train.  With AGX_PHMM_TRAINS_ON such a batch must plan as with trains off (the same waves) and give the
+    oracle's results wherever those are finite; the same batch without the byte does form trains."""
+    clean = synth.phmm_regions(5, 7, 5, 100, 300, seed=91)
+    wild = synth.phmm_regions(5, 7, 5, 100, 300, seed=91)
+    wild.q_ins[int(wild.roff[3]) + 17] = ord(" ")
+    _, ref = oracle.phmm_batch(wild, 0)
+    res = {}
+    try:
+        for name, b in (("clean", clean), ("wild", wild)):
+            for opt in (agx.PHMM_TRAINS_OFF, agx.PHMM_TRAINS_ON):
+                ctx.set_option(agx.OPT_PHMM_TRAINS, opt)
+                dev = ctx.phmm_batch(b, agx.PHMM_F32_FMA)
+                waves = dev.info().n_waves
+                dev.launch()
+                res[(name, opt)] = (waves, dev.results()[0])
+                dev.close()
+    finally:
+        ctx.set_option(agx.OPT_PHMM_TRAINS, agx.PHMM_TRAINS_AUTO)
+    assert res[("clean", agx.PHMM_TRAINS_ON)][0] < res[("clean", agx.PHMM_TRAINS_OFF)][0]
+    assert res[("wild", agx.PHMM_TRAINS_ON)][0] == res[("wild", agx.PHMM_TRAINS_OFF)][0]
+    ok = np.isfinite(ref)
+    assert ok.sum() >= ref.size - 5  # (the byte sits in one read: at most its five pairs)
+    for opt in (agx.PHMM_TRAINS_OFF, agx.PHMM_TRAINS_ON):
+        assert relerr(res[("wild", opt)][1][ok], ref[ok]) <= 1e-6
