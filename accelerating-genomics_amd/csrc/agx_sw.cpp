@@ -233,6 +233,7 @@ struct agx_sw_batch {
     DevBuf img, groups, waves, scores;
     DevBuf table; // substitution-matrix mode: kSwMatDim^2 int16 entries
     int rising = 0; // biased packed fill: 1 = stored values rise by |ge| per step, 4 = and by |ge| per column in classes of four (agx_sw_pk2_kernel.hip, KC)
+    bool wide = false; // rising == 4: the column classes' period is C / 2 in the classes built that way (sw_pk2_period), not four
     PinBuf out_stage; // page-locked landing block of the scores, taken at create: agx_sw_batch_scores allocates nothing
                       // (a first hipHostMalloc costs milliseconds, and hipvers' timed window is launch -> scores)
     bool matrix = false;
@@ -1165,6 +1166,7 @@ int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matri
     size_t img_dw = img0;
     std::vector<SwWave> waves;
     std::vector<ClassLaunch> launches;
+    uint32_t launched_classes = 0; // bit k: some wave runs kSwClasses[k]
     int64_t padded = 0;
     double t_waves = t_sort, t_records = t_sort;
     std::vector<uint8_t> groups_host; // plan-only: no pinned memory without a device
@@ -1196,6 +1198,7 @@ int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matri
             if (count) class_mask |= 1u << (k >> 6);
         }
         n_waves_total = n_waves;
+        launched_classes = class_mask;
         img_dw = dp.img_dw;
         groups_bytes = n_groups * sizeof(SwGroup2);
         waves_bytes = n_waves * sizeof(SwWave);
@@ -1244,6 +1247,7 @@ int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matri
             cl.C = kSwClasses[q.cls];
             cl.first_wave = (uint32_t)q.wave0;
             launches.push_back(cl);
+            launched_classes |= 1u << q.cls;
         }
         launches.back().n_waves += (uint32_t)q.n_waves;
         const size_t per_wave = (size_t)(64 / q.G);
@@ -1365,6 +1369,28 @@ int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matri
 
     } // host-made plan
     b->launches = launches;
+    // ---- class period of the column classes (rising == 4; agx_sw_pk2w_kernel.hip).  With period P column j of
+    // a lane carries (j mod P) |ge| where it carried at most 3 |ge|; P = the largest period among the classes this batch
+    // launches.  Every constant of the cell goes in as ONE 32-bit add of k * 0x10001, k of either sign, which is exact in both
+    // halves whenever both results lie in [0, 0x10000): what has to hold is that every half the cell produces is a pattern
+    // of [0x0400, 0x7c00).  From below that holds as before: each result is a true value >= B - max(|gf|, -mismatch) plus an
+    // offset that is never negative -- the wrap column's and the first column's diagonal sums land on class 0's offset
+    // (t + 1) |ge|, and so do f - P |ge| at the wrap and max(zl, fl) - c_end on arrival.  From above, with steps <= ll + 63:
+    //   the diagonal sum, at most (steps + P - 1) |ge| of offset:            B + (ls + 1) match + (ll + 62 + P) |ge|
+    //   z and the horizontal gap ahead of its wrap, (steps + P) |ge|:        B + ls match - |gf| + (ll + 63 + P) |ge|
+    //   the running maxima, (steps + P + 4) |ge| after their last rise:      B + ls match - |gf| + (ll + 67 + P) |ge|
+    // all of which B + (ls + 1) match + |gf| + (ll + 65 + P) |ge| bounds (|gf| >= |ge|): the rising cell's own rule with P for 4.
+    if (family == 2 && rising == 4) {
+        int period = 4;
+        for (int k = 0; k < kSwNumClasses; ++k)
+            if ((launched_classes >> k & 1u) && kSwClasses[k] <= kSwPackedMaxShort / 64) period = std::max(period, sw_pk2_period(kSwClasses[k]));
+        bool wide = period > 4 && (int64_t)bias + ((int64_t)longest_short + 1) * sc.match - prm.gf +
+                                          ((int64_t)longest_long + 65 + period) * -(int64_t)prm.ge < 0x7c00;
+        if (const char *e = agx_tune("AGX_SW_PERIOD")) wide = wide && !(e[0] == '4' && !e[1]); // "4": the narrow kernel, for A/B
+        b->wide = wide;
+        if (wide && ctx) agx_sw_pk2w_preload();
+        if (trace) fprintf(stderr, "[agx_sw_batch_create] class period %d of %d\n", wide ? period : 4, period);
+    }
     b->info.n_pairs = n_pairs;
     b->info.cells = cells;
     b->info.padded_cells = padded;
@@ -1541,9 +1567,9 @@ int agx_sw_batch_launch(agx_sw_batch *b)
             r = cl.C == 0 ? agx_sw_i32d_launch_any(prm, img, (const SwGroup2 *)b->groups.p, wv, cl.n_waves, scores, st)
                           : agx_sw_i32d_launch_class(cl.C, prm, img, (const SwGroup2 *)b->groups.p, wv, cl.n_waves, scores, st);
         else if (b->family == 2 && cl.C == 0)
-            r = agx_sw_pk2_launch_any(b->rising, prm, img, (const SwGroup2 *)b->groups.p, wv, cl.n_waves, scores, st);
+            r = agx_sw_pk2_launch_any(b->rising, b->wide, prm, img, (const SwGroup2 *)b->groups.p, wv, cl.n_waves, scores, st);
         else if (b->family == 2)
-            r = agx_sw_pk2_launch_class(cl.C, b->rising, prm, img, (const SwGroup2 *)b->groups.p, wv, cl.n_waves, scores, st);
+            r = agx_sw_pk2_launch_class(cl.C, b->rising, b->wide, prm, img, (const SwGroup2 *)b->groups.p, wv, cl.n_waves, scores, st);
         else if (b->family == 1)
             r = agx_sw_pk_launch_class(cl.C, prm, img, (const SwGroup2 *)b->groups.p, wv, cl.n_waves, scores, st);
         else

@@ -93,14 +93,25 @@ int agx_sw_pack_dna_launch(const uint8_t *raw, const uint64_t *off, uint64_t bas
                            uint32_t n_pairs, uint32_t *img, uint32_t *flag, int n_cu, hipStream_t s);
 int agx_sw_pk_launch_class(int cols_per_lane, const SwParams &prm, const uint32_t *img, const SwGroup2 *groups,
                            const SwWave *waves, uint32_t n_waves, int32_t *scores, hipStream_t s);
-int agx_sw_pk2_launch_class(int cols_per_lane, int rising, const SwParams &prm, const uint32_t *img, const SwGroup2 *groups,
+// The biased packed fill's column classes (rising == 4): column j of a lane carries (j mod P) |ge|.  P = 4 ("narrow") in every
+// class, or P = C / 2 ("wide", agx_sw_pk2w_kernel.hip) from 14 columns per lane on: the host chooses per batch (agx_sw.cpp,
+// "class period").  This is the period of class C's wide build; classes named in AGX_SW_PK2_KEEP_NARROW keep four there too
+// (their wide build passes 256 VGPRs or spills).
+#define AGX_SW_PK2_KEEP_NARROW(C) (false)
+constexpr int sw_pk2_period(int C) { return C >= 14 && !AGX_SW_PK2_KEEP_NARROW(C) ? C / 2 : 4; }
+int agx_sw_pk2_launch_class(int cols_per_lane, int rising, bool wide, const SwParams &prm, const uint32_t *img, const SwGroup2 *groups,
                             const SwWave *waves, uint32_t n_waves, int32_t *scores, hipStream_t s);
+int agx_sw_pk2w_launch_class(int cols_per_lane, const SwParams &prm, const uint32_t *img, const SwGroup2 *groups, const SwWave *waves,
+                             uint32_t n_waves, int32_t *scores, hipStream_t s);
+int agx_sw_pk2w_launch_any(const SwParams &prm, const uint32_t *img, const SwGroup2 *groups, const SwWave *waves, uint32_t n_waves,
+                           int32_t *scores, hipStream_t s);
+void agx_sw_pk2w_preload();
 // every class of a mixed batch in one launch: waves[].reserved holds each wave's columns per lane
 void agx_sw_pk2_preload();
 void agx_sw_pack_preload();
 void agx_sw_i32_preload();
-int agx_sw_pk2_launch_any(int rising, const SwParams &prm, const uint32_t *img, const SwGroup2 *groups, const SwWave *waves, uint32_t n_waves,
-                          int32_t *scores, hipStream_t s);
+int agx_sw_pk2_launch_any(int rising, bool wide, const SwParams &prm, const uint32_t *img, const SwGroup2 *groups, const SwWave *waves,
+                          uint32_t n_waves, int32_t *scores, hipStream_t s);
 // the 32-bit fill with the DNA-coded match: the packed plan's records and image, one pair of a lane group at a time
 int agx_sw_i32d_launch_any(const SwParams &prm, const uint32_t *img, const SwGroup2 *groups, const SwWave *waves, uint32_t n_waves, int32_t *scores,
                            hipStream_t s);
