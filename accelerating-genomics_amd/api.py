@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # only (libagx_tuning.so, -DAGX_TUNING): a process that sets one of them gets that library.
 TUNING_KNOBS = ("AGX_SW_KERNEL", "AGX_SW_TAIL_BETA", "AGX_SW_MAX_C", "AGX_SW_FORCE_C", "AGX_SW_MAX_CLASSES", "AGX_SW_WAVES_PER_CLASS",
                 "AGX_SW_SORT_WAVES", "AGX_SW_ONE_LAUNCH", "AGX_SW_DNA", "AGX_SW_RISE", "AGX_SW_PERIOD", "AGX_PHMM_PLAIN_CELL", "AGX_TRACE_CREATE", "AGX_HOST_THREADS", "AGX_FANOUT", "AGX_PHMM_TAB_BUDGET", "AGX_PHMM_MAX_C",
-                "AGX_PHMM_FORCE_C", "AGX_PHMM_TAIL_BETA", "AGX_PHMM_MAX_CLASSES", "AGX_PHMM_NO_LUT", "AGX_TRACE_POOL", "AGX_NO_STREAM_PRIO", "AGX_SW_I32_CLASSIC", "AGX_SW_PIECE_MB", "AGX_SW_PIECE_MIN_PAIRS", "AGX_PHMM_NO_ROWS", "AGX_PHMM_NO_TRAINS", "AGX_PHMM_LUT_ONE_LOOP", "AGX_SW_HOST_PLAN", "AGX_PHMM_NO_RING")
+                "AGX_PHMM_FORCE_C", "AGX_PHMM_TAIL_BETA", "AGX_PHMM_MAX_CLASSES", "AGX_PHMM_NO_LUT", "AGX_TRACE_POOL", "AGX_NO_STREAM_PRIO", "AGX_SW_I32_CLASSIC", "AGX_SW_PIECE_MB", "AGX_SW_PIECE_MIN_PAIRS", "AGX_PHMM_NO_ROWS", "AGX_PHMM_NO_TRAINS", "AGX_PHMM_LUT_ONE_LOOP", "AGX_SW_HOST_PLAN", "AGX_PHMM_NO_RING", "AGX_TRACE_CIGAR")
 _DEFAULT_LIB = "libagx_tuning.so" if any(k in os.environ for k in TUNING_KNOBS) else "libagx.so"
 LIB_PATH = os.environ.get("AGX_LIB_PATH", os.path.join(_HERE, _DEFAULT_LIB))  # override: kernel experiments only
 
@@ -27,10 +27,15 @@ SwHit = np.dtype([("score", np.int32), ("a_begin", np.int32), ("a_end", np.int32
 # agx_sw_stat as a numpy record: matches and aligned pairs of the reported alignment (include/agx.h, "Alignment statistics")
 SwStat = np.dtype([("matches", np.int32), ("pairs", np.int32)])
 SW_STATS_MAX_QUERY_LEN = 1792
+# CIGARs (include/agx.h, "Alignment itself"): an operation is length << 4 | one of the BAM codes below
+SW_CIGAR_MAX_QUERY_LEN = 2048
+CIGAR_INS, CIGAR_DEL, CIGAR_EQ, CIGAR_DIFF = 1, 2, 7, 8
+_CIGAR_CHARS = {CIGAR_INS: "I", CIGAR_DEL: "D", CIGAR_EQ: "=", CIGAR_DIFF: "X"}
 OPT_SW_KERNEL = 1
 OPT_SW_PLANNER = 2
 SW_PLANNER_AUTO, SW_PLANNER_HOST, SW_PLANNER_DEVICE = 0, 1, 2
 OPT_PHMM_TRAINS = 3
+OPT_SW_TRACE_BYTES = 4  # device memory one chunk of traced pairs may take (SwBatch.cigars); default 1 GiB
 PHMM_TRAINS_AUTO, PHMM_TRAINS_OFF, PHMM_TRAINS_ON = 0, 1, 2
 SW_KERNEL_AUTO, SW_KERNEL_INT32, SW_KERNEL_PACKED_SIGNED, SW_KERNEL_PACKED_BIASED = 0, 1, 2, 3
 PHMM_F64, PHMM_F64_FMA, PHMM_F32, PHMM_F32_FMA = 0, 1, 2, 3
@@ -45,6 +50,7 @@ SYMBOLS = [
     "agx_sw_batch_create_align", "agx_sw_batch_hits", "agx_sw_align", "agx_sw_batch_create_align_mode", "agx_sw_align_mode",
     "agx_sw_batch_create_align_matrix", "agx_sw_align_matrix",
     "agx_sw_batch_create_align_stats", "agx_sw_batch_stats", "agx_sw_align_stats",
+    "agx_sw_batch_create_align_cigar", "agx_sw_batch_cigars", "agx_sw_batch_cigar_info", "agx_sw_align_cigar",
     "agx_sw_score", "agx_sw_score_multi", "agx_sw_score_devices", "agx_sw_shard_cuts",
     "agx_phmm_batch_create", "agx_phmm_batch_launch", "agx_phmm_batch_results", "agx_phmm_batch_bind_results", "agx_phmm_batch_info",
     "agx_phmm_batch_destroy", "agx_phmm_forward", "agx_phmm_forward_multi", "agx_phmm_forward_devices", "agx_phmm_shard_cuts",
@@ -64,6 +70,17 @@ class AgxError(RuntimeError):
 class SwInfo(C.Structure):
     _fields_ = [("n_pairs", C.c_int64), ("cells", C.c_int64), ("padded_cells", C.c_int64), ("input_bytes", C.c_int64),
                 ("n_launches", C.c_int32), ("n_waves", C.c_int32), ("planned_on_device", C.c_int32), ("reserved", C.c_int32)]
+
+
+class SwCigarInfo(C.Structure):
+    """agx_sw_cigar_info: what the last SwBatch.cigars() of a batch did."""
+    _fields_ = [("n_traced", C.c_int64), ("trace_cells", C.c_int64), ("trace_bytes_peak", C.c_int64), ("n_chunks", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+def cigar_string(ops) -> str:
+    """The operations of one pair (uint32: length << 4 | op) as CIGAR text with '=' and 'X'; '*' for none."""
+    return "".join("%d%s" % (int(v) >> 4, _CIGAR_CHARS[int(v) & 15]) for v in ops) or "*"
 
 
 class SwScoring(C.Structure):
@@ -174,6 +191,12 @@ def lib():
         l.agx_sw_batch_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         l.agx_sw_align_stats.argtypes = [C.c_void_p, C.POINTER(SwScoring), C.POINTER(SwMatrix), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                          C.c_void_p, C.c_void_p]
+        l.agx_sw_batch_create_align_cigar.argtypes = [C.c_void_p, C.POINTER(SwScoring), C.POINTER(SwMatrix), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                      C.c_int64, C.POINTER(C.c_void_p)]
+        l.agx_sw_batch_cigars.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
+        l.agx_sw_batch_cigar_info.argtypes = [C.c_void_p, C.POINTER(SwCigarInfo)]
+        l.agx_sw_align_cigar.argtypes = [C.c_void_p, C.POINTER(SwScoring), C.POINTER(SwMatrix), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
         l.agx_sw_score.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
         l.agx_sw_score_multi.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
         l.agx_sw_score_devices.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
@@ -277,8 +300,20 @@ class Context:
         return ms.value
 
     # ---- Smith-Waterman
-    def sw_batch(self, b, scoring=None, matrix=None, align=0, mode=SW_MODE_LOCAL, stats=False) -> "SwBatch":
-        return SwBatch(self, b, scoring, matrix, align, mode, stats)
+    def sw_batch(self, b, scoring=None, matrix=None, align=0, mode=SW_MODE_LOCAL, stats=False, cigar=False) -> "SwBatch":
+        return SwBatch(self, b, scoring, matrix, align, mode, stats, cigar)
+
+    def sw_align_cigar(self, b, scoring=None, mode=SW_MODE_LOCAL, matrix=None):
+        """b: synth.SWBatch -> (SwHit records as SW_ALIGN_SPANS gives them, op_off uint64[n + 1], ops uint32), one-shot:
+        pair p's operations are ops[op_off[p]:op_off[p + 1]] (cigar_string turns them into text)."""
+        hits, op_off = np.empty(b.n_pairs, SwHit), np.zeros(b.n_pairs + 1, np.uint64)
+        cap = int(b.len.sum())  # an alignment has at most one operation per symbol
+        ops = np.empty(max(cap, 1), np.uint32)
+        sc = C.byref(SwScoring(*scoring)) if scoring is not None else None
+        mx = C.byref(matrix) if matrix is not None else None
+        _check(lib().agx_sw_align_cigar(self._h, sc, mx, mode, _ptr(b.bases), _ptr(b.off), _ptr(b.len), b.n_pairs, _ptr(hits), _ptr(op_off),
+                                        _ptr(ops), cap))
+        return hits, op_off, ops[:int(op_off[b.n_pairs])].copy()
 
     def sw_align_stats(self, b, scoring=None, mode=SW_MODE_LOCAL, matrix=None):
         """b: synth.SWBatch -> (SwHit records as SW_ALIGN_SPANS gives them, SwStat records: matches and pairs), one-shot."""
@@ -324,13 +359,22 @@ class Context:
 class SwBatch:
     """agx_sw_batch: a scheduled batch resident in HBM (ctx=None: planned on the host only)."""
 
-    def __init__(self, ctx, b, scoring=None, matrix=None, align=0, mode=SW_MODE_LOCAL, stats=False):
+    def __init__(self, ctx, b, scoring=None, matrix=None, align=0, mode=SW_MODE_LOCAL, stats=False, cigar=False):
         """scoring: None (the reference's +1/-1/-3/-1) or (match, mismatch, gap_open, gap_extend);
         matrix: an SwMatrix instead (score-only and align batches alike); align: SW_ALIGN_ENDS / SW_ALIGN_SPANS for a batch that also answers hits();
-        mode: SW_MODE_* of an align batch (local, global, fit, extension); stats=True: a SPANS batch that also answers stats()."""
+        mode: SW_MODE_* of an align batch (local, global, fit, extension); stats=True: a SPANS batch that also answers stats();
+        cigar=True: a SPANS batch that also answers cigars() (not together with stats)."""
         self.ctx = ctx
         self.n_pairs = b.n_pairs
         self._h = C.c_void_p()
+        if cigar:
+            if stats or align not in (0, SW_ALIGN_SPANS):
+                raise AgxError(E_ARG, "a cigar batch is a SW_ALIGN_SPANS batch, and not a stats batch as well")
+            sc = C.byref(SwScoring(*scoring)) if scoring is not None else None
+            mx = C.byref(matrix) if matrix is not None else None
+            _check(lib().agx_sw_batch_create_align_cigar(ctx._h if ctx else None, sc, mx, mode, _ptr(b.bases), _ptr(b.off), _ptr(b.len),
+                                                         b.n_pairs, C.byref(self._h)))
+            return
         if stats:
             if align not in (0, SW_ALIGN_SPANS):
                 raise AgxError(E_ARG, "a stats batch is a SW_ALIGN_SPANS batch")
@@ -385,6 +429,21 @@ class SwBatch:
         hits, stats = np.empty(self.n_pairs, SwHit), np.empty(self.n_pairs, SwStat)
         _check(lib().agx_sw_batch_stats(self._h, _ptr(hits), _ptr(stats)))
         return hits, stats
+
+    def cigars(self):
+        """agx_sw_batch_cigars: (SwHit records, op_off uint64[n + 1], ops uint32) in the caller's pair order (cigar batches only);
+        the sizing call and the real one, which the library answers from one computation."""
+        hits, op_off = np.empty(self.n_pairs, SwHit), np.zeros(self.n_pairs + 1, np.uint64)
+        _check(lib().agx_sw_batch_cigars(self._h, _ptr(hits), _ptr(op_off), None, 0))
+        total = int(op_off[self.n_pairs])
+        ops = np.empty(max(total, 1), np.uint32)
+        _check(lib().agx_sw_batch_cigars(self._h, _ptr(hits), _ptr(op_off), _ptr(ops), total))
+        return hits, op_off, ops[:total]
+
+    def cigar_info(self) -> SwCigarInfo:
+        info = SwCigarInfo()
+        _check(lib().agx_sw_batch_cigar_info(self._h, C.byref(info)))
+        return info
 
     def bind_scores(self, out):
         """agx_sw_batch_bind_scores: out = a page-locked int32 array (host_array) or None."""

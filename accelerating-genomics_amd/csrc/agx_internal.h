@@ -118,6 +118,7 @@ struct agx_ctx {
     int opt_sw_kernel = 0;
     int opt_sw_planner = 0;
     int opt_phmm_trains = 0;
+    int64_t opt_sw_trace_bytes = (int64_t)1 << 30; // AGX_OPT_SW_TRACE_BYTES
 };
 
 int agx_ctx_prepare_fanout(agx_ctx *c); // side streams + events for batches of several launches

@@ -620,9 +620,9 @@ extern "C" {
 const char *agx_version(void)
 {
 #ifdef AGX_TUNING
-    return "agx 0.3.3 (gfx950, tuning build)";
+    return "agx 0.3.4 (gfx950, tuning build)";
 #else
-    return "agx 0.3.3 (gfx950)";
+    return "agx 0.3.4 (gfx950)";
 #endif
 }
 const char *agx_last_error(void) { return g_err; }
@@ -763,6 +763,10 @@ int agx_ctx_set_option(agx_ctx *c, int key, int64_t value)
     case AGX_OPT_PHMM_TRAINS:
         if (value < AGX_PHMM_TRAINS_AUTO || value > AGX_PHMM_TRAINS_ON) break;
         c->opt_phmm_trains = (int)value;
+        return AGX_OK;
+    case AGX_OPT_SW_TRACE_BYTES:
+        if (value < 1) break;
+        c->opt_sw_trace_bytes = value;
         return AGX_OK;
     default: break;
     }

@@ -218,6 +218,22 @@ struct agx_sw_batch {
     int stats = 0;
     DevBuf lstat;       // stats == 2: L of every pair's captured cell
     PinBuf lstat_stage; // its page-locked landing block
+    // agx_sw_batch_create_align_cigar: 0 = no CIGARs; 1 = a cigar batch (a SPANS batch that keeps its sequences
+    // and answers agx_sw_batch_cigars); 2 = the internal GLOBAL batch of one chunk of spans, whose fill is the traced build
+    int cigar = 0;
+    // cigar == 2: where every group's directions start (dwords), one walk record per pair, and the extents they add up to;
+    // the trace block itself is lent by cigars_impl for the time of one chunk
+    std::vector<uint64_t> tr_goff;
+    std::vector<SwWalkRec> tr_walk;
+    uint64_t tr_dwords = 0, tr_slot_words = 0;
+    DevBuf goff, walkrec;
+    uint32_t *trace_p = nullptr;
+    // cigar == 1: the answer of the last agx_sw_batch_cigars, kept until the next launch
+    bool cig_valid = false;
+    std::vector<agx_sw_hit> cig_hits;
+    std::vector<uint64_t> cig_off;
+    std::vector<uint32_t> cig_ops;
+    agx_sw_cigar_info cig_info{};
     // modes other than LOCAL: pairs with an empty side whose score is not the zero the device array holds for them
     std::vector<int64_t> fix_pair;
     std::vector<int32_t> fix_score;
@@ -253,7 +269,7 @@ struct agx_sw_batch {
 namespace {
 int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matrix *matrix, const uint8_t *bases,
                  const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_batch **out, bool defer = false, int align = 0, int mode = 0,
-                 int stats = 0);
+                 int stats = 0, int cigar = 0);
 int finish_create(agx_sw_batch *b);
 void drop_pending(agx_sw_batch *b);
 }
@@ -275,6 +291,8 @@ void agx_sw_batch_destroy(agx_sw_batch *b)
     b->ends_stage.release();
     b->lstat.release();
     b->lstat_stage.release();
+    b->goff.release();
+    b->walkrec.release();
     agx_ctx_release(b->ctx); // the batch's own reference: a context outlives its batches
     delete b;
 }
@@ -494,7 +512,8 @@ int launch_device_plan(agx_ctx *ctx, DevPlan &dp, agx_sw_batch *b, uint32_t n_pa
 }
 
 int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matrix *matrix, const uint8_t *bases,
-                 const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_batch **out, bool defer, int align, int mode, int stats)
+                 const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_batch **out, bool defer, int align, int mode, int stats,
+                 int cigar)
 {
     if (!out) {
         agx_set_error("agx_sw_batch_create: out is NULL");
@@ -599,7 +618,9 @@ int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matri
     // no wide classes in matrix mode; an align batch lays the FIRST sequence across the lanes (agx_sw_loc_kernel.hip), its limit is on that one
     // (a stats batch: the classes the stats builds exist for bound the query, also where the batch's own fill is the plain one --
     // its begin pass is not)
+    // (a cigar batch: likewise the classes the traced builds exist for)
     const uint32_t hard_max_short = stats    ? (uint32_t)AGX_SW_STATS_MAX_QUERY_LEN
+                                    : cigar  ? (uint32_t)AGX_SW_CIGAR_MAX_QUERY_LEN
                                     : matrix ? (uint32_t)kSwPackedMaxShort
                                     : align  ? (uint32_t)AGX_SW_ALIGN_MAX_QUERY_LEN
                                              : AGX_SW_MAX_SHORT_LEN;
@@ -707,7 +728,7 @@ int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matri
                 longest_short, longest_long);
     const bool packed = family >= 1 && family <= 3;
     const bool coded_plan = family == 2 || family == 3; // the packed plan of the biased fill (one launch for all classes)
-    const double *costs = stats == 2 ? kSwStatsClassCost : class_costs(family); // (the stats builds: fewer classes)
+    const double *costs = stats == 2 ? kSwStatsClassCost : cigar == 2 ? kSwTraceClassCost : class_costs(family); // (the stats and traced builds: fewer classes)
     const int slots = packed ? 2 : 1;
 
     // plan-only batches check the symbols on the host; with a device the pack kernel does it
@@ -754,7 +775,11 @@ int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matri
         if (family == 3) agx_sw_i32d_preload();
         if (family == 0 && !matrix) agx_sw_i32_preload();
         if (family == 4 && stats != 2) (matrix ? agx_sw_loc_mat_preload : agx_sw_loc_preload)();
-        if (family == 5 && stats != 2) (matrix ? agx_sw_anch_mat_preload : agx_sw_anch_preload)();
+        if (family == 5 && stats != 2 && cigar != 2) (matrix ? agx_sw_anch_mat_preload : agx_sw_anch_preload)();
+        if (cigar == 2) {
+            (matrix ? agx_sw_trace_mat_preload : agx_sw_trace_preload)();
+            agx_sw_walk_preload();
+        }
         if (family == 4 && stats == 2) (matrix ? agx_sw_loc_mat_stats_preload : agx_sw_loc_stats_preload)();
         if (family == 5 && stats == 2) (matrix ? agx_sw_anch_mat_stats_preload : agx_sw_anch_stats_preload)();
     }
@@ -763,6 +788,7 @@ int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matri
     b->align = align;
     b->mode = mode;
     b->stats = stats;
+    b->cigar = cigar;
     b->scoring = sc;
     b->prm = prm;
     b->prm.n_out = (uint32_t)n_pairs + 1u;
@@ -1365,6 +1391,33 @@ int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matri
                         reinterpret_cast<SwGroup *>(groups_data)[q.group0 + (size_t)g] = SwGroup{xd, yd, ll, outi};
                 }
         });
+    if (cigar == 2) { // the traced fill: every group's directions behind one another, in group order (one pair per group)
+        b->tr_goff.assign(n_groups, 0);
+        b->tr_walk.assign((size_t)n_pairs, SwWalkRec{});
+        uint64_t at = 0;
+        for (const Bucket &q : bk)
+            for (size_t g = 0; g < q.n_groups; ++g) {
+                const PairPlan &pp = plan[q.first + g];
+                const int C = kSwClasses[q.cls];
+                b->tr_goff[q.group0 + g] = at;
+                SwWalkRec &r = b->tr_walk[pp.pair];
+                r.goff = at;
+                r.x_dw = x_dw[q.first + g];
+                r.y_dw = y_dw[q.first + g];
+                r.ca = pp.lx();
+                r.cb = pp.ly;
+                r.G = (uint16_t)q.G;
+                r.C = (uint16_t)C;
+                at += sw_trace_dwords(q.G, pp.ly, C);
+            }
+        b->tr_dwords = at;
+        uint64_t words = 0;
+        for (SwWalkRec &r : b->tr_walk) {
+            r.slot = words;
+            words += (uint64_t)r.ca + r.cb;
+        }
+        b->tr_slot_words = words;
+    }
     t_records = agx_now_ms();
 
     } // host-made plan
@@ -1425,6 +1478,8 @@ int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matri
     if (!rc && align) rc = b->ends_stage.alloc(ctx, ((size_t)n_pairs + 1) * sizeof(uint32_t));
     if (!rc && stats == 2) rc = b->lstat.alloc(ctx, ((size_t)n_pairs + 1) * sizeof(uint32_t));
     if (!rc && stats == 2) rc = b->lstat_stage.alloc(ctx, ((size_t)n_pairs + 1) * sizeof(uint32_t));
+    if (!rc && cigar == 2) rc = b->goff.alloc(ctx, std::max<size_t>(b->tr_goff.size(), 1) * sizeof(uint64_t));
+    if (!rc && cigar == 2) rc = b->walkrec.alloc(ctx, std::max<size_t>(b->tr_walk.size(), 1) * sizeof(SwWalkRec));
     if (!rc && launches.size() > 1) rc = agx_ctx_prepare_fanout(ctx);
     if (rc) return rc;
     hipStream_t cs = ctx->copy;
@@ -1441,6 +1496,10 @@ int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matri
     if (e == hipSuccess && !device_plan && waves_bytes) e = hipMemcpyAsync(b->waves.p, h_waves.p, waves_bytes, hipMemcpyHostToDevice, cs);
     if (e == hipSuccess && matrix)
         e = hipMemcpyAsync(b->table.p, table.data(), table.size() * sizeof(int16_t), hipMemcpyHostToDevice, ts);
+    if (e == hipSuccess && cigar == 2 && !b->tr_goff.empty())
+        e = hipMemcpyAsync(b->goff.p, b->tr_goff.data(), b->tr_goff.size() * sizeof(uint64_t), hipMemcpyHostToDevice, ts);
+    if (e == hipSuccess && cigar == 2 && !b->tr_walk.empty())
+        e = hipMemcpyAsync(b->walkrec.p, b->tr_walk.data(), b->tr_walk.size() * sizeof(SwWalkRec), hipMemcpyHostToDevice, ts);
     // pairs with an empty side are never touched by a kernel: their score is this zero
     if (e == hipSuccess) e = hipMemsetAsync(b->scores.p, 0, b->scores.bytes, ts);
     if (e == hipSuccess && align) e = hipMemsetAsync(b->ends.p, 0xff, b->ends.bytes, ts); // ... and their end cell is "none"
@@ -1524,6 +1583,11 @@ int agx_sw_batch_launch(agx_sw_batch *b)
     if (b->pending && b->pending->ready) AGX_HIP(hipStreamWaitEvent(b->ctx->stream, b->pending->ready, 0));
     SwParams prm = b->prm;
     if (b->bound) prm.n_out = (uint32_t)b->n_pairs; // the caller's array has no spare slot
+    b->cig_valid = false; // what agx_sw_batch_cigars kept belongs to the launch before
+    if (b->cigar == 2 && !b->trace_p && b->tr_dwords) {
+        agx_set_error("agx_sw_batch_launch: a traced fill without its trace block");
+        return AGX_E_INTERNAL;
+    }
     FanOut fan(b->ctx, (int)b->launches.size());
     rc = fan.begin();
     if (rc) return rc;
@@ -1538,7 +1602,13 @@ int agx_sw_batch_launch(agx_sw_batch *b)
         const int anch_capture = b->mode != AGX_SW_MODE_EXTEND, anch_flags = b->mode == AGX_SW_MODE_FIT ? 1 : b->mode == AGX_SW_MODE_GLOBAL ? 2 : 0;
         int r;
         uint32_t *lstat = (uint32_t *)b->lstat.p;
-        if (b->stats == 2 && b->family == 5 && b->matrix)
+        if (b->cigar == 2 && b->matrix)
+            r = agx_sw_trace_mat_launch_class(cl.C, prm, img, (const SwGroup *)b->groups.p, wv, cl.n_waves, scores, (uint32_t *)b->ends.p, b->trace_p,
+                                              (const uint64_t *)b->goff.p, (const int16_t *)b->table.p, st);
+        else if (b->cigar == 2)
+            r = agx_sw_trace_launch_class(cl.C, prm, img, (const SwGroup *)b->groups.p, wv, cl.n_waves, scores, (uint32_t *)b->ends.p, b->trace_p,
+                                          (const uint64_t *)b->goff.p, st);
+        else if (b->stats == 2 && b->family == 5 && b->matrix)
             r = agx_sw_anch_mat_stats_launch_class(cl.C, anch_capture, anch_flags, prm, img, (const SwGroup *)b->groups.p, wv, cl.n_waves, scores,
                                                    (uint32_t *)b->ends.p, lstat, (const int16_t *)b->table.p, st);
         else if (b->stats == 2 && b->family == 5)
@@ -1767,11 +1837,11 @@ agx_sw_hit empty_side_hit(int mode, int what, const agx_sw_scoring &sc, uint32_t
 
 // an align batch under match/mismatch scoring (matrix == NULL) or under a substitution matrix (scoring unused)
 int create_align(const char *who, agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matrix *matrix, int mode, int what,
-                 const uint8_t *bases, const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_batch **out, bool stats = false)
+                 const uint8_t *bases, const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_batch **out, bool stats = false, bool cigar = false)
 {
     if (mode < AGX_SW_MODE_LOCAL || mode > AGX_SW_MODE_EXTEND_QUERY) {
         if (out) *out = nullptr;
-        agx_set_error("%s%s: mode = %d is not one of AGX_SW_MODE_LOCAL .. AGX_SW_MODE_EXTEND_QUERY (0..4)", who, matrix || stats ? "" : "_mode", mode);
+        agx_set_error("%s%s: mode = %d is not one of AGX_SW_MODE_LOCAL .. AGX_SW_MODE_EXTEND_QUERY (0..4)", who, matrix || stats || cigar ? "" : "_mode", mode);
         return AGX_E_ARG;
     }
     if (what != AGX_SW_ALIGN_ENDS && what != AGX_SW_ALIGN_SPANS) {
@@ -1783,8 +1853,8 @@ int create_align(const char *who, agx_ctx *ctx, const agx_sw_scoring *scoring, c
     agx_sw_batch *b = nullptr;
     // a stats batch: LOCAL and FIT keep the plain forward fill (their begin pass carries L), the pinned modes' only fill carries it
     const int stats_kind = !stats ? 0 : (mode == AGX_SW_MODE_LOCAL || mode == AGX_SW_MODE_FIT) ? 1 : 2;
-    const int max_query = stats ? AGX_SW_STATS_MAX_QUERY_LEN : AGX_SW_ALIGN_MAX_QUERY_LEN;
-    int rc = create_batch(ctx, scoring, matrix, bases, off, len, n_pairs, &b, false, what, mode, stats_kind);
+    const int max_query = stats ? AGX_SW_STATS_MAX_QUERY_LEN : cigar ? AGX_SW_CIGAR_MAX_QUERY_LEN : AGX_SW_ALIGN_MAX_QUERY_LEN;
+    int rc = create_batch(ctx, scoring, matrix, bases, off, len, n_pairs, &b, false, what, mode, stats_kind, cigar ? 1 : 0);
     if (rc) return rc;
     struct Drop {
         agx_sw_batch *b;
@@ -1806,8 +1876,9 @@ int create_align(const char *who, agx_ctx *ctx, const agx_sw_scoring *scoring, c
             }
         }
     if (ctx && n_pairs > 0) b->seq_len.assign(len, len + 2 * n_pairs); // agx_sw_batch_hits checks every end cell against them
-    if (ctx && what == AGX_SW_ALIGN_SPANS && n_pairs > 0 && (mode == AGX_SW_MODE_LOCAL || mode == AGX_SW_MODE_FIT)) {
-        // the begin pass reads the sequences again, long after this call: a dense copy of the batch's own
+    if (ctx && what == AGX_SW_ALIGN_SPANS && n_pairs > 0 && (mode == AGX_SW_MODE_LOCAL || mode == AGX_SW_MODE_FIT || cigar)) {
+        // the begin pass (and a cigar batch's traced fill of the spans) reads the sequences again, long after this call: a dense
+        // copy of the batch's own
         b->seq_off.resize((size_t)n_pairs * 2);
         uint64_t at = 0;
         for (int64_t k = 0; k < 2 * n_pairs; ++k) {
@@ -2065,6 +2136,331 @@ int agx_sw_batch_stats(agx_sw_batch *b, agx_sw_hit *hits, agx_sw_stat *stats)
         }
     return AGX_OK;
     AGX_GUARD_END("agx_sw_batch_stats")
+}
+
+} // extern "C"
+
+namespace {
+// What one traced pair may take of the chunk budget: its directions in the class that needs the most dwords for its length (the
+// plan is made per chunk and chooses later), plus its operation slot.  Independent of the plan, so the cut is the caller's.
+uint64_t trace_bytes_bound(uint32_t ca, uint32_t cb)
+{
+    uint64_t worst = 0;
+#define AGX_SW_BOUND(CC)                                                           \
+    if ((ca + CC - 1u) / CC <= 64u) worst = std::max(worst, sw_trace_dwords((int)((ca + CC - 1u) / CC), cb, CC));
+    AGX_SW_FOR_EACH_TRACE_CLASS(AGX_SW_BOUND)
+#undef AGX_SW_BOUND
+    return 4u * (worst + (uint64_t)ca + cb);
+}
+
+// The host's check of one CIGAR (include/agx.h, "Alignment itself"): runs well-formed and merged, exactly x and y consumed,
+// every '=' / 'X' true of the symbols, and the operations rescored give `score`.  code: the matrix's byte map, or NULL.
+bool cigar_checks(const uint32_t *ops, uint64_t n_ops, const uint8_t *x, int64_t ca, const uint8_t *y, int64_t cb, const agx_sw_scoring &s,
+                  const agx_sw_matrix *m, int64_t score)
+{
+    int64_t i = 0, j = 0, total = 0;
+    uint32_t prev = 0;
+    for (uint64_t k = 0; k < n_ops; ++k) {
+        const uint32_t op = ops[k] & 15u;
+        const int64_t len = ops[k] >> 4;
+        if (len == 0 || op == prev) return false;
+        prev = op;
+        if (op == AGX_CIGAR_EQ || op == AGX_CIGAR_DIFF) {
+            if (j + len > ca || i + len > cb) return false;
+            for (int64_t t = 0; t < len; ++t, ++i, ++j) {
+                const bool same = m ? m->code[x[j]] == m->code[y[i]] : x[j] == y[i];
+                if (same != (op == AGX_CIGAR_EQ)) return false;
+                total += m ? m->score[m->code[x[j]]][m->code[y[i]]] : same ? s.match : s.mismatch;
+            }
+        } else if (op == AGX_CIGAR_INS) {
+            j += len;
+            total += s.gap_open + len * s.gap_extend;
+        } else if (op == AGX_CIGAR_DEL) {
+            i += len;
+            total += s.gap_open + len * s.gap_extend;
+        } else
+            return false;
+    }
+    return i == cb && j == ca && total == score;
+}
+
+// agx_sw_batch_cigars: hits (SPANS), then one traced GLOBAL fill, walk and gather per chunk of spans; the answer goes into the
+// batch (cig_hits, cig_off, cig_ops).  DESIGN.md 4.1f.
+int cigars_impl(agx_sw_batch *b)
+{
+    const int64_t n = b->n_pairs;
+    b->cig_valid = false;
+    b->cig_info = agx_sw_cigar_info{};
+    b->cig_hits.assign((size_t)n, agx_sw_hit{});
+    b->cig_off.assign((size_t)n + 1, 0);
+    b->cig_ops.clear();
+    int rc = hits_impl(b, b->cig_hits.data(), nullptr);
+    if (rc || n == 0) {
+        b->cig_valid = !rc;
+        return rc;
+    }
+    agx_ctx *ctx = b->ctx;
+    const agx_sw_hit *hits = b->cig_hits.data();
+    const agx_sw_matrix *mat = b->matrix ? &b->mat : nullptr;
+    const agx_sw_scoring s = b->scoring; // (under a matrix: its gap_open and gap_extend, which is all that is read of it)
+    auto span = [&](int64_t p, int64_t &ca, int64_t &cb) {
+        const agx_sw_hit &h = hits[p];
+        ca = h.a_begin >= 0 && h.a_end >= h.a_begin ? (int64_t)h.a_end - h.a_begin + 1 : 0;
+        cb = h.b_begin >= 0 && h.b_end >= h.b_begin ? (int64_t)h.b_end - h.b_begin + 1 : 0;
+    };
+    // ---- pairs answered without a fill, and the list of the others
+    std::vector<uint32_t> count((size_t)n, 0), lone((size_t)n, 0); // operations per pair; the only one of a pair with an empty side
+    std::vector<int64_t> traced;
+    int64_t cells = 0;
+    for (int64_t p = 0; p < n; ++p) {
+        int64_t ca, cb;
+        span(p, ca, cb);
+        if (ca && cb) {
+            traced.push_back(p);
+            cells += ca * cb;
+        } else if (ca || cb) {
+            count[(size_t)p] = 1;
+            lone[(size_t)p] = (uint32_t)(ca ? ca : cb) << 4 | (uint32_t)(ca ? AGX_CIGAR_INS : AGX_CIGAR_DEL);
+        }
+    }
+    b->cig_info.n_traced = (int64_t)traced.size();
+    b->cig_info.trace_cells = cells;
+    // ---- chunks of traced pairs, in the caller's order, by the budget
+    const uint64_t budget = (uint64_t)ctx->opt_sw_trace_bytes;
+    std::vector<std::vector<uint32_t>> chunk_ops;  // every chunk's runs, dense
+    std::vector<uint64_t> where((size_t)n, 0);     // a traced pair's first run in its chunk's array
+    std::vector<uint32_t> chunk_of((size_t)n, 0);
+    hipStream_t st = ctx->stream;
+    // tuning build, AGX_TRACE_CIGAR: kernel-only times of every chunk's traced fill, walk and gather (HIP events on the stream)
+    const bool timed = agx_tune("AGX_TRACE_CIGAR") != nullptr;
+    struct Events {
+        hipEvent_t e[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+        ~Events()
+        {
+            for (hipEvent_t v : e)
+                if (v) (void)hipEventDestroy(v);
+        }
+    } ev;
+    if (timed)
+        for (hipEvent_t &v : ev.e) AGX_HIP(hipEventCreate(&v));
+    for (size_t first = 0; first < traced.size();) {
+        size_t last = first;
+        uint64_t bytes = 0;
+        while (last < traced.size()) {
+            int64_t ca, cb;
+            span(traced[last], ca, cb);
+            const uint64_t need = trace_bytes_bound((uint32_t)ca, (uint32_t)cb);
+            if (last > first && bytes + need > budget) break;
+            bytes += need;
+            ++last;
+        }
+        const int64_t m = (int64_t)(last - first);
+        // the spans as a batch of their own, not reversed
+        std::vector<uint64_t> soff((size_t)m * 2);
+        std::vector<uint32_t> slen((size_t)m * 2);
+        uint64_t at = 0;
+        for (int64_t k = 0; k < m; ++k) {
+            int64_t ca, cb;
+            span(traced[first + (size_t)k], ca, cb);
+            soff[(size_t)(2 * k)] = at;
+            slen[(size_t)(2 * k)] = (uint32_t)ca;
+            at += (uint64_t)ca;
+            soff[(size_t)(2 * k + 1)] = at;
+            slen[(size_t)(2 * k + 1)] = (uint32_t)cb;
+            at += (uint64_t)cb;
+        }
+        std::vector<uint8_t> sub((size_t)at);
+        agx_parallel_for(m, 4096, [&](int64_t lo, int64_t hi, int) {
+            for (int64_t k = lo; k < hi; ++k) {
+                const int64_t p = traced[first + (size_t)k];
+                memcpy(sub.data() + soff[(size_t)(2 * k)], b->seq.data() + b->seq_off[(size_t)(2 * p)] + hits[p].a_begin, slen[(size_t)(2 * k)]);
+                memcpy(sub.data() + soff[(size_t)(2 * k + 1)], b->seq.data() + b->seq_off[(size_t)(2 * p + 1)] + hits[p].b_begin, slen[(size_t)(2 * k + 1)]);
+            }
+        });
+        agx_sw_batch *tb = nullptr;
+        rc = create_batch(ctx, &b->scoring, mat, sub.data(), soff.data(), slen.data(), m, &tb, false, AGX_SW_ALIGN_ENDS, AGX_SW_MODE_GLOBAL, 0, 2);
+        if (rc) return rc;
+        struct Drop { // every exit: nothing may still run on the blocks when they go back to the pool
+            agx_sw_batch *b;
+            DevBuf trace, slots, runs, dst, dense;
+            PinBuf h_runs, h_dense;
+            ~Drop()
+            {
+                (void)hipStreamSynchronize(b->ctx->stream);
+                trace.release();
+                slots.release();
+                runs.release();
+                dst.release();
+                dense.release();
+                h_runs.release();
+                h_dense.release();
+                agx_sw_batch_destroy(b);
+            }
+        } d{tb, {}, {}, {}, {}, {}, {}, {}};
+        rc = d.trace.alloc(ctx, std::max<uint64_t>(tb->tr_dwords, 1) * 4);
+        if (!rc) rc = d.slots.alloc(ctx, std::max<uint64_t>(tb->tr_slot_words, 1) * 4);
+        if (!rc) rc = d.runs.alloc(ctx, (size_t)m * sizeof(uint32_t));
+        if (!rc) rc = d.dst.alloc(ctx, (size_t)m * sizeof(uint64_t));
+        if (!rc) rc = d.h_runs.alloc(ctx, (size_t)m * sizeof(uint32_t));
+        if (rc) return rc;
+        b->cig_info.trace_bytes_peak = std::max<int64_t>(b->cig_info.trace_bytes_peak, (int64_t)((tb->tr_dwords + tb->tr_slot_words) * 4));
+        ++b->cig_info.n_chunks;
+        tb->trace_p = (uint32_t *)d.trace.p;
+        if (timed) AGX_HIP(hipEventRecord(ev.e[0], st));
+        rc = agx_sw_batch_launch(tb);
+        if (rc) return rc;
+        if (timed) AGX_HIP(hipEventRecord(ev.e[1], st));
+        if (agx_sw_walk_launch((const SwWalkRec *)tb->walkrec.p, (uint32_t)m, (const uint32_t *)tb->img.p, (const uint32_t *)d.trace.p, (uint32_t *)d.slots.p,
+                               (uint32_t *)d.runs.p, st)) {
+            agx_set_error("agx_sw_batch_cigars: walk kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
+            return AGX_E_HIP;
+        }
+        if (timed) AGX_HIP(hipEventRecord(ev.e[2], st));
+        AGX_HIP(hipMemcpyAsync(d.h_runs.p, d.runs.p, (size_t)m * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        std::vector<agx_sw_hit> th((size_t)m);
+        rc = hits_impl(tb, th.data(), nullptr); // (waits for the stream: the run counts have landed too)
+        if (rc) return rc;
+        const uint32_t *runs = (const uint32_t *)d.h_runs.p;
+        std::vector<uint64_t> dst((size_t)m);
+        uint64_t total = 0;
+        for (int64_t k = 0; k < m; ++k) {
+            const int64_t p = traced[first + (size_t)k];
+            if (th[(size_t)k].score != hits[p].score || runs[k] == 0 || runs[k] > (uint64_t)slen[(size_t)(2 * k)] + slen[(size_t)(2 * k + 1)]) {
+                agx_set_error("agx_sw_batch_cigars: pair %lld (mode %d): the traced fill of its span a %d..%d, b %d..%d gives score %d in %u runs, the hit %d",
+                              (long long)p, b->mode, hits[p].a_begin, hits[p].a_end, hits[p].b_begin, hits[p].b_end, th[(size_t)k].score, runs[k],
+                              hits[p].score);
+                return AGX_E_INTERNAL;
+            }
+            dst[(size_t)k] = total;
+            where[(size_t)p] = total;
+            chunk_of[(size_t)p] = (uint32_t)chunk_ops.size();
+            count[(size_t)p] = runs[k];
+            total += runs[k];
+        }
+        rc = d.dense.alloc(ctx, (size_t)total * sizeof(uint32_t));
+        if (!rc) rc = d.h_dense.alloc(ctx, (size_t)total * sizeof(uint32_t));
+        if (rc) return rc;
+        AGX_HIP(hipMemcpyAsync(d.dst.p, dst.data(), (size_t)m * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        if (timed) AGX_HIP(hipEventRecord(ev.e[3], st));
+        if (agx_sw_gather_launch((const SwWalkRec *)tb->walkrec.p, (uint32_t)m, (const uint32_t *)d.slots.p, (const uint32_t *)d.runs.p,
+                                 (const uint64_t *)d.dst.p, (uint32_t *)d.dense.p, st)) {
+            agx_set_error("agx_sw_batch_cigars: gather kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
+            return AGX_E_HIP;
+        }
+        if (timed) AGX_HIP(hipEventRecord(ev.e[4], st));
+        AGX_HIP(hipMemcpyAsync(d.h_dense.p, d.dense.p, (size_t)total * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        AGX_HIP(hipStreamSynchronize(st));
+        if (timed) {
+            float fill = 0, walk = 0, gather = 0;
+            AGX_HIP(hipEventElapsedTime(&gather, ev.e[3], ev.e[4]));
+            AGX_HIP(hipEventElapsedTime(&fill, ev.e[0], ev.e[1]));
+            AGX_HIP(hipEventElapsedTime(&walk, ev.e[1], ev.e[2]));
+            fprintf(stderr, "[agx_sw_batch_cigars] chunk %d: %lld pairs, %.1f MB of directions, %.1f MB of slots: traced fill %.3f ms, walk %.3f ms, gather %.3f ms, %llu runs\n",
+                    b->cig_info.n_chunks - 1, (long long)m, tb->tr_dwords * 4 / 1e6, tb->tr_slot_words * 4 / 1e6, fill, walk, gather, (unsigned long long)total);
+        }
+        chunk_ops.emplace_back((const uint32_t *)d.h_dense.p, (const uint32_t *)d.h_dense.p + total);
+        first = last;
+    } // (Drop returns the chunk's blocks before the next chunk takes its own)
+    // ---- the caller's layout, and every CIGAR checked before it leaves
+    for (int64_t p = 0; p < n; ++p) b->cig_off[(size_t)p + 1] = b->cig_off[(size_t)p] + count[(size_t)p];
+    b->cig_ops.resize((size_t)b->cig_off[(size_t)n]);
+    std::vector<int64_t> bad((size_t)agx_host_threads(), -1);
+    agx_parallel_for(n, 4096, [&](int64_t lo, int64_t hi, int tid) {
+        for (int64_t p = lo; p < hi; ++p) {
+            int64_t ca, cb;
+            span(p, ca, cb);
+            uint32_t *out = b->cig_ops.data() + b->cig_off[(size_t)p];
+            const uint32_t c = count[(size_t)p];
+            if (ca && cb) memcpy(out, chunk_ops[chunk_of[(size_t)p]].data() + where[(size_t)p], (size_t)c * sizeof(uint32_t));
+            else if (c) out[0] = lone[(size_t)p];
+            const uint8_t *x = ca ? b->seq.data() + b->seq_off[(size_t)(2 * p)] + hits[p].a_begin : nullptr;
+            const uint8_t *y = cb ? b->seq.data() + b->seq_off[(size_t)(2 * p + 1)] + hits[p].b_begin : nullptr;
+            if (!cigar_checks(out, c, x, ca, y, cb, s, mat, hits[p].score) && bad[(size_t)tid] < 0) bad[(size_t)tid] = p;
+        }
+    });
+    for (int64_t p : bad)
+        if (p >= 0) {
+            agx_set_error("agx_sw_batch_cigars: pair %lld (mode %d): its %u operations do not consume the span a %d..%d, b %d..%d, disagree with the "
+                          "symbols or do not rescore to %d",
+                          (long long)p, b->mode, count[(size_t)p], hits[p].a_begin, hits[p].a_end, hits[p].b_begin, hits[p].b_end, hits[p].score);
+            return AGX_E_INTERNAL;
+        }
+    b->cig_valid = true;
+    return AGX_OK;
+}
+} // namespace
+
+extern "C" {
+
+int agx_sw_batch_cigars(agx_sw_batch *b, agx_sw_hit *hits, uint64_t *op_off, uint32_t *ops, uint64_t ops_cap)
+{
+    if (!b || !op_off) {
+        agx_set_error("agx_sw_batch_cigars: null argument");
+        return AGX_E_ARG;
+    }
+    if (b->cigar != 1 || b->align != AGX_SW_ALIGN_SPANS) {
+        agx_set_error("agx_sw_batch_cigars: not a cigar batch (create it with agx_sw_batch_create_align_cigar)");
+        return AGX_E_ARG;
+    }
+    if (!b->ctx) {
+        agx_set_error("this batch was planned without a context (no device): it has no CIGARs");
+        return AGX_E_NODEVICE;
+    }
+    AGX_GUARD_BEGIN
+    if (!b->cig_valid) {
+        const int rc = cigars_impl(b);
+        if (rc) return rc;
+    }
+    const int64_t n = b->n_pairs;
+    memcpy(op_off, b->cig_off.data(), ((size_t)n + 1) * sizeof(uint64_t));
+    if (hits && n) memcpy(hits, b->cig_hits.data(), (size_t)n * sizeof(agx_sw_hit));
+    const uint64_t total = b->cig_off[(size_t)n];
+    if (!ops) return AGX_OK; // the sizing call
+    if (ops_cap < total) {
+        agx_set_error("agx_sw_batch_cigars: ops_cap = %llu, the batch has %llu operations", (unsigned long long)ops_cap, (unsigned long long)total);
+        return AGX_E_ARG;
+    }
+    if (total) memcpy(ops, b->cig_ops.data(), (size_t)total * sizeof(uint32_t));
+    return AGX_OK;
+    AGX_GUARD_END("agx_sw_batch_cigars")
+}
+
+int agx_sw_batch_cigar_info(const agx_sw_batch *b, agx_sw_cigar_info *info)
+{
+    if (!b || !info) {
+        agx_set_error("agx_sw_batch_cigar_info: null argument");
+        return AGX_E_ARG;
+    }
+    if (b->cigar != 1) {
+        agx_set_error("agx_sw_batch_cigar_info: not a cigar batch (create it with agx_sw_batch_create_align_cigar)");
+        return AGX_E_ARG;
+    }
+    *info = b->cig_info;
+    return AGX_OK;
+}
+
+int agx_sw_batch_create_align_cigar(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matrix *matrix, int mode, const uint8_t *bases,
+                                    const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_batch **out)
+{
+    if (scoring && matrix) {
+        if (out) *out = nullptr;
+        agx_set_error("agx_sw_batch_create_align_cigar: both scoring and matrix given; exactly one way of scoring");
+        return AGX_E_ARG;
+    }
+    return create_align("agx_sw_batch_create_align_cigar", ctx, scoring, matrix, mode, AGX_SW_ALIGN_SPANS, bases, off, len, n_pairs, out, false, true);
+}
+
+int agx_sw_align_cigar(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matrix *matrix, int mode, const uint8_t *bases,
+                       const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_hit *hits, uint64_t *op_off, uint32_t *ops, uint64_t ops_cap)
+{
+    agx_sw_batch *b = nullptr;
+    int rc = agx_sw_batch_create_align_cigar(ctx, scoring, matrix, mode, bases, off, len, n_pairs, &b);
+    if (rc) return rc;
+    rc = agx_sw_batch_launch(b);
+    if (!rc) rc = agx_sw_batch_cigars(b, hits, op_off, ops, ops_cap);
+    if (rc && b->ctx) (void)hipStreamSynchronize(b->ctx->stream); // the blocks go back to the pools: nothing may still run on them
+    agx_sw_batch_destroy(b);
+    return rc;
 }
 
 int agx_sw_align(agx_ctx *ctx, const agx_sw_scoring *scoring, int what, const uint8_t *bases, const uint64_t *off,

@@ -5,6 +5,8 @@
 #include <algorithm>
 #include <cstdint>
 
+#include "../../include/agx.h"
+
 // One alignment pair = one group of G lanes.  Offsets are in 4-byte words into the packed
 // image: x (the shorter sequence, zero-padded to G*C bytes rounded up to 4, plus one spare word),
 // y (the longer, padded to 4).
@@ -164,6 +166,42 @@ void agx_sw_loc_stats_preload();
 void agx_sw_loc_mat_stats_preload();
 void agx_sw_anch_stats_preload();
 void agx_sw_anch_mat_stats_preload();
+// the TRACED anchored fill (agx_sw_trace_kernel.hip, agx_sw_trace_mat_kernel.hip): COL capture with the GLOBAL flag
+// only.  Besides score and end cell every cell leaves four bits -- where H came from and whether E / F extended -- at
+// trace + goff[group] + (step * G + lane) * W dwords, W = sw_trace_words(C); goff holds one 64-bit dword offset per group record.
+// Built for the classes below only: the matrix build reports a spilled register from 34 columns on, the match/mismatch build from
+// 36 (DESIGN.md 4.1f has the table), and one list serves both.
+#define AGX_SW_FOR_EACH_TRACE_CLASS(X) X(4) X(6) X(8) X(10) X(12) X(14) X(16) X(18) X(20) X(22) X(24) X(26) X(28) X(30) X(32)
+constexpr int kSwTraceTopClass = 32; // 64 x 32 = AGX_SW_CIGAR_MAX_QUERY_LEN
+// the int32 kernel's relative costs for the classes that are built (unmeasured for these kernels), 0 = not built
+static const double kSwTraceClassCost[] = {1.373, 1.250, 1.178, 1.138, 1.112, 1.080, 1.051, 1.033, 1.025, 1.022, 1.014, 1.014, 1.011, 1.007, 1.007, 0, 0, 0, 0, 0, 0, 0};
+static_assert(64 * kSwTraceTopClass == AGX_SW_CIGAR_MAX_QUERY_LEN, "the query limit of a cigar batch follows the widest traced class");
+constexpr int sw_trace_words(int C) { return (C + 7) / 8; } // dwords of one lane's nibbles of one step
+// the dwords a traced pair of ly rows occupies in class C on G lanes: steps 0 .. ly + G - 2 of G lanes
+inline uint64_t sw_trace_dwords(int G, uint32_t ly, int C) { return ((uint64_t)ly + (uint64_t)G - 1u) * (uint64_t)G * (uint64_t)sw_trace_words(C); }
+int agx_sw_trace_launch_class(int cols_per_lane, const SwParams &prm, const uint32_t *img, const SwGroup *groups, const SwWave *waves,
+                              uint32_t n_waves, int32_t *scores, uint32_t *ends, uint32_t *trace, const uint64_t *goff, hipStream_t s);
+int agx_sw_trace_mat_launch_class(int cols_per_lane, const SwParams &prm, const uint32_t *img, const SwGroup *groups, const SwWave *waves,
+                                  uint32_t n_waves, int32_t *scores, uint32_t *ends, uint32_t *trace, const uint64_t *goff, const int16_t *table,
+                                  hipStream_t s);
+void agx_sw_trace_preload();
+void agx_sw_trace_mat_preload();
+// the walk over a traced fill's directions (agx_sw_walk_kernel.hip): one lane per pair, from the corner in state H by the tie
+// rule of include/agx.h ("Alignment itself").  Operations (length << 4 | BAM code) land right-aligned in the pair's slot of
+// ca + cb words, so they read forwards; runs[pair] receives their number.  The gather kernel packs them at dst[pair].
+struct SwWalkRec {
+    uint64_t goff;       // the pair's directions, in dwords from the trace block
+    uint64_t slot;       // first word of its slot
+    uint32_t x_dw, y_dw; // its symbols in the image, as its group record has them
+    uint32_t ca, cb;     // columns (query), rows (target)
+    uint16_t G, C;       // lanes of its group, columns per lane
+    uint32_t reserved;
+};
+int agx_sw_walk_launch(const SwWalkRec *recs, uint32_t n, const uint32_t *img, const uint32_t *trace, uint32_t *slots, uint32_t *runs,
+                       hipStream_t s);
+int agx_sw_gather_launch(const SwWalkRec *recs, uint32_t n, const uint32_t *slots, const uint32_t *runs, const uint64_t *dst, uint32_t *out,
+                         hipStream_t s);
+void agx_sw_walk_preload();
 
 // ---- device-side planning (agx_sw_plan_kernel.hip): the O(pairs) passes of the planner as kernels
 constexpr uint32_t kSwPlanEmptyKey = 1u << 27;           // sort key of a pair with an empty side: behind every bucket

@@ -43,8 +43,20 @@
 // Capture reads the score word only: ANY as the locating fill does, COL by strict improvement of the selected column's
 // score; L is what the chosen cell holds.
 //
-// (shared by agx_sw_anch_kernel.hip, agx_sw_anch_mat_kernel.hip and their _stats builds; opens an anonymous namespace that
-// the including file closes after its launch helper)
+// TRACE (agx_sw_trace_kernel.hip, agx_sw_trace_mat_kernel.hip; DESIGN.md 4.1f; COL capture with the GLOBAL flag only): every cell
+// also leaves four bits, all from values it computes anyway.  Bits 0..1: where H came from -- 0 the diagonal (v == s), else 1 E
+// (v == ev), else 2 F: the order is the tie rule "diagonal, then D, then I".  Bit 2: E extended, e[j] > up before their
+// maximum; bit 3: F extended, f > zleft before theirs -- strict, so a tie opens.  up stands for H[r-1] + open + extend and
+// e[j] for E[r-1] + extend at one offset (the stored values rise by |ge| per step, which is what adding ge to e would undo),
+// zleft and f likewise for column c - 1: a cell's inputs share one offset, so the comparisons are the true ones.  Boundaries
+// need nothing of their own: a group's first lane has fl == zl == zb, not greater, so column 0 opens its F from the boundary
+// column, and the top reset leaves e = minus infinity, so row 0 opens its E from row -1 -- what "open on ties" and E = F =
+// minus infinity on the boundaries ask for.  The nibbles of a lane's C cells of one step fill W = ceil(C / 8) dwords, stored
+// at trace + goff[group] + (t G + gl) W dwords: the lanes of a group write consecutive pieces of one step.  Only rows 0 ..
+// ly - 1 of a lane are stored (steps gl .. ly - 1 + gl), so (t G + gl) W < (ly + G - 1) G W, the extent the host reserves.
+//
+// (shared by agx_sw_anch_kernel.hip, agx_sw_anch_mat_kernel.hip, their _stats builds and the two traced builds; opens an
+// anonymous namespace that the including file closes after its launch helper)
 #include "agx_sw.h"
 
 #include <type_traits>
@@ -76,11 +88,30 @@ __device__ __forceinline__ S anch_lift(int v)
 __device__ __forceinline__ int anch_score(int v) { return v; }
 __device__ __forceinline__ int anch_score(long long v) { return (int)(v >> 32); }
 
-template <int C, bool COL, bool MAT, bool STATS = false>
+// TRACE: W dwords to p (4-byte aligned) as one store where the widths allow, W = 5 as four and one
+typedef uint32_t anch_u2 __attribute__((ext_vector_type(2), aligned(4)));
+typedef uint32_t anch_u3 __attribute__((ext_vector_type(3), aligned(4)));
+typedef uint32_t anch_u4 __attribute__((ext_vector_type(4), aligned(4)));
+template <int W>
+__device__ __forceinline__ void anch_store_words(uint32_t *p, const uint32_t *w)
+{
+    static_assert(W >= 1 && W <= 5, "classes up to 40 columns");
+    if constexpr (W == 1) p[0] = w[0];
+    else if constexpr (W == 2) *reinterpret_cast<anch_u2 *>(p) = anch_u2{w[0], w[1]};
+    else if constexpr (W == 3) *reinterpret_cast<anch_u3 *>(p) = anch_u3{w[0], w[1], w[2]};
+    else {
+        *reinterpret_cast<anch_u4 *>(p) = anch_u4{w[0], w[1], w[2], w[3]};
+        if constexpr (W == 5) p[4] = w[4];
+    }
+}
+
+template <int C, bool COL, bool MAT, bool STATS = false, bool TRACE = false>
 __device__ __forceinline__ void anch_body(const SwParams &prm, const int flags, const uint32_t *__restrict__ img,
                                           const SwGroup *__restrict__ groups, const SwWave w, int32_t *__restrict__ scores,
-                                          uint32_t *__restrict__ ends, const int16_t *sub, uint32_t *__restrict__ lstat = nullptr)
+                                          uint32_t *__restrict__ ends, const int16_t *sub, uint32_t *__restrict__ lstat = nullptr,
+                                          uint32_t *__restrict__ trace = nullptr, const uint64_t *__restrict__ goff = nullptr)
 {
+    static_assert(!TRACE || (COL && !STATS), "the traced build is the GLOBAL fill of scores");
     using S = typename std::conditional<STATS, long long, int>::type;
     using U = typename std::conditional<STATS, unsigned long long, uint32_t>::type;
     constexpr int XW = (C + 3) / 4; // dwords holding this lane's C symbols
@@ -149,6 +180,13 @@ __device__ __forceinline__ void anch_body(const SwParams &prm, const int flags, 
         for (int j = 0; j < C; ++j) xrow[j] = (int)((xw[j >> 2] >> (8 * (j & 3))) & 0xffu) * (kSwMatDim * 2);
     }
 
+    // TRACE: where this lane's dwords of step t go (advanced by one step's G W dwords as t is)
+    constexpr int TW = (C + 7) / 8;
+    [[maybe_unused]] uint32_t *tp = nullptr;
+    if constexpr (TRACE) {
+        if (active) tp = trace + goff[w.first_group + grp] + (size_t)gl * TW;
+    }
+
     uint32_t q0 = row_quad(0), q1 = row_quad(1), q2 = row_quad(2);
     const int steps = (int)w.steps;
     uint32_t rows = 0;
@@ -191,10 +229,17 @@ __device__ __forceinline__ void anch_body(const SwParams &prm, const int flags, 
         // STATS: a pair counts in the rows of b only; MAT: identical symbols = this column's row offset equals the step's
         const uint32_t row_inc = yc != kPadRow ? 1u : 0u;
         const int yrow = yc != kPadRow ? yc * (kSwMatDim * 2) : -1;
+        [[maybe_unused]] uint32_t tw[TW];
+        if constexpr (TRACE) {
+#pragma unroll
+            for (int k = 0; k < TW; ++k) tw[k] = 0;
+        }
 #pragma unroll
         for (int j = 0; j < C; ++j) {
             const int xs = (int)((xw[j >> 2] >> (8 * (j & 3))) & 0xffu);
             const S up = z[j];
+            [[maybe_unused]] uint32_t nib = 0;
+            if constexpr (TRACE) nib = ((uint32_t)(up - e[j]) >> 31) << 2 | ((uint32_t)(zleft - f) >> 31) << 3; // sign bits: no difference wraps
             const S ev = max(up, e[j]);
             f = max(zleft, f);
             if (j) f += anch_lift<S>(ge);
@@ -210,7 +255,18 @@ __device__ __forceinline__ void anch_body(const SwParams &prm, const int flags, 
             else
                 s = zd + (xs == yc ? s_match + lag : s_mis + lag);
             const S v = max(max(ev, f), s);
-            const S zn = v + anch_lift<S>(gf + age);
+            if constexpr (TRACE) {
+                const uint32_t not_s = (uint32_t)(s - v) >> 31, not_e = (uint32_t)(ev - v) >> 31; // v is their maximum
+                nib |= not_s + (not_s & not_e);
+                tw[j >> 3] |= nib << (4 * (j & 7));
+            }
+            S zn = v + anch_lift<S>(gf + age);
+            // (the bits are off the cell's chain: left to itself the scheduler defers them and keeps seven values per column
+            // alive for it -- 229 registers at 16 columns.  Tying them to the value the next column waits for keeps them here.)
+            if constexpr (TRACE) {
+                if (j + 1 < C) asm volatile("" : "+v"(tw[j >> 3]), "+v"(zn), "+v"(z[j + 1]));
+                else asm volatile("" : "+v"(tw[j >> 3]), "+v"(zn));
+            }
             e[j] = ev;
             z[j] = zn;
             zd = up;
@@ -250,6 +306,10 @@ __device__ __forceinline__ void anch_body(const SwParams &prm, const int flags, 
                 hit_t = t;
                 hit_j = col;
             }
+        }
+        if constexpr (TRACE) {
+            if (active && t >= gl && t <= t_last) anch_store_words<TW>(tp, tw); // rows 0 .. ly - 1 of this lane
+            tp += (size_t)G * TW;
         }
         z_last = zleft;
         f_last = f;

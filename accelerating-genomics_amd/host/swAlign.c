@@ -1,5 +1,5 @@
 /*
- * swAlign <file_path> [local|global|fit|extend|extend-query][+stats]: where the best alignment of every pair ends and begins
+ * swAlign <file_path> [local|global|fit|extend|extend-query][+stats|+cigar]: where the best alignment of every pair ends and begins
  * (default: local; the other modes are include/agx.h's "Alignment modes").
  * swAlign <file_path> <mode> <matrix_file> [gap_open gap_extend]: the same under a substitution matrix (gaps default to
  * -11 -1).  The matrix file is the usual text layout: '#' comment lines, one line of symbols, then one row per symbol
@@ -15,6 +15,10 @@
  *     score a_begin a_end b_begin b_end matches pairs
  * the identical symbols and the aligned pairs of that alignment (include/agx.h, "Alignment statistics"; queries up to
  * AGX_SW_STATS_MAX_QUERY_LEN).  Without the suffix the output is what it was.
+ * Or the suffix "+cigar" (local+cigar, fit+cigar ...), with or without a matrix file: every line then ends in the alignment,
+ *     score a_begin a_end b_begin b_end CIGAR
+ * as text with '=', 'X', 'I' and 'D' over the span the line names, "*" for an alignment that consumes nothing (include/agx.h,
+ * "Alignment itself"; queries up to AGX_SW_CIGAR_MAX_QUERY_LEN).  "+stats+cigar" is not offered.
  *   AGX_CLI_CHUNK_PAIRS   pairs per agx_sw_align call (default 262144)
  */
 #include <stdio.h>
@@ -108,13 +112,17 @@ int main(int argc, char *argv[])
 {
     static const char *const words[] = {"local", "global", "fit", "extend", "extend-query"}; /* AGX_SW_MODE_* 0..4 */
     int mode = argc == 2 ? AGX_SW_MODE_LOCAL : -1;
-    int with_stats = 0;
+    int with_stats = 0, with_cigar = 0;
     for (int k = 0; (argc == 3 || argc == 4 || argc == 6) && k < 5; k++) {
         const size_t n = strlen(words[k]);
         if (!strcmp(argv[2], words[k])) mode = k;
         if (!strncmp(argv[2], words[k], n) && !strcmp(argv[2] + n, "+stats")) {
             mode = k;
             with_stats = 1;
+        }
+        if (!strncmp(argv[2], words[k], n) && !strcmp(argv[2] + n, "+cigar")) {
+            mode = k;
+            with_cigar = 1;
         }
     }
     if (mode < 0) {
@@ -123,7 +131,8 @@ int main(int argc, char *argv[])
                 "       %s <file_path> <mode> <matrix_file> [gap_open gap_extend]\n"
                 "With a matrix file ('#' comments, a line of symbols, a row per symbol: the symbol and its integers; symmetric,\n"
                 "letters in either case) gaps default to -11 -1 and the line ends (\\n, \\r\\n) are stripped, not aligned.\n"
-                "<mode>+stats (local+stats, fit+stats ...): every line ends in two more numbers, matches and aligned pairs.\n",
+                "<mode>+stats (local+stats, fit+stats ...): every line ends in two more numbers, matches and aligned pairs.\n"
+                "<mode>+cigar (local+cigar, fit+cigar ...): every line ends in the alignment as CIGAR text (=, X, I, D; * for none).\n",
                 argv[0], argv[0]);
         return 1;
     }
@@ -166,7 +175,12 @@ int main(int argc, char *argv[])
         if (t->n_pairs > 0) {
             agx_sw_hit *hits = (agx_sw_hit *)malloc(sizeof(agx_sw_hit) * (size_t)t->n_pairs);
             agx_sw_stat *stats = with_stats ? (agx_sw_stat *)malloc(sizeof(agx_sw_stat) * (size_t)t->n_pairs) : NULL;
-            if (!hits || (with_stats && !stats)) {
+            uint64_t *op_off = with_cigar ? (uint64_t *)malloc(sizeof(uint64_t) * ((size_t)t->n_pairs + 1)) : NULL;
+            uint32_t *ops = NULL;
+            uint64_t ops_cap = 0; /* an alignment has at most one operation per symbol */
+            for (int64_t k = 0; with_cigar && k < 2 * t->n_pairs; k++) ops_cap += t->len[k];
+            if (with_cigar) ops = (uint32_t *)malloc(sizeof(uint32_t) * (size_t)(ops_cap + 1));
+            if (!hits || (with_stats && !stats) || (with_cigar && (!op_off || !ops))) {
                 fprintf(stderr, "swAlign: out of memory\n");
                 status = EXIT_FAILURE;
             }
@@ -184,6 +198,12 @@ int main(int argc, char *argv[])
                     fprintf(stderr, "swAlign: %s\n", agx_last_error());
                     status = EXIT_FAILURE;
                 }
+            } else if (!status && with_cigar) {
+                if (agx_sw_align_cigar(ctx, NULL, with_matrix ? &matrix : NULL, mode, t->bases, t->off, t->len, t->n_pairs, hits, op_off, ops, ops_cap) !=
+                    AGX_OK) {
+                    fprintf(stderr, "swAlign: %s\n", agx_last_error());
+                    status = EXIT_FAILURE;
+                }
             } else if (!status && (with_matrix ? agx_sw_align_matrix(ctx, &matrix, mode, AGX_SW_ALIGN_SPANS, t->bases, t->off, t->len, t->n_pairs, hits)
                                         : agx_sw_align_mode(ctx, NULL, mode, AGX_SW_ALIGN_SPANS, t->bases, t->off, t->len, t->n_pairs, hits)) != AGX_OK) {
                 fprintf(stderr, "swAlign: %s\n", agx_last_error());
@@ -193,11 +213,22 @@ int main(int argc, char *argv[])
                 for (int64_t p = 0; p < t->n_pairs; p++)
                     printf("%d %d %d %d %d %d %d\n", hits[p].score, hits[p].a_begin, hits[p].a_end, hits[p].b_begin, hits[p].b_end, stats[p].matches,
                            stats[p].pairs);
+            else if (!status && with_cigar)
+                for (int64_t p = 0; p < t->n_pairs; p++) {
+                    printf("%d %d %d %d %d ", hits[p].score, hits[p].a_begin, hits[p].a_end, hits[p].b_begin, hits[p].b_end);
+                    for (uint64_t k = op_off[p]; k < op_off[p + 1]; k++) {
+                        const unsigned op = ops[k] & 15u;
+                        printf("%u%c", ops[k] >> 4, op == AGX_CIGAR_INS ? 'I' : op == AGX_CIGAR_DEL ? 'D' : op == AGX_CIGAR_EQ ? '=' : 'X');
+                    }
+                    printf(op_off[p] == op_off[p + 1] ? "*\n" : "\n");
+                }
             else if (!status)
                 for (int64_t p = 0; p < t->n_pairs; p++)
                     printf("%d %d %d %d %d\n", hits[p].score, hits[p].a_begin, hits[p].a_end, hits[p].b_begin, hits[p].b_end);
             free(hits);
             free(stats);
+            free(op_off);
+            free(ops);
         }
         agx_sw_text_free(t);
     }

@@ -89,6 +89,8 @@ int agx_ctx_sync(agx_ctx *ctx);
 #define AGX_PHMM_TRAINS_AUTO 0 /* two reads of a region share their lane groups where the batch is large enough for it to pay */
 #define AGX_PHMM_TRAINS_OFF 1  /* every read drains before the next enters (the schedule of rounds 1 and 2) */
 #define AGX_PHMM_TRAINS_ON 2   /* wherever two reads can share a group, whatever the batch size */
+#define AGX_OPT_SW_TRACE_BYTES 4 /* agx_sw_batch_cigars: device memory one chunk of traced pairs may take, direction words and operation
+                                  * slots together; default 1 GiB, a value below 1 is AGX_E_ARG ("Alignment itself" below) */
 int agx_ctx_set_option(agx_ctx *ctx, int key, int64_t value);
 /* Brings the HIP runtime and the process-wide contexts of these devices up (the ones agx_*_devices / agx_*_multi /
  * agx_pairHMM use) without computing anything: about 0.2 s that a host can spend on another thread while it
@@ -299,6 +301,74 @@ int agx_sw_batch_stats(agx_sw_batch *b, agx_sw_hit *hits /* may be NULL */, agx_
 /* One-shot: create_align_stats + launch + stats + destroy. */
 int agx_sw_align_stats(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matrix *matrix, int mode, const uint8_t *bases,
                        const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_hit *hits /* may be NULL */, agx_sw_stat *stats);
+
+/*
+ * Alignment itself: the CIGAR of every pair of an align batch, from a traced fill of the reported span.
+ * For a pair, let score, a_begin..a_end, b_begin..b_end be exactly what an AGX_SW_ALIGN_SPANS batch of the same mode and
+ * scoring reports.  x = a[a_begin..a_end], length ca, is the query; y = b[b_begin..b_end], length cb, the target; w(i,j) is
+ * what the diagonal move adds for y[i-1], x[j-1] (match / mismatch, or the matrix entry); o = gap_open + gap_extend,
+ * e = gap_extend.  Whatever the mode, the reported alignment is a GLOBAL alignment of x with y.  Pinned Gotoh, for
+ * 0 <= i <= cb, 0 <= j <= ca:
+ *   H[0][0] = 0;  H[0][j] = gap_open + j e (j > 0);  H[i][0] = gap_open + i e (i > 0);  E[0][j] = F[i][0] = -infinity
+ *   E[i][j] = max(H[i-1][j] + o, E[i-1][j] + e)      (consumes a target symbol only: D)
+ *   F[i][j] = max(H[i][j-1] + o, F[i][j-1] + e)      (consumes a query symbol only:  I)
+ *   H[i][j] = max(H[i-1][j-1] + w(i,j), E[i][j], F[i][j])
+ * H[cb][ca] == score always holds.  The CIGAR is the path found by walking back from (cb, ca) in state H; the tie rule
+ * prefers the diagonal, then D, then I, and opens a gap before it extends one:
+ *   state H, i > 0 and j > 0:  if H[i][j] == H[i-1][j-1] + w(i,j) emit '=' or 'X' and go to (i-1, j-1) in state H;
+ *                              otherwise, if H[i][j] == E[i][j], go to state E at the same cell; otherwise to state F there.
+ *   state E at (i, j):         emit D.  If E[i-1][j] + e > H[i-1][j] + o (strictly) stay in E at (i-1, j), otherwise go to
+ *                              H at (i-1, j).
+ *   state F at (i, j):         emit I.  Stay in F at (i, j-1) only on strict F[i][j-1] + e > H[i][j-1] + o, otherwise go to
+ *                              H at (i, j-1).
+ *   state H with i == 0:       emit j x I and stop.       state H with j == 0:  emit i x D and stop.
+ * The emitted operations are reversed and equal neighbours merged into maximal runs.  An operation is
+ * uint32_t = length << 4 | op with the BAM codes below.  '=' means identical input bytes; under a matrix identical symbol
+ * codes, whatever that entry scores -- the rule `matches` uses in the stats contract.
+ * Answered without a fill: nothing consumed gives zero operations (a LOCAL or EXTEND score of 0, both sides empty);
+ * ca == 0 < cb gives cb D; cb == 0 < ca gives ca I (GLOBAL with an empty side, FIT / EXTEND_QUERY with b_end = -1).
+ * Soft clips are the caller's arithmetic from the hit.
+ * Relation to the stats ("Alignment statistics"): the CIGAR is ONE optimal alignment of the span, the stats describe the
+ * optimal alignment with the most matches.  So sum('=') <= matches, and where they are equal sum('=' + 'X') <= pairs.
+ * Limits: the query of a cigar batch is at most AGX_SW_CIGAR_MAX_QUERY_LEN (a longer one fails the create with AGX_E_LIMIT, in
+ * every mode), the target AGX_SW_ALIGN_MAX_TARGET_LEN.
+ * Memory: the traced fill writes four bits per cell of the span.  agx_sw_batch_cigars cuts the traced pairs into chunks in
+ * the caller's order: a chunk takes pairs until the next one would pass AGX_OPT_SW_TRACE_BYTES (directions and operation
+ * slots together, counted by a bound that does not depend on the plan), and always at least one.  The largest pair the
+ * limits admit (2048 x 65 535) needs about 67 MB of directions plus its slot, so no pair is refused for size.  The block is
+ * returned to the context's pool after every chunk: a resident batch holds none of it between calls.
+ */
+#define AGX_CIGAR_INS 1
+#define AGX_CIGAR_DEL 2
+#define AGX_CIGAR_EQ 7
+#define AGX_CIGAR_DIFF 8
+#define AGX_SW_CIGAR_MAX_QUERY_LEN 2048 /* 64 lanes x 32 columns (the four widest lane classes are not built with the trace) */
+typedef struct agx_sw_cigar_info { /* of the last agx_sw_batch_cigars on this batch */
+    int64_t n_traced;              /* pairs that needed a traced fill (ca > 0 and cb > 0) */
+    int64_t trace_cells;           /* sum ca*cb over them */
+    int64_t trace_bytes_peak;      /* largest device block held for directions + operation slots at one time */
+    int32_t n_chunks, reserved;
+} agx_sw_cigar_info;
+/* A cigar batch is an AGX_SW_ALIGN_SPANS batch of `mode` that can also answer agx_sw_batch_cigars.  Exactly one way of scoring,
+ * as agx_sw_batch_create_align_stats.  launch, scores, hits, bind_scores (accepted and ignored) behave as on a stats batch;
+ * agx_sw_batch_stats on it is AGX_E_ARG (the two do not combine).  ctx may be NULL: plan only. */
+int agx_sw_batch_create_align_cigar(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matrix *matrix, int mode, const uint8_t *bases,
+                                    const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_batch **out);
+/* Waits for the launched fill.  Writes hits (may be NULL) and op_off[0..n_pairs] always; pair p's operations are
+ * ops[op_off[p] .. op_off[p+1]).  ops == NULL is the sizing call: AGX_OK with op_off filled.  ops != NULL with
+ * ops_cap < op_off[n_pairs]: AGX_E_ARG, the message names the count needed, ops is left untouched.  The result is kept in the
+ * batch until the next launch or the destroy, so the sizing call followed by the real one costs one computation.
+ * Every CIGAR is checked on the host before it is returned: the traced fill's corner score equals the hit's score, the
+ * operations consume exactly ca and cb, every '=' and 'X' agrees with the symbols, no two neighbouring runs share an op,
+ * and rescoring the operations (o for the first cell of a run of I or D, e for each further one) gives the score --
+ * AGX_E_INTERNAL naming the pair otherwise: no CIGAR is returned that the library cannot vouch for.
+ * AGX_E_ARG on a batch that was not created by agx_sw_batch_create_align_cigar. */
+int agx_sw_batch_cigars(agx_sw_batch *b, agx_sw_hit *hits /* may be NULL */, uint64_t *op_off, uint32_t *ops, uint64_t ops_cap);
+int agx_sw_batch_cigar_info(const agx_sw_batch *b, agx_sw_cigar_info *info);
+/* One-shot: create_align_cigar + launch + cigars + destroy.  ops_cap >= sum(len) always suffices. */
+int agx_sw_align_cigar(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matrix *matrix, int mode, const uint8_t *bases,
+                       const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_hit *hits /* may be NULL */, uint64_t *op_off,
+                       uint32_t *ops, uint64_t ops_cap);
 
 /* One-shot: create + launch + scores + destroy. */
 int agx_sw_score(agx_ctx *ctx, const uint8_t *bases, const uint64_t *off, const uint32_t *len, int64_t n_pairs,
