@@ -29,6 +29,9 @@ SwStat = np.dtype([("matches", np.int32), ("pairs", np.int32)])
 SW_STATS_MAX_QUERY_LEN = 1792
 # CIGARs (include/agx.h, "Alignment itself"): an operation is length << 4 | one of the BAM codes below
 SW_CIGAR_MAX_QUERY_LEN = 2048
+# banded batches (include/agx.h, "Banded alignment"): both sides up to SW_BAND_MAX_LEN, at most SW_BAND_MAX_WIDTH diagonals
+SW_BAND_MAX_LEN = 65535
+SW_BAND_MAX_WIDTH = 2048
 CIGAR_INS, CIGAR_DEL, CIGAR_EQ, CIGAR_DIFF = 1, 2, 7, 8
 _CIGAR_CHARS = {CIGAR_INS: "I", CIGAR_DEL: "D", CIGAR_EQ: "=", CIGAR_DIFF: "X"}
 OPT_SW_KERNEL = 1
@@ -51,6 +54,7 @@ SYMBOLS = [
     "agx_sw_batch_create_align_matrix", "agx_sw_align_matrix",
     "agx_sw_batch_create_align_stats", "agx_sw_batch_stats", "agx_sw_align_stats",
     "agx_sw_batch_create_align_cigar", "agx_sw_batch_cigars", "agx_sw_batch_cigar_info", "agx_sw_align_cigar",
+    "agx_sw_batch_create_align_band", "agx_sw_align_band",
     "agx_sw_score", "agx_sw_score_multi", "agx_sw_score_devices", "agx_sw_shard_cuts",
     "agx_phmm_batch_create", "agx_phmm_batch_launch", "agx_phmm_batch_results", "agx_phmm_batch_bind_results", "agx_phmm_batch_info",
     "agx_phmm_batch_destroy", "agx_phmm_forward", "agx_phmm_forward_multi", "agx_phmm_forward_devices", "agx_phmm_shard_cuts",
@@ -197,6 +201,9 @@ def lib():
         l.agx_sw_batch_cigar_info.argtypes = [C.c_void_p, C.POINTER(SwCigarInfo)]
         l.agx_sw_align_cigar.argtypes = [C.c_void_p, C.POINTER(SwScoring), C.POINTER(SwMatrix), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
+        l.agx_sw_batch_create_align_band.argtypes = [C.c_void_p, C.POINTER(SwScoring), C.c_int, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                     C.c_int64, C.POINTER(C.c_void_p)]
+        l.agx_sw_align_band.argtypes = [C.c_void_p, C.POINTER(SwScoring), C.c_int, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
         l.agx_sw_score.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
         l.agx_sw_score_multi.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
         l.agx_sw_score_devices.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
@@ -300,8 +307,16 @@ class Context:
         return ms.value
 
     # ---- Smith-Waterman
-    def sw_batch(self, b, scoring=None, matrix=None, align=0, mode=SW_MODE_LOCAL, stats=False, cigar=False) -> "SwBatch":
-        return SwBatch(self, b, scoring, matrix, align, mode, stats, cigar)
+    def sw_batch(self, b, scoring=None, matrix=None, align=0, mode=SW_MODE_LOCAL, stats=False, cigar=False, band=None) -> "SwBatch":
+        return SwBatch(self, b, scoring, matrix, align, mode, stats, cigar, band)
+
+    def sw_align_band(self, b, mode, band, scoring=None) -> np.ndarray:
+        """b: synth.SWBatch -> SwHit records of the BANDED alignment (include/agx.h, "Banded alignment"), one-shot.
+        mode: SW_MODE_GLOBAL or SW_MODE_EXTEND; band: the half-width w >= 0; sequences up to SW_BAND_MAX_LEN on both sides."""
+        out = np.empty(b.n_pairs, SwHit)
+        sc = C.byref(SwScoring(*scoring)) if scoring is not None else None
+        _check(lib().agx_sw_align_band(self._h, sc, mode, band, _ptr(b.bases), _ptr(b.off), _ptr(b.len), b.n_pairs, _ptr(out)))
+        return out
 
     def sw_align_cigar(self, b, scoring=None, mode=SW_MODE_LOCAL, matrix=None):
         """b: synth.SWBatch -> (SwHit records as SW_ALIGN_SPANS gives them, op_off uint64[n + 1], ops uint32), one-shot:
@@ -359,14 +374,23 @@ class Context:
 class SwBatch:
     """agx_sw_batch: a scheduled batch resident in HBM (ctx=None: planned on the host only)."""
 
-    def __init__(self, ctx, b, scoring=None, matrix=None, align=0, mode=SW_MODE_LOCAL, stats=False, cigar=False):
+    def __init__(self, ctx, b, scoring=None, matrix=None, align=0, mode=SW_MODE_LOCAL, stats=False, cigar=False, band=None):
         """scoring: None (the reference's +1/-1/-3/-1) or (match, mismatch, gap_open, gap_extend);
         matrix: an SwMatrix instead (score-only and align batches alike); align: SW_ALIGN_ENDS / SW_ALIGN_SPANS for a batch that also answers hits();
         mode: SW_MODE_* of an align batch (local, global, fit, extension); stats=True: a SPANS batch that also answers stats();
-        cigar=True: a SPANS batch that also answers cigars() (not together with stats)."""
+        cigar=True: a SPANS batch that also answers cigars() (not together with stats);
+        band=w: a BANDED batch of mode SW_MODE_GLOBAL or SW_MODE_EXTEND (half-width w; it answers hits() as a SPANS batch does;
+        no matrix, stats or cigar)."""
         self.ctx = ctx
         self.n_pairs = b.n_pairs
         self._h = C.c_void_p()
+        if band is not None:
+            if matrix is not None or stats or cigar or align not in (0, SW_ALIGN_SPANS):
+                raise AgxError(E_ARG, "a banded batch is a SW_ALIGN_SPANS batch under match/mismatch scoring: no matrix, stats or cigar")
+            sc = C.byref(SwScoring(*scoring)) if scoring is not None else None
+            _check(lib().agx_sw_batch_create_align_band(ctx._h if ctx else None, sc, mode, band, _ptr(b.bases), _ptr(b.off), _ptr(b.len),
+                                                        b.n_pairs, C.byref(self._h)))
+            return
         if cigar:
             if stats or align not in (0, SW_ALIGN_SPANS):
                 raise AgxError(E_ARG, "a cigar batch is a SW_ALIGN_SPANS batch, and not a stats batch as well")

@@ -237,6 +237,12 @@ struct agx_sw_batch {
     // modes other than LOCAL: pairs with an empty side whose score is not the zero the device array holds for them
     std::vector<int64_t> fix_pair;
     std::vector<int32_t> fix_score;
+    // agx_sw_batch_create_align_band: a banded batch -- align = SPANS, mode GLOBAL or EXTEND, its records are
+    // SwBandGroup, its image bytes, launches[].C the diagonals per lane; band_pos receives EXTEND's i << 16 | j per pair
+    bool banded = false;
+    int32_t band = 0;
+    DevBuf band_pos;
+    PinBuf band_pos_stage;
     agx_sw_scoring scoring{};
     DevBuf ends;        // per pair: row << kSwLocColBits | column of the end cell, written by the locating fill
     PinBuf ends_stage;  // its page-locked landing block
@@ -291,6 +297,8 @@ void agx_sw_batch_destroy(agx_sw_batch *b)
     b->ends_stage.release();
     b->lstat.release();
     b->lstat_stage.release();
+    b->band_pos.release();
+    b->band_pos_stage.release();
     b->goff.release();
     b->walkrec.release();
     agx_ctx_release(b->ctx); // the batch's own reference: a context outlives its batches
@@ -1565,7 +1573,361 @@ int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matri
 
 } // namespace
 
+// ------------------------------------------------------------------ banded batches (include/agx.h, "Banded alignment")
+namespace {
+
+agx_sw_hit empty_side_hit(int mode, int what, const agx_sw_scoring &sc, uint32_t la, uint32_t lb);
+
+// The band of a pair: GLOBAL widens it by the length difference, EXTEND keeps it around the main diagonal.
+inline void band_limits(int mode, int64_t w, int64_t la, int64_t lb, int64_t &dlo, int64_t &dhi)
+{
+    const int64_t diff = mode == AGX_SW_MODE_GLOBAL ? la - lb : 0;
+    dlo = std::min<int64_t>(0, diff) - w;
+    dhi = std::max<int64_t>(0, diff) + w;
+}
+
+// Lane tiling of a band of `width` diagonals over lb rows: K diagonals per lane, G = ceil(width / K) lanes per group, 64 / G
+// groups per wave.  A wave step costs about kBandStepCells cells' worth of instructions besides its K cells (the exchanges, the
+// cell mask, the window shift, the loop: counted in the K = 8 disassembly) and a group runs lb + G steps; the
+// class with the least lane time per pair wins, ties go to the wider one (fewer steps).
+constexpr int kBandStepCells = 5;
+inline void band_tiling(int width, uint32_t lb, int &cls, int &G)
+{
+    double best = 0;
+    cls = -1;
+    for (int c = kSwNumBandClasses - 1; c >= 0; --c) {
+        const int K = kSwBandClasses[c], g = (width + K - 1) / K;
+        if (g > 64) continue;
+        const double cost = ((double)lb + g) * (kBandStepCells + K) / (double)(64 / g);
+        if (cls < 0 || cost < best) {
+            best = cost;
+            cls = c;
+            G = g;
+        }
+    }
+}
+
+struct BandPlan { // one pair with work, as the sort moves it
+    uint32_t pair, la, lb;
+    int32_t dlo, dhi;
+    uint8_t cls, G;
+};
+
+int create_band(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t band, const uint8_t *bases, const uint64_t *off,
+                const uint32_t *len, int64_t n_pairs, agx_sw_batch **out)
+{
+    const char *who = "agx_sw_batch_create_align_band";
+    if (!out) {
+        agx_set_error("%s: out is NULL", who);
+        return AGX_E_ARG;
+    }
+    *out = nullptr;
+    if (mode < AGX_SW_MODE_LOCAL || mode > AGX_SW_MODE_EXTEND_QUERY) {
+        agx_set_error("%s: mode = %d is not one of AGX_SW_MODE_LOCAL .. AGX_SW_MODE_EXTEND_QUERY (0..4)", who, mode);
+        return AGX_E_ARG;
+    }
+    if (mode != AGX_SW_MODE_GLOBAL && mode != AGX_SW_MODE_EXTEND) {
+        agx_set_error("%s: mode = %d has a free start or a column capture; a band around the main diagonal serves AGX_SW_MODE_GLOBAL and "
+                      "AGX_SW_MODE_EXTEND only",
+                      who, mode);
+        return AGX_E_ARG;
+    }
+    if (band < 0) {
+        agx_set_error("%s: band = %d is negative", who, band);
+        return AGX_E_ARG;
+    }
+    int rc = ctx ? agx_bind(ctx) : AGX_OK;
+    if (rc) return rc;
+    if (n_pairs < 0 || (n_pairs > 0 && (!off || !len))) {
+        agx_set_error("%s: bad arguments (n_pairs=%lld)", who, (long long)n_pairs);
+        return AGX_E_ARG;
+    }
+    if (n_pairs > 0x7fffffffLL / 2) {
+        agx_set_error("%s: more than 2^30 pairs in one batch", who);
+        return AGX_E_LIMIT;
+    }
+    const agx_sw_scoring ref_scoring = AGX_SW_SCORING_REFERENCE;
+    const agx_sw_scoring sc = scoring ? *scoring : ref_scoring;
+    if (sc.match < 1 || sc.match > 12 || sc.mismatch > 0 || sc.mismatch < sc.match - 128 || sc.gap_open > 0 || sc.gap_open < -1000 ||
+        sc.gap_extend > 0 || sc.gap_extend < -1000) {
+        agx_set_error("scoring {match %d, mismatch %d, open %d, extend %d} outside the supported range", sc.match, sc.mismatch, sc.gap_open,
+                      sc.gap_extend);
+        return AGX_E_LIMIT;
+    }
+
+    // ---- pass A: limits, band, lane tiling
+    std::vector<BandPlan> plan;
+    int64_t cells = 0;
+    for (int64_t p = 0; p < n_pairs; ++p) {
+        const uint32_t la = len[2 * p], lb = len[2 * p + 1];
+        if (la > (uint32_t)AGX_SW_BAND_MAX_LEN || lb > (uint32_t)AGX_SW_BAND_MAX_LEN) {
+            agx_set_error("pair %lld: lengths %u x %u exceed the supported %d on either side of a banded batch", (long long)p, la, lb,
+                          AGX_SW_BAND_MAX_LEN);
+            return AGX_E_LIMIT;
+        }
+        int64_t dlo, dhi;
+        band_limits(mode, band, la, lb, dlo, dhi);
+        if (dhi - dlo + 1 > AGX_SW_BAND_MAX_WIDTH) {
+            agx_set_error("pair %lld: lengths %u x %u at band %d need %lld diagonals, supported %d", (long long)p, la, lb, band,
+                          (long long)(dhi - dlo + 1), AGX_SW_BAND_MAX_WIDTH);
+            return AGX_E_LIMIT;
+        }
+        cells += (int64_t)la * lb;
+        if (!la || !lb) continue; // answered by the formulas
+        if (!bases) {
+            agx_set_error("%s: bases is NULL", who);
+            return AGX_E_ARG;
+        }
+        BandPlan e{(uint32_t)p, la, lb, (int32_t)dlo, (int32_t)dhi, 0, 0};
+        int cls = 0, G = 1;
+        band_tiling((int)(dhi - dlo + 1), lb, cls, G);
+        e.cls = (uint8_t)cls;
+        e.G = (uint8_t)G;
+        plan.push_back(e);
+    }
+    // ---- sort: class, lanes per group, then rows falling -- the groups of a wave step alike (lb + G)
+    std::sort(plan.begin(), plan.end(), [](const BandPlan &x, const BandPlan &y) {
+        if (x.cls != y.cls) return x.cls < y.cls;
+        if (x.G != y.G) return x.G < y.G;
+        if (x.lb != y.lb) return x.lb > y.lb;
+        return x.pair < y.pair;
+    });
+    // ---- waves, group records, image offsets
+    const size_t n_fill = plan.size();
+    std::vector<SwBandGroup> groups(n_fill);
+    std::vector<SwWave> waves;
+    std::vector<ClassLaunch> launches;
+    uint64_t img_dw = 0;
+    int64_t padded = 0;
+    for (size_t k = 0; k < n_fill;) {
+        const BandPlan &h = plan[k];
+        const int K = kSwBandClasses[h.cls], G = h.G, per_wave = 64 / G;
+        size_t end = k;
+        while (end < n_fill && end - k < (size_t)per_wave && plan[end].cls == h.cls && plan[end].G == h.G) ++end;
+        SwWave w{};
+        w.first_group = (uint32_t)k;
+        w.n_groups = (uint16_t)(end - k);
+        w.G = (uint16_t)G;
+        w.steps = h.lb + (uint32_t)G; // the wave's longest target comes first
+        w.reserved = (uint32_t)K;
+        if (launches.empty() || launches.back().C != K) {
+            ClassLaunch cl;
+            cl.C = K;
+            cl.first_wave = (uint32_t)waves.size();
+            launches.push_back(cl);
+        }
+        ++launches.back().n_waves;
+        waves.push_back(w);
+        padded += (int64_t)w.steps * 64 * K;
+        for (; k < end; ++k) {
+            const BandPlan &e = plan[k];
+            SwBandGroup &g = groups[k];
+            const int q0 = e.dlo + G * K - G;
+            g.fpad = (uint32_t)(((-q0) % 4 + 4) % 4);
+            g.x_dw = (uint32_t)img_dw;
+            img_dw += (g.fpad + e.la + 3) / 4 + 1;
+            g.y_dw = (uint32_t)img_dw;
+            img_dw += (e.lb + 4) / 4 + 1;
+            g.la_lb = e.la | e.lb << 16;
+            g.dlo = e.dlo;
+            g.dhi = e.dhi;
+            g.out = e.pair;
+            g.reserved = 0;
+            if (img_dw > 0xffffffffull) {
+                agx_set_error("pair %u: the batch's sequences exceed the 16 GiB a banded batch's image may take", e.pair);
+                return AGX_E_LIMIT;
+            }
+        }
+    }
+
+    agx_sw_batch *b = new agx_sw_batch();
+    DrainOnError done(ctx, [&] { agx_sw_batch_destroy(b); }); // (an error exit behind a queued copy drains the copy stream first)
+    agx_ctx_retain(ctx);
+    b->ctx = ctx;
+    b->n_pairs = n_pairs;
+    b->banded = true;
+    b->band = band;
+    b->family = 5;
+    b->align = AGX_SW_ALIGN_SPANS;
+    b->mode = mode;
+    b->scoring = sc;
+    b->prm.ge = sc.gap_extend;
+    b->prm.gf = sc.gap_open + sc.gap_extend;
+    b->prm.hd = sc.match - b->prm.gf;
+    b->prm.delta = sc.match - sc.mismatch;
+    b->prm.n_out = (uint32_t)n_pairs;
+    b->launches = launches;
+    b->info.n_pairs = n_pairs;
+    b->info.cells = cells;
+    b->info.padded_cells = padded;
+    b->info.input_bytes = (int64_t)(img_dw * 4);
+    b->info.n_launches = (int32_t)launches.size();
+    b->info.n_waves = (int32_t)waves.size();
+    if (!ctx) {
+        *out = b;
+        b = nullptr;
+        done.ok = true;
+        return AGX_OK;
+    }
+    agx_sw_band_preload();
+    if (n_pairs > 0) b->seq_len.assign(len, len + 2 * n_pairs);
+    PinBuf h_img, h_groups, h_waves;
+    struct Temps {
+        PinBuf *a, *b, *c;
+        ~Temps()
+        {
+            a->release();
+            b->release();
+            c->release();
+        }
+    };
+    if (n_fill) {
+        // ---- the image, built on the host (it touches every byte once: the symbol check rides along)
+        rc = h_img.alloc(ctx, (size_t)img_dw * 4);
+        if (!rc) rc = h_groups.alloc(ctx, n_fill * sizeof(SwBandGroup));
+        if (!rc) rc = h_waves.alloc(ctx, waves.size() * sizeof(SwWave));
+        Temps temps{&h_img, &h_groups, &h_waves}; // released after `done` below has drained (it is declared later, so runs first)
+        DrainOnError drain(ctx, [] {});
+        if (rc) return rc;
+        memcpy(h_groups.p, groups.data(), n_fill * sizeof(SwBandGroup));
+        memcpy(h_waves.p, waves.data(), waves.size() * sizeof(SwWave));
+        std::vector<int64_t> bad((size_t)agx_host_threads(), -1);
+        uint8_t *im = (uint8_t *)h_img.p;
+        agx_parallel_for((int64_t)n_fill, 64, [&](int64_t lo, int64_t hi, int t) {
+            int64_t first_bad = -1;
+            for (int64_t k = lo; k < hi; ++k) {
+                const SwBandGroup &g = groups[(size_t)k];
+                const uint32_t la = g.la_lb & 0xffffu, lb = g.la_lb >> 16;
+                const uint8_t *sa = bases + off[2 * (size_t)g.out], *sb = bases + off[2 * (size_t)g.out + 1];
+                uint8_t *xa = im + (size_t)g.x_dw * 4, *ya = im + (size_t)g.y_dw * 4;
+                const size_t xbytes = ((size_t)(g.fpad + la + 3) / 4 + 1) * 4, ybytes = ((size_t)(lb + 4) / 4 + 1) * 4;
+                memset(xa, 0, g.fpad);
+                memcpy(xa + g.fpad, sa, la);
+                memset(xa + g.fpad + la, 0, xbytes - g.fpad - la);
+                ya[0] = 0;
+                memcpy(ya + 1, sb, lb);
+                memset(ya + 1 + lb, 0, ybytes - 1 - lb);
+                if ((memchr(sa, 0, la) || memchr(sb, 0, lb)) && (first_bad < 0 || (int64_t)g.out < first_bad)) first_bad = g.out;
+            }
+            bad[(size_t)t] = first_bad;
+        });
+        int64_t first_bad = -1;
+        for (int64_t v : bad)
+            if (v >= 0 && (first_bad < 0 || v < first_bad)) first_bad = v;
+        if (first_bad >= 0) {
+            agx_set_error("pair %lld contains byte 0x00, which is reserved as the padding symbol", (long long)first_bad);
+            return AGX_E_SYMBOL;
+        }
+        rc = b->img.alloc(ctx, (size_t)img_dw * 4);
+        if (!rc) rc = b->groups.alloc(ctx, n_fill * sizeof(SwBandGroup));
+        if (!rc) rc = b->waves.alloc(ctx, waves.size() * sizeof(SwWave));
+        if (!rc && launches.size() > 1) rc = agx_ctx_prepare_fanout(ctx);
+        if (rc) return rc;
+        hipStream_t cs = ctx->copy;
+        AGX_HIP(hipMemcpyAsync(b->img.p, h_img.p, (size_t)img_dw * 4, hipMemcpyHostToDevice, cs));
+        AGX_HIP(hipMemcpyAsync(b->groups.p, h_groups.p, n_fill * sizeof(SwBandGroup), hipMemcpyHostToDevice, cs));
+        AGX_HIP(hipMemcpyAsync(b->waves.p, h_waves.p, waves.size() * sizeof(SwWave), hipMemcpyHostToDevice, cs));
+        // results and their landing blocks (a later failure leaves behind the queued copies: `drain` waits for them)
+        const size_t words = (size_t)n_pairs * sizeof(uint32_t);
+        rc = b->scores.alloc(ctx, words);
+        if (!rc) rc = b->band_pos.alloc(ctx, words);
+        if (!rc) rc = b->out_stage.alloc(ctx, words);
+        if (!rc) rc = b->band_pos_stage.alloc(ctx, words);
+        if (rc) return rc;
+        AGX_HIP(hipStreamSynchronize(cs));
+        drain.ok = true;
+    }
+    *out = b;
+    b = nullptr;
+    done.ok = true;
+    return AGX_OK;
+}
+
+int band_launch(agx_sw_batch *b)
+{
+    if (b->launches.empty()) return AGX_OK;
+    FanOut fan(b->ctx, (int)b->launches.size());
+    int rc = fan.begin();
+    if (rc) return rc;
+    int k = 0;
+    // widest class first: its waves have the longest steps
+    for (auto it = b->launches.rbegin(); it != b->launches.rend(); ++it) {
+        const ClassLaunch &cl = *it;
+        if (agx_sw_band_launch_class(cl.C, b->mode == AGX_SW_MODE_EXTEND, b->prm, (const uint32_t *)b->img.p, (const SwBandGroup *)b->groups.p,
+                                     (const SwWave *)b->waves.p + cl.first_wave, cl.n_waves, (int32_t *)b->scores.p, (uint32_t *)b->band_pos.p,
+                                     fan.stream(k++))) {
+            agx_set_error("sw_fill_band<%d> launch failed: %s", cl.C, hipGetErrorString(hipGetLastError()));
+            return AGX_E_HIP;
+        }
+    }
+    return fan.end();
+}
+
+// waits for the launched fill and builds the hits by the contract's rules, in the caller's pair order
+int band_hits(agx_sw_batch *b, agx_sw_hit *hits)
+{
+    int rc = agx_bind(b->ctx);
+    if (rc) return rc;
+    hipStream_t st = b->ctx->stream;
+    const int64_t n = b->n_pairs;
+    const bool filled = !b->launches.empty();
+    if (filled) {
+        AGX_HIP(hipMemcpyAsync(b->out_stage.p, b->scores.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        if (b->mode == AGX_SW_MODE_EXTEND)
+            AGX_HIP(hipMemcpyAsync(b->band_pos_stage.p, b->band_pos.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    }
+    AGX_HIP(hipStreamSynchronize(st));
+    const int32_t *sc = (const int32_t *)b->out_stage.p;
+    const uint32_t *ps = (const uint32_t *)b->band_pos_stage.p;
+    for (int64_t p = 0; p < n; ++p) {
+        const uint32_t la = b->seq_len[(size_t)(2 * p)], lb = b->seq_len[(size_t)(2 * p + 1)];
+        if (!la || !lb) {
+            hits[p] = empty_side_hit(b->mode, AGX_SW_ALIGN_SPANS, b->scoring, la, lb);
+            continue;
+        }
+        agx_sw_hit h{sc[p], 0, (int32_t)la - 1, 0, (int32_t)lb - 1};
+        if (b->mode == AGX_SW_MODE_EXTEND) {
+            if (h.score <= 0)
+                h = agx_sw_hit{0, -1, -1, -1, -1};
+            else {
+                const uint32_t i = ps[p] >> 16, j = ps[p] & 0xffffu;
+                if (i < 1 || i > lb || j < 1 || j > la) {
+                    agx_set_error("pair %lld: the banded fill reported the end cell (%u, %u) outside the %u x %u matrix", (long long)p, i, j, lb, la);
+                    return AGX_E_INTERNAL;
+                }
+                h.b_end = (int32_t)i - 1;
+                h.a_end = (int32_t)j - 1;
+            }
+        }
+        hits[p] = h;
+    }
+    return AGX_OK;
+}
+
+} // namespace
+
 extern "C" {
+
+int agx_sw_batch_create_align_band(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t band, const uint8_t *bases,
+                                   const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_batch **out)
+{
+    AGX_GUARD_BEGIN
+    return create_band(ctx, scoring, mode, band, bases, off, len, n_pairs, out);
+    AGX_GUARD_END("agx_sw_batch_create_align_band")
+}
+
+int agx_sw_align_band(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t band, const uint8_t *bases, const uint64_t *off,
+                      const uint32_t *len, int64_t n_pairs, agx_sw_hit *hits)
+{
+    agx_sw_batch *b = nullptr;
+    int rc = agx_sw_batch_create_align_band(ctx, scoring, mode, band, bases, off, len, n_pairs, &b);
+    if (rc) return rc;
+    rc = agx_sw_batch_launch(b);
+    if (!rc) rc = agx_sw_batch_hits(b, hits);
+    if (rc && b->ctx) (void)hipStreamSynchronize(b->ctx->stream); // the blocks go back to the pools: nothing may still run on them
+    agx_sw_batch_destroy(b);
+    return rc;
+}
 
 int agx_sw_batch_launch(agx_sw_batch *b)
 {
@@ -1579,6 +1941,7 @@ int agx_sw_batch_launch(agx_sw_batch *b)
     }
     int rc = agx_bind(b->ctx);
     if (rc) return rc;
+    if (b->banded) return band_launch(b);
     // a batch whose create was not finished: its fill waits for the pack kernel on the device, not on the host
     if (b->pending && b->pending->ready) AGX_HIP(hipStreamWaitEvent(b->ctx->stream, b->pending->ready, 0));
     SwParams prm = b->prm;
@@ -1665,6 +2028,14 @@ int agx_sw_batch_scores(agx_sw_batch *b, int32_t *scores)
     }
     int rc = agx_bind(b->ctx);
     if (rc) return rc;
+    if (b->banded) { // the mode's score is the hit's
+        AGX_GUARD_BEGIN
+        std::vector<agx_sw_hit> h((size_t)b->n_pairs);
+        rc = band_hits(b, h.data());
+        for (int64_t p = 0; !rc && p < b->n_pairs; ++p) scores[p] = h[(size_t)p].score;
+        return rc;
+        AGX_GUARD_END("agx_sw_batch_scores")
+    }
     if (b->pending) { // (the pieces of agx_sw_score finish before they fetch; kept for safety)
         rc = finish_create(b);
         if (rc) return rc;
@@ -2073,6 +2444,7 @@ int agx_sw_batch_hits(agx_sw_batch *b, agx_sw_hit *hits)
         return AGX_E_NODEVICE;
     }
     AGX_GUARD_BEGIN
+    if (b->banded) return band_hits(b, hits);
     return hits_impl(b, hits, nullptr);
     AGX_GUARD_END("agx_sw_batch_hits")
 }

@@ -203,6 +203,26 @@ int agx_sw_gather_launch(const SwWalkRec *recs, uint32_t n, const uint32_t *slot
                          hipStream_t s);
 void agx_sw_walk_preload();
 
+// ---- the banded fill of agx_sw_batch_create_align_band (agx_sw_band_kernel.hip): the lanes of a group own the
+// diagonals dlo .. dhi of one pair, K consecutive ones per lane.  Its image is bytes: a (the query) behind fpad zero bytes, b (the
+// target) behind one byte, each padded with zeros to a dword; its waves are SwWave records (G lanes per group, steps = max lb + G).
+struct SwBandGroup {
+    uint32_t x_dw;    // a: fpad zero bytes, la symbols, zeros to the dword
+    uint32_t y_dw;    // b: one byte, lb symbols, zeros to the dword
+    uint32_t la_lb;   // la | lb << 16
+    int32_t dlo, dhi; // the band: dlo <= j - i <= dhi
+    uint32_t out;     // the caller's pair number
+    uint32_t fpad;    // (-(dlo + G K - G)) mod 4: the byte the group's last lane loads at step t is dword-aligned when t % 4 == 0
+    uint32_t reserved;
+};
+#define AGX_SW_FOR_EACH_BAND_CLASS(X) X(4) X(8) X(16) X(32)
+static const int kSwBandClasses[] = {4, 8, 16, 32};
+constexpr int kSwNumBandClasses = 4;
+static_assert(64 * 32 == AGX_SW_BAND_MAX_WIDTH, "the widest band is 64 lanes of the widest class");
+int agx_sw_band_launch_class(int diags_per_lane, int extend, const SwParams &prm, const uint32_t *img, const SwBandGroup *groups,
+                             const SwWave *waves, uint32_t n_waves, int32_t *scores, uint32_t *pos, hipStream_t s);
+void agx_sw_band_preload();
+
 // ---- device-side planning (agx_sw_plan_kernel.hip): the O(pairs) passes of the planner as kernels
 constexpr uint32_t kSwPlanEmptyKey = 1u << 27;           // sort key of a pair with an empty side: behind every bucket
 constexpr uint32_t kSwPlanWaveKeyMax = (1u << 24) - 1u;  // wave dispatch key = this - steps x columns per lane

@@ -1,0 +1,266 @@
+// Smith-Waterman BANDED fill for gfx950: pinned-start Gotoh (no zero floor, gap-initialised boundaries) over the cells within a
+// fixed distance of the main diagonal.  Behind agx_sw_batch_create_align_band, modes GLOBAL and EXTEND (include/agx.h, "Banded
+// alignment"; DESIGN.md 4.1g).  The anchored fill (agx_sw_anch_kernel.inc) lays the query's COLUMNS across the lanes; here the
+// lanes own DIAGONALS, so neither side has a column limit and the cost is length x band.
+//
+// Matrix.  Cell (i, j): i symbols of b (target) and j of a (query) consumed, 0 <= i <= lb, 0 <= j <= la, diagonal d = j - i,
+// inside the band iff dlo <= d <= dhi.  A group of G lanes owns one pair; lane gl owns the K diagonals d0 + k, d0 = dlo + gl K,
+// k = 0 .. K - 1 (G K >= dhi - dlo + 1; the slots beyond dhi are masked).  State per diagonal, in registers: z = H + gf
+// (gf = gap_open + gap_extend, what both gap recurrences read) and e = E, int32, TRUE values -- no rising offset.
+//
+// Step t: lane gl fills row i = t - gl of its diagonals, left to right (k = 0 .. K - 1 is j = i + d0 + k).  A cell reads
+//   left  (i, j - 1)      diagonal d - 1: the cell before it in this step; for k = 0 lane gl - 1's last cell of step t - 1
+//                         (DPP wave_shr:1 of z and f), a group's first lane substitutes minus infinity
+//   diag  (i - 1, j - 1)  diagonal d:     its own z[k] of the step before
+//   up    (i - 1, j)      diagonal d + 1: its own z[k + 1], e[k + 1] of the step before (read before cell k + 1 overwrites them);
+//                         for k = K - 1 the FIRST cell lane gl + 1 computes in this very step (it is one row behind).
+// Hence two phases: every lane computes cell 0, hands its z and e to the left (DPP wave_shl:1; a group's last lane substitutes
+// minus infinity), then computes cells 1 .. K - 1.
+//
+// Symbols.  b[i - 1] of a lane's row enters at the group's first lane and moves one lane per step (wave_shr:1), as in the
+// anchored fill; a row outside 1 .. lb carries kBandRowPad, which equals no byte.  The query runs the other way: lane gl holds the
+// K bytes a[j0 - 1 .. j0 + K - 2], j0 = i + d0, in K / 4 dwords and shifts them by one byte per step (v_alignbyte); the byte that
+// enters on top is byte 1 of lane gl + 1's window of the same step (wave_shl:1), and the group's last lane takes it from the
+// image: a[q0 + t], q0 = dlo + G K - G.  The host stores a behind (-q0 mod 4) zero bytes, so that byte sits at a dword boundary
+// when t is a multiple of four in every group of the wave, and b behind one byte for the same reason: both loaders read one
+// dword per four steps, three quads ahead.  Positions outside a read as 0, the padding symbol (byte 0x00 is refused on input).
+//
+// Boundaries and masking.  Only H is masked: after a cell is computed its z is replaced by minus infinity unless
+// 0 <= i <= lb, 0 <= j <= la and d <= dhi -- one bit per cell of a mask made once per step.  E and F of masked cells stay as
+// computed; they are read only by other masked cells or come out as minus infinity anyway:
+//   rows i < 0, columns j < 0, columns j > la and diagonals > dhi have nothing but masked cells above them (a column leaves the
+//       band upwards at dhi, where the last lane reads minus infinity), so their E derives from minus infinity; their F is read
+//       to the right only, by cells of the same row that are masked as well (j > la, d > dhi) or take the left boundary (j < 0:
+//       all of row i left of column 0 is masked, so F(i, 0) = max(z, f) of minus infinities = "F is minus infinity in column 0").
+//   rows i > lb are read by rows > lb only.
+//   Row 0 and column 0 then come out of the plain recurrence: H(0, j) = F = gap_open + j ge from H(0, 0), E(0, j) = minus
+//       infinity, and likewise down column 0.  H(0, 0) = 0 itself: when a lane reaches row 0 (one compare per step, taken once)
+//       it sets the diagonal input of diagonal 0 -- "H(-1, -1)" -- to minus the mismatch score; padding never matches, so the
+//       diagonal move gives exactly 0 and E, F there are minus infinity.  That value is also read as "up" by (0, -1), whose H is
+//       masked and whose E feeds column -1 only.
+//
+// No wrap.  Minus infinity is kBandNegInf = -2^30.  A value derived from it has gap costs added along one row of the band (F) or
+// one column's stretch inside the band (E) before a masked H cuts the chain: at most 2048 cells of at most 1000 each, so it
+// stays above -2^30 - 2.05e6 > -2^31 and below -2^30 + 2048 * 12.  True values: an in-band cell of the matrix always has a path
+// from the origin inside the band (along row 0 or column 0, then its diagonal), so under (12, -116, -1000, -1000) at
+// la = lb = 65535 every true H lies within [-2000 - 131070 * 1000, 12 * 65535] = [-1.311e8, 7.9e5]; z, e and f add at most two
+// gap costs to that.  -1.32e8 > -2^30 + 2.5e4: a true value always beats a derived minus infinity, and nothing wraps.
+//
+// Capture.  GLOBAL: the lane and register that own diagonal la - lb hold z of (lb, la) after the step of row lb.  EXTEND: every
+// lane keeps the first strict improvement of its row maximum over its running maximum, which starts at H(0, 0) = 0 -- rows come
+// in rising i, and within a row it takes the leftmost cell; masked cells are minus infinity and never win.  The group reduces by
+// (score, then i, then j); the position word is i << 16 | j (both <= 65535).
+//
+// (included by agx_sw_band_kernel.hip; opens an anonymous namespace that the including file closes after its launch helper)
+#include "agx_sw.h"
+
+namespace {
+
+constexpr int kBandRowPad = 0x100; // never equals a byte
+constexpr int kBandNegInf = -(1 << 30);
+
+__device__ __forceinline__ int band_shr1(int old, int v)
+{
+    // DPP wave_shr:1 -- lane i receives lane i-1's v; lane 0 keeps old
+    return __builtin_amdgcn_update_dpp(old, v, 0x138, 0xf, 0xf, false);
+}
+__device__ __forceinline__ int band_shl1(int old, int v)
+{
+    // DPP wave_shl:1 -- lane i receives lane i+1's v; lane 63 keeps old
+    return __builtin_amdgcn_update_dpp(old, v, 0x130, 0xf, 0xf, false);
+}
+
+template <int K, bool EXT>
+__device__ __forceinline__ void band_body(const SwParams &prm, const uint32_t *__restrict__ img, const SwBandGroup *__restrict__ groups,
+                                          const SwWave w, int32_t *__restrict__ scores, uint32_t *__restrict__ pos)
+{
+    static_assert(K % 4 == 0 && K >= 4 && K <= 32, "the query window is whole dwords and the cell mask one dword");
+    constexpr int XW = K / 4;
+    const int ge = prm.ge, gf = prm.gf, s_match = prm.hd, s_mis = prm.hd - prm.delta; // the diagonal move on z: score - gf
+    const int lane = threadIdx.x & 63;
+    const int G = w.G;
+    const int grp = lane / G;
+    const int gl = lane - grp * G;
+    const bool active = grp < (int)w.n_groups;
+    const bool first = gl == 0, last = gl == G - 1;
+
+    SwBandGroup g;
+    g.x_dw = g.y_dw = g.la_lb = g.out = g.fpad = g.reserved = 0;
+    g.dlo = g.dhi = 0;
+    if (active) g = groups[w.first_group + grp];
+    const int la = (int)(g.la_lb & 0xffffu), lb = (int)(g.la_lb >> 16);
+    const int d0 = g.dlo + gl * K;
+    const int kmax = min(K - 1, g.dhi - d0); // the last in-band slot of this lane (negative: none)
+    const int k0 = -d0;                      // the slot of diagonal 0, if this lane owns it
+
+    // the query window at step 0: a[j0 - 1 + k], j0 = d0 - gl
+    uint32_t xw[XW];
+    {
+        const uint8_t *ab = reinterpret_cast<const uint8_t *>(img + g.x_dw) + g.fpad;
+#pragma unroll
+        for (int n = 0; n < XW; ++n) xw[n] = 0;
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const int idx = d0 - gl - 1 + k;
+            const uint32_t by = (active && idx >= 0 && idx < la) ? ab[idx] : 0u;
+            xw[k >> 2] |= by << (8 * (k & 3));
+        }
+    }
+    // the two loaders: b at the group's first lane, the query byte that enters the band at its last lane
+    const bool feeder = active && first, loader = active && last;
+    const uint32_t *yp = img + g.y_dw;
+    const int nyq = (lb + 4) >> 2; // one byte in front of b
+    auto row_quad = [&](int q) -> uint32_t { return (feeder && q < nyq) ? yp[q] : 0u; };
+    const uint32_t *xp = img + g.x_dw;
+    const int q0x = g.dlo + G * K - G;      // a[q0x + t] enters at step t
+    const int rel0 = ((int)g.fpad + q0x) / 4; // exact: the host chose fpad so
+    const int nxd = ((int)g.fpad + la + 3) >> 2;
+    auto col_quad = [&](int q) -> uint32_t { return (loader && (uint32_t)(rel0 + q) < (uint32_t)nxd) ? xp[rel0 + q] : 0u; };
+
+    int z[K], e[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) z[k] = e[k] = kBandNegInf;
+    int z_last = kBandNegInf, f_last = kBandNegInf, yc_prev = kBandRowPad;
+    int best = gf, hit_i = -1, hit_k = 0; // EXTEND: H(0, 0) = 0 as z
+    int corner = 0;                       // GLOBAL
+    const int dc = la - lb - g.dlo;       // GLOBAL: the corner's diagonal, counted from dlo
+    const int kc = dc - gl * K;           // its slot here, if 0 <= kc < K
+
+    uint32_t q0 = row_quad(0), q1 = row_quad(1), q2 = row_quad(2);
+    uint32_t x0 = col_quad(0), x1 = col_quad(1), x2 = col_quad(2);
+    const int steps = (int)w.steps;
+    uint32_t rows = 0, xrows = 0;
+    int t = 0;
+
+    auto step = [&]() __attribute__((always_inline)) {
+        const int i = t - gl;
+        const int fresh = (t >= 1 && t <= lb) ? (int)(rows & 0xffu) : kBandRowPad;
+        rows >>= 8;
+        const uint32_t xin = xrows & 0xffu;
+        xrows >>= 8;
+        int zl = band_shr1(kBandNegInf, z_last);
+        int fl = band_shr1(kBandNegInf, f_last);
+        int yc = band_shr1(fresh, yc_prev);
+        if (first) {
+            zl = kBandNegInf;
+            fl = kBandNegInf;
+            yc = fresh;
+        }
+        if (i == 0) { // row 0 of this lane: the diagonal input that makes H(0, 0) = 0
+            // (the slot is compared here, once per lane: hoisted out of the loop the K compares hold K scalar register pairs)
+            int slot = k0;
+            asm volatile("" : "+v"(slot));
+#pragma unroll
+            for (int k = 0; k < K; ++k) z[k] = k == slot ? -s_mis : z[k];
+        }
+        // which of this step's cells exist
+        const int j0 = i + d0;
+        const int klo = max(0, -j0), khi = min(kmax, la - j0);
+        const bool any = (uint32_t)i <= (uint32_t)lb && khi >= klo;
+        const uint32_t mask = any ? ((2u << (khi & 31)) - 1u) & (~0u << (klo & 31)) : 0u;
+        auto keep = [&](int v, int k) -> int {
+            const int m = (int)(mask << (31 - k)) >> 31; // all ones where cell k exists
+            return (v & m) | (kBandNegInf & ~m);
+        };
+
+        // phase 1: the first cell
+        int f, zleft;
+        {
+            const int ev = max(z[1], e[1] + ge);
+            f = max(zl, fl + ge);
+            const int xs = (int)(xw[0] & 0xffu);
+            const int s = z[0] + (xs == yc ? s_match : s_mis);
+            zleft = keep(max(max(ev, f), s) + gf, 0);
+            e[0] = ev;
+            z[0] = zleft;
+        }
+        // phase 2: it is the up input of the left neighbour's last diagonal
+        int rz = band_shl1(kBandNegInf, z[0]);
+        int re = band_shl1(kBandNegInf, e[0]);
+        if (last) rz = re = kBandNegInf;
+#pragma unroll
+        for (int k = 1; k < K; ++k) {
+            const int uz = k + 1 < K ? z[k + 1] : rz;
+            const int ue = k + 1 < K ? e[k + 1] : re;
+            const int ev = max(uz, ue + ge);
+            f = max(zleft, f + ge);
+            const int xs = (int)((xw[k >> 2] >> (8 * (k & 3))) & 0xffu);
+            const int s = z[k] + (xs == yc ? s_match : s_mis);
+            zleft = keep(max(max(ev, f), s) + gf, k);
+            e[k] = ev;
+            z[k] = zleft;
+        }
+
+        if constexpr (EXT) {
+            int m = z[0];
+#pragma unroll
+            for (int k = 1; k < K; ++k) m = max(m, z[k]);
+            if (m > best) { // a higher score than in any earlier row of this lane's diagonals
+                int col = 0;
+#pragma unroll
+                for (int k = K - 1; k >= 0; --k) col = z[k] == m ? k : col; // the leftmost cell of the row that holds it
+                best = m;
+                hit_i = i;
+                hit_k = col;
+            }
+        } else {
+            if (i == lb) {
+                int slot = kc; // (as above)
+                asm volatile("" : "+v"(slot));
+#pragma unroll
+                for (int k = 0; k < K; ++k) corner = k == slot ? z[k] : corner;
+            }
+        }
+
+        // the query window moves on by one symbol
+        const uint32_t nb = (uint32_t)band_shl1(0, (int)xw[0]);
+        const uint32_t top = last ? xin : nb >> 8;
+#pragma unroll
+        for (int n = 0; n + 1 < XW; ++n) xw[n] = __builtin_amdgcn_alignbyte(xw[n + 1], xw[n], 1);
+        xw[XW - 1] = __builtin_amdgcn_alignbyte(top, xw[XW - 1], 1);
+
+        z_last = zleft;
+        f_last = f;
+        yc_prev = yc;
+        ++t;
+    };
+
+    const int quads = steps >> 2;
+    for (int q = 0; q < quads; ++q) {
+        rows = q0;
+        q0 = q1;
+        q1 = q2;
+        q2 = row_quad(q + 3);
+        xrows = x0;
+        x0 = x1;
+        x1 = x2;
+        x2 = col_quad(q + 3);
+#pragma unroll
+        for (int b = 0; b < 4; ++b) step();
+    }
+    rows = q0;
+    xrows = x0;
+#pragma unroll 1
+    while (t < steps) step();
+
+    if constexpr (EXT) {
+        best -= gf;
+        uint32_t key = hit_i < 0 ? 0xffffffffu : ((uint32_t)hit_i << 16) | (uint32_t)(hit_i + d0 + hit_k);
+        // over the group's lanes by the rule: score, then row, then column (G need not be a power of two)
+        for (int o = 1; o < G; o <<= 1) {
+            const int ob = __shfl_down(best, o);
+            const uint32_t ok = (uint32_t)__shfl_down((int)key, o);
+            if (gl + o < G && (ob > best || (ob == best && ok < key))) {
+                best = ob;
+                key = ok;
+            }
+        }
+        if (feeder) {
+            scores[g.out] = best;
+            pos[g.out] = key;
+        }
+    } else {
+        if (active && kc >= 0 && kc < K) scores[g.out] = corner - gf;
+    }
+}
+

@@ -19,6 +19,11 @@
  *     score a_begin a_end b_begin b_end CIGAR
  * as text with '=', 'X', 'I' and 'D' over the span the line names, "*" for an alignment that consumes nothing (include/agx.h,
  * "Alignment itself"; queries up to AGX_SW_CIGAR_MAX_QUERY_LEN).  "+stats+cigar" is not offered.
+ * Or the suffix "+band=W" on global and extend (global+band=64, extend+band=200): the BANDED alignment of half-width W
+ * (include/agx.h, "Banded alignment"), for long similar pairs -- both sides up to AGX_SW_BAND_MAX_LEN symbols.  The lines are
+ *     score a_begin a_end b_begin b_end
+ * and the input is read with a line buffer of 65 536 bytes, so lines of up to 65 535 bytes stay whole (without the suffix the
+ * reader keeps the reference's 1 000).  Not with another mode, not together with +stats / +cigar or a matrix file.
  *   AGX_CLI_CHUNK_PAIRS   pairs per agx_sw_align call (default 262144)
  */
 #include <stdio.h>
@@ -112,10 +117,22 @@ int main(int argc, char *argv[])
 {
     static const char *const words[] = {"local", "global", "fit", "extend", "extend-query"}; /* AGX_SW_MODE_* 0..4 */
     int mode = argc == 2 ? AGX_SW_MODE_LOCAL : -1;
-    int with_stats = 0, with_cigar = 0;
+    int with_stats = 0, with_cigar = 0, with_band = 0;
+    int32_t band = 0;
     for (int k = 0; (argc == 3 || argc == 4 || argc == 6) && k < 5; k++) {
         const size_t n = strlen(words[k]);
         if (!strcmp(argv[2], words[k])) mode = k;
+        if (!strncmp(argv[2], words[k], n) && !strncmp(argv[2] + n, "+band=", 6)) {
+            /* W: digits only, up to the end of the word; global and extend only, and no matrix file */
+            const char *w = argv[2] + n + 6;
+            char *end;
+            const long v = strtol(w, &end, 10);
+            if (isdigit((unsigned char)*w) && !*end && v <= 0x7fffffffL && argc == 3 && (k == AGX_SW_MODE_GLOBAL || k == AGX_SW_MODE_EXTEND)) {
+                mode = k;
+                with_band = 1;
+                band = (int32_t)v;
+            }
+        }
         if (!strncmp(argv[2], words[k], n) && !strcmp(argv[2] + n, "+stats")) {
             mode = k;
             with_stats = 1;
@@ -132,7 +149,9 @@ int main(int argc, char *argv[])
                 "With a matrix file ('#' comments, a line of symbols, a row per symbol: the symbol and its integers; symmetric,\n"
                 "letters in either case) gaps default to -11 -1 and the line ends (\\n, \\r\\n) are stripped, not aligned.\n"
                 "<mode>+stats (local+stats, fit+stats ...): every line ends in two more numbers, matches and aligned pairs.\n"
-                "<mode>+cigar (local+cigar, fit+cigar ...): every line ends in the alignment as CIGAR text (=, X, I, D; * for none).\n",
+                "<mode>+cigar (local+cigar, fit+cigar ...): every line ends in the alignment as CIGAR text (=, X, I, D; * for none).\n"
+                "global+band=W, extend+band=W: the banded alignment of half-width W >= 0 for long pairs (lines of up to 65535 bytes);\n"
+                "not with another mode, +stats, +cigar or a matrix file.\n",
                 argv[0], argv[0]);
         return 1;
     }
@@ -159,7 +178,7 @@ int main(int argc, char *argv[])
     const char *cp = getenv("AGX_CLI_CHUNK_PAIRS");
     const int64_t chunk_pairs = cp && atoll(cp) > 0 ? atoll(cp) : 262144;
     agx_sw_reader *reader = NULL;
-    if (agx_sw_reader_open(argv[1], 0, &reader) != AGX_OK) {
+    if (agx_sw_reader_open(argv[1], with_band ? 65536 : 0, &reader) != AGX_OK) {
         fprintf(stderr, "swAlign: %s\n", agx_last_error());
         return EXIT_FAILURE;
     }
@@ -201,6 +220,11 @@ int main(int argc, char *argv[])
             } else if (!status && with_cigar) {
                 if (agx_sw_align_cigar(ctx, NULL, with_matrix ? &matrix : NULL, mode, t->bases, t->off, t->len, t->n_pairs, hits, op_off, ops, ops_cap) !=
                     AGX_OK) {
+                    fprintf(stderr, "swAlign: %s\n", agx_last_error());
+                    status = EXIT_FAILURE;
+                }
+            } else if (!status && with_band) {
+                if (agx_sw_align_band(ctx, NULL, mode, band, t->bases, t->off, t->len, t->n_pairs, hits) != AGX_OK) {
                     fprintf(stderr, "swAlign: %s\n", agx_last_error());
                     status = EXIT_FAILURE;
                 }

@@ -370,6 +370,42 @@ int agx_sw_align_cigar(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw
                        const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_hit *hits /* may be NULL */, uint64_t *op_off,
                        uint32_t *ops, uint64_t ops_cap);
 
+/*
+ * Banded alignment: global and extension alignment of long, similar pairs.  Only the cells within a fixed distance of the main
+ * diagonal are filled: the cost is length x band, and NEITHER side has a column limit.  a, b, la, lb, D[i][j] (pinned start, no
+ * zero floor) and the gap costs are those of "Alignment modes".  A batch has one half-width band = w >= 0; a cell (i, j) is
+ * inside the band iff dlo <= j - i <= dhi:
+ *   mode                 dlo                    dhi                    score                              end cell
+ *   AGX_SW_MODE_GLOBAL   min(0, la - lb) - w    max(0, la - lb) + w    D[lb][la]                          (lb-1, la-1)
+ *   AGX_SW_MODE_EXTEND   -w                     +w                     max over the in-band cells,        smallest i, then smallest j among
+ *                                                                      D[0][0] = 0 included, so >= 0      the maxima; score 0: all four -1
+ * The GLOBAL band is widened by the length difference: both corners are inside and connected, so a global score is always finite.
+ * Cells outside the band do not exist: H = E = F = -infinity there and nothing is read from them.  Of row 0 and column 0 only
+ * the in-band parts exist: D[0][j] = gap_open + j gap_extend for 0 < j <= dhi, D[i][0] likewise for 0 < i <= -dlo; E is
+ * -infinity on row 0 and F in column 0.  Begins are what a pinned-start AGX_SW_ALIGN_SPANS batch reports: 0 (an empty range is
+ * begin 0, end -1; EXTEND with score 0 keeps -1 for all four); there is no second fill.  A pair with an empty side is answered
+ * by the formulas without a fill: GLOBAL with la = 0 gives gap_open + lb gap_extend, both sides empty 0, EXTEND 0.
+ * A band wide enough to hold the whole matrix reports exactly what agx_sw_align_mode(..., AGX_SW_ALIGN_SPANS, ...) reports for
+ * the same mode and scoring: that is so for w >= min(la, lb) in GLOBAL and for w >= max(la, lb) in EXTEND.
+ * Limits: la, lb <= AGX_SW_BAND_MAX_LEN on BOTH sides, and width = dhi - dlo + 1 <= AGX_SW_BAND_MAX_WIDTH (64 lanes x 32
+ * diagonals): |la - lb| + 2w + 1 in GLOBAL, 2w + 1 in EXTEND.  A pair beyond either fails the create with AGX_E_LIMIT, the
+ * message names the pair.  band < 0: AGX_E_ARG.  LOCAL, FIT and EXTEND_QUERY have a free start or a column capture; a band
+ * around the main diagonal means nothing for them without a diagonal offset: AGX_E_ARG, as for a mode outside 0..4.
+ * scoring: agx_sw_scoring with its limits, NULL = the reference's constants.  Byte 0x00 is refused (AGX_E_SYMBOL) as elsewhere.
+ * Deliberately left out: no substitution matrix, no statistics, no CIGAR on banded batches.
+ * The batch behaves like the other align batches: agx_sw_batch_launch (re)launches, agx_sw_batch_scores returns the mode's
+ * score, agx_sw_batch_hits the hits in the caller's pair order, agx_sw_batch_bind_scores is accepted and ignored;
+ * agx_sw_batch_stats and agx_sw_batch_cigars return AGX_E_ARG.  ctx may be NULL: plan only.  In agx_sw_info, cells stays
+ * sum la*lb as given and padded_cells is lane-steps x diagonals per lane actually issued.
+ */
+#define AGX_SW_BAND_MAX_LEN 65535
+#define AGX_SW_BAND_MAX_WIDTH 2048
+int agx_sw_batch_create_align_band(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t band, const uint8_t *bases,
+                                   const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_batch **out);
+/* One-shot: create_align_band + launch + hits + destroy. */
+int agx_sw_align_band(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t band, const uint8_t *bases, const uint64_t *off,
+                      const uint32_t *len, int64_t n_pairs, agx_sw_hit *hits);
+
 /* One-shot: create + launch + scores + destroy. */
 int agx_sw_score(agx_ctx *ctx, const uint8_t *bases, const uint64_t *off, const uint32_t *len, int64_t n_pairs,
                  int32_t *scores);
