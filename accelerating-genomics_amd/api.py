@@ -55,6 +55,7 @@ SYMBOLS = [
     "agx_sw_batch_create_align_stats", "agx_sw_batch_stats", "agx_sw_align_stats",
     "agx_sw_batch_create_align_cigar", "agx_sw_batch_cigars", "agx_sw_batch_cigar_info", "agx_sw_align_cigar",
     "agx_sw_batch_create_align_band", "agx_sw_align_band",
+    "agx_sw_batch_create_align_band_cigar", "agx_sw_align_band_cigar", "agx_sw_band_cigar_bytes_bound", "agx_sw_cigar_in_band",
     "agx_sw_score", "agx_sw_score_multi", "agx_sw_score_devices", "agx_sw_shard_cuts",
     "agx_phmm_batch_create", "agx_phmm_batch_launch", "agx_phmm_batch_results", "agx_phmm_batch_bind_results", "agx_phmm_batch_info",
     "agx_phmm_batch_destroy", "agx_phmm_forward", "agx_phmm_forward_multi", "agx_phmm_forward_devices", "agx_phmm_shard_cuts",
@@ -204,6 +205,13 @@ def lib():
         l.agx_sw_batch_create_align_band.argtypes = [C.c_void_p, C.POINTER(SwScoring), C.c_int, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                                      C.c_int64, C.POINTER(C.c_void_p)]
         l.agx_sw_align_band.argtypes = [C.c_void_p, C.POINTER(SwScoring), C.c_int, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        l.agx_sw_batch_create_align_band_cigar.argtypes = [C.c_void_p, C.POINTER(SwScoring), C.c_int, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                           C.c_int64, C.POINTER(C.c_void_p)]
+        l.agx_sw_align_band_cigar.argtypes = [C.c_void_p, C.POINTER(SwScoring), C.c_int, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
+        l.agx_sw_band_cigar_bytes_bound.argtypes = [C.c_int32, C.c_uint32, C.c_uint32]
+        l.agx_sw_band_cigar_bytes_bound.restype = C.c_uint64
+        l.agx_sw_cigar_in_band.argtypes = [C.c_void_p, C.c_uint64, C.c_int32, C.c_int32]
         l.agx_sw_score.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
         l.agx_sw_score_multi.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
         l.agx_sw_score_devices.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
@@ -318,6 +326,17 @@ class Context:
         _check(lib().agx_sw_align_band(self._h, sc, mode, band, _ptr(b.bases), _ptr(b.off), _ptr(b.len), b.n_pairs, _ptr(out)))
         return out
 
+    def sw_align_band_cigar(self, b, mode, band, scoring=None):
+        """b: synth.SWBatch -> (SwHit records as sw_align_band gives them, op_off uint64[n + 1], ops uint32), one-shot: the CIGAR of
+        every pair inside its band (include/agx.h, "CIGARs for banded batches")."""
+        hits, op_off = np.empty(b.n_pairs, SwHit), np.zeros(b.n_pairs + 1, np.uint64)
+        cap = int(b.len.sum())  # an alignment has at most one operation per symbol
+        ops = np.empty(max(cap, 1), np.uint32)
+        sc = C.byref(SwScoring(*scoring)) if scoring is not None else None
+        _check(lib().agx_sw_align_band_cigar(self._h, sc, mode, band, _ptr(b.bases), _ptr(b.off), _ptr(b.len), b.n_pairs, _ptr(hits), _ptr(op_off),
+                                             _ptr(ops), cap))
+        return hits, op_off, ops[:int(op_off[b.n_pairs])].copy()
+
     def sw_align_cigar(self, b, scoring=None, mode=SW_MODE_LOCAL, matrix=None):
         """b: synth.SWBatch -> (SwHit records as SW_ALIGN_SPANS gives them, op_off uint64[n + 1], ops uint32), one-shot:
         pair p's operations are ops[op_off[p]:op_off[p + 1]] (cigar_string turns them into text)."""
@@ -380,16 +399,16 @@ class SwBatch:
         mode: SW_MODE_* of an align batch (local, global, fit, extension); stats=True: a SPANS batch that also answers stats();
         cigar=True: a SPANS batch that also answers cigars() (not together with stats);
         band=w: a BANDED batch of mode SW_MODE_GLOBAL or SW_MODE_EXTEND (half-width w; it answers hits() as a SPANS batch does;
-        no matrix, stats or cigar)."""
+        no matrix or stats; with cigar=True a banded cigar batch, which also answers cigars())."""
         self.ctx = ctx
         self.n_pairs = b.n_pairs
         self._h = C.c_void_p()
         if band is not None:
-            if matrix is not None or stats or cigar or align not in (0, SW_ALIGN_SPANS):
-                raise AgxError(E_ARG, "a banded batch is a SW_ALIGN_SPANS batch under match/mismatch scoring: no matrix, stats or cigar")
+            if matrix is not None or stats or align not in (0, SW_ALIGN_SPANS):
+                raise AgxError(E_ARG, "a banded batch is a SW_ALIGN_SPANS batch under match/mismatch scoring: no matrix or stats")
             sc = C.byref(SwScoring(*scoring)) if scoring is not None else None
-            _check(lib().agx_sw_batch_create_align_band(ctx._h if ctx else None, sc, mode, band, _ptr(b.bases), _ptr(b.off), _ptr(b.len),
-                                                        b.n_pairs, C.byref(self._h)))
+            create = lib().agx_sw_batch_create_align_band_cigar if cigar else lib().agx_sw_batch_create_align_band
+            _check(create(ctx._h if ctx else None, sc, mode, band, _ptr(b.bases), _ptr(b.off), _ptr(b.len), b.n_pairs, C.byref(self._h)))
             return
         if cigar:
             if stats or align not in (0, SW_ALIGN_SPANS):

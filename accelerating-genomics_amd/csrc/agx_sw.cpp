@@ -243,6 +243,12 @@ struct agx_sw_batch {
     int32_t band = 0;
     DevBuf band_pos;
     PinBuf band_pos_stage;
+    // agx_sw_batch_create_align_band_cigar: banded with cigar == 1.  The traced fills of agx_sw_batch_cigars read
+    // the resident image through copies of the group records with the span's lengths: the records in plan order, every pair's
+    // record (kNoBandRec: an empty side) and its tiling; seq / seq_off hold the symbols for the host's checks
+    std::vector<SwBandGroup> band_groups;
+    std::vector<uint32_t> band_rec;
+    std::vector<uint8_t> band_cls, band_G;
     agx_sw_scoring scoring{};
     DevBuf ends;        // per pair: row << kSwLocColBits | column of the end cell, written by the locating fill
     PinBuf ends_stage;  // its page-locked landing block
@@ -1613,10 +1619,12 @@ struct BandPlan { // one pair with work, as the sort moves it
     uint8_t cls, G;
 };
 
+constexpr uint32_t kNoBandRec = 0xffffffffu;
+
 int create_band(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t band, const uint8_t *bases, const uint64_t *off,
-                const uint32_t *len, int64_t n_pairs, agx_sw_batch **out)
+                const uint32_t *len, int64_t n_pairs, agx_sw_batch **out, bool cigar = false)
 {
-    const char *who = "agx_sw_batch_create_align_band";
+    const char *who = cigar ? "agx_sw_batch_create_align_band_cigar" : "agx_sw_batch_create_align_band";
     if (!out) {
         agx_set_error("%s: out is NULL", who);
         return AGX_E_ARG;
@@ -1747,6 +1755,7 @@ int create_band(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t b
     b->n_pairs = n_pairs;
     b->banded = true;
     b->band = band;
+    b->cigar = cigar ? 1 : 0;
     b->family = 5;
     b->align = AGX_SW_ALIGN_SPANS;
     b->mode = mode;
@@ -1771,6 +1780,30 @@ int create_band(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t b
     }
     agx_sw_band_preload();
     if (n_pairs > 0) b->seq_len.assign(len, len + 2 * n_pairs);
+    if (cigar) { // what the traced fills of the spans and the host's checks need, long after this call
+        agx_sw_band_trace_preload();
+        agx_sw_walk_preload();
+        b->band_groups = groups;
+        b->band_rec.assign((size_t)n_pairs, kNoBandRec);
+        b->band_cls.resize(n_fill);
+        b->band_G.resize(n_fill);
+        for (size_t k = 0; k < n_fill; ++k) {
+            b->band_rec[plan[k].pair] = (uint32_t)k;
+            b->band_cls[k] = plan[k].cls;
+            b->band_G[k] = plan[k].G;
+        }
+        b->seq_off.resize((size_t)n_pairs * 2);
+        uint64_t at = 0;
+        for (int64_t k = 0; k < 2 * n_pairs; ++k) {
+            b->seq_off[(size_t)k] = at;
+            at += len[k];
+        }
+        b->seq.resize((size_t)at);
+        agx_parallel_for(2 * n_pairs, 8192, [&](int64_t lo, int64_t hi, int) {
+            for (int64_t k = lo; k < hi; ++k)
+                if (len[k] && bases) memcpy(b->seq.data() + b->seq_off[(size_t)k], bases + off[k], len[k]);
+        }); // (bases == NULL: every pair has an empty side, and a lone run of I or D reads no symbol)
+    }
     PinBuf h_img, h_groups, h_waves;
     struct Temps {
         PinBuf *a, *b, *c;
@@ -1845,6 +1878,7 @@ int create_band(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t b
 
 int band_launch(agx_sw_batch *b)
 {
+    b->cig_valid = false; // what agx_sw_batch_cigars kept belongs to the launch before
     if (b->launches.empty()) return AGX_OK;
     FanOut fan(b->ctx, (int)b->launches.size());
     int rc = fan.begin();
@@ -2760,9 +2794,363 @@ int cigars_impl(agx_sw_batch *b)
     b->cig_valid = true;
     return AGX_OK;
 }
+
+// ---- CIGARs of banded batches (include/agx.h, "CIGARs for banded batches")
+
+// What one traced pair of a banded cigar batch may take of the chunk budget: its directions in the class that needs the most
+// dwords for its band width and its rows, plus its operation slot.  Independent of the plan, as trace_bytes_bound.
+uint64_t band_trace_bytes_bound(uint32_t width, uint32_t ca, uint32_t cb)
+{
+    uint64_t worst = 0;
+    for (int c = 0; c < kSwNumBandClasses; ++c) {
+        const uint32_t K = (uint32_t)kSwBandClasses[c], G = (width + K - 1u) / K;
+        if (G >= 1u && G <= 64u) worst = std::max(worst, sw_band_trace_dwords((int)G, cb, (int)K));
+    }
+    return 4u * (worst + (uint64_t)ca + cb);
+}
+
+// The band-aware part of the host's check: from (0, 0), after every operation dlo <= j - i <= dhi (within a run j - i moves one
+// way only, so the run's end decides).
+bool cigar_in_band(const uint32_t *ops, uint64_t n_ops, int64_t dlo, int64_t dhi)
+{
+    int64_t d = 0;
+    if (d < dlo || d > dhi) return false;
+    for (uint64_t k = 0; k < n_ops; ++k) {
+        const uint32_t op = ops[k] & 15u;
+        const int64_t len = ops[k] >> 4;
+        if (op == AGX_CIGAR_INS) d += len;
+        else if (op == AGX_CIGAR_DEL) d -= len;
+        else if (op != AGX_CIGAR_EQ && op != AGX_CIGAR_DIFF) return false;
+        if (d < dlo || d > dhi) return false;
+    }
+    return true;
+}
+
+// in-band cells (1 <= i <= cb, 1 <= j <= ca, dlo <= j - i <= dhi) of a span
+int64_t band_cells(int64_t ca, int64_t cb, int64_t dlo, int64_t dhi)
+{
+    int64_t cells = 0;
+    for (int64_t i = 1; i <= cb; ++i) {
+        const int64_t lo = std::max<int64_t>(1, i + dlo), hi = std::min<int64_t>(ca, i + dhi);
+        if (hi >= lo) cells += hi - lo + 1;
+    }
+    return cells;
+}
+
+// agx_sw_batch_cigars on a banded cigar batch: hits, then per chunk of spans one traced banded fill (corner capture, whatever the
+// mode: the span's global alignment inside the pair's band), the band-aware walk and the gather.  The fills read the batch's
+// resident image through copies of its group records that carry the span's lengths, in the tiling the batch planned.
+int band_cigars_impl(agx_sw_batch *b)
+{
+    const int64_t n = b->n_pairs;
+    b->cig_valid = false;
+    b->cig_info = agx_sw_cigar_info{};
+    b->cig_hits.assign((size_t)n, agx_sw_hit{});
+    b->cig_off.assign((size_t)n + 1, 0);
+    b->cig_ops.clear();
+    int rc = band_hits(b, b->cig_hits.data());
+    if (rc || n == 0) {
+        b->cig_valid = !rc;
+        return rc;
+    }
+    agx_ctx *ctx = b->ctx;
+    const agx_sw_hit *hits = b->cig_hits.data();
+    const agx_sw_scoring s = b->scoring;
+    auto span = [&](int64_t p, int64_t &ca, int64_t &cb) { // begins are 0
+        const agx_sw_hit &h = hits[p];
+        ca = h.a_begin >= 0 && h.a_end >= h.a_begin ? (int64_t)h.a_end - h.a_begin + 1 : 0;
+        cb = h.b_begin >= 0 && h.b_end >= h.b_begin ? (int64_t)h.b_end - h.b_begin + 1 : 0;
+    };
+    auto limits = [&](int64_t p, int64_t &dlo, int64_t &dhi) { // the band the score was computed in
+        band_limits(b->mode, b->band, b->seq_len[(size_t)(2 * p)], b->seq_len[(size_t)(2 * p + 1)], dlo, dhi);
+    };
+    std::vector<uint32_t> count((size_t)n, 0), lone((size_t)n, 0);
+    std::vector<int64_t> traced;
+    int64_t cells = 0;
+    for (int64_t p = 0; p < n; ++p) {
+        int64_t ca, cb;
+        span(p, ca, cb);
+        if (ca && cb) {
+            if (b->band_rec[(size_t)p] == kNoBandRec) {
+                agx_set_error("agx_sw_batch_cigars: pair %lld has a span of %lld x %lld and no fill", (long long)p, (long long)ca, (long long)cb);
+                return AGX_E_INTERNAL;
+            }
+            int64_t dlo, dhi;
+            limits(p, dlo, dhi);
+            traced.push_back(p);
+            cells += band_cells(ca, cb, dlo, dhi);
+        } else if (ca || cb) {
+            count[(size_t)p] = 1;
+            lone[(size_t)p] = (uint32_t)(ca ? ca : cb) << 4 | (uint32_t)(ca ? AGX_CIGAR_INS : AGX_CIGAR_DEL);
+        }
+    }
+    b->cig_info.n_traced = (int64_t)traced.size();
+    b->cig_info.trace_cells = cells;
+    const uint64_t budget = (uint64_t)ctx->opt_sw_trace_bytes;
+    std::vector<std::vector<uint32_t>> chunk_ops;
+    std::vector<uint64_t> where((size_t)n, 0);
+    std::vector<uint32_t> chunk_of((size_t)n, 0);
+    hipStream_t st = ctx->stream;
+    const bool timed = agx_tune("AGX_TRACE_CIGAR") != nullptr;
+    struct Events {
+        hipEvent_t e[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+        ~Events()
+        {
+            for (hipEvent_t v : e)
+                if (v) (void)hipEventDestroy(v);
+        }
+    } ev;
+    if (timed)
+        for (hipEvent_t &v : ev.e) AGX_HIP(hipEventCreate(&v));
+    auto width_of = [&](int64_t p) {
+        const SwBandGroup &g = b->band_groups[b->band_rec[(size_t)p]];
+        return (uint32_t)(g.dhi - g.dlo + 1);
+    };
+    for (size_t first = 0; first < traced.size();) {
+        size_t last = first;
+        uint64_t bytes = 0;
+        while (last < traced.size()) {
+            int64_t ca, cb;
+            span(traced[last], ca, cb);
+            const uint64_t need = band_trace_bytes_bound(width_of(traced[last]), (uint32_t)ca, (uint32_t)cb);
+            if (last > first && bytes + need > budget) break;
+            bytes += need;
+            ++last;
+        }
+        const int64_t m = (int64_t)(last - first);
+        // ---- the chunk's plan: the batch's tiling per pair, waves of one (class, lanes per group), longest span first
+        struct Item {
+            uint32_t k, rec, cb;
+            uint8_t cls, G;
+        };
+        std::vector<Item> items((size_t)m);
+        for (int64_t k = 0; k < m; ++k) {
+            const int64_t p = traced[first + (size_t)k];
+            int64_t ca, cb;
+            span(p, ca, cb);
+            const uint32_t rec = b->band_rec[(size_t)p];
+            items[(size_t)k] = Item{(uint32_t)k, rec, (uint32_t)cb, b->band_cls[rec], b->band_G[rec]};
+        }
+        std::sort(items.begin(), items.end(), [](const Item &x, const Item &y) {
+            if (x.cls != y.cls) return x.cls < y.cls;
+            if (x.G != y.G) return x.G < y.G;
+            if (x.cb != y.cb) return x.cb > y.cb;
+            return x.k < y.k;
+        });
+        std::vector<SwBandGroup> groups((size_t)m);
+        std::vector<uint64_t> goff((size_t)m);
+        std::vector<SwWalkRec> walk((size_t)m);
+        std::vector<SwBandWalkRec> bwalk((size_t)m);
+        std::vector<SwWave> waves;
+        std::vector<ClassLaunch> launches;
+        uint64_t tr_dwords = 0, slot_words = 0;
+        for (size_t k = 0; k < (size_t)m;) {
+            const Item &h = items[k];
+            const int K = kSwBandClasses[h.cls], G = h.G, per_wave = 64 / G;
+            size_t end = k;
+            while (end < (size_t)m && end - k < (size_t)per_wave && items[end].cls == h.cls && items[end].G == h.G) ++end;
+            SwWave w{};
+            w.first_group = (uint32_t)k;
+            w.n_groups = (uint16_t)(end - k);
+            w.G = (uint16_t)G;
+            w.steps = h.cb + (uint32_t)G;
+            w.reserved = (uint32_t)K;
+            if (launches.empty() || launches.back().C != K) {
+                ClassLaunch cl;
+                cl.C = K;
+                cl.first_wave = (uint32_t)waves.size();
+                launches.push_back(cl);
+            }
+            ++launches.back().n_waves;
+            waves.push_back(w);
+            for (; k < end; ++k) {
+                const Item &e = items[k];
+                const int64_t p = traced[first + e.k];
+                int64_t ca, cb;
+                span(p, ca, cb);
+                SwBandGroup g = b->band_groups[e.rec]; // image offsets, band and fpad as planned; the span's lengths
+                g.la_lb = (uint32_t)ca | (uint32_t)cb << 16;
+                g.out = e.k;
+                groups[k] = g;
+                goff[k] = tr_dwords;
+                SwWalkRec &r = walk[e.k];
+                r.goff = tr_dwords;
+                r.slot = 0; // below, in the caller's order
+                r.x_dw = g.x_dw;
+                r.y_dw = g.y_dw;
+                r.ca = (uint32_t)ca;
+                r.cb = (uint32_t)cb;
+                r.G = (uint16_t)G;
+                r.C = (uint16_t)K;
+                r.reserved = 0;
+                int ks = 0;
+                while ((1 << ks) < K) ++ks;
+                bwalk[e.k] = SwBandWalkRec{g.dlo, g.dhi, g.fpad, (uint32_t)ks};
+                tr_dwords += sw_band_trace_dwords(G, (uint32_t)cb, K);
+            }
+        }
+        for (int64_t k = 0; k < m; ++k) {
+            walk[(size_t)k].slot = slot_words;
+            slot_words += (uint64_t)walk[(size_t)k].ca + walk[(size_t)k].cb;
+        }
+        std::vector<uint64_t> dst((size_t)m);
+        struct Drop { // every exit: nothing may still run on the blocks when they go back to the pool
+            agx_ctx *ctx;
+            DevBuf groups, waves, goff, walk, bwalk, scores, trace, slots, runs, dst, dense;
+            PinBuf h_runs, h_scores, h_dense;
+            ~Drop()
+            {
+                (void)hipStreamSynchronize(ctx->stream);
+                for (DevBuf *v : {&groups, &waves, &goff, &walk, &bwalk, &scores, &trace, &slots, &runs, &dst, &dense}) v->release();
+                for (PinBuf *v : {&h_runs, &h_scores, &h_dense}) v->release();
+            }
+        } d{ctx, {}, {}, {}, {}, {}, {}, {}, {}, {}, {}, {}, {}, {}, {}};
+        rc = d.groups.alloc(ctx, (size_t)m * sizeof(SwBandGroup));
+        if (!rc) rc = d.waves.alloc(ctx, waves.size() * sizeof(SwWave));
+        if (!rc) rc = d.goff.alloc(ctx, (size_t)m * sizeof(uint64_t));
+        if (!rc) rc = d.walk.alloc(ctx, (size_t)m * sizeof(SwWalkRec));
+        if (!rc) rc = d.bwalk.alloc(ctx, (size_t)m * sizeof(SwBandWalkRec));
+        if (!rc) rc = d.scores.alloc(ctx, (size_t)m * sizeof(int32_t));
+        if (!rc) rc = d.trace.alloc(ctx, std::max<uint64_t>(tr_dwords, 4) * 4);
+        if (!rc) rc = d.slots.alloc(ctx, std::max<uint64_t>(slot_words, 1) * 4);
+        if (!rc) rc = d.runs.alloc(ctx, (size_t)m * sizeof(uint32_t));
+        if (!rc) rc = d.dst.alloc(ctx, (size_t)m * sizeof(uint64_t));
+        if (!rc) rc = d.h_runs.alloc(ctx, (size_t)m * sizeof(uint32_t));
+        if (!rc) rc = d.h_scores.alloc(ctx, (size_t)m * sizeof(int32_t));
+        if (rc) return rc;
+        b->cig_info.trace_bytes_peak = std::max<int64_t>(b->cig_info.trace_bytes_peak, (int64_t)((tr_dwords + slot_words) * 4));
+        ++b->cig_info.n_chunks;
+        AGX_HIP(hipMemcpyAsync(d.groups.p, groups.data(), (size_t)m * sizeof(SwBandGroup), hipMemcpyHostToDevice, st));
+        AGX_HIP(hipMemcpyAsync(d.waves.p, waves.data(), waves.size() * sizeof(SwWave), hipMemcpyHostToDevice, st));
+        AGX_HIP(hipMemcpyAsync(d.goff.p, goff.data(), (size_t)m * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        AGX_HIP(hipMemcpyAsync(d.walk.p, walk.data(), (size_t)m * sizeof(SwWalkRec), hipMemcpyHostToDevice, st));
+        AGX_HIP(hipMemcpyAsync(d.bwalk.p, bwalk.data(), (size_t)m * sizeof(SwBandWalkRec), hipMemcpyHostToDevice, st));
+        if (timed) AGX_HIP(hipEventRecord(ev.e[0], st));
+        for (auto it = launches.rbegin(); it != launches.rend(); ++it) // widest class first, one after the other on the stream
+            if (agx_sw_band_trace_launch_class(it->C, b->prm, (const uint32_t *)b->img.p, (const SwBandGroup *)d.groups.p,
+                                               (const SwWave *)d.waves.p + it->first_wave, it->n_waves, (int32_t *)d.scores.p, (uint32_t *)d.trace.p,
+                                               (const uint64_t *)d.goff.p, st)) {
+                agx_set_error("sw_fill_band_trace<%d> launch failed: %s", it->C, hipGetErrorString(hipGetLastError()));
+                return AGX_E_HIP;
+            }
+        if (timed) AGX_HIP(hipEventRecord(ev.e[1], st));
+        if (agx_sw_band_walk_launch((const SwWalkRec *)d.walk.p, (const SwBandWalkRec *)d.bwalk.p, (uint32_t)m, (const uint32_t *)b->img.p,
+                                    (const uint32_t *)d.trace.p, (uint32_t *)d.slots.p, (uint32_t *)d.runs.p, st)) {
+            agx_set_error("agx_sw_batch_cigars: walk kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
+            return AGX_E_HIP;
+        }
+        if (timed) AGX_HIP(hipEventRecord(ev.e[2], st));
+        AGX_HIP(hipMemcpyAsync(d.h_runs.p, d.runs.p, (size_t)m * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        AGX_HIP(hipMemcpyAsync(d.h_scores.p, d.scores.p, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        AGX_HIP(hipStreamSynchronize(st));
+        const uint32_t *runs = (const uint32_t *)d.h_runs.p;
+        const int32_t *tsc = (const int32_t *)d.h_scores.p;
+        uint64_t total = 0;
+        for (int64_t k = 0; k < m; ++k) {
+            const int64_t p = traced[first + (size_t)k];
+            const SwWalkRec &r = walk[(size_t)k];
+            if (tsc[k] != hits[p].score || runs[k] == 0 || runs[k] > (uint64_t)r.ca + r.cb) { // (kSwWalkFailed: the walk left the band)
+                agx_set_error("agx_sw_batch_cigars: pair %lld (mode %d, band %d): the traced fill of its span a 0..%d, b 0..%d gives score %d in %u runs%s, "
+                              "the hit %d",
+                              (long long)p, b->mode, b->band, hits[p].a_end, hits[p].b_end, tsc[k], runs[k],
+                              runs[k] == kSwWalkFailed ? " (the walk left the band)" : "", hits[p].score);
+                return AGX_E_INTERNAL;
+            }
+            dst[(size_t)k] = total;
+            where[(size_t)p] = total;
+            chunk_of[(size_t)p] = (uint32_t)chunk_ops.size();
+            count[(size_t)p] = runs[k];
+            total += runs[k];
+        }
+        rc = d.dense.alloc(ctx, (size_t)total * sizeof(uint32_t));
+        if (!rc) rc = d.h_dense.alloc(ctx, (size_t)total * sizeof(uint32_t));
+        if (rc) return rc;
+        AGX_HIP(hipMemcpyAsync(d.dst.p, dst.data(), (size_t)m * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        if (timed) AGX_HIP(hipEventRecord(ev.e[3], st));
+        if (agx_sw_gather_launch((const SwWalkRec *)d.walk.p, (uint32_t)m, (const uint32_t *)d.slots.p, (const uint32_t *)d.runs.p,
+                                 (const uint64_t *)d.dst.p, (uint32_t *)d.dense.p, st)) {
+            agx_set_error("agx_sw_batch_cigars: gather kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
+            return AGX_E_HIP;
+        }
+        if (timed) AGX_HIP(hipEventRecord(ev.e[4], st));
+        AGX_HIP(hipMemcpyAsync(d.h_dense.p, d.dense.p, (size_t)total * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        AGX_HIP(hipStreamSynchronize(st));
+        if (timed) {
+            float fill = 0, walk_ms = 0, gather = 0;
+            AGX_HIP(hipEventElapsedTime(&gather, ev.e[3], ev.e[4]));
+            AGX_HIP(hipEventElapsedTime(&fill, ev.e[0], ev.e[1]));
+            AGX_HIP(hipEventElapsedTime(&walk_ms, ev.e[1], ev.e[2]));
+            fprintf(stderr, "[agx_sw_batch_cigars] chunk %d: %lld pairs, %.1f MB of directions, %.1f MB of slots: traced fill %.3f ms, walk %.3f ms, gather %.3f ms, %llu runs\n",
+                    b->cig_info.n_chunks - 1, (long long)m, tr_dwords * 4 / 1e6, slot_words * 4 / 1e6, fill, walk_ms, gather, (unsigned long long)total);
+        }
+        chunk_ops.emplace_back((const uint32_t *)d.h_dense.p, (const uint32_t *)d.h_dense.p + total);
+        first = last;
+    } // (Drop returns the chunk's blocks before the next chunk takes its own)
+    // ---- the caller's layout, and every CIGAR checked before it leaves
+    for (int64_t p = 0; p < n; ++p) b->cig_off[(size_t)p + 1] = b->cig_off[(size_t)p] + count[(size_t)p];
+    b->cig_ops.resize((size_t)b->cig_off[(size_t)n]);
+    std::vector<int64_t> bad((size_t)agx_host_threads(), -1);
+    agx_parallel_for(n, 4096, [&](int64_t lo, int64_t hi, int tid) {
+        for (int64_t p = lo; p < hi; ++p) {
+            int64_t ca, cb, dlo, dhi;
+            span(p, ca, cb);
+            limits(p, dlo, dhi);
+            uint32_t *out = b->cig_ops.data() + b->cig_off[(size_t)p];
+            const uint32_t c = count[(size_t)p];
+            if (ca && cb) memcpy(out, chunk_ops[chunk_of[(size_t)p]].data() + where[(size_t)p], (size_t)c * sizeof(uint32_t));
+            else if (c) out[0] = lone[(size_t)p];
+            const uint8_t *x = ca ? b->seq.data() + b->seq_off[(size_t)(2 * p)] : nullptr;
+            const uint8_t *y = cb ? b->seq.data() + b->seq_off[(size_t)(2 * p + 1)] : nullptr;
+            if ((!cigar_checks(out, c, x, ca, y, cb, s, nullptr, hits[p].score) || !cigar_in_band(out, c, dlo, dhi)) && bad[(size_t)tid] < 0)
+                bad[(size_t)tid] = p;
+        }
+    });
+    for (int64_t p : bad)
+        if (p >= 0) {
+            agx_set_error("agx_sw_batch_cigars: pair %lld (mode %d, band %d): its %u operations do not consume the span a 0..%d, b 0..%d, disagree with "
+                          "the symbols, leave the band or do not rescore to %d",
+                          (long long)p, b->mode, b->band, count[(size_t)p], hits[p].a_end, hits[p].b_end, hits[p].score);
+            return AGX_E_INTERNAL;
+        }
+    b->cig_valid = true;
+    return AGX_OK;
+}
 } // namespace
 
 extern "C" {
+
+uint64_t agx_sw_band_cigar_bytes_bound(int32_t width, uint32_t ca, uint32_t cb)
+{
+    if (width < 1 || width > AGX_SW_BAND_MAX_WIDTH) return 0;
+    return band_trace_bytes_bound((uint32_t)width, ca, cb);
+}
+
+int agx_sw_cigar_in_band(const uint32_t *ops, uint64_t n_ops, int32_t dlo, int32_t dhi)
+{
+    if (!ops && n_ops) return 0;
+    return cigar_in_band(ops, n_ops, dlo, dhi) ? 1 : 0;
+}
+
+int agx_sw_batch_create_align_band_cigar(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t band, const uint8_t *bases,
+                                         const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_batch **out)
+{
+    AGX_GUARD_BEGIN
+    return create_band(ctx, scoring, mode, band, bases, off, len, n_pairs, out, true);
+    AGX_GUARD_END("agx_sw_batch_create_align_band_cigar")
+}
+
+int agx_sw_align_band_cigar(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t band, const uint8_t *bases, const uint64_t *off,
+                            const uint32_t *len, int64_t n_pairs, agx_sw_hit *hits, uint64_t *op_off, uint32_t *ops, uint64_t ops_cap)
+{
+    agx_sw_batch *b = nullptr;
+    int rc = agx_sw_batch_create_align_band_cigar(ctx, scoring, mode, band, bases, off, len, n_pairs, &b);
+    if (rc) return rc;
+    rc = agx_sw_batch_launch(b);
+    if (!rc) rc = agx_sw_batch_cigars(b, hits, op_off, ops, ops_cap);
+    if (rc && b->ctx) (void)hipStreamSynchronize(b->ctx->stream); // the blocks go back to the pools: nothing may still run on them
+    agx_sw_batch_destroy(b);
+    return rc;
+}
 
 int agx_sw_batch_cigars(agx_sw_batch *b, agx_sw_hit *hits, uint64_t *op_off, uint32_t *ops, uint64_t ops_cap)
 {
@@ -2771,7 +3159,7 @@ int agx_sw_batch_cigars(agx_sw_batch *b, agx_sw_hit *hits, uint64_t *op_off, uin
         return AGX_E_ARG;
     }
     if (b->cigar != 1 || b->align != AGX_SW_ALIGN_SPANS) {
-        agx_set_error("agx_sw_batch_cigars: not a cigar batch (create it with agx_sw_batch_create_align_cigar)");
+        agx_set_error("agx_sw_batch_cigars: not a cigar batch (create it with agx_sw_batch_create_align_cigar or agx_sw_batch_create_align_band_cigar)");
         return AGX_E_ARG;
     }
     if (!b->ctx) {
@@ -2780,7 +3168,7 @@ int agx_sw_batch_cigars(agx_sw_batch *b, agx_sw_hit *hits, uint64_t *op_off, uin
     }
     AGX_GUARD_BEGIN
     if (!b->cig_valid) {
-        const int rc = cigars_impl(b);
+        const int rc = b->banded ? band_cigars_impl(b) : cigars_impl(b);
         if (rc) return rc;
     }
     const int64_t n = b->n_pairs;

@@ -222,6 +222,28 @@ static_assert(64 * 32 == AGX_SW_BAND_MAX_WIDTH, "the widest band is 64 lanes of 
 int agx_sw_band_launch_class(int diags_per_lane, int extend, const SwParams &prm, const uint32_t *img, const SwBandGroup *groups,
                              const SwWave *waves, uint32_t n_waves, int32_t *scores, uint32_t *pos, hipStream_t s);
 void agx_sw_band_preload();
+// the TRACED banded fill and its walk (agx_sw_band_trace_kernel.hip): corner capture only.  Every cell of rows
+// 0 .. lb leaves four bits at trace + goff[group] + (step * G + lane) * sw_band_trace_words(K) dwords, nibble k of the lane's K
+// diagonals; goff holds one 64-bit dword offset per group record, a multiple of four (the K = 32 build stores 16 bytes at once).
+constexpr int sw_band_trace_words(int K) { return (K + 7) / 8; }
+// the dwords a traced pair of lb rows occupies in class K on G lanes: steps 0 .. lb + G - 1 of G lanes, rounded up to four
+inline uint64_t sw_band_trace_dwords(int G, uint32_t lb, int K)
+{
+    return (((uint64_t)lb + (uint64_t)G) * (uint64_t)G * (uint64_t)sw_band_trace_words(K) + 3u) & ~(uint64_t)3u;
+}
+int agx_sw_band_trace_launch_class(int diags_per_lane, const SwParams &prm, const uint32_t *img, const SwBandGroup *groups, const SwWave *waves,
+                                   uint32_t n_waves, int32_t *scores, uint32_t *trace, const uint64_t *goff, hipStream_t s);
+// the band-aware walk: pair p's SwWalkRec (G = lanes, C = diagonals per lane, x_dw / y_dw of its band image) and its band.  It
+// tests dlo <= j - i <= dhi, i <= cb, j <= ca before every load; a violation leaves kSwWalkFailed in runs[p].
+struct SwBandWalkRec {
+    int32_t dlo, dhi;
+    uint32_t fpad;   // zero bytes in front of a in the image
+    uint32_t kshift; // log2 of the diagonals per lane
+};
+constexpr uint32_t kSwWalkFailed = 0xffffffffu;
+int agx_sw_band_walk_launch(const SwWalkRec *recs, const SwBandWalkRec *band, uint32_t n, const uint32_t *img, const uint32_t *trace,
+                            uint32_t *slots, uint32_t *runs, hipStream_t s);
+void agx_sw_band_trace_preload();
 
 // ---- device-side planning (agx_sw_plan_kernel.hip): the O(pairs) passes of the planner as kernels
 constexpr uint32_t kSwPlanEmptyKey = 1u << 27;           // sort key of a pair with an empty side: behind every bucket

@@ -51,6 +51,28 @@
 // in rising i, and within a row it takes the leftmost cell; masked cells are minus infinity and never win.  The group reduces by
 // (score, then i, then j); the position word is i << 16 | j (both <= 65535).
 //
+// TRACE (agx_sw_band_trace_kernel.hip; include/agx.h, "CIGARs for banded batches"; DESIGN.md 4.1h): the corner-capture build also
+// leaves four bits per cell -- bits 0-1 where H came from (0 the diagonal, 1 E, 2 F; ties prefer the diagonal, then E), bit 2
+// "E extended" (ue + ge > uz, strictly), bit 3 "F extended" (f + ge > zleft, strictly).  A lane's K nibbles of a step are
+// sw_band_trace_words(K) dwords at trace + goff[group] + (t G + gl) words: step-major, a group's lanes side by side, one store
+// per lane and step (dwordx4 at K = 32).  Only rows 0 .. lb of the group are written, so a pair takes (lb + G) G words dwords
+// whatever the wave's step count is.  The walk (sw_walk_band) finds cell (i, j) at slot = j - i - dlo, lane slot / K, nibble
+// slot % K, step i + lane.
+// The trace does not mask E and F either, and the bits of masked or boundary cells cannot steer the walk.  The walk starts at
+// the corner, a true cell, reads cells with 1 <= i <= lb, 1 <= j <= la inside the band only, and ends at row 0 or column 0
+// without reading them.  Every such cell has the true cell (i - 1, j - 1) on its own diagonal, so max(s, ev, f) is a true
+// value; by "No wrap" a true value always beats one derived from minus infinity, so H never takes a source derived from minus
+// infinity and bits 0-1 always point at a true cell.  Bit 2 is read in state E at a cell whose E is true (H chose it, or the
+// cell below extended from it strictly): then max(uz, ue + ge) is true, and the bit is set only if ue + ge is the true one.
+// Bit 3 likewise.  A strict "extended" bit computed from two derived minus infinities belongs to a cell whose E (or F) is
+// itself derived, where the walk never stands in that state.  Along the edges:
+//   band's right edge (d = dhi): "up" is diagonal dhi + 1 -- a masked slot or the last lane's minus infinity; uz and ue are
+//       derived, E is derived, H does not choose it and nothing below extends from it.  F comes from diagonal dhi - 1, true.
+//   band's left edge (d = dlo): "left" is the first lane's minus infinity, F is derived; E comes from diagonal dlo + 1, true.
+//   row 1 reads row 0 as "up": H(0, j) is true for j <= dhi, E(0, j) derives from the masked rows above, so bit 2 is clear
+//       and the walk reaches row 0 in state H.  Column 1 reads column 0 as "left": F(i, 0) is a maximum of minus infinities,
+//       H(i, 0) is true for i <= -dlo, so bit 3 is clear and the walk reaches column 0 in state H.
+//
 // (included by agx_sw_band_kernel.hip; opens an anonymous namespace that the including file closes after its launch helper)
 #include "agx_sw.h"
 
@@ -70,10 +92,12 @@ __device__ __forceinline__ int band_shl1(int old, int v)
     return __builtin_amdgcn_update_dpp(old, v, 0x130, 0xf, 0xf, false);
 }
 
-template <int K, bool EXT>
+template <int K, bool EXT, bool TRACE = false>
 __device__ __forceinline__ void band_body(const SwParams &prm, const uint32_t *__restrict__ img, const SwBandGroup *__restrict__ groups,
-                                          const SwWave w, int32_t *__restrict__ scores, uint32_t *__restrict__ pos)
+                                          const SwWave w, int32_t *__restrict__ scores, uint32_t *__restrict__ pos,
+                                          uint32_t *trace = nullptr, const uint64_t *goff = nullptr)
 {
+    static_assert(!(TRACE && EXT), "the traced build captures the corner: an EXTEND span is traced as the global alignment it is");
     static_assert(K % 4 == 0 && K >= 4 && K <= 32, "the query window is whole dwords and the cell mask one dword");
     constexpr int XW = K / 4;
     const int ge = prm.ge, gf = prm.gf, s_match = prm.hd, s_mis = prm.hd - prm.delta; // the diagonal move on z: score - gf
@@ -126,6 +150,13 @@ __device__ __forceinline__ void band_body(const SwParams &prm, const uint32_t *_
     const int dc = la - lb - g.dlo;       // GLOBAL: the corner's diagonal, counted from dlo
     const int kc = dc - gl * K;           // its slot here, if 0 <= kc < K
 
+    // TRACE: this lane's nibbles of step t go to tp + t G TW
+    constexpr int TW = sw_band_trace_words(K);
+    uint32_t *tp = nullptr;
+    if constexpr (TRACE) {
+        if (active) tp = trace + goff[w.first_group + grp] + (uint32_t)(gl * TW);
+    }
+
     uint32_t q0 = row_quad(0), q1 = row_quad(1), q2 = row_quad(2);
     uint32_t x0 = col_quad(0), x1 = col_quad(1), x2 = col_quad(2);
     const int steps = (int)w.steps;
@@ -163,6 +194,17 @@ __device__ __forceinline__ void band_body(const SwParams &prm, const uint32_t *_
             return (v & m) | (kBandNegInf & ~m);
         };
 
+        // TRACE, per cell: where H came from (diagonal, then E, then F) | E extended << 2 | F extended << 3, both strictly:
+        // ue + ge > uz is ev > uz, and f + ge > zleft is the new f > the left cell's z, which z[k - 1] still holds.  Everything
+        // the trace computes stands inside its own blocks: the untraced builds compile to the code they had without it.  The
+        // nibble joins its dword at once and the chain passes through the same empty statement, so that no cell is begun before
+        // the nibble of the cell on its left is made: left to the scheduler, s, ev and f of all K cells stay live to the step's end.
+        [[maybe_unused]] uint32_t tw[TW];
+        [[maybe_unused]] auto dirs = [](int s, int ev, int f, bool e_ext, bool f_ext) -> uint32_t {
+            const uint32_t src = s >= max(ev, f) ? 0u : ev >= f ? 1u : 2u;
+            return src | (e_ext ? 4u : 0u) | (f_ext ? 8u : 0u);
+        };
+
         // phase 1: the first cell
         int f, zleft;
         {
@@ -171,6 +213,12 @@ __device__ __forceinline__ void band_body(const SwParams &prm, const uint32_t *_
             const int xs = (int)(xw[0] & 0xffu);
             const int s = z[0] + (xs == yc ? s_match : s_mis);
             zleft = keep(max(max(ev, f), s) + gf, 0);
+            if constexpr (TRACE) {
+                tw[0] = dirs(s, ev, f, ev > z[1], f > zl);
+#pragma unroll
+                for (int n = 1; n < TW; ++n) tw[n] = 0;
+                asm volatile("" : "+v"(tw[0]), "+v"(zleft));
+            }
             e[0] = ev;
             z[0] = zleft;
         }
@@ -187,8 +235,21 @@ __device__ __forceinline__ void band_body(const SwParams &prm, const uint32_t *_
             const int xs = (int)((xw[k >> 2] >> (8 * (k & 3))) & 0xffu);
             const int s = z[k] + (xs == yc ? s_match : s_mis);
             zleft = keep(max(max(ev, f), s) + gf, k);
+            if constexpr (TRACE) {
+                tw[k >> 3] |= dirs(s, ev, f, ev > uz, f > z[k - 1]) << (4 * (k & 7));
+                asm volatile("" : "+v"(tw[k >> 3]), "+v"(zleft));
+            }
             e[k] = ev;
             z[k] = zleft;
+        }
+
+        if constexpr (TRACE) { // rows 0 .. lb of this group only: the wave may step on for a longer neighbour
+            if (active && (uint32_t)i <= (uint32_t)lb) {
+                if constexpr (TW == 4) *reinterpret_cast<uint4 *>(tp) = make_uint4(tw[0], tw[1], tw[2], tw[3]);
+                else if constexpr (TW == 2) *reinterpret_cast<uint2 *>(tp) = make_uint2(tw[0], tw[1]);
+                else tp[0] = tw[0];
+            }
+            tp += G * TW;
         }
 
         if constexpr (EXT) {

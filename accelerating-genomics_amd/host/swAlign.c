@@ -1,5 +1,5 @@
 /*
- * swAlign <file_path> [local|global|fit|extend|extend-query][+stats|+cigar]: where the best alignment of every pair ends and begins
+ * swAlign <file_path> [local|global|fit|extend|extend-query][+stats|+cigar|+band=W|+cigar+band=W]: where the best alignment of every pair ends and begins
  * (default: local; the other modes are include/agx.h's "Alignment modes").
  * swAlign <file_path> <mode> <matrix_file> [gap_open gap_extend]: the same under a substitution matrix (gaps default to
  * -11 -1).  The matrix file is the usual text layout: '#' comment lines, one line of symbols, then one row per symbol
@@ -23,7 +23,10 @@
  * (include/agx.h, "Banded alignment"), for long similar pairs -- both sides up to AGX_SW_BAND_MAX_LEN symbols.  The lines are
  *     score a_begin a_end b_begin b_end
  * and the input is read with a line buffer of 65 536 bytes, so lines of up to 65 535 bytes stay whole (without the suffix the
- * reader keeps the reference's 1 000).  Not with another mode, not together with +stats / +cigar or a matrix file.
+ * reader keeps the reference's 1 000).  Not with another mode, not together with +stats or a matrix file.
+ * Or "+cigar+band=W" on global and extend, in this order (global+cigar+band=64): the banded alignment and its CIGAR inside the
+ * band (include/agx.h, "CIGARs for banded batches"), the lines of "+cigar" read with the line buffer of "+band=W".
+ * "global+band=3+cigar" is a usage error.
  *   AGX_CLI_CHUNK_PAIRS   pairs per agx_sw_align call (default 262144)
  */
 #include <stdio.h>
@@ -122,14 +125,16 @@ int main(int argc, char *argv[])
     for (int k = 0; (argc == 3 || argc == 4 || argc == 6) && k < 5; k++) {
         const size_t n = strlen(words[k]);
         if (!strcmp(argv[2], words[k])) mode = k;
-        if (!strncmp(argv[2], words[k], n) && !strncmp(argv[2] + n, "+band=", 6)) {
+        const int cigar_band = !strncmp(argv[2], words[k], n) && !strncmp(argv[2] + n, "+cigar+band=", 12); /* in this order only */
+        if (!strncmp(argv[2], words[k], n) && (cigar_band || !strncmp(argv[2] + n, "+band=", 6))) {
             /* W: digits only, up to the end of the word; global and extend only, and no matrix file */
-            const char *w = argv[2] + n + 6;
+            const char *w = argv[2] + n + (cigar_band ? 12 : 6);
             char *end;
             const long v = strtol(w, &end, 10);
             if (isdigit((unsigned char)*w) && !*end && v <= 0x7fffffffL && argc == 3 && (k == AGX_SW_MODE_GLOBAL || k == AGX_SW_MODE_EXTEND)) {
                 mode = k;
                 with_band = 1;
+                with_cigar = cigar_band;
                 band = (int32_t)v;
             }
         }
@@ -151,7 +156,8 @@ int main(int argc, char *argv[])
                 "<mode>+stats (local+stats, fit+stats ...): every line ends in two more numbers, matches and aligned pairs.\n"
                 "<mode>+cigar (local+cigar, fit+cigar ...): every line ends in the alignment as CIGAR text (=, X, I, D; * for none).\n"
                 "global+band=W, extend+band=W: the banded alignment of half-width W >= 0 for long pairs (lines of up to 65535 bytes);\n"
-                "not with another mode, +stats, +cigar or a matrix file.\n",
+                "not with another mode, +stats or a matrix file.\n"
+                "global+cigar+band=W, extend+cigar+band=W: the banded alignment with its CIGAR inside the band (in this order).\n",
                 argv[0], argv[0]);
         return 1;
     }
@@ -214,6 +220,11 @@ int main(int argc, char *argv[])
                 }
             if (!status && with_stats) {
                 if (agx_sw_align_stats(ctx, NULL, with_matrix ? &matrix : NULL, mode, t->bases, t->off, t->len, t->n_pairs, hits, stats) != AGX_OK) {
+                    fprintf(stderr, "swAlign: %s\n", agx_last_error());
+                    status = EXIT_FAILURE;
+                }
+            } else if (!status && with_cigar && with_band) {
+                if (agx_sw_align_band_cigar(ctx, NULL, mode, band, t->bases, t->off, t->len, t->n_pairs, hits, op_off, ops, ops_cap) != AGX_OK) {
                     fprintf(stderr, "swAlign: %s\n", agx_last_error());
                     status = EXIT_FAILURE;
                 }

@@ -392,7 +392,8 @@ int agx_sw_align_cigar(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw
  * message names the pair.  band < 0: AGX_E_ARG.  LOCAL, FIT and EXTEND_QUERY have a free start or a column capture; a band
  * around the main diagonal means nothing for them without a diagonal offset: AGX_E_ARG, as for a mode outside 0..4.
  * scoring: agx_sw_scoring with its limits, NULL = the reference's constants.  Byte 0x00 is refused (AGX_E_SYMBOL) as elsewhere.
- * Deliberately left out: no substitution matrix, no statistics, no CIGAR on banded batches.
+ * Deliberately left out: no substitution matrix and no statistics; CIGARs come from a banded cigar batch ("CIGARs for banded
+ * batches" below), not from this one.
  * The batch behaves like the other align batches: agx_sw_batch_launch (re)launches, agx_sw_batch_scores returns the mode's
  * score, agx_sw_batch_hits the hits in the caller's pair order, agx_sw_batch_bind_scores is accepted and ignored;
  * agx_sw_batch_stats and agx_sw_batch_cigars return AGX_E_ARG.  ctx may be NULL: plan only.  In agx_sw_info, cells stays
@@ -405,6 +406,50 @@ int agx_sw_batch_create_align_band(agx_ctx *ctx, const agx_sw_scoring *scoring, 
 /* One-shot: create_align_band + launch + hits + destroy. */
 int agx_sw_align_band(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t band, const uint8_t *bases, const uint64_t *off,
                       const uint32_t *len, int64_t n_pairs, agx_sw_hit *hits);
+
+/*
+ * CIGARs for banded batches: the alignment itself for the pairs only the band can align.  A banded cigar batch is a banded
+ * batch (mode GLOBAL or EXTEND, half-width band = w; the same limits, scoring, hits and errors) that also answers
+ * agx_sw_batch_cigars and agx_sw_batch_cigar_info.
+ * Spans: for a pair, score, a_end and b_end are exactly what the banded batch of the same mode, band and scoring reports;
+ * begins are 0.  x = a[0..a_end], length ca, is the query; y = b[0..b_end], length cb, the target.
+ * Band: the CIGAR is a path inside the pair's band, the one the score was computed in --
+ *   GLOBAL: dlo = min(0, la - lb) - w, dhi = max(0, la - lb) + w;   EXTEND: dlo = -w, dhi = +w.
+ * The EXTEND band is NOT widened by ca - cb: a wider band could hold a better path to the end cell than the one that was scored
+ * (|ca - cb| <= w holds because the end cell is in the band).  Cells outside the band do not exist: H = E = F = -infinity.
+ * Recurrence and tie rule are those of "Alignment itself" over the in-band cells only, row 0 and column 0 existing only inside
+ * the band: in state H prefer the diagonal, then E (D), then F (I); stay in a gap only on a strict E[i-1][j] + e > H[i-1][j] + o,
+ * likewise for F; state H with i == 0 emits j x I, with j == 0 i x D.  Whatever the mode, the reported alignment is a global
+ * alignment of x with y inside the band.  Operations, BAM codes, run merging, the sizing call, ops_cap, keeping the answer until
+ * the next launch, agx_sw_cigar_info, chunking by AGX_OPT_SW_TRACE_BYTES in the caller's order (always at least one pair per
+ * chunk) and returning the block to the pool after every chunk are as on a cigar batch; trace_cells is the number of in-band
+ * cells (1 <= i <= cb, 1 <= j <= ca) of the traced spans.
+ * Answered without a fill, as there: nothing consumed (EXTEND score 0, both sides empty) gives zero operations; ca == 0 < cb
+ * gives cb D, cb == 0 < ca gives ca I (for a GLOBAL pair with an empty side the band holds that run by construction).
+ * Every CIGAR is checked on the host before it is returned: the checks of agx_sw_batch_cigars, the traced fill's corner score
+ * against the hit's, and after every operation dlo <= j - i <= dhi -- AGX_E_INTERNAL naming the pair otherwise.
+ * Wide band: a band wide enough to hold the whole matrix returns exactly what agx_sw_align_cigar returns for the same mode and
+ * scoring, hit for hit and operation for operation: w >= min(la, lb) in GLOBAL, w >= max(la, lb) in EXTEND.
+ * No new limit.  The traced fill writes four bits per in-band cell, step-major: a pair whose band is tiled as G lanes of K
+ * diagonals (G K >= dhi - dlo + 1, K one of 4, 8, 16, 32, all four built with the trace) takes (cb + G) x G x ceil(K / 8) dwords.
+ * The largest pair the band admits, 65 535 rows x 2048 diagonals, is (65 535 + 64) x 64 x 4 dwords = 67.2 MB of directions plus
+ * its slot of ca + cb words, so no pair is refused for size.
+ * Unchanged: a plain banded batch keeps answering agx_sw_batch_cigars with AGX_E_ARG; agx_sw_batch_stats on a banded cigar
+ * batch is AGX_E_ARG.  ctx may be NULL: plan only.
+ */
+int agx_sw_batch_create_align_band_cigar(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t band, const uint8_t *bases,
+                                         const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_batch **out);
+/* One-shot: create_align_band_cigar + launch + cigars + destroy.  ops_cap >= sum(len) always suffices. */
+int agx_sw_align_band_cigar(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t band, const uint8_t *bases, const uint64_t *off,
+                            const uint32_t *len, int64_t n_pairs, agx_sw_hit *hits /* may be NULL */, uint64_t *op_off, uint32_t *ops,
+                            uint64_t ops_cap);
+/* Host only, no device.  What one traced pair of a banded cigar batch counts against AGX_OPT_SW_TRACE_BYTES: the directions of
+ * its cb rows in the tiling of `width` = dhi - dlo + 1 diagonals that takes the most, plus its slot; it does not depend on the
+ * plan.  0 for a width outside 1..AGX_SW_BAND_MAX_WIDTH. */
+uint64_t agx_sw_band_cigar_bytes_bound(int32_t width, uint32_t ca, uint32_t cb);
+/* Host only: 1 if the path of ops[0..n_ops) from (0, 0) keeps dlo <= j - i <= dhi after every operation (and starts inside),
+ * 0 if it leaves the band or holds an operation other than I, D, = and X.  The band check of agx_sw_batch_cigars. */
+int agx_sw_cigar_in_band(const uint32_t *ops, uint64_t n_ops, int32_t dlo, int32_t dhi);
 
 /* One-shot: create + launch + scores + destroy. */
 int agx_sw_score(agx_ctx *ctx, const uint8_t *bases, const uint64_t *off, const uint32_t *len, int64_t n_pairs,
