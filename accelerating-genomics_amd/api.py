@@ -56,6 +56,7 @@ SYMBOLS = [
     "agx_sw_batch_create_align_cigar", "agx_sw_batch_cigars", "agx_sw_batch_cigar_info", "agx_sw_align_cigar",
     "agx_sw_batch_create_align_band", "agx_sw_align_band",
     "agx_sw_batch_create_align_band_cigar", "agx_sw_align_band_cigar", "agx_sw_band_cigar_bytes_bound", "agx_sw_cigar_in_band",
+    "agx_sw_batch_create_align_band_diag", "agx_sw_align_band_diag",
     "agx_sw_score", "agx_sw_score_multi", "agx_sw_score_devices", "agx_sw_shard_cuts",
     "agx_phmm_batch_create", "agx_phmm_batch_launch", "agx_phmm_batch_results", "agx_phmm_batch_bind_results", "agx_phmm_batch_info",
     "agx_phmm_batch_destroy", "agx_phmm_forward", "agx_phmm_forward_multi", "agx_phmm_forward_devices", "agx_phmm_shard_cuts",
@@ -212,6 +213,10 @@ def lib():
         l.agx_sw_band_cigar_bytes_bound.argtypes = [C.c_int32, C.c_uint32, C.c_uint32]
         l.agx_sw_band_cigar_bytes_bound.restype = C.c_uint64
         l.agx_sw_cigar_in_band.argtypes = [C.c_void_p, C.c_uint64, C.c_int32, C.c_int32]
+        l.agx_sw_batch_create_align_band_diag.argtypes = [C.c_void_p, C.POINTER(SwScoring), C.c_int, C.c_int, C.c_int32, C.c_void_p, C.c_void_p,
+                                                          C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)]
+        l.agx_sw_align_band_diag.argtypes = [C.c_void_p, C.POINTER(SwScoring), C.c_int, C.c_int, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_int64, C.c_void_p]
         l.agx_sw_score.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
         l.agx_sw_score_multi.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
         l.agx_sw_score_devices.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
@@ -262,6 +267,16 @@ def device_count() -> int:
 
 def _ptr(a):
     return a.ctypes.data if a is not None and a.size else None
+
+
+def _diag(diag, n_pairs):
+    """diag of a band around a diagonal: None (0 for every pair), one int for every pair, or n_pairs ints -> int32 array or None"""
+    if diag is None:
+        return None
+    d = np.ascontiguousarray(np.broadcast_to(np.asarray(diag, np.int64), (n_pairs,)))
+    if d.size and (d.min() < -(1 << 31) or d.max() >= (1 << 31)):
+        raise AgxError(E_ARG, "diag does not fit 32 bits")
+    return d.astype(np.int32)
 
 
 class Context:
@@ -315,8 +330,17 @@ class Context:
         return ms.value
 
     # ---- Smith-Waterman
-    def sw_batch(self, b, scoring=None, matrix=None, align=0, mode=SW_MODE_LOCAL, stats=False, cigar=False, band=None) -> "SwBatch":
-        return SwBatch(self, b, scoring, matrix, align, mode, stats, cigar, band)
+    def sw_batch(self, b, scoring=None, matrix=None, align=0, mode=SW_MODE_LOCAL, stats=False, cigar=False, band=None, diag=None) -> "SwBatch":
+        return SwBatch(self, b, scoring, matrix, align, mode, stats, cigar, band, diag)
+
+    def sw_align_band_diag(self, b, mode, band, diag=None, what=SW_ALIGN_SPANS, scoring=None) -> np.ndarray:
+        """b: synth.SWBatch -> SwHit records of the alignment inside the band diag - band <= j - i <= diag + band (include/agx.h,
+        "Banded alignment around a diagonal"), one-shot.  mode: any SW_MODE_*; diag: None (0), one int, or one per pair."""
+        out = np.empty(b.n_pairs, SwHit)
+        sc = C.byref(SwScoring(*scoring)) if scoring is not None else None
+        d = _diag(diag, b.n_pairs)
+        _check(lib().agx_sw_align_band_diag(self._h, sc, mode, what, band, _ptr(d), _ptr(b.bases), _ptr(b.off), _ptr(b.len), b.n_pairs, _ptr(out)))
+        return out
 
     def sw_align_band(self, b, mode, band, scoring=None) -> np.ndarray:
         """b: synth.SWBatch -> SwHit records of the BANDED alignment (include/agx.h, "Banded alignment"), one-shot.
@@ -393,16 +417,26 @@ class Context:
 class SwBatch:
     """agx_sw_batch: a scheduled batch resident in HBM (ctx=None: planned on the host only)."""
 
-    def __init__(self, ctx, b, scoring=None, matrix=None, align=0, mode=SW_MODE_LOCAL, stats=False, cigar=False, band=None):
+    def __init__(self, ctx, b, scoring=None, matrix=None, align=0, mode=SW_MODE_LOCAL, stats=False, cigar=False, band=None, diag=None):
         """scoring: None (the reference's +1/-1/-3/-1) or (match, mismatch, gap_open, gap_extend);
         matrix: an SwMatrix instead (score-only and align batches alike); align: SW_ALIGN_ENDS / SW_ALIGN_SPANS for a batch that also answers hits();
         mode: SW_MODE_* of an align batch (local, global, fit, extension); stats=True: a SPANS batch that also answers stats();
         cigar=True: a SPANS batch that also answers cigars() (not together with stats);
         band=w: a BANDED batch of mode SW_MODE_GLOBAL or SW_MODE_EXTEND (half-width w; it answers hits() as a SPANS batch does;
-        no matrix or stats; with cigar=True a banded cigar batch, which also answers cigars())."""
+        no matrix or stats; with cigar=True a banded cigar batch, which also answers cigars());
+        band=w with diag=one int or one per pair: a batch BANDED AROUND A DIAGONAL, any mode, align = SW_ALIGN_ENDS or
+        SW_ALIGN_SPANS (0: SPANS); no matrix, stats or cigar."""
         self.ctx = ctx
         self.n_pairs = b.n_pairs
         self._h = C.c_void_p()
+        if diag is not None:
+            if band is None or matrix is not None or stats or cigar:
+                raise AgxError(E_ARG, "a batch banded around a diagonal takes band=w under match/mismatch scoring: no matrix, stats or cigar")
+            sc = C.byref(SwScoring(*scoring)) if scoring is not None else None
+            d = _diag(diag, b.n_pairs)
+            _check(lib().agx_sw_batch_create_align_band_diag(ctx._h if ctx else None, sc, mode, align or SW_ALIGN_SPANS, band, _ptr(d), _ptr(b.bases),
+                                                             _ptr(b.off), _ptr(b.len), b.n_pairs, C.byref(self._h)))
+            return
         if band is not None:
             if matrix is not None or stats or align not in (0, SW_ALIGN_SPANS):
                 raise AgxError(E_ARG, "a banded batch is a SW_ALIGN_SPANS batch under match/mismatch scoring: no matrix or stats")

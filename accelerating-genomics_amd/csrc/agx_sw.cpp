@@ -249,6 +249,12 @@ struct agx_sw_batch {
     std::vector<SwBandGroup> band_groups;
     std::vector<uint32_t> band_rec;
     std::vector<uint8_t> band_cls, band_G;
+    // agx_sw_batch_create_align_band_diag: banded with band_at set; align = ENDS or SPANS, any mode.  Per pair
+    // the centre diagonal and the first row the fill was given (kNoBandRow: no fill -- an empty side, or a LOCAL band that
+    // misses the matrix); the fill's rows are counted from there.  SPANS in LOCAL and FIT keep seq / seq_off for the begin pass
+    bool band_at = false;
+    std::vector<int32_t> band_diag;
+    std::vector<uint32_t> band_row0;
     agx_sw_scoring scoring{};
     DevBuf ends;        // per pair: row << kSwLocColBits | column of the end cell, written by the locating fill
     PinBuf ends_stage;  // its page-locked landing block
@@ -1617,14 +1623,42 @@ struct BandPlan { // one pair with work, as the sort moves it
     uint32_t pair, la, lb;
     int32_t dlo, dhi;
     uint8_t cls, G;
+    uint32_t row0; // a band around a diagonal: the fill is given b[row0 .. row0 + lb) and the band shifted by row0; else 0
 };
 
 constexpr uint32_t kNoBandRec = 0xffffffffu;
+constexpr uint32_t kNoBandRow = 0xffffffffu;
+
+// agx_sw_batch_create_align_band_diag's part of create_band: what to report and the centre diagonal of every pair (NULL: 0)
+struct BandAt {
+    int what;
+    const int32_t *diag;
+};
+
+// What the band dlo .. dhi must hold in `mode` (include/agx.h, "Banded alignment around a diagonal"): nullptr if it does, else
+// the words of the error message.
+inline const char *band_at_condition(int mode, int64_t la, int64_t lb, int64_t dlo, int64_t dhi)
+{
+    const bool origin = dlo <= 0 && 0 <= dhi;
+    switch (mode) {
+    case AGX_SW_MODE_GLOBAL:
+        if (!origin) return "does not hold the origin (diagonal 0)";
+        return dlo <= la - lb && la - lb <= dhi ? nullptr : "does not hold the corner (diagonal la - lb)";
+    case AGX_SW_MODE_EXTEND: return origin ? nullptr : "does not hold the origin (diagonal 0)";
+    case AGX_SW_MODE_EXTEND_QUERY:
+        if (!origin) return "does not hold the origin (diagonal 0)";
+        return dhi >= la - lb ? nullptr : "holds no cell of column la (dhi < la - lb)";
+    case AGX_SW_MODE_FIT:
+        if (dlo > 0) return "holds no cell of column 0 (dlo > 0)";
+        return dhi >= la - lb ? nullptr : "holds no cell of column la (dhi < la - lb)";
+    default: return nullptr; // LOCAL: a band that misses the matrix scores 0
+    }
+}
 
 int create_band(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t band, const uint8_t *bases, const uint64_t *off,
-                const uint32_t *len, int64_t n_pairs, agx_sw_batch **out, bool cigar = false)
+                const uint32_t *len, int64_t n_pairs, agx_sw_batch **out, bool cigar = false, const BandAt *at = nullptr)
 {
-    const char *who = cigar ? "agx_sw_batch_create_align_band_cigar" : "agx_sw_batch_create_align_band";
+    const char *who = at ? "agx_sw_batch_create_align_band_diag" : cigar ? "agx_sw_batch_create_align_band_cigar" : "agx_sw_batch_create_align_band";
     if (!out) {
         agx_set_error("%s: out is NULL", who);
         return AGX_E_ARG;
@@ -1634,7 +1668,11 @@ int create_band(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t b
         agx_set_error("%s: mode = %d is not one of AGX_SW_MODE_LOCAL .. AGX_SW_MODE_EXTEND_QUERY (0..4)", who, mode);
         return AGX_E_ARG;
     }
-    if (mode != AGX_SW_MODE_GLOBAL && mode != AGX_SW_MODE_EXTEND) {
+    if (at && at->what != AGX_SW_ALIGN_ENDS && at->what != AGX_SW_ALIGN_SPANS) {
+        agx_set_error("%s: what = %d is neither AGX_SW_ALIGN_ENDS nor AGX_SW_ALIGN_SPANS", who, at->what);
+        return AGX_E_ARG;
+    }
+    if (!at && mode != AGX_SW_MODE_GLOBAL && mode != AGX_SW_MODE_EXTEND) {
         agx_set_error("%s: mode = %d has a free start or a column capture; a band around the main diagonal serves AGX_SW_MODE_GLOBAL and "
                       "AGX_SW_MODE_EXTEND only",
                       who, mode);
@@ -1643,6 +1681,10 @@ int create_band(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t b
     if (band < 0) {
         agx_set_error("%s: band = %d is negative", who, band);
         return AGX_E_ARG;
+    }
+    if (at && 2 * (int64_t)band + 1 > AGX_SW_BAND_MAX_WIDTH) {
+        agx_set_error("%s: band = %d needs %lld diagonals, supported %d", who, band, 2 * (long long)band + 1, AGX_SW_BAND_MAX_WIDTH);
+        return AGX_E_LIMIT;
     }
     int rc = ctx ? agx_bind(ctx) : AGX_OK;
     if (rc) return rc;
@@ -1665,6 +1707,8 @@ int create_band(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t b
 
     // ---- pass A: limits, band, lane tiling
     std::vector<BandPlan> plan;
+    std::vector<uint32_t> row0s; // (at) per pair, for the batch
+    if (at) row0s.assign((size_t)n_pairs, kNoBandRow);
     int64_t cells = 0;
     for (int64_t p = 0; p < n_pairs; ++p) {
         const uint32_t la = len[2 * p], lb = len[2 * p + 1];
@@ -1673,8 +1717,35 @@ int create_band(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t b
                           AGX_SW_BAND_MAX_LEN);
             return AGX_E_LIMIT;
         }
-        int64_t dlo, dhi;
-        band_limits(mode, band, la, lb, dlo, dhi);
+        int64_t dlo, dhi, row0 = 0, rows = lb;
+        if (at) {
+            // exactly c - w .. c + w, never widened.  The band touches the rows max(0, -dhi) .. min(lb, la - dlo) only: the fill is
+            // given those rows of b and the band shifted by the first.  The shifted problem has the same boundary values: the
+            // pinned modes hold the origin, so their first row is 0; in FIT and LOCAL a first row > 0 means dhi < 0, the row above
+            // it holds no in-band cell with j >= 0, and the only in-band cell of the first row is (row0, 0), whose value (0) is
+            // what the fill gives the origin of its own matrix.
+            const int64_t c = at->diag ? at->diag[p] : 0;
+            if (c > (int64_t)AGX_SW_BAND_MAX_LEN + band || -c > (int64_t)AGX_SW_BAND_MAX_LEN + band) {
+                agx_set_error("pair %lld: diag = %lld lies beyond the supported %d + band on either side", (long long)p, (long long)c, AGX_SW_BAND_MAX_LEN);
+                return AGX_E_ARG;
+            }
+            dlo = c - band;
+            dhi = c + band;
+            if (const char *why = band_at_condition(mode, la, lb, dlo, dhi)) {
+                agx_set_error("pair %lld: lengths %u x %u in mode %d: the band %lld .. %lld (diag %lld, band %d) %s", (long long)p, la, lb, mode,
+                              (long long)dlo, (long long)dhi, (long long)c, band, why);
+                return AGX_E_ARG;
+            }
+            if (mode == AGX_SW_MODE_LOCAL && (dlo > (int64_t)la - 1 || dhi < 1 - (int64_t)lb)) { // no in-band cell with i, j >= 1: scores 0
+                cells += (int64_t)la * lb;
+                continue;
+            }
+            row0 = std::max<int64_t>(0, -dhi);
+            rows = std::min<int64_t>(lb, (int64_t)la - dlo) - row0;
+            dlo += row0;
+            dhi += row0;
+        } else
+            band_limits(mode, band, la, lb, dlo, dhi);
         if (dhi - dlo + 1 > AGX_SW_BAND_MAX_WIDTH) {
             agx_set_error("pair %lld: lengths %u x %u at band %d need %lld diagonals, supported %d", (long long)p, la, lb, band,
                           (long long)(dhi - dlo + 1), AGX_SW_BAND_MAX_WIDTH);
@@ -1686,9 +1757,10 @@ int create_band(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t b
             agx_set_error("%s: bases is NULL", who);
             return AGX_E_ARG;
         }
-        BandPlan e{(uint32_t)p, la, lb, (int32_t)dlo, (int32_t)dhi, 0, 0};
+        BandPlan e{(uint32_t)p, la, (uint32_t)rows, (int32_t)dlo, (int32_t)dhi, 0, 0, (uint32_t)row0};
+        if (at) row0s[(size_t)p] = (uint32_t)row0;
         int cls = 0, G = 1;
-        band_tiling((int)(dhi - dlo + 1), lb, cls, G);
+        band_tiling((int)(dhi - dlo + 1), e.lb, cls, G);
         e.cls = (uint8_t)cls;
         e.G = (uint8_t)G;
         plan.push_back(e);
@@ -1740,7 +1812,7 @@ int create_band(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t b
             g.dlo = e.dlo;
             g.dhi = e.dhi;
             g.out = e.pair;
-            g.reserved = 0;
+            g.reserved = e.row0; // (the kernels do not read it: the image build below does)
             if (img_dw > 0xffffffffull) {
                 agx_set_error("pair %u: the batch's sequences exceed the 16 GiB a banded batch's image may take", e.pair);
                 return AGX_E_LIMIT;
@@ -1757,7 +1829,8 @@ int create_band(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t b
     b->band = band;
     b->cigar = cigar ? 1 : 0;
     b->family = 5;
-    b->align = AGX_SW_ALIGN_SPANS;
+    b->align = at ? at->what : AGX_SW_ALIGN_SPANS;
+    b->band_at = at != nullptr;
     b->mode = mode;
     b->scoring = sc;
     b->prm.ge = sc.gap_extend;
@@ -1780,7 +1853,27 @@ int create_band(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t b
     }
     agx_sw_band_preload();
     if (n_pairs > 0) b->seq_len.assign(len, len + 2 * n_pairs);
-    if (cigar) { // what the traced fills of the spans and the host's checks need, long after this call
+    if (at) {
+        agx_sw_band_at_preload();
+        b->band_row0 = row0s;
+        if (at->diag) b->band_diag.assign(at->diag, at->diag + n_pairs);
+        else b->band_diag.assign((size_t)n_pairs, 0);
+    }
+    if (cigar || (at && at->what == AGX_SW_ALIGN_SPANS && (mode == AGX_SW_MODE_LOCAL || mode == AGX_SW_MODE_FIT))) {
+        // what the traced fills of the spans and the host's checks, or the begin pass, need long after this call
+        b->seq_off.resize((size_t)n_pairs * 2);
+        uint64_t at_byte = 0;
+        for (int64_t k = 0; k < 2 * n_pairs; ++k) {
+            b->seq_off[(size_t)k] = at_byte;
+            at_byte += len[k];
+        }
+        b->seq.resize((size_t)at_byte);
+        agx_parallel_for(2 * n_pairs, 8192, [&](int64_t lo, int64_t hi, int) {
+            for (int64_t k = lo; k < hi; ++k)
+                if (len[k] && bases) memcpy(b->seq.data() + b->seq_off[(size_t)k], bases + off[k], len[k]);
+        }); // (bases == NULL: every pair has an empty side, and a lone run of I or D reads no symbol)
+    }
+    if (cigar) {
         agx_sw_band_trace_preload();
         agx_sw_walk_preload();
         b->band_groups = groups;
@@ -1792,17 +1885,6 @@ int create_band(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t b
             b->band_cls[k] = plan[k].cls;
             b->band_G[k] = plan[k].G;
         }
-        b->seq_off.resize((size_t)n_pairs * 2);
-        uint64_t at = 0;
-        for (int64_t k = 0; k < 2 * n_pairs; ++k) {
-            b->seq_off[(size_t)k] = at;
-            at += len[k];
-        }
-        b->seq.resize((size_t)at);
-        agx_parallel_for(2 * n_pairs, 8192, [&](int64_t lo, int64_t hi, int) {
-            for (int64_t k = lo; k < hi; ++k)
-                if (len[k] && bases) memcpy(b->seq.data() + b->seq_off[(size_t)k], bases + off[k], len[k]);
-        }); // (bases == NULL: every pair has an empty side, and a lone run of I or D reads no symbol)
     }
     PinBuf h_img, h_groups, h_waves;
     struct Temps {
@@ -1831,7 +1913,7 @@ int create_band(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t b
             for (int64_t k = lo; k < hi; ++k) {
                 const SwBandGroup &g = groups[(size_t)k];
                 const uint32_t la = g.la_lb & 0xffffu, lb = g.la_lb >> 16;
-                const uint8_t *sa = bases + off[2 * (size_t)g.out], *sb = bases + off[2 * (size_t)g.out + 1];
+                const uint8_t *sa = bases + off[2 * (size_t)g.out], *sb = bases + off[2 * (size_t)g.out + 1] + g.reserved; // (row0)
                 uint8_t *xa = im + (size_t)g.x_dw * 4, *ya = im + (size_t)g.y_dw * 4;
                 const size_t xbytes = ((size_t)(g.fpad + la + 3) / 4 + 1) * 4, ybytes = ((size_t)(lb + 4) / 4 + 1) * 4;
                 memset(xa, 0, g.fpad);
@@ -1840,7 +1922,9 @@ int create_band(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t b
                 ya[0] = 0;
                 memcpy(ya + 1, sb, lb);
                 memset(ya + 1 + lb, 0, ybytes - 1 - lb);
-                if ((memchr(sa, 0, la) || memchr(sb, 0, lb)) && (first_bad < 0 || (int64_t)g.out < first_bad)) first_bad = g.out;
+                // (all of b, the rows a band around a diagonal leaves out included)
+                if ((memchr(sa, 0, la) || memchr(sb - g.reserved, 0, len[2 * (size_t)g.out + 1])) && (first_bad < 0 || (int64_t)g.out < first_bad))
+                    first_bad = g.out;
             }
             bad[(size_t)t] = first_bad;
         });
@@ -1887,6 +1971,15 @@ int band_launch(agx_sw_batch *b)
     // widest class first: its waves have the longest steps
     for (auto it = b->launches.rbegin(); it != b->launches.rend(); ++it) {
         const ClassLaunch &cl = *it;
+        if (b->band_at && b->mode != AGX_SW_MODE_GLOBAL && b->mode != AGX_SW_MODE_EXTEND) {
+            if (agx_sw_band_at_launch_class(cl.C, b->mode, b->prm, (const uint32_t *)b->img.p, (const SwBandGroup *)b->groups.p,
+                                            (const SwWave *)b->waves.p + cl.first_wave, cl.n_waves, (int32_t *)b->scores.p,
+                                            (uint32_t *)b->band_pos.p, fan.stream(k++))) {
+                agx_set_error("sw_fill_band_at<%d, %d> launch failed: %s", cl.C, b->mode, hipGetErrorString(hipGetLastError()));
+                return AGX_E_HIP;
+            }
+            continue;
+        }
         if (agx_sw_band_launch_class(cl.C, b->mode == AGX_SW_MODE_EXTEND, b->prm, (const uint32_t *)b->img.p, (const SwBandGroup *)b->groups.p,
                                      (const SwWave *)b->waves.p + cl.first_wave, cl.n_waves, (int32_t *)b->scores.p, (uint32_t *)b->band_pos.p,
                                      fan.stream(k++))) {
@@ -1897,9 +1990,145 @@ int band_launch(agx_sw_batch *b)
     return fan.end();
 }
 
+// band_hits of a batch around a diagonal (include/agx.h, "Banded alignment around a diagonal"): the fill's rows are counted from
+// the pair's first row; every reported cell is checked against the matrix and the band.  begins: run the begin pass of a SPANS
+// batch in LOCAL and FIT (agx_sw_batch_scores does not need it) -- a second batch of the same kind over the reversed prefixes,
+// whose band is the mirror image of the pair's: reversed, cell (i, j) of the span of cb rows and ca columns is (cb - i, ca - j),
+// so diagonal d becomes ca - cb - d and the centre c becomes ca - cb - c, the half-width stays.
+int band_at_hits(agx_sw_batch *b, agx_sw_hit *hits, bool begins)
+{
+    int rc = agx_bind(b->ctx);
+    if (rc) return rc;
+    hipStream_t st = b->ctx->stream;
+    const int64_t n = b->n_pairs;
+    const int mode = b->mode;
+    const bool cell = mode == AGX_SW_MODE_LOCAL || mode == AGX_SW_MODE_EXTEND, column = mode == AGX_SW_MODE_FIT || mode == AGX_SW_MODE_EXTEND_QUERY;
+    if (!b->launches.empty()) {
+        AGX_HIP(hipMemcpyAsync(b->out_stage.p, b->scores.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        if (cell || column) AGX_HIP(hipMemcpyAsync(b->band_pos_stage.p, b->band_pos.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    }
+    AGX_HIP(hipStreamSynchronize(st));
+    const int32_t *sc = (const int32_t *)b->out_stage.p;
+    const uint32_t *ps = (const uint32_t *)b->band_pos_stage.p;
+    const bool spans = b->align == AGX_SW_ALIGN_SPANS;
+    const agx_sw_hit nothing{0, -1, -1, -1, -1};
+    for (int64_t p = 0; p < n; ++p) {
+        const uint32_t la = b->seq_len[(size_t)(2 * p)], lb = b->seq_len[(size_t)(2 * p + 1)];
+        const uint32_t row0 = b->band_row0[(size_t)p];
+        if (!la || !lb) {
+            hits[p] = mode == AGX_SW_MODE_LOCAL ? nothing : empty_side_hit(mode, b->align, b->scoring, la, lb);
+            continue;
+        }
+        if (row0 == kNoBandRow) { // LOCAL: the band misses the matrix
+            hits[p] = nothing;
+            continue;
+        }
+        const int64_t dlo = (int64_t)b->band_diag[(size_t)p] - b->band, dhi = (int64_t)b->band_diag[(size_t)p] + b->band;
+        agx_sw_hit h{sc[p], -1, (int32_t)la - 1, -1, (int32_t)lb - 1};
+        int64_t i = lb, j = la;
+        bool ok = true, consumed = true;
+        if (cell) {
+            if (h.score <= 0) {
+                ok = h.score == 0;
+                h = nothing;
+                consumed = false;
+            } else {
+                i = (int64_t)(ps[p] >> 16) + row0;
+                j = ps[p] & 0xffffu;
+                ok = ps[p] != 0xffffffffu && i >= 1 && j >= 1;
+            }
+        } else if (column) {
+            i = (int64_t)ps[p] + row0;
+            ok = ps[p] <= 0xffffu;
+        }
+        if (consumed) {
+            if (!ok || i > lb || j > la || j - i < dlo || j - i > dhi) {
+                agx_set_error("agx_sw_batch_hits: pair %lld (mode %d, diag %d, band %d): score %d with end cell word 0x%08x is not an in-band cell of its "
+                              "%u x %u matrix",
+                              (long long)p, mode, b->band_diag[(size_t)p], b->band, sc[p], cell || column ? ps[p] : 0u, lb, la);
+                return AGX_E_INTERNAL;
+            }
+            h.b_end = (int32_t)i - 1;
+            h.a_end = (int32_t)j - 1;
+            if (spans && mode != AGX_SW_MODE_LOCAL) h.a_begin = h.b_begin = 0; // (FIT: b_begin follows below)
+        } else if (!ok) {
+            agx_set_error("agx_sw_batch_hits: pair %lld (mode %d): the banded fill gives the negative score %d", (long long)p, mode, sc[p]);
+            return AGX_E_INTERNAL;
+        }
+        hits[p] = h;
+    }
+    if (!begins || !spans || (mode != AGX_SW_MODE_LOCAL && mode != AGX_SW_MODE_FIT)) return AGX_OK;
+    const bool fit = mode == AGX_SW_MODE_FIT;
+
+    // ---- begin pass.  LOCAL: the pairs with a score; FIT: those that consume some of b.
+    std::vector<int64_t> pick;
+    for (int64_t p = 0; p < n; ++p)
+        if (fit ? hits[p].b_end >= 0 : hits[p].score > 0) pick.push_back(p);
+    const int64_t m = (int64_t)pick.size();
+    if (m == 0) return AGX_OK;
+    std::vector<uint64_t> roff((size_t)m * 2);
+    std::vector<uint32_t> rlen((size_t)m * 2);
+    std::vector<int32_t> rdiag((size_t)m);
+    uint64_t at = 0;
+    for (int64_t k = 0; k < m; ++k) {
+        const agx_sw_hit &h = hits[pick[(size_t)k]];
+        roff[(size_t)(2 * k)] = at;
+        rlen[(size_t)(2 * k)] = (uint32_t)h.a_end + 1u;
+        at += (uint64_t)h.a_end + 1u;
+        roff[(size_t)(2 * k + 1)] = at;
+        rlen[(size_t)(2 * k + 1)] = (uint32_t)h.b_end + 1u;
+        at += (uint64_t)h.b_end + 1u;
+        rdiag[(size_t)k] = (h.a_end + 1) - (h.b_end + 1) - b->band_diag[(size_t)pick[(size_t)k]];
+    }
+    std::vector<uint8_t> rev((size_t)at);
+    agx_parallel_for(m, 64, [&](int64_t lo, int64_t hi, int) {
+        for (int64_t k = lo; k < hi; ++k) {
+            const int64_t p = pick[(size_t)k];
+            for (int side = 0; side < 2; ++side) {
+                const uint8_t *src = b->seq.data() + b->seq_off[(size_t)(2 * p + side)];
+                uint8_t *dst = rev.data() + roff[(size_t)(2 * k + side)];
+                const uint32_t l = rlen[(size_t)(2 * k + side)];
+                for (uint32_t q = 0; q < l; ++q) dst[q] = src[l - 1u - q];
+            }
+        }
+    });
+    agx_sw_batch *rb = nullptr;
+    const BandAt rat{AGX_SW_ALIGN_ENDS, rdiag.data()};
+    rc = create_band(b->ctx, &b->scoring, fit ? AGX_SW_MODE_EXTEND_QUERY : AGX_SW_MODE_LOCAL, b->band, rev.data(), roff.data(), rlen.data(), m, &rb,
+                     false, &rat);
+    if (rc) return rc;
+    struct Drop {
+        agx_sw_batch *b;
+        ~Drop()
+        {
+            (void)hipStreamSynchronize(b->ctx->stream); // an error exit may leave its fill running
+            agx_sw_batch_destroy(b);
+        }
+    } drop{rb};
+    std::vector<agx_sw_hit> rh((size_t)m);
+    rc = agx_sw_batch_launch(rb);
+    if (!rc) rc = band_at_hits(rb, rh.data(), false);
+    if (rc) return rc;
+    for (int64_t k = 0; k < m; ++k) {
+        agx_sw_hit &h = hits[pick[(size_t)k]];
+        const agx_sw_hit &r = rh[(size_t)k];
+        // (FIT: the reverse fill may consume nothing of b -- all of a in one gap along row b_end + 1 -- which is b_begin = b_end + 1)
+        if (r.score != h.score || r.a_end > h.a_end || r.b_end > h.b_end || (fit ? r.a_end != h.a_end || r.b_end < -1 : r.a_end < 0 || r.b_end < 0)) {
+            agx_set_error("agx_sw_batch_hits: pair %lld: the reverse banded fill from its end cell (a %d, b %d) gives score %d at (a %d, b %d), the forward "
+                          "fill %d",
+                          (long long)pick[(size_t)k], h.a_end, h.b_end, r.score, r.a_end, r.b_end, h.score);
+            return AGX_E_INTERNAL;
+        }
+        if (!fit) h.a_begin = h.a_end - r.a_end;
+        h.b_begin = h.b_end - r.b_end;
+    }
+    return AGX_OK;
+}
+
 // waits for the launched fill and builds the hits by the contract's rules, in the caller's pair order
 int band_hits(agx_sw_batch *b, agx_sw_hit *hits)
 {
+    if (b->band_at) return band_at_hits(b, hits, true);
     int rc = agx_bind(b->ctx);
     if (rc) return rc;
     hipStream_t st = b->ctx->stream;
@@ -1955,6 +2184,28 @@ int agx_sw_align_band(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int
 {
     agx_sw_batch *b = nullptr;
     int rc = agx_sw_batch_create_align_band(ctx, scoring, mode, band, bases, off, len, n_pairs, &b);
+    if (rc) return rc;
+    rc = agx_sw_batch_launch(b);
+    if (!rc) rc = agx_sw_batch_hits(b, hits);
+    if (rc && b->ctx) (void)hipStreamSynchronize(b->ctx->stream); // the blocks go back to the pools: nothing may still run on them
+    agx_sw_batch_destroy(b);
+    return rc;
+}
+
+int agx_sw_batch_create_align_band_diag(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int what, int32_t band, const int32_t *diag,
+                                        const uint8_t *bases, const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_batch **out)
+{
+    AGX_GUARD_BEGIN
+    const BandAt at{what, diag};
+    return create_band(ctx, scoring, mode, band, bases, off, len, n_pairs, out, false, &at);
+    AGX_GUARD_END("agx_sw_batch_create_align_band_diag")
+}
+
+int agx_sw_align_band_diag(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int what, int32_t band, const int32_t *diag, const uint8_t *bases,
+                           const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_hit *hits)
+{
+    agx_sw_batch *b = nullptr;
+    int rc = agx_sw_batch_create_align_band_diag(ctx, scoring, mode, what, band, diag, bases, off, len, n_pairs, &b);
     if (rc) return rc;
     rc = agx_sw_batch_launch(b);
     if (!rc) rc = agx_sw_batch_hits(b, hits);
@@ -2065,7 +2316,7 @@ int agx_sw_batch_scores(agx_sw_batch *b, int32_t *scores)
     if (b->banded) { // the mode's score is the hit's
         AGX_GUARD_BEGIN
         std::vector<agx_sw_hit> h((size_t)b->n_pairs);
-        rc = band_hits(b, h.data());
+        rc = b->band_at ? band_at_hits(b, h.data(), false) : band_hits(b, h.data());
         for (int64_t p = 0; !rc && p < b->n_pairs; ++p) scores[p] = h[(size_t)p].score;
         return rc;
         AGX_GUARD_END("agx_sw_batch_scores")

@@ -213,7 +213,7 @@ struct SwBandGroup {
     int32_t dlo, dhi; // the band: dlo <= j - i <= dhi
     uint32_t out;     // the caller's pair number
     uint32_t fpad;    // (-(dlo + G K - G)) mod 4: the byte the group's last lane loads at step t is dword-aligned when t % 4 == 0
-    uint32_t reserved;
+    uint32_t reserved; // host only (no kernel reads it): a band around a diagonal starts b at this row, dlo / dhi are shifted by it
 };
 #define AGX_SW_FOR_EACH_BAND_CLASS(X) X(4) X(8) X(16) X(32)
 static const int kSwBandClasses[] = {4, 8, 16, 32};
@@ -222,6 +222,11 @@ static_assert(64 * 32 == AGX_SW_BAND_MAX_WIDTH, "the widest band is 64 lanes of 
 int agx_sw_band_launch_class(int diags_per_lane, int extend, const SwParams &prm, const uint32_t *img, const SwBandGroup *groups,
                              const SwWave *waves, uint32_t n_waves, int32_t *scores, uint32_t *pos, hipStream_t s);
 void agx_sw_band_preload();
+// the builds of the same body for a band around a caller-given diagonal (agx_sw_band_diag_kernel.hip): mode LOCAL,
+// FIT or EXTEND_QUERY; GLOBAL and EXTEND run agx_sw_band_launch_class.  pos[out]: LOCAL i << 16 | j, the others the row i.
+int agx_sw_band_at_launch_class(int diags_per_lane, int mode, const SwParams &prm, const uint32_t *img, const SwBandGroup *groups,
+                                const SwWave *waves, uint32_t n_waves, int32_t *scores, uint32_t *pos, hipStream_t s);
+void agx_sw_band_at_preload();
 // the TRACED banded fill and its walk (agx_sw_band_trace_kernel.hip): corner capture only.  Every cell of rows
 // 0 .. lb leaves four bits at trace + goff[group] + (step * G + lane) * sw_band_trace_words(K) dwords, nibble k of the lane's K
 // diagonals; goff holds one 64-bit dword offset per group record, a multiple of four (the K = 32 build stores 16 bytes at once).

@@ -73,6 +73,13 @@
 //       and the walk reaches row 0 in state H.  Column 1 reads column 0 as "left": F(i, 0) is a maximum of minus infinities,
 //       H(i, 0) is true for i <= -dlo, so bit 3 is clear and the walk reaches column 0 in state H.
 //
+// AT (agx_sw_band_diag_kernel.hip; include/agx.h, "Banded alignment around a diagonal"; DESIGN.md 4.1i): builds for a band around
+// a caller-given diagonal in the modes whose boundaries or capture differ -- LOCAL (zero floor z >= gf, no injection, ANY
+// capture), FIT (H = 0 in every in-band cell of column 0: the injection follows that column's slot -(i + d0) from step to step)
+// and EXTEND_QUERY; the last two capture the best cell of column la, slot la - i - d0, rows 0 .. lb, smallest row first.  That
+// file's head restates "No wrap" for them.  Nothing above assumes that the band is centred on the main diagonal: dlo and dhi come
+// from the group record, and the host may hand the fill a target that starts at a later row with the band shifted accordingly.
+//
 // (included by agx_sw_band_kernel.hip; opens an anonymous namespace that the including file closes after its launch helper)
 #include "agx_sw.h"
 
@@ -92,13 +99,19 @@ __device__ __forceinline__ int band_shl1(int old, int v)
     return __builtin_amdgcn_update_dpp(old, v, 0x130, 0xf, 0xf, false);
 }
 
-template <int K, bool EXT, bool TRACE = false>
+// AT: -1 for the builds above; else the mode of a build of agx_sw_band_diag_kernel.hip (LOCAL: EXT is set, it captures by the
+// ANY rule; FIT and EXTEND_QUERY capture column la).  Everything they add stands inside `if constexpr` blocks.
+template <int K, bool EXT, bool TRACE = false, int AT = -1>
 __device__ __forceinline__ void band_body(const SwParams &prm, const uint32_t *__restrict__ img, const SwBandGroup *__restrict__ groups,
                                           const SwWave w, int32_t *__restrict__ scores, uint32_t *__restrict__ pos,
                                           uint32_t *trace = nullptr, const uint64_t *goff = nullptr)
 {
     static_assert(!(TRACE && EXT), "the traced build captures the corner: an EXTEND span is traced as the global alignment it is");
     static_assert(K % 4 == 0 && K >= 4 && K <= 32, "the query window is whole dwords and the cell mask one dword");
+    static_assert(AT == -1 || (!TRACE && EXT == (AT == AGX_SW_MODE_LOCAL) &&
+                               (AT == AGX_SW_MODE_LOCAL || AT == AGX_SW_MODE_FIT || AT == AGX_SW_MODE_EXTEND_QUERY)),
+                  "GLOBAL and EXTEND around a diagonal run the plain builds: their boundaries and captures are the same");
+    constexpr bool AT_LOCAL = AT == AGX_SW_MODE_LOCAL, AT_FIT = AT == AGX_SW_MODE_FIT, AT_COL = AT_FIT || AT == AGX_SW_MODE_EXTEND_QUERY;
     constexpr int XW = K / 4;
     const int ge = prm.ge, gf = prm.gf, s_match = prm.hd, s_mis = prm.hd - prm.delta; // the diagonal move on z: score - gf
     const int lane = threadIdx.x & 63;
@@ -149,6 +162,7 @@ __device__ __forceinline__ void band_body(const SwParams &prm, const uint32_t *_
     int corner = 0;                       // GLOBAL
     const int dc = la - lb - g.dlo;       // GLOBAL: the corner's diagonal, counted from dlo
     const int kc = dc - gl * K;           // its slot here, if 0 <= kc < K
+    [[maybe_unused]] int cbest = kBandNegInf, cap_i = -1; // AT_COL: the best z of column la so far and its row
 
     // TRACE: this lane's nibbles of step t go to tp + t G TW
     constexpr int TW = sw_band_trace_words(K);
@@ -177,7 +191,18 @@ __device__ __forceinline__ void band_body(const SwParams &prm, const uint32_t *_
             fl = kBandNegInf;
             yc = fresh;
         }
-        if (i == 0) { // row 0 of this lane: the diagonal input that makes H(0, 0) = 0
+        if constexpr (AT_FIT) {
+            // column 0 of this lane's row: the diagonal input that makes H(i, 0) = 0 in every row 0 .. lb.  The slot moves down by
+            // one per step and crosses the lanes; the branch is taken only while column 0 is inside the band (2w + 1 rows).
+            int slot = -(i + d0);
+            if ((uint32_t)slot < (uint32_t)K && (uint32_t)i <= (uint32_t)lb) {
+                asm volatile("" : "+v"(slot));
+#pragma unroll
+                for (int k = 0; k < K; ++k) z[k] = k == slot ? -s_mis : z[k];
+            }
+        } else if constexpr (AT_LOCAL) {
+            // no injection: a diagonal input of minus infinity under the zero floor gives H = 0 on row 0 and in column 0
+        } else if (i == 0) { // row 0 of this lane: the diagonal input that makes H(0, 0) = 0
             // (the slot is compared here, once per lane: hoisted out of the loop the K compares hold K scalar register pairs)
             int slot = k0;
             asm volatile("" : "+v"(slot));
@@ -212,7 +237,8 @@ __device__ __forceinline__ void band_body(const SwParams &prm, const uint32_t *_
             f = max(zl, fl + ge);
             const int xs = (int)(xw[0] & 0xffu);
             const int s = z[0] + (xs == yc ? s_match : s_mis);
-            zleft = keep(max(max(ev, f), s) + gf, 0);
+            if constexpr (AT_LOCAL) zleft = keep(max(max(max(ev, f), s), 0) + gf, 0); // the zero floor: z >= gf
+            else zleft = keep(max(max(ev, f), s) + gf, 0);
             if constexpr (TRACE) {
                 tw[0] = dirs(s, ev, f, ev > z[1], f > zl);
 #pragma unroll
@@ -234,7 +260,8 @@ __device__ __forceinline__ void band_body(const SwParams &prm, const uint32_t *_
             f = max(zleft, f + ge);
             const int xs = (int)((xw[k >> 2] >> (8 * (k & 3))) & 0xffu);
             const int s = z[k] + (xs == yc ? s_match : s_mis);
-            zleft = keep(max(max(ev, f), s) + gf, k);
+            if constexpr (AT_LOCAL) zleft = keep(max(max(max(ev, f), s), 0) + gf, k);
+            else zleft = keep(max(max(ev, f), s) + gf, k);
             if constexpr (TRACE) {
                 tw[k >> 3] |= dirs(s, ev, f, ev > uz, f > z[k - 1]) << (4 * (k & 7));
                 asm volatile("" : "+v"(tw[k >> 3]), "+v"(zleft));
@@ -263,6 +290,20 @@ __device__ __forceinline__ void band_body(const SwParams &prm, const uint32_t *_
                 best = m;
                 hit_i = i;
                 hit_k = col;
+            }
+        } else if constexpr (AT_COL) {
+            // cell (i, la) stands in slot la - i - d0, which also moves by one per step; rows 0 .. lb only.  A masked cell is
+            // exactly minus infinity and never improves on the start value; rows come in rising i, so the smallest i wins.
+            int slot = la - i - d0;
+            if ((uint32_t)slot < (uint32_t)K && (uint32_t)i <= (uint32_t)lb) {
+                asm volatile("" : "+v"(slot));
+                int v = kBandNegInf;
+#pragma unroll
+                for (int k = 0; k < K; ++k) v = k == slot ? z[k] : v;
+                if (v > cbest) {
+                    cbest = v;
+                    cap_i = i;
+                }
             }
         } else {
             if (i == lb) {
@@ -318,6 +359,21 @@ __device__ __forceinline__ void band_body(const SwParams &prm, const uint32_t *_
         }
         if (feeder) {
             scores[g.out] = best;
+            pos[g.out] = key;
+        }
+    } else if constexpr (AT_COL) {
+        // over the group's lanes: score, then row (no lane of an admitted pair's group is without a cell of column la)
+        uint32_t key = (uint32_t)cap_i;
+        for (int o = 1; o < G; o <<= 1) {
+            const int ob = __shfl_down(cbest, o);
+            const uint32_t ok = (uint32_t)__shfl_down((int)key, o);
+            if (gl + o < G && (ob > cbest || (ob == cbest && ok < key))) {
+                cbest = ob;
+                key = ok;
+            }
+        }
+        if (feeder) {
+            scores[g.out] = cbest - gf;
             pos[g.out] = key;
         }
     } else {

@@ -27,6 +27,11 @@
  * Or "+cigar+band=W" on global and extend, in this order (global+cigar+band=64): the banded alignment and its CIGAR inside the
  * band (include/agx.h, "CIGARs for banded batches"), the lines of "+cigar" read with the line buffer of "+band=W".
  * "global+band=3+cigar" is a usage error.
+ * Or the suffix "+band=W@D" on any mode (fit+band=64@0, local+band=200@-1500, extend-query+band=32@0): the alignment inside the
+ * band D - W <= j - i <= D + W around the diagonal D, one signed number for every pair of the file (include/agx.h, "Banded
+ * alignment around a diagonal"); the lines of "+band=W", read with its line buffer.  Not together with +stats, +cigar or a
+ * matrix file: "global+cigar+band=8@0" is a usage error.  Without "@D" nothing changes: "global+band=64" is the banded
+ * alignment of "Banded alignment", "fit+band=3" a usage error.
  *   AGX_CLI_CHUNK_PAIRS   pairs per agx_sw_align call (default 262144)
  */
 #include <stdio.h>
@@ -120,8 +125,8 @@ int main(int argc, char *argv[])
 {
     static const char *const words[] = {"local", "global", "fit", "extend", "extend-query"}; /* AGX_SW_MODE_* 0..4 */
     int mode = argc == 2 ? AGX_SW_MODE_LOCAL : -1;
-    int with_stats = 0, with_cigar = 0, with_band = 0;
-    int32_t band = 0;
+    int with_stats = 0, with_cigar = 0, with_band = 0, with_diag = 0;
+    int32_t band = 0, diag = 0;
     for (int k = 0; (argc == 3 || argc == 4 || argc == 6) && k < 5; k++) {
         const size_t n = strlen(words[k]);
         if (!strcmp(argv[2], words[k])) mode = k;
@@ -136,6 +141,22 @@ int main(int argc, char *argv[])
                 with_band = 1;
                 with_cigar = cigar_band;
                 band = (int32_t)v;
+            }
+        }
+        if (!strncmp(argv[2], words[k], n) && !strncmp(argv[2] + n, "+band=", 6) && argc == 3) {
+            /* W@D: digits, '@', an optional '-' and digits, up to the end of the word; any mode, no matrix file */
+            const char *w = argv[2] + n + 6;
+            char *end, *end2;
+            const long v = strtol(w, &end, 10);
+            if (isdigit((unsigned char)*w) && *end == '@' && v <= 0x7fffffffL) {
+                const char *d = end + 1;
+                const long c = strtol(d, &end2, 10);
+                if (isdigit((unsigned char)d[*d == '-']) && !*end2 && c >= -0x7fffffffL && c <= 0x7fffffffL) {
+                    mode = k;
+                    with_band = with_diag = 1;
+                    band = (int32_t)v;
+                    diag = (int32_t)c;
+                }
             }
         }
         if (!strncmp(argv[2], words[k], n) && !strcmp(argv[2] + n, "+stats")) {
@@ -157,7 +178,9 @@ int main(int argc, char *argv[])
                 "<mode>+cigar (local+cigar, fit+cigar ...): every line ends in the alignment as CIGAR text (=, X, I, D; * for none).\n"
                 "global+band=W, extend+band=W: the banded alignment of half-width W >= 0 for long pairs (lines of up to 65535 bytes);\n"
                 "not with another mode, +stats or a matrix file.\n"
-                "global+cigar+band=W, extend+cigar+band=W: the banded alignment with its CIGAR inside the band (in this order).\n",
+                "global+cigar+band=W, extend+cigar+band=W: the banded alignment with its CIGAR inside the band (in this order).\n"
+                "<mode>+band=W@D (fit+band=64@0, local+band=200@-1500): the alignment inside the band D-W <= j-i <= D+W around the\n"
+                "diagonal D, in any mode; not with +stats, +cigar or a matrix file.\n",
                 argv[0], argv[0]);
         return 1;
     }
@@ -234,6 +257,17 @@ int main(int argc, char *argv[])
                     fprintf(stderr, "swAlign: %s\n", agx_last_error());
                     status = EXIT_FAILURE;
                 }
+            } else if (!status && with_diag) {
+                int32_t *dg = (int32_t *)malloc(sizeof(int32_t) * (size_t)t->n_pairs);
+                for (int64_t p = 0; dg && p < t->n_pairs; p++) dg[p] = diag;
+                if (!dg) {
+                    fprintf(stderr, "swAlign: out of memory\n");
+                    status = EXIT_FAILURE;
+                } else if (agx_sw_align_band_diag(ctx, NULL, mode, AGX_SW_ALIGN_SPANS, band, dg, t->bases, t->off, t->len, t->n_pairs, hits) != AGX_OK) {
+                    fprintf(stderr, "swAlign: %s\n", agx_last_error());
+                    status = EXIT_FAILURE;
+                }
+                free(dg);
             } else if (!status && with_band) {
                 if (agx_sw_align_band(ctx, NULL, mode, band, t->bases, t->off, t->len, t->n_pairs, hits) != AGX_OK) {
                     fprintf(stderr, "swAlign: %s\n", agx_last_error());

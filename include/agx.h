@@ -390,7 +390,8 @@ int agx_sw_align_cigar(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw
  * Limits: la, lb <= AGX_SW_BAND_MAX_LEN on BOTH sides, and width = dhi - dlo + 1 <= AGX_SW_BAND_MAX_WIDTH (64 lanes x 32
  * diagonals): |la - lb| + 2w + 1 in GLOBAL, 2w + 1 in EXTEND.  A pair beyond either fails the create with AGX_E_LIMIT, the
  * message names the pair.  band < 0: AGX_E_ARG.  LOCAL, FIT and EXTEND_QUERY have a free start or a column capture; a band
- * around the main diagonal means nothing for them without a diagonal offset: AGX_E_ARG, as for a mode outside 0..4.
+ * around the main diagonal means nothing for them without a diagonal offset: AGX_E_ARG, as for a mode outside 0..4 (they are
+ * served by "Banded alignment around a diagonal" below).
  * scoring: agx_sw_scoring with its limits, NULL = the reference's constants.  Byte 0x00 is refused (AGX_E_SYMBOL) as elsewhere.
  * Deliberately left out: no substitution matrix and no statistics; CIGARs come from a banded cigar batch ("CIGARs for banded
  * batches" below), not from this one.
@@ -450,6 +451,66 @@ uint64_t agx_sw_band_cigar_bytes_bound(int32_t width, uint32_t ca, uint32_t cb);
 /* Host only: 1 if the path of ops[0..n_ops) from (0, 0) keeps dlo <= j - i <= dhi after every operation (and starts inside),
  * 0 if it leaves the band or holds an operation other than I, D, = and X.  The band check of agx_sw_batch_cigars. */
 int agx_sw_cigar_in_band(const uint32_t *ops, uint64_t n_ops, int32_t dlo, int32_t dhi);
+
+/*
+ * Banded alignment around a diagonal: all five modes inside a band around a caller-given diagonal, e.g. a 10 000-base read placed
+ * in a 60 000-base window near where a seed chain says it lies (FIT at diag = minus the expected start).  a, b, la, lb, D[i][j],
+ * the gap costs, the zero floor of LOCAL, the tie rules and the coordinates are those of "Alignment coordinates" and "Alignment
+ * modes"; what = AGX_SW_ALIGN_ENDS or AGX_SW_ALIGN_SPANS.
+ * Band: for pair p, with c = diag[p] (diag == NULL: 0 for every pair) and w = band, a cell (i, j) is inside the band iff
+ *   dlo = c - w <= j - i <= dhi = c + w,
+ * exactly, in every mode: it is never widened (the GLOBAL widening of "Banded alignment" stays that entry's).  Cells outside the
+ * band do not exist: H = E = F = -infinity there and nothing is read from them; of row 0 and column 0 only the in-band parts
+ * exist.  band < 0: AGX_E_ARG.  2w + 1 > AGX_SW_BAND_MAX_WIDTH (w > 1023): AGX_E_LIMIT.  |c| > AGX_SW_BAND_MAX_LEN + w:
+ * AGX_E_ARG naming the pair.  la, lb <= AGX_SW_BAND_MAX_LEN (AGX_E_LIMIT naming the pair).
+ * Boundaries, by the recurrence over the in-band cells:
+ *   pinned modes (GLOBAL, EXTEND, EXTEND_QUERY)  D[0][0] = 0; D[0][j] and D[i][0] are the gap-initialised values where the in-band
+ *                                                chain from (0, 0) reaches them (0 < j <= dhi, 0 < i <= -dlo)
+ *   FIT                                          D[i][0] = 0 for every in-band (i, 0), 0 <= i <= lb; row 0 as in the pinned modes,
+ *                                                so it exists beyond (0, 0) only if (0, 0) is inside the band
+ *   LOCAL                                        the zero floor in every in-band cell
+ * What the band must hold -- otherwise the create fails with AGX_E_ARG and the message names the pair:
+ *   AGX_SW_MODE_GLOBAL        dlo <= 0 <= dhi and dlo <= la - lb <= dhi
+ *   AGX_SW_MODE_EXTEND        dlo <= 0 <= dhi
+ *   AGX_SW_MODE_EXTEND_QUERY  dlo <= 0 <= dhi and dhi >= la - lb
+ *   AGX_SW_MODE_FIT           dlo <= 0 and dhi >= la - lb   (an in-band cell in column 0 and one in column la, rows 0..lb)
+ *   AGX_SW_MODE_LOCAL         nothing: with no in-band cell at 1 <= i <= lb, 1 <= j <= la the pair scores 0 without a fill
+ * Under these conditions every score is finite: the band clipped to the matrix is convex, so a monotone path inside it joins a
+ * start cell to an end cell.  The conditions are checked for every pair, those with an empty side included; such pairs are then
+ * answered by the formulas of "Alignment modes" without a fill (LOCAL: score 0, all four positions -1).
+ * Results: score and end cell follow the mode's rule, taken over in-band cells only --
+ *   LOCAL, EXTEND          the maximum (EXTEND: D[0][0] = 0 included), then the smallest b_end, then the smallest a_end; a score
+ *                          of 0 gives all four positions -1
+ *   FIT, EXTEND_QUERY      the maximum of D[i][la] over the in-band i in 0..lb, with the smallest such i: a_end = la - 1, b_end = i - 1
+ *   GLOBAL                 D[lb][la]
+ * AGX_SW_ALIGN_ENDS leaves the begins at -1.  AGX_SW_ALIGN_SPANS: the pinned modes begin at 0 (EXTEND with score 0 keeps -1).
+ * LOCAL: the begin cell is the contract's -- latest in b, then latest in a -- among the alignments INSIDE THE BAND of that score
+ * that end in the end cell; it is found by a second banded LOCAL fill of the reversed prefixes a[a_end..0], b[b_end..0] around
+ * the mirror image of the band, centre (a_end + 1) - (b_end + 1) - c, the same w.  FIT: a_begin = 0 and b_begin = the latest
+ * start among the in-band alignments of that score that consume b through b_end (0 when b_end = -1; b_end + 1 when the latest
+ * one consumes nothing of b: all of a in one gap along row b_end + 1), found by a second banded EXTEND_QUERY fill of reversed a
+ * against reversed b[0..b_end] around centre la - (b_end + 1) - c.  In both the reverse score must equal the forward one:
+ * AGX_E_INTERNAL naming the pair otherwise.
+ * Equivalences:
+ *   a band that holds the whole matrix (c - w <= -lb and c + w >= la) reports exactly what agx_sw_align_mode reports for the same
+ *       mode, `what` and scoring;
+ *   EXTEND with diag == NULL reports what agx_sw_align_band(AGX_SW_MODE_EXTEND) reports for the same band;
+ *   GLOBAL with c = 0 on pairs with la == lb reports what agx_sw_align_band(AGX_SW_MODE_GLOBAL) reports.
+ * Cost: the band touches the rows max(0, -dhi) .. min(lb, la - dlo) only, and only those are filled: a read of 2000 in a window of
+ * 65 535 costs about 2000 x width.  In agx_sw_info, cells stays sum la*lb as given, padded_cells is what is issued.
+ * The batch behaves like a banded batch: agx_sw_batch_launch (re)launches, agx_sw_batch_scores returns the mode's score,
+ * agx_sw_batch_hits the hits in the caller's pair order, agx_sw_batch_bind_scores is accepted and ignored, agx_sw_batch_info
+ * works; agx_sw_batch_stats and agx_sw_batch_cigars return AGX_E_ARG.  ctx may be NULL: plan only.  scoring and byte 0x00 as in
+ * "Banded alignment".  Unchanged: agx_sw_batch_create_align_band still refuses LOCAL, FIT and EXTEND_QUERY with AGX_E_ARG.
+ * Deliberately left out: CIGARs for these batches (the next step: the traced fill is already a global fill of a span, it needs
+ * only the per-pair band), substitution matrices, statistics, and a z-drop.
+ */
+int agx_sw_batch_create_align_band_diag(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int what, int32_t band,
+                                        const int32_t *diag /* n_pairs, or NULL = 0 for every pair */, const uint8_t *bases,
+                                        const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_batch **out);
+/* One-shot: create_align_band_diag + launch + hits + destroy. */
+int agx_sw_align_band_diag(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int what, int32_t band, const int32_t *diag,
+                           const uint8_t *bases, const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_hit *hits);
 
 /* One-shot: create + launch + scores + destroy. */
 int agx_sw_score(agx_ctx *ctx, const uint8_t *bases, const uint64_t *off, const uint32_t *len, int64_t n_pairs,

@@ -1,0 +1,443 @@
+"""Banded alignment around a diagonal on the device (agx_sw_batch_create_align_band_diag / agx_sw_align_band_diag: all five modes
+inside the band diag - band <= j - i <= diag + band): every comparison is exact, all five fields of every pair, against the
+by-definition checker of tests/sw_band_diag_ref.py -- or, where the header states an equivalence, against the entry it names."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import accelerating_genomics_amd.api as agx
+import accelerating_genomics_amd.synth as synth
+from tests import sw_band_diag_ref as bd
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ACGT = np.frombuffer(b"ACGT", np.uint8)
+FIELDS = ("score", "a_begin", "a_end", "b_begin", "b_end")
+LOCAL, GLOBAL, FIT, EXTEND, EXTEND_QUERY = bd.MODES
+ENDS, SPANS = bd.ENDS, bd.SPANS
+MODES = pytest.mark.parametrize("mode", bd.MODES, ids=[bd.MODE_NAMES[m] for m in bd.MODES])
+NEW_MODES = pytest.mark.parametrize("mode", [LOCAL, FIT, EXTEND_QUERY], ids=["local", "fit", "extend-query"])
+WHATS = pytest.mark.parametrize("what", [ENDS, SPANS], ids=["ends", "spans"])
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    with agx.Context(0) as c:
+        yield c
+
+
+def _same(got, want, what=""):
+    for f in FIELDS:
+        bad = np.nonzero(got[f] != want[f])[0]
+        assert bad.size == 0, "%s %s: %d pairs differ, first %d: got %s, want %s" % (what, f, bad.size, bad[0], got[bad[0]], want[bad[0]])
+
+
+def _batch(ctx, b, mode, w, diag, what=SPANS, scoring=None, relaunch=False):
+    dev = ctx.sw_batch(b, scoring=scoring, mode=mode, align=what, band=w, diag=diag)
+    try:
+        dev.launch()
+        got = dev.hits()
+        assert np.array_equal(dev.scores(), got["score"])  # agx_sw_batch_scores returns the mode's score
+        if relaunch:
+            dev.launch()
+            _same(dev.hits(), got, "relaunch")
+        return got
+    finally:
+        dev.close()
+
+
+def _check(ctx, b, mode, w, diag, what=SPANS, scoring=None, one_shot=True):
+    """Batch and one-shot against the checker."""
+    want = bd.align(b, mode, w, diag, what, scoring)
+    name = "%s w=%d %s" % (bd.MODE_NAMES[mode], w, "spans" if what == SPANS else "ends")
+    _same(_batch(ctx, b, mode, w, diag, what, scoring), want, name + " batch")
+    if one_shot:
+        _same(ctx.sw_align_band_diag(b, mode, w, diag, what, scoring), want, name + " one-shot")
+    return want
+
+
+def _rand(rng, n):
+    return ACGT[rng.integers(0, 4, size=n)].tobytes()
+
+
+def _mutate(rng, a, sub=0.03, indel=0.01, longest=6):
+    """a with `sub` substitutions and `indel` insertions / deletions of 1..longest symbols per position."""
+    arr = np.frombuffer(a, np.uint8).copy()
+    hit = rng.random(arr.size) < sub
+    arr[hit] = ACGT[rng.integers(0, 4, size=int(hit.sum()))]
+    out, at = [], 0
+    for p in np.nonzero(rng.random(arr.size) < indel)[0]:
+        if p < at:
+            continue
+        out.append(arr[at:p].tobytes())
+        g = int(rng.integers(1, longest + 1))
+        if rng.random() < 0.5:
+            out.append(_rand(rng, g))
+            at = int(p)
+        else:
+            at = int(p) + g
+    out.append(arr[at:].tobytes())
+    return b"".join(out)
+
+
+def _admitted(mode, b, diag, w):
+    return [bd.admits(mode, int(b.len[2 * p]), int(b.len[2 * p + 1]), int(diag[p]), w) for p in range(b.n_pairs)]
+
+
+_cache = {}
+
+
+def _shared(name, make):
+    if name not in _cache:
+        _cache[name] = make()
+    return _cache[name]
+
+
+# ---- 1. every small shape
+
+
+def _small_pool():
+    rng = np.random.default_rng(161)
+    pool = {}
+    for la in range(1, 15):
+        for lb in range(1, 15):
+            a = _rand(rng, la)
+            pool[la, lb] = (a, _rand(rng, lb) if (la + lb) % 2 else (a * (lb // la + 1))[:lb])
+    return pool
+
+
+@MODES
+@WHATS
+@pytest.mark.parametrize("w", [0, 1, 2, 5])
+def test_every_small_shape_and_every_centre(ctx, mode, what, w):
+    """All (la, lb) in 1..14 x 1..14, half of the pairs related, at every centre the mode admits (LOCAL: out to where the band has
+    left the matrix on either side), all in one batch through the per-pair diag: fewer rows than lanes, bands that leave the
+    matrix, start and captured column at every slot."""
+    pool = _shared("small", _small_pool)
+    seqs, diag = [], []
+    for (la, lb), (a, t) in pool.items():
+        for c in range(-lb - w - 2, la + w + 3):
+            if bd.admits(mode, la, lb, c, w):
+                seqs += [a, t]
+                diag.append(c)
+    assert len(diag) >= 14  # (GLOBAL at w = 0 admits only la == lb at c = 0)
+    _check(ctx, synth.sw_from_seqs(seqs), mode, w, np.array(diag, np.int32), what)
+
+
+# ---- 2. every lane tiling
+
+WIDTHS = [0, 1, 3, 4, 7, 8, 15, 16, 31, 32, 63, 64, 127, 128, 255, 256, 511, 512, 1023]
+
+
+def _tiling_batch(mode, w):
+    """Related pairs of about n x n symbols (n = 300, or 2600 for the three widest bands, where only long rows fill every lane's
+    diagonals), the target shifted by a few symbols; one centre per pair, drawn near the shift and moved to 0 where the mode does
+    not admit it (la == lb there)."""
+    rng = np.random.default_rng(162 + w)
+    n, pairs = (2600, 6) if w >= 511 else (300, 24)
+    seqs, diag = [], []
+    for _ in range(pairs):
+        a = _rand(rng, int(rng.integers(n - 20, n + 21)))
+        s = int(rng.integers(0, min(w, 30) + 1))
+        t = (_rand(rng, s) + _mutate(rng, a))[:int(rng.integers(n - 20, n + 21))]
+        c = -s + int(rng.integers(-min(w, 3), min(w, 3) + 1))
+        if mode == LOCAL and rng.random() < 0.3:
+            c = int(rng.integers(-len(t), len(a) + 1))  # anywhere
+        if not bd.admits(mode, len(a), len(t), c, w):
+            c, t = 0, t[:len(a)] + _rand(rng, max(0, len(a) - len(t)))
+        seqs += [a, t]
+        diag.append(c)
+    return synth.sw_from_seqs(seqs), np.array(diag, np.int32)
+
+
+@NEW_MODES
+@pytest.mark.parametrize("w", WIDTHS)
+def test_every_lane_tiling(ctx, mode, w):
+    """Every band width at which the planner's class or lane count changes, in the three modes with builds of their own."""
+    b, diag = _tiling_batch(mode, w)
+    assert all(_admitted(mode, b, diag, w))
+    _check(ctx, b, mode, w, diag, SPANS, one_shot=False)
+
+
+# ---- 3. the moving slots
+
+
+@WHATS
+def test_fit_start_and_captured_column_slide_through_every_slot(ctx, what):
+    """FIT of a short read against 3 000 symbols at w = 40: the read is planted at s, the band centred at -s + delta.  Column 0 and
+    column la each stay in the band for 2w + 1 rows, in which their slots pass through every lane and register of the group.  The
+    last two deltas put the plant outside the band; where the table does not admit the centre (dlo > 0 at s = 0, dhi < la - lb at
+    the far end) the create refuses it naming the pair."""
+    rng = np.random.default_rng(163)
+    w, lb = 40, 3000
+    seqs, diag, refused = [], [], []
+    for la in (1, 5, 37):
+        for s in (0, 1, 1499, 2963):
+            read = _rand(rng, la)
+            window = bytearray(_rand(rng, lb))
+            window[s:s + la] = read
+            for delta in (-w, -1, 0, 1, w, w + 1, -w - 1):
+                c = -s + delta
+                if bd.admits(FIT, la, lb, c, w):
+                    seqs += [read, bytes(window)]
+                    diag.append(c)
+                else:
+                    refused.append((read, bytes(window), c))
+    assert len(diag) >= 70 and refused
+    b, diag = synth.sw_from_seqs(seqs), np.array(diag, np.int32)
+    want = _check(ctx, b, FIT, w, diag, what)
+    planted = want["score"] == b.len[0::2].astype(np.int32)  # la x match: the plant itself
+    assert planted.sum() >= 3 * 4 * 4 and not planted.all()
+    for read, window, c in refused:
+        with pytest.raises(agx.AgxError) as e:
+            ctx.sw_align_band_diag(synth.sw_from_seqs([b"ACGT", b"ACGT", read, window]), FIT, w, [0, c], what)
+        assert e.value.code == agx.E_ARG and "pair 1:" in str(e.value)
+
+
+# ---- 4. ties
+
+
+@MODES
+@WHATS
+def test_ties_in_homopolymers_and_repeats(ctx, mode, what):
+    """Homopolymers and two-letter repeats: the maximum is reached in many cells and by many alignments -- the smallest end, and
+    under SPANS the latest begin."""
+    seqs, diag, ws = [], [], []
+    for w in (0, 3, 50):
+        for n in (1, 2, 5, 13, 40):
+            for m in (1, 2, 5, 13, 40):
+                for a, t in ((b"A" * n, b"A" * m), (b"AC" * n, b"AC" * m), (b"AC" * n, b"CA" * m), (b"AC" * n, b"A" * m)):
+                    for c in sorted({0, 1, -1, 2, -2, len(a) - len(t), (len(a) - len(t)) // 2, -len(t) + 1}):
+                        if bd.admits(mode, len(a), len(t), c, w):
+                            seqs += [a, t]
+                            diag.append(c)
+                            ws.append(w)
+    ws, diag = np.array(ws), np.array(diag, np.int32)
+    for w in (0, 3, 50):
+        pick = np.nonzero(ws == w)[0]
+        assert pick.size >= 16  # (GLOBAL at w = 0 admits only la == lb at c = 0)
+        b = synth.sw_from_seqs([s for p in pick for s in (seqs[2 * p], seqs[2 * p + 1])])
+        for scoring in (None, (1, 0, 0, 0)):
+            _check(ctx, b, mode, w, diag[pick], what, scoring, one_shot=False)
+
+
+# ---- 5. scoring
+
+
+def _mixed(n_pairs, lo, hi, seed, w, mode, empties=False):
+    """Reads in windows: a of lo..hi symbols, b = a flank, the mutated read, a flank; the centre near minus the left flank, moved
+    where the mode does not admit it."""
+    rng = np.random.default_rng(seed)
+    seqs, diag = [], []
+    for p in range(n_pairs):
+        a = _rand(rng, int(rng.integers(lo, hi + 1)))
+        s = int(rng.integers(0, 60))
+        t = _rand(rng, s) + (_mutate(rng, a) if p % 3 else _rand(rng, len(a))) + _rand(rng, int(rng.integers(0, 60)))
+        if empties and p % 41 == 0:
+            a = b""
+        if empties and p % 43 == 0:
+            t = b""
+        c = -s + int(rng.integers(-3, 4))
+        if mode == LOCAL and p % 29 == 0:
+            c = len(a) + w + 5  # the band misses the matrix: scores 0 without a fill
+        for alt in (c, min(c, w), 0, (len(a) - len(t)) // 2, len(a) - len(t)):
+            if bd.admits(mode, len(a), len(t), alt, w):
+                c = alt
+                break
+        else:  # GLOBAL with |la - lb| > 2w: cut b to a's length
+            t, c = t[:len(a)] + _rand(rng, max(0, len(a) - len(t))), 0
+        seqs += [a, t]
+        diag.append(c)
+    return synth.sw_from_seqs(seqs), np.array(diag, np.int32)
+
+
+@MODES
+@pytest.mark.parametrize("scoring", [(12, -116, -1000, -1000), (1, 0, 0, 0), (3, -2, 0, -1), (2, -3, -5, -2)], ids=str)
+def test_scoring(ctx, mode, scoring):
+    b, diag = _mixed(256, 20, 200, 165, 10, mode)
+    assert all(_admitted(mode, b, diag, 10))
+    _check(ctx, b, mode, 10, diag, SPANS, scoring, one_shot=False)
+
+
+# ---- 6. the longest pairs
+
+
+@pytest.mark.parametrize("mode", [FIT, LOCAL], ids=["fit", "local"])
+def test_longest_pair_on_the_main_diagonal(ctx, mode):
+    """65 535 x 65 535 at c = 0, w = 16."""
+    rng = np.random.default_rng(166)
+    a = _rand(rng, 65535)
+    t = _mutate(rng, a, sub=0.05, indel=0.0005, longest=3)
+    t = (t + _rand(rng, 65535))[:65535]
+    b = synth.sw_from_seqs([a, t])
+    assert list(b.len) == [65535, 65535]
+    want = _check(ctx, b, mode, 16, 0, SPANS, one_shot=False)
+    assert want["score"][0] > 1000
+
+
+def test_a_read_at_the_far_end_of_the_longest_window(ctx):
+    """2 000 x 65 535, FIT around c = -63 000 at w = 128: the fill is given about 2 000 + 2w rows of the window, not all of it."""
+    rng = np.random.default_rng(167)
+    read = _rand(rng, 2000)
+    window = bytearray(_rand(rng, 65535))
+    planted = _mutate(rng, read)
+    window[63010:63010 + len(planted)] = planted
+    b = synth.sw_from_seqs([read, bytes(window[:65535])])
+    assert list(b.len) == [2000, 65535]
+    want = _check(ctx, b, FIT, 128, -63000, SPANS)
+    assert want["score"][0] > 1500 and 62990 < want["b_begin"][0] < 63030
+    dev = ctx.sw_batch(b, mode=FIT, band=128, diag=-63000)
+    try:
+        assert dev.info().padded_cells <= 64 * 32 * (2000 + 257 + 64)
+    finally:
+        dev.close()
+
+
+# ---- 7. the whole matrix in the band
+
+
+def _up_to_400():
+    rng = np.random.default_rng(168)
+    seqs = []
+    for k in range(96):
+        la, lb = (int(v) for v in rng.integers(0 if k % 8 == 0 else 1, 401, size=2))
+        a = _rand(rng, la)
+        t = _rand(rng, lb) if k % 3 == 0 else (_rand(rng, lb // 3) + _mutate(rng, a) + _rand(rng, lb))[:lb]
+        seqs += [a, t]
+    return synth.sw_from_seqs(seqs)
+
+
+@MODES
+@WHATS
+@pytest.mark.parametrize("c", [0, 37, -101], ids=str)
+def test_a_band_that_holds_the_whole_matrix_equals_the_unbanded_fill(ctx, mode, what, c):
+    """c - w <= -lb and c + w >= la for every pair: exactly what agx_sw_align_mode reports, empty sides included."""
+    b = _shared("up_to_400", _up_to_400)
+    w = 400 + abs(c)
+    got = _batch(ctx, b, mode, w, c, what)
+    _same(got, ctx.sw_align(b, what, mode=mode), "%s c=%d against the unbanded fill" % (bd.MODE_NAMES[mode], c))
+    _same(got, bd.align(b, mode, w, c, what), "against the checker")
+
+
+# ---- 8. the old entry's equivalences
+
+
+@pytest.mark.parametrize("w", [0, 5, 40, 300])
+def test_equivalences_with_the_band_around_the_main_diagonal(ctx, w):
+    """EXTEND with diag == NULL is agx_sw_align_band(EXTEND); GLOBAL at c = 0 on pairs with la == lb is agx_sw_align_band(GLOBAL).
+    The old entry runs unchanged beside the new one."""
+    rng = np.random.default_rng(169)
+    seqs, square = [], []
+    for k in range(64):
+        a = _rand(rng, int(rng.integers(0 if k % 16 == 0 else 1, 700)))
+        t = _mutate(rng, a, indel=0.004) if k % 4 else _rand(rng, int(rng.integers(1, 700)))
+        seqs += [a, t]
+        square += [a, (t + _rand(rng, len(a)))[:len(a)]]
+    b = synth.sw_from_seqs(seqs)
+    old = ctx.sw_align_band(b, EXTEND, w)
+    _same(ctx.sw_align_band_diag(b, EXTEND, w), old, "extend, diag = None")
+    _same(_batch(ctx, b, EXTEND, w, 0), old, "extend, diag = 0")
+    _same(ctx.sw_align_band(b, EXTEND, w), old, "the old entry again")
+    b = synth.sw_from_seqs(square)
+    old = ctx.sw_align_band(b, GLOBAL, w)
+    _same(ctx.sw_align_band_diag(b, GLOBAL, w, 0), old, "global, c = 0, la == lb")
+    _same(bd.align(b, GLOBAL, w, 0), old, "the checker")
+    for mode in (LOCAL, FIT, EXTEND_QUERY):  # the old entry still refuses them
+        with pytest.raises(agx.AgxError) as e:
+            ctx.sw_align_band(b, mode, w)
+        assert e.value.code == agx.E_ARG
+
+
+# ---- 9. batch handling
+
+
+@MODES
+def test_mixed_batch_order_relaunch_and_scores(ctx, mode):
+    """1 024 reads of 30..600 symbols in their windows at w = 24, with empty sides and (LOCAL) bands that miss the matrix: results
+    in the caller's order, a relaunch reproduces them, scores() is hits()["score"], bind_scores is accepted and ignored."""
+    b, diag = _mixed(1024, 30, 600, 170, 24, mode, empties=True)
+    assert all(_admitted(mode, b, diag, 24)) and int((b.len == 0).sum()) > 20
+    want = bd.align(b, mode, 24, diag)
+    dev = ctx.sw_batch(b, mode=mode, band=24, diag=diag)
+    try:
+        assert dev.info().n_launches >= 1 and dev.info().cells == b.cells()
+        bound = agx.host_array(b.n_pairs, np.int32)
+        bound[:] = -77
+        dev.bind_scores(bound)
+        dev.launch()
+        got = dev.hits()
+        _same(got, want, "batch")
+        assert np.array_equal(dev.scores(), got["score"])
+        assert np.all(bound == -77)  # ignored: nothing is written there
+        dev.bind_scores(None)
+        dev.launch()
+        _same(dev.hits(), want, "relaunch")
+        with pytest.raises(agx.AgxError) as e:
+            dev.stats()
+        assert e.value.code == agx.E_ARG
+        with pytest.raises(agx.AgxError) as e:
+            dev.cigars()
+        assert e.value.code == agx.E_ARG
+    finally:
+        dev.close()
+    _same(_batch(ctx, b, mode, 24, diag, ENDS), bd.align(b, mode, 24, diag, ENDS), "ends")
+    # the same pairs in another order give the same hits in that order
+    perm = np.random.default_rng(171).permutation(b.n_pairs)
+    shuffled = synth.sw_from_seqs([s for p in perm for s in (b.seq(2 * int(p)), b.seq(2 * int(p) + 1))])
+    _same(ctx.sw_align_band_diag(shuffled, mode, 24, diag[perm]), want[perm], "shuffled")
+    if mode == LOCAL:
+        missed = np.nonzero((diag - 24 > b.len[0::2].astype(np.int64) - 1) & (b.len[0::2] > 0) & (b.len[1::2] > 0))[0]
+        assert missed.size > 10 and np.all(want["score"][missed] == 0) and np.all(want["a_end"][missed] == -1)
+    # an empty batch
+    assert ctx.sw_align_band_diag(synth.sw_from_seqs([]), mode, 3).size == 0
+
+
+# ---- 10. byte 0x00
+
+
+def test_byte_zero_is_refused(ctx):
+    b = synth.sw_from_seqs([b"ACGT", b"ACGT", b"AC\x00T", b"ACGT"])
+    for mode in bd.MODES:
+        with pytest.raises(agx.AgxError) as e:
+            ctx.sw_align_band_diag(b, mode, 2)
+        assert e.value.code == agx.E_SYMBOL and "pair 1" in str(e.value)
+    # also in the rows of the target that the band does not touch
+    b = synth.sw_from_seqs([b"ACGT", b"ACGT", b"ACGT", b"\x00" + b"ACGT" * 30])
+    with pytest.raises(agx.AgxError) as e:
+        ctx.sw_align_band_diag(b, FIT, 2, [0, -100])
+    assert e.value.code == agx.E_SYMBOL and "pair 1" in str(e.value)
+
+
+# ---- 11. the command line
+
+
+@pytest.mark.parametrize("word,mode,w,c", [("fit", FIT, 64, 0), ("local", LOCAL, 200, -30)])
+def test_swalign_prints_what_the_api_returns(ctx, tmp_path, word, mode, w, c):
+    exe = os.path.join(ROOT, "accelerating-genomics_amd", "bin", "swAlign")
+    rng = np.random.default_rng(172)
+    long = tmp_path / "long.in"
+    lines = []
+    for _ in range(2):
+        a = _rand(rng, 5000)
+        lines += [a, _rand(rng, 30) + _mutate(rng, a, indel=0.002, longest=5) + _rand(rng, 40)]
+    long.write_bytes(b"%d\n" % len(lines) + b"".join(s + b"\n" for s in lines))
+    paths = [str(long)] + ([os.path.join(ROOT, "tests", "golden", "sw_mixed.in")] if mode == LOCAL else [])
+    for path in paths:
+        out = subprocess.run([exe, path, "%s+band=%d@%d" % (word, w, c)], capture_output=True, timeout=300, check=True).stdout
+        _, b, _ = agx.read_sw_text(path, 65536)
+        assert b.n_pairs > 0
+        hits = ctx.sw_align_band_diag(b, mode, w, c)
+        assert out == b"".join(b"%d %d %d %d %d\n" % tuple(int(v) for v in h) for h in hits)
+        _same(hits, bd.align(b, mode, w, c), word)
+    _, b, _ = agx.read_sw_text(str(long), 65536)
+    assert list(b.len[:2]) == [5001, len(lines[1]) + 1]  # whole lines, the newline kept: the default buffer would split them
+    for bad_word in ("fit+cigar+band=8@0", "global+cigar+band=8@0", "fit+band=8@0+cigar", "fit+band=3", "fit+band=8@", "fit+band=@3", "fit+band=x@0",
+                     "fit+band=8@x", "fit+stats+band=8@0"):
+        bad = subprocess.run([exe, str(long), bad_word], capture_output=True, timeout=60)
+        assert bad.returncode != 0 and b"Usage" in bad.stderr and not bad.stdout, bad_word
+    # the mode's condition is the library's: a band that does not reach column 0 in FIT names the pair
+    bad = subprocess.run([exe, str(long), "fit+band=8@100"], capture_output=True, timeout=60)
+    assert bad.returncode != 0 and b"pair 0" in bad.stderr and not bad.stdout
