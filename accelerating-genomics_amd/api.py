@@ -57,6 +57,7 @@ SYMBOLS = [
     "agx_sw_batch_create_align_band", "agx_sw_align_band",
     "agx_sw_batch_create_align_band_cigar", "agx_sw_align_band_cigar", "agx_sw_band_cigar_bytes_bound", "agx_sw_cigar_in_band",
     "agx_sw_batch_create_align_band_diag", "agx_sw_align_band_diag",
+    "agx_sw_batch_create_align_band_diag_cigar", "agx_sw_align_band_diag_cigar", "agx_sw_band_span_record",
     "agx_sw_score", "agx_sw_score_multi", "agx_sw_score_devices", "agx_sw_shard_cuts",
     "agx_phmm_batch_create", "agx_phmm_batch_launch", "agx_phmm_batch_results", "agx_phmm_batch_bind_results", "agx_phmm_batch_info",
     "agx_phmm_batch_destroy", "agx_phmm_forward", "agx_phmm_forward_multi", "agx_phmm_forward_devices", "agx_phmm_shard_cuts",
@@ -82,6 +83,12 @@ class SwCigarInfo(C.Structure):
     """agx_sw_cigar_info: what the last SwBatch.cigars() of a batch did."""
     _fields_ = [("n_traced", C.c_int64), ("trace_cells", C.c_int64), ("trace_bytes_peak", C.c_int64), ("n_chunks", C.c_int32),
                 ("reserved", C.c_int32)]
+
+
+class SwBandSpan(C.Structure):
+    """agx_sw_band_span: where the traced fill of a span starts inside a banded batch's image (agx_sw_band_span_record)."""
+    _fields_ = [("ca", C.c_uint32), ("cb", C.c_uint32), ("x_bytes", C.c_uint32), ("y_dwords", C.c_uint32), ("phase", C.c_uint32),
+                ("dlo", C.c_int32), ("dhi", C.c_int32), ("steps", C.c_uint32)]
 
 
 def cigar_string(ops) -> str:
@@ -217,6 +224,12 @@ def lib():
                                                           C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)]
         l.agx_sw_align_band_diag.argtypes = [C.c_void_p, C.POINTER(SwScoring), C.c_int, C.c_int, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_void_p, C.c_int64, C.c_void_p]
+        l.agx_sw_batch_create_align_band_diag_cigar.argtypes = [C.c_void_p, C.POINTER(SwScoring), C.c_int, C.c_int32, C.c_void_p, C.c_void_p,
+                                                                C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)]
+        l.agx_sw_align_band_diag_cigar.argtypes = [C.c_void_p, C.POINTER(SwScoring), C.c_int, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                   C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
+        l.agx_sw_band_span_record.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                              C.POINTER(SwBandSpan)]
         l.agx_sw_score.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
         l.agx_sw_score_multi.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
         l.agx_sw_score_devices.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
@@ -342,6 +355,18 @@ class Context:
         _check(lib().agx_sw_align_band_diag(self._h, sc, mode, what, band, _ptr(d), _ptr(b.bases), _ptr(b.off), _ptr(b.len), b.n_pairs, _ptr(out)))
         return out
 
+    def sw_align_band_diag_cigar(self, b, mode, band, diag=None, scoring=None):
+        """b: synth.SWBatch -> (SwHit records as sw_align_band_diag(what=SW_ALIGN_SPANS) gives them, op_off uint64[n + 1], ops uint32),
+        one-shot: the CIGAR of every pair inside its band around diag (include/agx.h, "CIGARs for batches banded around a diagonal")."""
+        hits, op_off = np.empty(b.n_pairs, SwHit), np.zeros(b.n_pairs + 1, np.uint64)
+        cap = int(b.len.sum())  # an alignment has at most one operation per symbol
+        ops = np.empty(max(cap, 1), np.uint32)
+        sc = C.byref(SwScoring(*scoring)) if scoring is not None else None
+        d = _diag(diag, b.n_pairs)
+        _check(lib().agx_sw_align_band_diag_cigar(self._h, sc, mode, band, _ptr(d), _ptr(b.bases), _ptr(b.off), _ptr(b.len), b.n_pairs,
+                                                  _ptr(hits), _ptr(op_off), _ptr(ops), cap))
+        return hits, op_off, ops[:int(op_off[b.n_pairs])].copy()
+
     def sw_align_band(self, b, mode, band, scoring=None) -> np.ndarray:
         """b: synth.SWBatch -> SwHit records of the BANDED alignment (include/agx.h, "Banded alignment"), one-shot.
         mode: SW_MODE_GLOBAL or SW_MODE_EXTEND; band: the half-width w >= 0; sequences up to SW_BAND_MAX_LEN on both sides."""
@@ -425,15 +450,21 @@ class SwBatch:
         band=w: a BANDED batch of mode SW_MODE_GLOBAL or SW_MODE_EXTEND (half-width w; it answers hits() as a SPANS batch does;
         no matrix or stats; with cigar=True a banded cigar batch, which also answers cigars());
         band=w with diag=one int or one per pair: a batch BANDED AROUND A DIAGONAL, any mode, align = SW_ALIGN_ENDS or
-        SW_ALIGN_SPANS (0: SPANS); no matrix, stats or cigar."""
+        SW_ALIGN_SPANS (0: SPANS); no matrix or stats; with cigar=True (SPANS only) it also answers cigars()."""
         self.ctx = ctx
         self.n_pairs = b.n_pairs
         self._h = C.c_void_p()
         if diag is not None:
-            if band is None or matrix is not None or stats or cigar:
-                raise AgxError(E_ARG, "a batch banded around a diagonal takes band=w under match/mismatch scoring: no matrix, stats or cigar")
+            if band is None or matrix is not None or stats:
+                raise AgxError(E_ARG, "a batch banded around a diagonal takes band=w under match/mismatch scoring: no matrix or stats")
             sc = C.byref(SwScoring(*scoring)) if scoring is not None else None
             d = _diag(diag, b.n_pairs)
+            if cigar:
+                if align not in (0, SW_ALIGN_SPANS):
+                    raise AgxError(E_ARG, "a cigar batch is a SW_ALIGN_SPANS batch")
+                _check(lib().agx_sw_batch_create_align_band_diag_cigar(ctx._h if ctx else None, sc, mode, band, _ptr(d), _ptr(b.bases), _ptr(b.off),
+                                                                       _ptr(b.len), b.n_pairs, C.byref(self._h)))
+                return
             _check(lib().agx_sw_batch_create_align_band_diag(ctx._h if ctx else None, sc, mode, align or SW_ALIGN_SPANS, band, _ptr(d), _ptr(b.bases),
                                                              _ptr(b.off), _ptr(b.len), b.n_pairs, C.byref(self._h)))
             return

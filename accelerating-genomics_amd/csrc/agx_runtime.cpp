@@ -620,9 +620,9 @@ extern "C" {
 const char *agx_version(void)
 {
 #ifdef AGX_TUNING
-    return "agx 0.3.7 (gfx950, tuning build)";
+    return "agx 0.3.8 (gfx950, tuning build)";
 #else
-    return "agx 0.3.7 (gfx950)";
+    return "agx 0.3.8 (gfx950)";
 #endif
 }
 const char *agx_last_error(void) { return g_err; }

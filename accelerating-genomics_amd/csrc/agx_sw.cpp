@@ -252,6 +252,8 @@ struct agx_sw_batch {
     // agx_sw_batch_create_align_band_diag: banded with band_at set; align = ENDS or SPANS, any mode.  Per pair
     // the centre diagonal and the first row the fill was given (kNoBandRow: no fill -- an empty side, or a LOCAL band that
     // misses the matrix); the fill's rows are counted from there.  SPANS in LOCAL and FIT keep seq / seq_off for the begin pass
+    // agx_sw_batch_create_align_band_diag_cigar: band_at with cigar == 1 and align = SPANS; it keeps band_groups,
+    // band_rec, band_cls, band_G and seq like a banded cigar batch, in every mode
     bool band_at = false;
     std::vector<int32_t> band_diag;
     std::vector<uint32_t> band_row0;
@@ -1658,7 +1660,8 @@ inline const char *band_at_condition(int mode, int64_t la, int64_t lb, int64_t d
 int create_band(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t band, const uint8_t *bases, const uint64_t *off,
                 const uint32_t *len, int64_t n_pairs, agx_sw_batch **out, bool cigar = false, const BandAt *at = nullptr)
 {
-    const char *who = at ? "agx_sw_batch_create_align_band_diag" : cigar ? "agx_sw_batch_create_align_band_cigar" : "agx_sw_batch_create_align_band";
+    const char *who = at ? (cigar ? "agx_sw_batch_create_align_band_diag_cigar" : "agx_sw_batch_create_align_band_diag")
+                         : (cigar ? "agx_sw_batch_create_align_band_cigar" : "agx_sw_batch_create_align_band");
     if (!out) {
         agx_set_error("%s: out is NULL", who);
         return AGX_E_ARG;
@@ -1875,6 +1878,7 @@ int create_band(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t b
     }
     if (cigar) {
         agx_sw_band_trace_preload();
+        if (at) agx_sw_band_trace_at_preload();
         agx_sw_walk_preload();
         b->band_groups = groups;
         b->band_rec.assign((size_t)n_pairs, kNoBandRec);
@@ -3088,9 +3092,34 @@ int64_t band_cells(int64_t ca, int64_t cb, int64_t dlo, int64_t dhi)
     return cells;
 }
 
+// Where the traced fill of a span starts inside a banded batch's resident image (include/agx.h, agx_sw_band_span_record; the
+// head of agx_sw_band_diag_trace_kernel.hip has the argument).  false: the span does not lie in the image or in the band.
+bool band_span_record(uint32_t la, uint32_t rows, uint32_t row0, uint32_t fpad, int64_t dlo, int64_t dhi, int lanes, const agx_sw_hit &h,
+                      agx_sw_band_span &o)
+{
+    if (lanes < 1 || lanes > 64 || dhi < dlo) return false;
+    if (h.a_begin < 0 || h.b_begin < 0 || h.a_end < h.a_begin || h.b_end < h.b_begin) return false;
+    if ((uint32_t)h.a_end >= la || (uint32_t)h.b_begin < row0 || (uint64_t)h.b_end >= (uint64_t)row0 + rows) return false;
+    const int64_t s = (int64_t)h.b_begin - row0, shift = s - h.a_begin;
+    const int64_t ca = (int64_t)h.a_end - h.a_begin + 1, cb = (int64_t)h.b_end - h.b_begin + 1;
+    const int64_t lo = dlo + shift, hi = dhi + shift;
+    if (lo > 0 || hi < 0 || ca - cb < lo || ca - cb > hi) return false; // the begin and the end cell
+    o.ca = (uint32_t)ca;
+    o.cb = (uint32_t)cb;
+    o.x_bytes = fpad + (uint32_t)h.a_begin;
+    o.phase = (uint32_t)(s & 3);
+    o.y_dwords = (uint32_t)((s - o.phase) / 4);
+    o.dlo = (int32_t)lo;
+    o.dhi = (int32_t)hi;
+    o.steps = (uint32_t)cb + (uint32_t)lanes + o.phase;
+    return true;
+}
+
 // agx_sw_batch_cigars on a banded cigar batch: hits, then per chunk of spans one traced banded fill (corner capture, whatever the
 // mode: the span's global alignment inside the pair's band), the band-aware walk and the gather.  The fills read the batch's
-// resident image through copies of its group records that carry the span's lengths, in the tiling the batch planned.
+// resident image through copies of its group records that carry the span's lengths, in the tiling the batch planned.  A batch
+// around a diagonal (band_at) has spans that begin anywhere: its records are those of band_span_record, its fill and walk the
+// builds that start inside the image (agx_sw_band_diag_trace_kernel.hip); every span of the other batches begins at (0, 0).
 int band_cigars_impl(agx_sw_batch *b)
 {
     const int64_t n = b->n_pairs;
@@ -3107,13 +3136,21 @@ int band_cigars_impl(agx_sw_batch *b)
     agx_ctx *ctx = b->ctx;
     const agx_sw_hit *hits = b->cig_hits.data();
     const agx_sw_scoring s = b->scoring;
-    auto span = [&](int64_t p, int64_t &ca, int64_t &cb) { // begins are 0
+    const bool at = b->band_at;
+    auto span = [&](int64_t p, int64_t &ca, int64_t &cb) { // (begins are 0 unless the batch is banded around a diagonal)
         const agx_sw_hit &h = hits[p];
         ca = h.a_begin >= 0 && h.a_end >= h.a_begin ? (int64_t)h.a_end - h.a_begin + 1 : 0;
         cb = h.b_begin >= 0 && h.b_end >= h.b_begin ? (int64_t)h.b_end - h.b_begin + 1 : 0;
     };
-    auto limits = [&](int64_t p, int64_t &dlo, int64_t &dhi) { // the band the score was computed in
-        band_limits(b->mode, b->band, b->seq_len[(size_t)(2 * p)], b->seq_len[(size_t)(2 * p + 1)], dlo, dhi);
+    auto limits = [&](int64_t p, int64_t &dlo, int64_t &dhi) { // the band the score was computed in, counted from the begin cell
+        if (!at) {
+            band_limits(b->mode, b->band, b->seq_len[(size_t)(2 * p)], b->seq_len[(size_t)(2 * p + 1)], dlo, dhi);
+            return;
+        }
+        const agx_sw_hit &h = hits[p];
+        const int64_t delta = h.a_begin >= 0 && h.b_begin >= 0 ? (int64_t)h.a_begin - h.b_begin : b->band_diag[(size_t)p]; // (no begin cell: no path)
+        dlo = (int64_t)b->band_diag[(size_t)p] - b->band - delta;
+        dhi = (int64_t)b->band_diag[(size_t)p] + b->band - delta;
     };
     std::vector<uint32_t> count((size_t)n, 0), lone((size_t)n, 0);
     std::vector<int64_t> traced;
@@ -3220,6 +3257,24 @@ int band_cigars_impl(agx_sw_batch *b)
                 int64_t ca, cb;
                 span(p, ca, cb);
                 SwBandGroup g = b->band_groups[e.rec]; // image offsets, band and fpad as planned; the span's lengths
+                uint32_t phase = 0;
+                if (at) { // the span begins inside the image
+                    agx_sw_band_span sp;
+                    if (!band_span_record(g.la_lb & 0xffffu, g.la_lb >> 16, g.reserved, g.fpad, g.dlo, g.dhi, G, hits[p], sp) || sp.ca != (uint32_t)ca ||
+                        sp.cb != (uint32_t)cb) {
+                        agx_set_error("agx_sw_batch_cigars: pair %lld (mode %d, diag %d, band %d): its span a %d..%d, b %d..%d does not lie in the rows "
+                                      "%u.. of its image or its begin or end cell is outside the band",
+                                      (long long)p, b->mode, b->band_diag[(size_t)p], b->band, hits[p].a_begin, hits[p].a_end, hits[p].b_begin,
+                                      hits[p].b_end, g.reserved);
+                        return AGX_E_INTERNAL;
+                    }
+                    g.y_dw += sp.y_dwords;
+                    g.fpad = sp.x_bytes;
+                    g.dlo = sp.dlo;
+                    g.dhi = sp.dhi;
+                    g.reserved = phase = sp.phase;
+                    waves.back().steps = std::max(waves.back().steps, sp.steps);
+                }
                 g.la_lb = (uint32_t)ca | (uint32_t)cb << 16;
                 g.out = e.k;
                 groups[k] = g;
@@ -3233,7 +3288,7 @@ int band_cigars_impl(agx_sw_batch *b)
                 r.cb = (uint32_t)cb;
                 r.G = (uint16_t)G;
                 r.C = (uint16_t)K;
-                r.reserved = 0;
+                r.reserved = phase;
                 int ks = 0;
                 while ((1 << ks) < K) ++ks;
                 bwalk[e.k] = SwBandWalkRec{g.dlo, g.dhi, g.fpad, (uint32_t)ks};
@@ -3278,15 +3333,16 @@ int band_cigars_impl(agx_sw_batch *b)
         AGX_HIP(hipMemcpyAsync(d.bwalk.p, bwalk.data(), (size_t)m * sizeof(SwBandWalkRec), hipMemcpyHostToDevice, st));
         if (timed) AGX_HIP(hipEventRecord(ev.e[0], st));
         for (auto it = launches.rbegin(); it != launches.rend(); ++it) // widest class first, one after the other on the stream
-            if (agx_sw_band_trace_launch_class(it->C, b->prm, (const uint32_t *)b->img.p, (const SwBandGroup *)d.groups.p,
-                                               (const SwWave *)d.waves.p + it->first_wave, it->n_waves, (int32_t *)d.scores.p, (uint32_t *)d.trace.p,
-                                               (const uint64_t *)d.goff.p, st)) {
-                agx_set_error("sw_fill_band_trace<%d> launch failed: %s", it->C, hipGetErrorString(hipGetLastError()));
+            if ((at ? agx_sw_band_trace_at_launch_class : agx_sw_band_trace_launch_class)(
+                    it->C, b->prm, (const uint32_t *)b->img.p, (const SwBandGroup *)d.groups.p, (const SwWave *)d.waves.p + it->first_wave, it->n_waves,
+                    (int32_t *)d.scores.p, (uint32_t *)d.trace.p, (const uint64_t *)d.goff.p, st)) {
+                agx_set_error("sw_fill_band_trace%s<%d> launch failed: %s", at ? "_at" : "", it->C, hipGetErrorString(hipGetLastError()));
                 return AGX_E_HIP;
             }
         if (timed) AGX_HIP(hipEventRecord(ev.e[1], st));
-        if (agx_sw_band_walk_launch((const SwWalkRec *)d.walk.p, (const SwBandWalkRec *)d.bwalk.p, (uint32_t)m, (const uint32_t *)b->img.p,
-                                    (const uint32_t *)d.trace.p, (uint32_t *)d.slots.p, (uint32_t *)d.runs.p, st)) {
+        if ((at ? agx_sw_band_walk_at_launch : agx_sw_band_walk_launch)((const SwWalkRec *)d.walk.p, (const SwBandWalkRec *)d.bwalk.p, (uint32_t)m,
+                                                                        (const uint32_t *)b->img.p, (const uint32_t *)d.trace.p, (uint32_t *)d.slots.p,
+                                                                        (uint32_t *)d.runs.p, st)) {
             agx_set_error("agx_sw_batch_cigars: walk kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
             return AGX_E_HIP;
         }
@@ -3301,9 +3357,9 @@ int band_cigars_impl(agx_sw_batch *b)
             const int64_t p = traced[first + (size_t)k];
             const SwWalkRec &r = walk[(size_t)k];
             if (tsc[k] != hits[p].score || runs[k] == 0 || runs[k] > (uint64_t)r.ca + r.cb) { // (kSwWalkFailed: the walk left the band)
-                agx_set_error("agx_sw_batch_cigars: pair %lld (mode %d, band %d): the traced fill of its span a 0..%d, b 0..%d gives score %d in %u runs%s, "
+                agx_set_error("agx_sw_batch_cigars: pair %lld (mode %d, band %d): the traced fill of its span a %d..%d, b %d..%d gives score %d in %u runs%s, "
                               "the hit %d",
-                              (long long)p, b->mode, b->band, hits[p].a_end, hits[p].b_end, tsc[k], runs[k],
+                              (long long)p, b->mode, b->band, hits[p].a_begin, hits[p].a_end, hits[p].b_begin, hits[p].b_end, tsc[k], runs[k],
                               runs[k] == kSwWalkFailed ? " (the walk left the band)" : "", hits[p].score);
                 return AGX_E_INTERNAL;
             }
@@ -3350,17 +3406,18 @@ int band_cigars_impl(agx_sw_batch *b)
             const uint32_t c = count[(size_t)p];
             if (ca && cb) memcpy(out, chunk_ops[chunk_of[(size_t)p]].data() + where[(size_t)p], (size_t)c * sizeof(uint32_t));
             else if (c) out[0] = lone[(size_t)p];
-            const uint8_t *x = ca ? b->seq.data() + b->seq_off[(size_t)(2 * p)] : nullptr;
-            const uint8_t *y = cb ? b->seq.data() + b->seq_off[(size_t)(2 * p + 1)] : nullptr;
-            if ((!cigar_checks(out, c, x, ca, y, cb, s, nullptr, hits[p].score) || !cigar_in_band(out, c, dlo, dhi)) && bad[(size_t)tid] < 0)
+            const uint8_t *x = ca ? b->seq.data() + b->seq_off[(size_t)(2 * p)] + hits[p].a_begin : nullptr;
+            const uint8_t *y = cb ? b->seq.data() + b->seq_off[(size_t)(2 * p + 1)] + hits[p].b_begin : nullptr;
+            if ((!cigar_checks(out, c, x, ca, y, cb, s, nullptr, hits[p].score) || (c && !cigar_in_band(out, c, dlo, dhi))) && bad[(size_t)tid] < 0)
                 bad[(size_t)tid] = p;
         }
     });
     for (int64_t p : bad)
         if (p >= 0) {
-            agx_set_error("agx_sw_batch_cigars: pair %lld (mode %d, band %d): its %u operations do not consume the span a 0..%d, b 0..%d, disagree with "
-                          "the symbols, leave the band or do not rescore to %d",
-                          (long long)p, b->mode, b->band, count[(size_t)p], hits[p].a_end, hits[p].b_end, hits[p].score);
+            agx_set_error("agx_sw_batch_cigars: pair %lld (mode %d, band %d): its %u operations do not consume the span a %d..%d, b %d..%d, disagree "
+                          "with the symbols, leave the band or do not rescore to %d",
+                          (long long)p, b->mode, b->band, count[(size_t)p], hits[p].a_begin, hits[p].a_end, hits[p].b_begin, hits[p].b_end,
+                          hits[p].score);
             return AGX_E_INTERNAL;
         }
     b->cig_valid = true;
@@ -3374,6 +3431,42 @@ uint64_t agx_sw_band_cigar_bytes_bound(int32_t width, uint32_t ca, uint32_t cb)
 {
     if (width < 1 || width > AGX_SW_BAND_MAX_WIDTH) return 0;
     return band_trace_bytes_bound((uint32_t)width, ca, cb);
+}
+
+int agx_sw_band_span_record(uint32_t la, uint32_t rows, uint32_t row0, uint32_t fpad, int32_t dlo, int32_t dhi, int32_t lanes,
+                            const agx_sw_hit *hit, agx_sw_band_span *out)
+{
+    agx_sw_band_span sp;
+    if (!hit || !out || !band_span_record(la, rows, row0, fpad, dlo, dhi, lanes, *hit, sp)) {
+        agx_set_error("agx_sw_band_span_record: null argument, an empty side, a span outside the image, lanes outside 1..64 or a begin or end cell "
+                      "outside the band");
+        return AGX_E_ARG;
+    }
+    *out = sp;
+    return AGX_OK;
+}
+
+int agx_sw_batch_create_align_band_diag_cigar(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t band, const int32_t *diag,
+                                              const uint8_t *bases, const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_batch **out)
+{
+    AGX_GUARD_BEGIN
+    const BandAt at{AGX_SW_ALIGN_SPANS, diag};
+    return create_band(ctx, scoring, mode, band, bases, off, len, n_pairs, out, true, &at);
+    AGX_GUARD_END("agx_sw_batch_create_align_band_diag_cigar")
+}
+
+int agx_sw_align_band_diag_cigar(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t band, const int32_t *diag, const uint8_t *bases,
+                                 const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_hit *hits, uint64_t *op_off, uint32_t *ops,
+                                 uint64_t ops_cap)
+{
+    agx_sw_batch *b = nullptr;
+    int rc = agx_sw_batch_create_align_band_diag_cigar(ctx, scoring, mode, band, diag, bases, off, len, n_pairs, &b);
+    if (rc) return rc;
+    rc = agx_sw_batch_launch(b);
+    if (!rc) rc = agx_sw_batch_cigars(b, hits, op_off, ops, ops_cap);
+    if (rc && b->ctx) (void)hipStreamSynchronize(b->ctx->stream); // the blocks go back to the pools: nothing may still run on them
+    agx_sw_batch_destroy(b);
+    return rc;
 }
 
 int agx_sw_cigar_in_band(const uint32_t *ops, uint64_t n_ops, int32_t dlo, int32_t dhi)
@@ -3410,7 +3503,8 @@ int agx_sw_batch_cigars(agx_sw_batch *b, agx_sw_hit *hits, uint64_t *op_off, uin
         return AGX_E_ARG;
     }
     if (b->cigar != 1 || b->align != AGX_SW_ALIGN_SPANS) {
-        agx_set_error("agx_sw_batch_cigars: not a cigar batch (create it with agx_sw_batch_create_align_cigar or agx_sw_batch_create_align_band_cigar)");
+        agx_set_error("agx_sw_batch_cigars: not a cigar batch (create it with agx_sw_batch_create_align_cigar, agx_sw_batch_create_align_band_cigar or "
+                      "agx_sw_batch_create_align_band_diag_cigar)");
         return AGX_E_ARG;
     }
     if (!b->ctx) {

@@ -214,6 +214,7 @@ struct SwBandGroup {
     uint32_t out;     // the caller's pair number
     uint32_t fpad;    // (-(dlo + G K - G)) mod 4: the byte the group's last lane loads at step t is dword-aligned when t % 4 == 0
     uint32_t reserved; // host only (no kernel reads it): a band around a diagonal starts b at this row, dlo / dhi are shifted by it
+                       // (the span records of sw_fill_band_trace_at alone carry their start phase here)
 };
 #define AGX_SW_FOR_EACH_BAND_CLASS(X) X(4) X(8) X(16) X(32)
 static const int kSwBandClasses[] = {4, 8, 16, 32};
@@ -249,6 +250,14 @@ constexpr uint32_t kSwWalkFailed = 0xffffffffu;
 int agx_sw_band_walk_launch(const SwWalkRec *recs, const SwBandWalkRec *band, uint32_t n, const uint32_t *img, const uint32_t *trace,
                             uint32_t *slots, uint32_t *runs, hipStream_t s);
 void agx_sw_band_trace_preload();
+// the same for a span that begins inside the resident image (agx_sw_band_diag_trace_kernel.hip): the group record
+// is the span's (agx_sw_band_span_record: la_lb the span, dlo / dhi and fpad shifted, y_dw moved by whole dwords) with the start
+// phase 0 .. 3 in `reserved`, and the wave steps max(cb + phase) + G times; the walk's SwWalkRec.reserved holds the phase too
+int agx_sw_band_trace_at_launch_class(int diags_per_lane, const SwParams &prm, const uint32_t *img, const SwBandGroup *groups, const SwWave *waves,
+                                      uint32_t n_waves, int32_t *scores, uint32_t *trace, const uint64_t *goff, hipStream_t s);
+int agx_sw_band_walk_at_launch(const SwWalkRec *recs, const SwBandWalkRec *band, uint32_t n, const uint32_t *img, const uint32_t *trace,
+                               uint32_t *slots, uint32_t *runs, hipStream_t s);
+void agx_sw_band_trace_at_preload();
 
 // ---- device-side planning (agx_sw_plan_kernel.hip): the O(pairs) passes of the planner as kernels
 constexpr uint32_t kSwPlanEmptyKey = 1u << 27;           // sort key of a pair with an empty side: behind every bucket

@@ -80,6 +80,12 @@
 // file's head restates "No wrap" for them.  Nothing above assumes that the band is centred on the main diagonal: dlo and dhi come
 // from the group record, and the host may hand the fill a target that starts at a later row with the band shifted accordingly.
 //
+// PH (agx_sw_band_diag_trace_kernel.hip; include/agx.h, "CIGARs for batches banded around a diagonal"; DESIGN.md 4.1j): the traced
+// build for a span that begins INSIDE the resident image.  The group record's `reserved` holds a start phase r = 0 .. 3 and the
+// step counter runs as t' = t - r: rows, injection, capture and the trace are in terms of t', the two loaders in terms of t, so
+// that both still read whole dwords at t = 0 (mod 4).  That file's head has the argument and says what the bytes outside the span
+// do.  r = 0 is the plain traced build, step for step.
+//
 // (included by agx_sw_band_kernel.hip; opens an anonymous namespace that the including file closes after its launch helper)
 #include "agx_sw.h"
 
@@ -101,7 +107,7 @@ __device__ __forceinline__ int band_shl1(int old, int v)
 
 // AT: -1 for the builds above; else the mode of a build of agx_sw_band_diag_kernel.hip (LOCAL: EXT is set, it captures by the
 // ANY rule; FIT and EXTEND_QUERY capture column la).  Everything they add stands inside `if constexpr` blocks.
-template <int K, bool EXT, bool TRACE = false, int AT = -1>
+template <int K, bool EXT, bool TRACE = false, int AT = -1, bool PH = false>
 __device__ __forceinline__ void band_body(const SwParams &prm, const uint32_t *__restrict__ img, const SwBandGroup *__restrict__ groups,
                                           const SwWave w, int32_t *__restrict__ scores, uint32_t *__restrict__ pos,
                                           uint32_t *trace = nullptr, const uint64_t *goff = nullptr)
@@ -111,6 +117,7 @@ __device__ __forceinline__ void band_body(const SwParams &prm, const uint32_t *_
     static_assert(AT == -1 || (!TRACE && EXT == (AT == AGX_SW_MODE_LOCAL) &&
                                (AT == AGX_SW_MODE_LOCAL || AT == AGX_SW_MODE_FIT || AT == AGX_SW_MODE_EXTEND_QUERY)),
                   "GLOBAL and EXTEND around a diagonal run the plain builds: their boundaries and captures are the same");
+    static_assert(!PH || (TRACE && AT == -1), "the start phase belongs to the traced build");
     constexpr bool AT_LOCAL = AT == AGX_SW_MODE_LOCAL, AT_FIT = AT == AGX_SW_MODE_FIT, AT_COL = AT_FIT || AT == AGX_SW_MODE_EXTEND_QUERY;
     constexpr int XW = K / 4;
     const int ge = prm.ge, gf = prm.gf, s_match = prm.hd, s_mis = prm.hd - prm.delta; // the diagonal move on z: score - gf
@@ -129,6 +136,11 @@ __device__ __forceinline__ void band_body(const SwParams &prm, const uint32_t *_
     const int d0 = g.dlo + gl * K;
     const int kmax = min(K - 1, g.dhi - d0); // the last in-band slot of this lane (negative: none)
     const int k0 = -d0;                      // the slot of diagonal 0, if this lane owns it
+    [[maybe_unused]] int ph = 0, glp = gl; // PH: the start phase, and gl + r: this lane's row at step t is t - glp
+    if constexpr (PH) {
+        ph = (int)(g.reserved & 3u);
+        glp = gl + ph;
+    }
 
     // the query window at step 0: a[j0 - 1 + k], j0 = d0 - gl
     uint32_t xw[XW];
@@ -138,7 +150,7 @@ __device__ __forceinline__ void band_body(const SwParams &prm, const uint32_t *_
         for (int n = 0; n < XW; ++n) xw[n] = 0;
 #pragma unroll
         for (int k = 0; k < K; ++k) {
-            const int idx = d0 - gl - 1 + k;
+            const int idx = d0 - (PH ? glp : gl) - 1 + k; // (PH: the row at step 0 is -gl - r)
             const uint32_t by = (active && idx >= 0 && idx < la) ? ab[idx] : 0u;
             xw[k >> 2] |= by << (8 * (k & 3));
         }
@@ -146,11 +158,11 @@ __device__ __forceinline__ void band_body(const SwParams &prm, const uint32_t *_
     // the two loaders: b at the group's first lane, the query byte that enters the band at its last lane
     const bool feeder = active && first, loader = active && last;
     const uint32_t *yp = img + g.y_dw;
-    const int nyq = (lb + 4) >> 2; // one byte in front of b
+    const int nyq = (lb + (PH ? ph : 0) + 4) >> 2; // one byte in front of b (PH: and r more)
     auto row_quad = [&](int q) -> uint32_t { return (feeder && q < nyq) ? yp[q] : 0u; };
     const uint32_t *xp = img + g.x_dw;
     const int q0x = g.dlo + G * K - G;      // a[q0x + t] enters at step t
-    const int rel0 = ((int)g.fpad + q0x) / 4; // exact: the host chose fpad so
+    const int rel0 = ((int)g.fpad + q0x - (PH ? ph : 0)) / 4; // exact: the host chose fpad so
     const int nxd = ((int)g.fpad + la + 3) >> 2;
     auto col_quad = [&](int q) -> uint32_t { return (loader && (uint32_t)(rel0 + q) < (uint32_t)nxd) ? xp[rel0 + q] : 0u; };
 
@@ -169,6 +181,7 @@ __device__ __forceinline__ void band_body(const SwParams &prm, const uint32_t *_
     uint32_t *tp = nullptr;
     if constexpr (TRACE) {
         if (active) tp = trace + goff[w.first_group + grp] + (uint32_t)(gl * TW);
+        if constexpr (PH) tp -= ph * G * TW; // step t writes at t' = t - r; nothing is stored before t' = gl
     }
 
     uint32_t q0 = row_quad(0), q1 = row_quad(1), q2 = row_quad(2);
@@ -178,8 +191,9 @@ __device__ __forceinline__ void band_body(const SwParams &prm, const uint32_t *_
     int t = 0;
 
     auto step = [&]() __attribute__((always_inline)) {
-        const int i = t - gl;
-        const int fresh = (t >= 1 && t <= lb) ? (int)(rows & 0xffu) : kBandRowPad;
+        const int i = t - (PH ? glp : gl);
+        // (PH: 1 <= t' <= lb is 1 <= i <= lb in a group's first lane, and no other lane's `fresh` is read)
+        const int fresh = (PH ? (uint32_t)(i - 1) < (uint32_t)lb : (t >= 1 && t <= lb)) ? (int)(rows & 0xffu) : kBandRowPad;
         rows >>= 8;
         const uint32_t xin = xrows & 0xffu;
         xrows >>= 8;

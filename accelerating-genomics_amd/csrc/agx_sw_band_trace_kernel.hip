@@ -6,7 +6,8 @@
 // (cb, ca) in state H; cell (i, j) is nibble slot % K of lane slot / K at step i + lane, slot = j - i - dlo.  Before every load
 // it tests dlo <= j - i <= dhi, i <= cb and j <= ca, so slot < G K and step < cb + G: no word of the block, whatever it holds,
 // can lead a load out of the pair's own directions.  A path that leaves the band (or a boundary run outside it) stores
-// kSwWalkFailed in runs[pair].  Runs land right-aligned in the pair's slot of ca + cb words; sw_gather packs them.
+// kSwWalkFailed in runs[pair].  Runs land right-aligned in the pair's slot of ca + cb words; sw_gather packs them.  Its body
+// stands in agx_sw_band_walk.inc, which the walk of spans that begin inside the image shares.
 #include "agx_sw_band_kernel.inc"
 
 template <int K>
@@ -23,74 +24,8 @@ __global__ void __launch_bounds__(64) sw_walk_band(const SwWalkRec *__restrict__
                                                    const uint32_t *__restrict__ img, const uint32_t *__restrict__ trace,
                                                    uint32_t *__restrict__ slots, uint32_t *__restrict__ runs)
 {
-    const uint32_t p = blockIdx.x * 64u + threadIdx.x;
-    if (p >= n) return;
-    const SwWalkRec r = recs[p];
-    const SwBandWalkRec bw = band[p];
-    const uint32_t G = r.G, ks = bw.kshift, W = (uint32_t)sw_band_trace_words((int)r.C);
-    const uint32_t *tr = trace + r.goff;
-    const uint8_t *x = reinterpret_cast<const uint8_t *>(img + r.x_dw) + bw.fpad;  // x[j - 1]
-    const uint8_t *y = reinterpret_cast<const uint8_t *>(img + r.y_dw) + 1;        // y[i - 1]
-    uint32_t *out = slots + r.slot + ((uint64_t)r.ca + r.cb); // one past the slot's last word
-    uint32_t i = r.cb, j = r.ca, n_runs = 0, op = 0, len = 0;
-    int state = 0; // 0 H, 1 E, 2 F
-    bool failed = false;
-    auto emit = [&](uint32_t o, uint32_t k) {
-        if (o == op) len += k;
-        else {
-            if (len) {
-                *--out = len << 4 | op;
-                ++n_runs;
-            }
-            op = o;
-            len = k;
-        }
-    };
-    while (i || j) {
-        const int d = (int)j - (int)i;
-        if (d < bw.dlo || d > bw.dhi || i > r.cb || j > r.ca) {
-            failed = true;
-            break;
-        }
-        // Row 0 and column 0 are reached in state H (the fill's head comment); the test does not ask the state.  The run along
-        // the boundary stays in the band: it ends at diagonal 0.
-        if (i == 0) {
-            emit(1u, j);
-            break;
-        }
-        if (j == 0) {
-            emit(2u, i);
-            break;
-        }
-        const uint32_t slot = (uint32_t)(d - bw.dlo), lane = slot >> ks, k = slot - (lane << ks);
-        if (lane >= G) { // (G K >= dhi - dlo + 1 by the plan; a record that says otherwise must not steer a load)
-            failed = true;
-            break;
-        }
-        const uint32_t nib = tr[((uint64_t)(i + lane) * G + lane) * W + (k >> 3)] >> (4u * (k & 7u)) & 15u;
-        if (state == 0) {
-            const uint32_t src = nib & 3u;
-            if (src == 0u) {
-                emit(x[j - 1u] == y[i - 1u] ? 7u : 8u, 1u);
-                --i;
-                --j;
-            } else
-                state = (int)src;
-        } else if (state == 1) {
-            emit(2u, 1u);
-            state = nib & 4u ? 1 : 0;
-            --i;
-        } else {
-            emit(1u, 1u);
-            state = nib & 8u ? 2 : 0;
-            --j;
-        }
-    }
-    if (len) {
-        *--out = len << 4 | op;
-        ++n_runs;
-    }
-    runs[p] = failed ? kSwWalkFailed : n_runs;
+    constexpr bool AT = false;
+#include "agx_sw_band_walk.inc"
 }
 
 } // namespace

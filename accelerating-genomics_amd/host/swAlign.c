@@ -1,5 +1,5 @@
 /*
- * swAlign <file_path> [local|global|fit|extend|extend-query][+stats|+cigar|+band=W|+cigar+band=W]: where the best alignment of every pair ends and begins
+ * swAlign <file_path> [local|global|fit|extend|extend-query][+stats|+cigar|+band=W|+cigar+band=W|+band=W@D|+bandcigar=W@D]: where the best alignment of every pair ends and begins
  * (default: local; the other modes are include/agx.h's "Alignment modes").
  * swAlign <file_path> <mode> <matrix_file> [gap_open gap_extend]: the same under a substitution matrix (gaps default to
  * -11 -1).  The matrix file is the usual text layout: '#' comment lines, one line of symbols, then one row per symbol
@@ -32,6 +32,10 @@
  * alignment around a diagonal"); the lines of "+band=W", read with its line buffer.  Not together with +stats, +cigar or a
  * matrix file: "global+cigar+band=8@0" is a usage error.  Without "@D" nothing changes: "global+band=64" is the banded
  * alignment of "Banded alignment", "fit+band=3" a usage error.
+ * Or the suffix "+bandcigar=W@D" on any mode (fit+bandcigar=64@-1500, local+bandcigar=200@0): the alignment inside the band
+ * around the diagonal D AND its CIGAR inside that band (include/agx.h, "CIGARs for batches banded around a diagonal"): the lines
+ * of "+band=W@D" with the CIGAR text appended as "+cigar" formats it, read with the line buffer of "+band=W".  W and D as in
+ * "+band=W@D", both required; no matrix file.
  *   AGX_CLI_CHUNK_PAIRS   pairs per agx_sw_align call (default 262144)
  */
 #include <stdio.h>
@@ -143,9 +147,10 @@ int main(int argc, char *argv[])
                 band = (int32_t)v;
             }
         }
-        if (!strncmp(argv[2], words[k], n) && !strncmp(argv[2] + n, "+band=", 6) && argc == 3) {
+        const int band_cigar = !strncmp(argv[2], words[k], n) && !strncmp(argv[2] + n, "+bandcigar=", 11); /* W@D only */
+        if (!strncmp(argv[2], words[k], n) && (band_cigar || !strncmp(argv[2] + n, "+band=", 6)) && argc == 3) {
             /* W@D: digits, '@', an optional '-' and digits, up to the end of the word; any mode, no matrix file */
-            const char *w = argv[2] + n + 6;
+            const char *w = argv[2] + n + (band_cigar ? 11 : 6);
             char *end, *end2;
             const long v = strtol(w, &end, 10);
             if (isdigit((unsigned char)*w) && *end == '@' && v <= 0x7fffffffL) {
@@ -154,6 +159,7 @@ int main(int argc, char *argv[])
                 if (isdigit((unsigned char)d[*d == '-']) && !*end2 && c >= -0x7fffffffL && c <= 0x7fffffffL) {
                     mode = k;
                     with_band = with_diag = 1;
+                    with_cigar = band_cigar;
                     band = (int32_t)v;
                     diag = (int32_t)c;
                 }
@@ -180,7 +186,8 @@ int main(int argc, char *argv[])
                 "not with another mode, +stats or a matrix file.\n"
                 "global+cigar+band=W, extend+cigar+band=W: the banded alignment with its CIGAR inside the band (in this order).\n"
                 "<mode>+band=W@D (fit+band=64@0, local+band=200@-1500): the alignment inside the band D-W <= j-i <= D+W around the\n"
-                "diagonal D, in any mode; not with +stats, +cigar or a matrix file.\n",
+                "diagonal D, in any mode; not with +stats, +cigar or a matrix file.\n"
+                "<mode>+bandcigar=W@D (fit+bandcigar=64@-1500): the same with its CIGAR inside that band appended; no matrix file.\n",
                 argv[0], argv[0]);
         return 1;
     }
@@ -246,6 +253,18 @@ int main(int argc, char *argv[])
                     fprintf(stderr, "swAlign: %s\n", agx_last_error());
                     status = EXIT_FAILURE;
                 }
+            } else if (!status && with_cigar && with_diag) {
+                int32_t *dg = (int32_t *)malloc(sizeof(int32_t) * (size_t)t->n_pairs);
+                for (int64_t p = 0; dg && p < t->n_pairs; p++) dg[p] = diag;
+                if (!dg) {
+                    fprintf(stderr, "swAlign: out of memory\n");
+                    status = EXIT_FAILURE;
+                } else if (agx_sw_align_band_diag_cigar(ctx, NULL, mode, band, dg, t->bases, t->off, t->len, t->n_pairs, hits, op_off, ops, ops_cap) !=
+                           AGX_OK) {
+                    fprintf(stderr, "swAlign: %s\n", agx_last_error());
+                    status = EXIT_FAILURE;
+                }
+                free(dg);
             } else if (!status && with_cigar && with_band) {
                 if (agx_sw_align_band_cigar(ctx, NULL, mode, band, t->bases, t->off, t->len, t->n_pairs, hits, op_off, ops, ops_cap) != AGX_OK) {
                     fprintf(stderr, "swAlign: %s\n", agx_last_error());

@@ -502,8 +502,8 @@ int agx_sw_cigar_in_band(const uint32_t *ops, uint64_t n_ops, int32_t dlo, int32
  * agx_sw_batch_hits the hits in the caller's pair order, agx_sw_batch_bind_scores is accepted and ignored, agx_sw_batch_info
  * works; agx_sw_batch_stats and agx_sw_batch_cigars return AGX_E_ARG.  ctx may be NULL: plan only.  scoring and byte 0x00 as in
  * "Banded alignment".  Unchanged: agx_sw_batch_create_align_band still refuses LOCAL, FIT and EXTEND_QUERY with AGX_E_ARG.
- * Deliberately left out: CIGARs for these batches (the next step: the traced fill is already a global fill of a span, it needs
- * only the per-pair band), substitution matrices, statistics, and a z-drop.
+ * CIGARs come from "CIGARs for batches banded around a diagonal" below.  Deliberately left out: substitution matrices,
+ * statistics, and a z-drop.
  */
 int agx_sw_batch_create_align_band_diag(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int what, int32_t band,
                                         const int32_t *diag /* n_pairs, or NULL = 0 for every pair */, const uint8_t *bases,
@@ -511,6 +511,57 @@ int agx_sw_batch_create_align_band_diag(agx_ctx *ctx, const agx_sw_scoring *scor
 /* One-shot: create_align_band_diag + launch + hits + destroy. */
 int agx_sw_align_band_diag(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int what, int32_t band, const int32_t *diag,
                            const uint8_t *bases, const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_hit *hits);
+
+/*
+ * CIGARs for batches banded around a diagonal: the alignment itself for a read placed in its window.  The batch is a batch of
+ * "Banded alignment around a diagonal" with what = AGX_SW_ALIGN_SPANS -- any of the five modes, the same band c - w .. c + w per
+ * pair, the same conditions on what the band must hold, limits, trimmed rows, hits and errors -- that also answers
+ * agx_sw_batch_cigars and agx_sw_batch_cigar_info.
+ * Per pair: hits[p] is exactly what the band-diag SPANS batch of the same mode, band, diag and scoring reports.  The CIGAR consumes
+ * a[a_begin..a_end] and b[b_begin..b_end].  Its path, run from the begin cell (b_begin, a_begin), stays within
+ * dlo <= j - i <= dhi of the FULL matrix (dlo = c - w, dhi = c + w); seen from the span, whose cell (i', j') is
+ * (b_begin + i', a_begin + j'), that is the band dlo - delta .. dhi - delta with delta = a_begin - b_begin, the same width.  It
+ * rescores to `score`.  Among such paths it is the one the tie rule of "CIGARs for banded batches" picks, applied to the global
+ * alignment of the span inside that band: in state H prefer the diagonal, then E (D), then F (I); a gap extends only on a strict
+ * improvement.  Cells outside the band do not exist.
+ * Lone cases: a span with one empty side gives a lone run, ca I or cb D (ca = a_end - a_begin + 1, cb = b_end - b_begin + 1) --
+ * FIT's b_begin = b_end + 1 (all of a in one gap along row b_end + 1) included -- and that run is checked against the band like
+ * any other path.  A pair with no aligned symbol (a LOCAL pair of score 0, or one whose band misses the matrix; an empty pair)
+ * has no operations; its text form is "*".
+ * Equivalences: a band that holds the whole matrix returns exactly what agx_sw_align_cigar returns for the same mode and
+ * scoring; EXTEND with diag == NULL what agx_sw_align_band_cigar(AGX_SW_MODE_EXTEND) returns for the same band; GLOBAL with
+ * c = 0 on pairs with la == lb what agx_sw_align_band_cigar(AGX_SW_MODE_GLOBAL) returns.
+ * agx_sw_batch_cigars uploads no sequence byte: the traced fill of a span starts inside the batch's resident image, wherever
+ * the span begins.  Operations, BAM codes, run merging, the sizing call, ops_cap, keeping the answer until the
+ * next launch, chunking under AGX_OPT_SW_TRACE_BYTES (agx_sw_band_cigar_bytes_bound(2w + 1, ca, cb) per traced pair, a pair
+ * beyond the budget alone in its chunk), agx_sw_cigar_info and the host's check of every CIGAR before it leaves (AGX_E_INTERNAL
+ * naming the pair) are as in "CIGARs for banded batches".  ctx may be NULL: plan only.
+ * Unchanged: a plain band-diag batch keeps answering agx_sw_batch_cigars with AGX_E_ARG; agx_sw_batch_stats on this batch gives
+ * AGX_E_ARG.  Deliberately left out: substitution matrices, statistics, and a z-drop.
+ */
+int agx_sw_batch_create_align_band_diag_cigar(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t band,
+                                              const int32_t *diag /* n_pairs, or NULL = 0 for every pair */, const uint8_t *bases,
+                                              const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_batch **out);
+/* One-shot: create_align_band_diag_cigar + launch + cigars + destroy.  ops_cap >= sum(len) always suffices. */
+int agx_sw_align_band_diag_cigar(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t band, const int32_t *diag,
+                                 const uint8_t *bases, const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_hit *hits,
+                                 uint64_t *op_off, uint32_t *ops, uint64_t ops_cap);
+/* Host only, no device.  How the traced fill of a span starts inside a banded batch's resident image.  The image holds the
+ * query a behind `fpad` bytes and the rows b[row0 .. row0 + rows) behind one byte, packed for a fill from row0 in the band
+ * dlo .. dhi COUNTED FROM row0 (j - (i - row0)) on `lanes` lanes per pair.  For a hit with a non-empty span on both sides the
+ * record says where the fill of that span reads: */
+typedef struct agx_sw_band_span {
+    uint32_t ca, cb;   /* the span: columns (query symbols), rows (target symbols) */
+    uint32_t x_bytes;  /* bytes in front of a[a_begin] behind the image's query: fpad + a_begin */
+    uint32_t y_dwords; /* whole dwords the target's offset moves on by: (s - phase) / 4, s = b_begin - row0 */
+    uint32_t phase;    /* s mod 4: the fill runs its step counter as t - phase, and b[b_begin] is byte 1 + phase behind the moved offset */
+    int32_t dlo, dhi;  /* the band in span coordinates: both limits moved by s - a_begin, the width unchanged */
+    uint32_t steps;    /* cb + lanes + phase */
+} agx_sw_band_span;
+/* AGX_E_ARG (nothing written) if a side of the span is empty, the span does not lie in the image (a_end >= la, b_begin < row0,
+ * b_end >= row0 + rows), lanes is outside 1..64, or its begin or end cell is outside the band. */
+int agx_sw_band_span_record(uint32_t la, uint32_t rows, uint32_t row0, uint32_t fpad, int32_t dlo, int32_t dhi, int32_t lanes,
+                            const agx_sw_hit *hit, agx_sw_band_span *out);
 
 /* One-shot: create + launch + scores + destroy. */
 int agx_sw_score(agx_ctx *ctx, const uint8_t *bases, const uint64_t *off, const uint32_t *len, int64_t n_pairs,
