@@ -10,16 +10,20 @@
 // while the caller's `bases` and `off` arrays travel to the device as they are; a device kernel
 // (agx_sw_pack_kernel.hip) then builds the padded image and checks the symbols.  No byte of a sequence
 // is touched by the host.
-#include "agx_sw.h"
+//
+// This file: the tiling tables, the create of a score-only batch (which every other kind of batch is built on), launch, scores
+// and the one-shot and multi-device calls.  Align batches are in agx_sw_align.cpp, banded ones in agx_sw_band.cpp, CIGARs in
+// agx_sw_cigar.cpp; agx_sw_batch.h holds the batch object they share.
+#include "agx_sw_batch.h"
 
-#include <algorithm>
 #include <cmath>
 #include <memory>
 #include <mutex>
 #include <thread>
 
-#include "agx_internal.h"
 #include "agx_parallel.h"
+
+using namespace agx_sw_host;
 
 namespace {
 
@@ -191,11 +195,6 @@ struct PairPlan {                    // 12 bytes: the sorts move these
     uint32_t lx() const { return lxo & 0x7fffu; }
 };
 
-struct ClassLaunch {
-    int C = 0;
-    uint32_t first_wave = 0, n_waves = 0;
-};
-
 // one (class, G) run of the sorted plan: entry j of the run is slot j % slots of its group j / slots,
 // a wave takes 64 / G groups
 struct Bucket {
@@ -207,89 +206,7 @@ struct Bucket {
 
 } // namespace
 
-struct agx_sw_batch {
-    agx_ctx *ctx = nullptr; // retained
-    int family = 0;         // 0 int32, 1 packed signed, 2 packed biased, 3 int32 on the packed plan's coded image, 4 locating int32, 5 anchored int32
-    // align batches (agx_sw_batch_create_align): 0 = a score-only batch, else AGX_SW_ALIGN_ENDS / _SPANS
-    int align = 0;
-    int mode = 0; // AGX_SW_MODE_*: anything but LOCAL runs the anchored fill (agx_sw_anch_kernel.hip)
-    // agx_sw_batch_create_align_stats: 0 = no statistics; 1 = a stats batch whose own fill is the plain one (LOCAL,
-    // FIT: the begin pass carries L); 2 = this batch's fill is the stats build and writes L = matches << 12 | pairs per pair
-    int stats = 0;
-    DevBuf lstat;       // stats == 2: L of every pair's captured cell
-    PinBuf lstat_stage; // its page-locked landing block
-    // agx_sw_batch_create_align_cigar: 0 = no CIGARs; 1 = a cigar batch (a SPANS batch that keeps its sequences
-    // and answers agx_sw_batch_cigars); 2 = the internal GLOBAL batch of one chunk of spans, whose fill is the traced build
-    int cigar = 0;
-    // cigar == 2: where every group's directions start (dwords), one walk record per pair, and the extents they add up to;
-    // the trace block itself is lent by cigars_impl for the time of one chunk
-    std::vector<uint64_t> tr_goff;
-    std::vector<SwWalkRec> tr_walk;
-    uint64_t tr_dwords = 0, tr_slot_words = 0;
-    DevBuf goff, walkrec;
-    uint32_t *trace_p = nullptr;
-    // cigar == 1: the answer of the last agx_sw_batch_cigars, kept until the next launch
-    bool cig_valid = false;
-    std::vector<agx_sw_hit> cig_hits;
-    std::vector<uint64_t> cig_off;
-    std::vector<uint32_t> cig_ops;
-    agx_sw_cigar_info cig_info{};
-    // modes other than LOCAL: pairs with an empty side whose score is not the zero the device array holds for them
-    std::vector<int64_t> fix_pair;
-    std::vector<int32_t> fix_score;
-    // agx_sw_batch_create_align_band: a banded batch -- align = SPANS, mode GLOBAL or EXTEND, its records are
-    // SwBandGroup, its image bytes, launches[].C the diagonals per lane; band_pos receives EXTEND's i << 16 | j per pair
-    bool banded = false;
-    int32_t band = 0;
-    DevBuf band_pos;
-    PinBuf band_pos_stage;
-    // agx_sw_batch_create_align_band_cigar: banded with cigar == 1.  The traced fills of agx_sw_batch_cigars read
-    // the resident image through copies of the group records with the span's lengths: the records in plan order, every pair's
-    // record (kNoBandRec: an empty side) and its tiling; seq / seq_off hold the symbols for the host's checks
-    std::vector<SwBandGroup> band_groups;
-    std::vector<uint32_t> band_rec;
-    std::vector<uint8_t> band_cls, band_G;
-    // agx_sw_batch_create_align_band_diag: banded with band_at set; align = ENDS or SPANS, any mode.  Per pair
-    // the centre diagonal and the first row the fill was given (kNoBandRow: no fill -- an empty side, or a LOCAL band that
-    // misses the matrix); the fill's rows are counted from there.  SPANS in LOCAL and FIT keep seq / seq_off for the begin pass
-    // agx_sw_batch_create_align_band_diag_cigar: band_at with cigar == 1 and align = SPANS; it keeps band_groups,
-    // band_rec, band_cls, band_G and seq like a banded cigar batch, in every mode
-    bool band_at = false;
-    std::vector<int32_t> band_diag;
-    std::vector<uint32_t> band_row0;
-    agx_sw_scoring scoring{};
-    DevBuf ends;        // per pair: row << kSwLocColBits | column of the end cell, written by the locating fill
-    PinBuf ends_stage;  // its page-locked landing block
-    // SPANS: the sequences, dense, for the begin pass (the caller's arrays need not outlive the create)
-    std::vector<uint8_t> seq;
-    std::vector<uint64_t> seq_off;
-    std::vector<uint32_t> seq_len;
-    SwParams prm{};
-    int64_t n_pairs = 0;
-    DevBuf img, groups, waves, scores;
-    DevBuf table; // substitution-matrix mode: kSwMatDim^2 int16 entries
-    int rising = 0; // biased packed fill: 1 = stored values rise by |ge| per step, 4 = and by |ge| per column in classes of four (agx_sw_pk2_kernel.hip, KC)
-    bool wide = false; // rising == 4: the column classes' period is C / 2 in the classes built that way (sw_pk2_period), not four
-    PinBuf out_stage; // page-locked landing block of the scores, taken at create: agx_sw_batch_scores allocates nothing
-                      // (a first hipHostMalloc costs milliseconds, and hipvers' timed window is launch -> scores)
-    bool matrix = false;
-    agx_sw_matrix mat{}; // ... and the caller's matrix itself: an align batch's begin pass creates its own batch from it
-    std::vector<ClassLaunch> launches;
-    agx_sw_info info{};
-    // A batch created without the closing wait (the pieces of agx_sw_score): its upload, planning and pack kernels may
-    // still be running; the temporaries they use, the event a launch has to wait for and the symbol check's verdict
-    // are held here until finish_create().
-    struct SwPending *pending = nullptr;
-    // agx_sw_batch_bind_scores: a page-locked array of the caller's that launches write their scores into themselves
-    // (only a batch planned in file order does: its waves then write consecutive bytes)
-    bool file_order = false;
-    int32_t *bound = nullptr;
-};
-
 namespace {
-int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matrix *matrix, const uint8_t *bases,
-                 const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_batch **out, bool defer = false, int align = 0, int mode = 0,
-                 int stats = 0, int cigar = 0);
 int finish_create(agx_sw_batch *b);
 void drop_pending(agx_sw_batch *b);
 }
@@ -532,6 +449,10 @@ int launch_device_plan(agx_ctx *ctx, DevPlan &dp, agx_sw_batch *b, uint32_t n_pa
     AGX_HIP(hipEventRecord(dp.done, ps));
     return AGX_OK;
 }
+
+} // namespace
+
+namespace agx_sw_host {
 
 int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matrix *matrix, const uint8_t *bases,
                  const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_batch **out, bool defer, int align, int mode, int stats,
@@ -1585,638 +1506,9 @@ int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matri
     return AGX_OK;
 }
 
-} // namespace
-
-// ------------------------------------------------------------------ banded batches (include/agx.h, "Banded alignment")
-namespace {
-
-agx_sw_hit empty_side_hit(int mode, int what, const agx_sw_scoring &sc, uint32_t la, uint32_t lb);
-
-// The band of a pair: GLOBAL widens it by the length difference, EXTEND keeps it around the main diagonal.
-inline void band_limits(int mode, int64_t w, int64_t la, int64_t lb, int64_t &dlo, int64_t &dhi)
-{
-    const int64_t diff = mode == AGX_SW_MODE_GLOBAL ? la - lb : 0;
-    dlo = std::min<int64_t>(0, diff) - w;
-    dhi = std::max<int64_t>(0, diff) + w;
-}
-
-// Lane tiling of a band of `width` diagonals over lb rows: K diagonals per lane, G = ceil(width / K) lanes per group, 64 / G
-// groups per wave.  A wave step costs about kBandStepCells cells' worth of instructions besides its K cells (the exchanges, the
-// cell mask, the window shift, the loop: counted in the K = 8 disassembly) and a group runs lb + G steps; the
-// class with the least lane time per pair wins, ties go to the wider one (fewer steps).
-constexpr int kBandStepCells = 5;
-inline void band_tiling(int width, uint32_t lb, int &cls, int &G)
-{
-    double best = 0;
-    cls = -1;
-    for (int c = kSwNumBandClasses - 1; c >= 0; --c) {
-        const int K = kSwBandClasses[c], g = (width + K - 1) / K;
-        if (g > 64) continue;
-        const double cost = ((double)lb + g) * (kBandStepCells + K) / (double)(64 / g);
-        if (cls < 0 || cost < best) {
-            best = cost;
-            cls = c;
-            G = g;
-        }
-    }
-}
-
-struct BandPlan { // one pair with work, as the sort moves it
-    uint32_t pair, la, lb;
-    int32_t dlo, dhi;
-    uint8_t cls, G;
-    uint32_t row0; // a band around a diagonal: the fill is given b[row0 .. row0 + lb) and the band shifted by row0; else 0
-};
-
-constexpr uint32_t kNoBandRec = 0xffffffffu;
-constexpr uint32_t kNoBandRow = 0xffffffffu;
-
-// agx_sw_batch_create_align_band_diag's part of create_band: what to report and the centre diagonal of every pair (NULL: 0)
-struct BandAt {
-    int what;
-    const int32_t *diag;
-};
-
-// What the band dlo .. dhi must hold in `mode` (include/agx.h, "Banded alignment around a diagonal"): nullptr if it does, else
-// the words of the error message.
-inline const char *band_at_condition(int mode, int64_t la, int64_t lb, int64_t dlo, int64_t dhi)
-{
-    const bool origin = dlo <= 0 && 0 <= dhi;
-    switch (mode) {
-    case AGX_SW_MODE_GLOBAL:
-        if (!origin) return "does not hold the origin (diagonal 0)";
-        return dlo <= la - lb && la - lb <= dhi ? nullptr : "does not hold the corner (diagonal la - lb)";
-    case AGX_SW_MODE_EXTEND: return origin ? nullptr : "does not hold the origin (diagonal 0)";
-    case AGX_SW_MODE_EXTEND_QUERY:
-        if (!origin) return "does not hold the origin (diagonal 0)";
-        return dhi >= la - lb ? nullptr : "holds no cell of column la (dhi < la - lb)";
-    case AGX_SW_MODE_FIT:
-        if (dlo > 0) return "holds no cell of column 0 (dlo > 0)";
-        return dhi >= la - lb ? nullptr : "holds no cell of column la (dhi < la - lb)";
-    default: return nullptr; // LOCAL: a band that misses the matrix scores 0
-    }
-}
-
-int create_band(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t band, const uint8_t *bases, const uint64_t *off,
-                const uint32_t *len, int64_t n_pairs, agx_sw_batch **out, bool cigar = false, const BandAt *at = nullptr)
-{
-    const char *who = at ? (cigar ? "agx_sw_batch_create_align_band_diag_cigar" : "agx_sw_batch_create_align_band_diag")
-                         : (cigar ? "agx_sw_batch_create_align_band_cigar" : "agx_sw_batch_create_align_band");
-    if (!out) {
-        agx_set_error("%s: out is NULL", who);
-        return AGX_E_ARG;
-    }
-    *out = nullptr;
-    if (mode < AGX_SW_MODE_LOCAL || mode > AGX_SW_MODE_EXTEND_QUERY) {
-        agx_set_error("%s: mode = %d is not one of AGX_SW_MODE_LOCAL .. AGX_SW_MODE_EXTEND_QUERY (0..4)", who, mode);
-        return AGX_E_ARG;
-    }
-    if (at && at->what != AGX_SW_ALIGN_ENDS && at->what != AGX_SW_ALIGN_SPANS) {
-        agx_set_error("%s: what = %d is neither AGX_SW_ALIGN_ENDS nor AGX_SW_ALIGN_SPANS", who, at->what);
-        return AGX_E_ARG;
-    }
-    if (!at && mode != AGX_SW_MODE_GLOBAL && mode != AGX_SW_MODE_EXTEND) {
-        agx_set_error("%s: mode = %d has a free start or a column capture; a band around the main diagonal serves AGX_SW_MODE_GLOBAL and "
-                      "AGX_SW_MODE_EXTEND only",
-                      who, mode);
-        return AGX_E_ARG;
-    }
-    if (band < 0) {
-        agx_set_error("%s: band = %d is negative", who, band);
-        return AGX_E_ARG;
-    }
-    if (at && 2 * (int64_t)band + 1 > AGX_SW_BAND_MAX_WIDTH) {
-        agx_set_error("%s: band = %d needs %lld diagonals, supported %d", who, band, 2 * (long long)band + 1, AGX_SW_BAND_MAX_WIDTH);
-        return AGX_E_LIMIT;
-    }
-    int rc = ctx ? agx_bind(ctx) : AGX_OK;
-    if (rc) return rc;
-    if (n_pairs < 0 || (n_pairs > 0 && (!off || !len))) {
-        agx_set_error("%s: bad arguments (n_pairs=%lld)", who, (long long)n_pairs);
-        return AGX_E_ARG;
-    }
-    if (n_pairs > 0x7fffffffLL / 2) {
-        agx_set_error("%s: more than 2^30 pairs in one batch", who);
-        return AGX_E_LIMIT;
-    }
-    const agx_sw_scoring ref_scoring = AGX_SW_SCORING_REFERENCE;
-    const agx_sw_scoring sc = scoring ? *scoring : ref_scoring;
-    if (sc.match < 1 || sc.match > 12 || sc.mismatch > 0 || sc.mismatch < sc.match - 128 || sc.gap_open > 0 || sc.gap_open < -1000 ||
-        sc.gap_extend > 0 || sc.gap_extend < -1000) {
-        agx_set_error("scoring {match %d, mismatch %d, open %d, extend %d} outside the supported range", sc.match, sc.mismatch, sc.gap_open,
-                      sc.gap_extend);
-        return AGX_E_LIMIT;
-    }
-
-    // ---- pass A: limits, band, lane tiling
-    std::vector<BandPlan> plan;
-    std::vector<uint32_t> row0s; // (at) per pair, for the batch
-    if (at) row0s.assign((size_t)n_pairs, kNoBandRow);
-    int64_t cells = 0;
-    for (int64_t p = 0; p < n_pairs; ++p) {
-        const uint32_t la = len[2 * p], lb = len[2 * p + 1];
-        if (la > (uint32_t)AGX_SW_BAND_MAX_LEN || lb > (uint32_t)AGX_SW_BAND_MAX_LEN) {
-            agx_set_error("pair %lld: lengths %u x %u exceed the supported %d on either side of a banded batch", (long long)p, la, lb,
-                          AGX_SW_BAND_MAX_LEN);
-            return AGX_E_LIMIT;
-        }
-        int64_t dlo, dhi, row0 = 0, rows = lb;
-        if (at) {
-            // exactly c - w .. c + w, never widened.  The band touches the rows max(0, -dhi) .. min(lb, la - dlo) only: the fill is
-            // given those rows of b and the band shifted by the first.  The shifted problem has the same boundary values: the
-            // pinned modes hold the origin, so their first row is 0; in FIT and LOCAL a first row > 0 means dhi < 0, the row above
-            // it holds no in-band cell with j >= 0, and the only in-band cell of the first row is (row0, 0), whose value (0) is
-            // what the fill gives the origin of its own matrix.
-            const int64_t c = at->diag ? at->diag[p] : 0;
-            if (c > (int64_t)AGX_SW_BAND_MAX_LEN + band || -c > (int64_t)AGX_SW_BAND_MAX_LEN + band) {
-                agx_set_error("pair %lld: diag = %lld lies beyond the supported %d + band on either side", (long long)p, (long long)c, AGX_SW_BAND_MAX_LEN);
-                return AGX_E_ARG;
-            }
-            dlo = c - band;
-            dhi = c + band;
-            if (const char *why = band_at_condition(mode, la, lb, dlo, dhi)) {
-                agx_set_error("pair %lld: lengths %u x %u in mode %d: the band %lld .. %lld (diag %lld, band %d) %s", (long long)p, la, lb, mode,
-                              (long long)dlo, (long long)dhi, (long long)c, band, why);
-                return AGX_E_ARG;
-            }
-            if (mode == AGX_SW_MODE_LOCAL && (dlo > (int64_t)la - 1 || dhi < 1 - (int64_t)lb)) { // no in-band cell with i, j >= 1: scores 0
-                cells += (int64_t)la * lb;
-                continue;
-            }
-            row0 = std::max<int64_t>(0, -dhi);
-            rows = std::min<int64_t>(lb, (int64_t)la - dlo) - row0;
-            dlo += row0;
-            dhi += row0;
-        } else
-            band_limits(mode, band, la, lb, dlo, dhi);
-        if (dhi - dlo + 1 > AGX_SW_BAND_MAX_WIDTH) {
-            agx_set_error("pair %lld: lengths %u x %u at band %d need %lld diagonals, supported %d", (long long)p, la, lb, band,
-                          (long long)(dhi - dlo + 1), AGX_SW_BAND_MAX_WIDTH);
-            return AGX_E_LIMIT;
-        }
-        cells += (int64_t)la * lb;
-        if (!la || !lb) continue; // answered by the formulas
-        if (!bases) {
-            agx_set_error("%s: bases is NULL", who);
-            return AGX_E_ARG;
-        }
-        BandPlan e{(uint32_t)p, la, (uint32_t)rows, (int32_t)dlo, (int32_t)dhi, 0, 0, (uint32_t)row0};
-        if (at) row0s[(size_t)p] = (uint32_t)row0;
-        int cls = 0, G = 1;
-        band_tiling((int)(dhi - dlo + 1), e.lb, cls, G);
-        e.cls = (uint8_t)cls;
-        e.G = (uint8_t)G;
-        plan.push_back(e);
-    }
-    // ---- sort: class, lanes per group, then rows falling -- the groups of a wave step alike (lb + G)
-    std::sort(plan.begin(), plan.end(), [](const BandPlan &x, const BandPlan &y) {
-        if (x.cls != y.cls) return x.cls < y.cls;
-        if (x.G != y.G) return x.G < y.G;
-        if (x.lb != y.lb) return x.lb > y.lb;
-        return x.pair < y.pair;
-    });
-    // ---- waves, group records, image offsets
-    const size_t n_fill = plan.size();
-    std::vector<SwBandGroup> groups(n_fill);
-    std::vector<SwWave> waves;
-    std::vector<ClassLaunch> launches;
-    uint64_t img_dw = 0;
-    int64_t padded = 0;
-    for (size_t k = 0; k < n_fill;) {
-        const BandPlan &h = plan[k];
-        const int K = kSwBandClasses[h.cls], G = h.G, per_wave = 64 / G;
-        size_t end = k;
-        while (end < n_fill && end - k < (size_t)per_wave && plan[end].cls == h.cls && plan[end].G == h.G) ++end;
-        SwWave w{};
-        w.first_group = (uint32_t)k;
-        w.n_groups = (uint16_t)(end - k);
-        w.G = (uint16_t)G;
-        w.steps = h.lb + (uint32_t)G; // the wave's longest target comes first
-        w.reserved = (uint32_t)K;
-        if (launches.empty() || launches.back().C != K) {
-            ClassLaunch cl;
-            cl.C = K;
-            cl.first_wave = (uint32_t)waves.size();
-            launches.push_back(cl);
-        }
-        ++launches.back().n_waves;
-        waves.push_back(w);
-        padded += (int64_t)w.steps * 64 * K;
-        for (; k < end; ++k) {
-            const BandPlan &e = plan[k];
-            SwBandGroup &g = groups[k];
-            const int q0 = e.dlo + G * K - G;
-            g.fpad = (uint32_t)(((-q0) % 4 + 4) % 4);
-            g.x_dw = (uint32_t)img_dw;
-            img_dw += (g.fpad + e.la + 3) / 4 + 1;
-            g.y_dw = (uint32_t)img_dw;
-            img_dw += (e.lb + 4) / 4 + 1;
-            g.la_lb = e.la | e.lb << 16;
-            g.dlo = e.dlo;
-            g.dhi = e.dhi;
-            g.out = e.pair;
-            g.reserved = e.row0; // (the kernels do not read it: the image build below does)
-            if (img_dw > 0xffffffffull) {
-                agx_set_error("pair %u: the batch's sequences exceed the 16 GiB a banded batch's image may take", e.pair);
-                return AGX_E_LIMIT;
-            }
-        }
-    }
-
-    agx_sw_batch *b = new agx_sw_batch();
-    DrainOnError done(ctx, [&] { agx_sw_batch_destroy(b); }); // (an error exit behind a queued copy drains the copy stream first)
-    agx_ctx_retain(ctx);
-    b->ctx = ctx;
-    b->n_pairs = n_pairs;
-    b->banded = true;
-    b->band = band;
-    b->cigar = cigar ? 1 : 0;
-    b->family = 5;
-    b->align = at ? at->what : AGX_SW_ALIGN_SPANS;
-    b->band_at = at != nullptr;
-    b->mode = mode;
-    b->scoring = sc;
-    b->prm.ge = sc.gap_extend;
-    b->prm.gf = sc.gap_open + sc.gap_extend;
-    b->prm.hd = sc.match - b->prm.gf;
-    b->prm.delta = sc.match - sc.mismatch;
-    b->prm.n_out = (uint32_t)n_pairs;
-    b->launches = launches;
-    b->info.n_pairs = n_pairs;
-    b->info.cells = cells;
-    b->info.padded_cells = padded;
-    b->info.input_bytes = (int64_t)(img_dw * 4);
-    b->info.n_launches = (int32_t)launches.size();
-    b->info.n_waves = (int32_t)waves.size();
-    if (!ctx) {
-        *out = b;
-        b = nullptr;
-        done.ok = true;
-        return AGX_OK;
-    }
-    agx_sw_band_preload();
-    if (n_pairs > 0) b->seq_len.assign(len, len + 2 * n_pairs);
-    if (at) {
-        agx_sw_band_at_preload();
-        b->band_row0 = row0s;
-        if (at->diag) b->band_diag.assign(at->diag, at->diag + n_pairs);
-        else b->band_diag.assign((size_t)n_pairs, 0);
-    }
-    if (cigar || (at && at->what == AGX_SW_ALIGN_SPANS && (mode == AGX_SW_MODE_LOCAL || mode == AGX_SW_MODE_FIT))) {
-        // what the traced fills of the spans and the host's checks, or the begin pass, need long after this call
-        b->seq_off.resize((size_t)n_pairs * 2);
-        uint64_t at_byte = 0;
-        for (int64_t k = 0; k < 2 * n_pairs; ++k) {
-            b->seq_off[(size_t)k] = at_byte;
-            at_byte += len[k];
-        }
-        b->seq.resize((size_t)at_byte);
-        agx_parallel_for(2 * n_pairs, 8192, [&](int64_t lo, int64_t hi, int) {
-            for (int64_t k = lo; k < hi; ++k)
-                if (len[k] && bases) memcpy(b->seq.data() + b->seq_off[(size_t)k], bases + off[k], len[k]);
-        }); // (bases == NULL: every pair has an empty side, and a lone run of I or D reads no symbol)
-    }
-    if (cigar) {
-        agx_sw_band_trace_preload();
-        if (at) agx_sw_band_trace_at_preload();
-        agx_sw_walk_preload();
-        b->band_groups = groups;
-        b->band_rec.assign((size_t)n_pairs, kNoBandRec);
-        b->band_cls.resize(n_fill);
-        b->band_G.resize(n_fill);
-        for (size_t k = 0; k < n_fill; ++k) {
-            b->band_rec[plan[k].pair] = (uint32_t)k;
-            b->band_cls[k] = plan[k].cls;
-            b->band_G[k] = plan[k].G;
-        }
-    }
-    PinBuf h_img, h_groups, h_waves;
-    struct Temps {
-        PinBuf *a, *b, *c;
-        ~Temps()
-        {
-            a->release();
-            b->release();
-            c->release();
-        }
-    };
-    if (n_fill) {
-        // ---- the image, built on the host (it touches every byte once: the symbol check rides along)
-        rc = h_img.alloc(ctx, (size_t)img_dw * 4);
-        if (!rc) rc = h_groups.alloc(ctx, n_fill * sizeof(SwBandGroup));
-        if (!rc) rc = h_waves.alloc(ctx, waves.size() * sizeof(SwWave));
-        Temps temps{&h_img, &h_groups, &h_waves}; // released after `done` below has drained (it is declared later, so runs first)
-        DrainOnError drain(ctx, [] {});
-        if (rc) return rc;
-        memcpy(h_groups.p, groups.data(), n_fill * sizeof(SwBandGroup));
-        memcpy(h_waves.p, waves.data(), waves.size() * sizeof(SwWave));
-        std::vector<int64_t> bad((size_t)agx_host_threads(), -1);
-        uint8_t *im = (uint8_t *)h_img.p;
-        agx_parallel_for((int64_t)n_fill, 64, [&](int64_t lo, int64_t hi, int t) {
-            int64_t first_bad = -1;
-            for (int64_t k = lo; k < hi; ++k) {
-                const SwBandGroup &g = groups[(size_t)k];
-                const uint32_t la = g.la_lb & 0xffffu, lb = g.la_lb >> 16;
-                const uint8_t *sa = bases + off[2 * (size_t)g.out], *sb = bases + off[2 * (size_t)g.out + 1] + g.reserved; // (row0)
-                uint8_t *xa = im + (size_t)g.x_dw * 4, *ya = im + (size_t)g.y_dw * 4;
-                const size_t xbytes = ((size_t)(g.fpad + la + 3) / 4 + 1) * 4, ybytes = ((size_t)(lb + 4) / 4 + 1) * 4;
-                memset(xa, 0, g.fpad);
-                memcpy(xa + g.fpad, sa, la);
-                memset(xa + g.fpad + la, 0, xbytes - g.fpad - la);
-                ya[0] = 0;
-                memcpy(ya + 1, sb, lb);
-                memset(ya + 1 + lb, 0, ybytes - 1 - lb);
-                // (all of b, the rows a band around a diagonal leaves out included)
-                if ((memchr(sa, 0, la) || memchr(sb - g.reserved, 0, len[2 * (size_t)g.out + 1])) && (first_bad < 0 || (int64_t)g.out < first_bad))
-                    first_bad = g.out;
-            }
-            bad[(size_t)t] = first_bad;
-        });
-        int64_t first_bad = -1;
-        for (int64_t v : bad)
-            if (v >= 0 && (first_bad < 0 || v < first_bad)) first_bad = v;
-        if (first_bad >= 0) {
-            agx_set_error("pair %lld contains byte 0x00, which is reserved as the padding symbol", (long long)first_bad);
-            return AGX_E_SYMBOL;
-        }
-        rc = b->img.alloc(ctx, (size_t)img_dw * 4);
-        if (!rc) rc = b->groups.alloc(ctx, n_fill * sizeof(SwBandGroup));
-        if (!rc) rc = b->waves.alloc(ctx, waves.size() * sizeof(SwWave));
-        if (!rc && launches.size() > 1) rc = agx_ctx_prepare_fanout(ctx);
-        if (rc) return rc;
-        hipStream_t cs = ctx->copy;
-        AGX_HIP(hipMemcpyAsync(b->img.p, h_img.p, (size_t)img_dw * 4, hipMemcpyHostToDevice, cs));
-        AGX_HIP(hipMemcpyAsync(b->groups.p, h_groups.p, n_fill * sizeof(SwBandGroup), hipMemcpyHostToDevice, cs));
-        AGX_HIP(hipMemcpyAsync(b->waves.p, h_waves.p, waves.size() * sizeof(SwWave), hipMemcpyHostToDevice, cs));
-        // results and their landing blocks (a later failure leaves behind the queued copies: `drain` waits for them)
-        const size_t words = (size_t)n_pairs * sizeof(uint32_t);
-        rc = b->scores.alloc(ctx, words);
-        if (!rc) rc = b->band_pos.alloc(ctx, words);
-        if (!rc) rc = b->out_stage.alloc(ctx, words);
-        if (!rc) rc = b->band_pos_stage.alloc(ctx, words);
-        if (rc) return rc;
-        AGX_HIP(hipStreamSynchronize(cs));
-        drain.ok = true;
-    }
-    *out = b;
-    b = nullptr;
-    done.ok = true;
-    return AGX_OK;
-}
-
-int band_launch(agx_sw_batch *b)
-{
-    b->cig_valid = false; // what agx_sw_batch_cigars kept belongs to the launch before
-    if (b->launches.empty()) return AGX_OK;
-    FanOut fan(b->ctx, (int)b->launches.size());
-    int rc = fan.begin();
-    if (rc) return rc;
-    int k = 0;
-    // widest class first: its waves have the longest steps
-    for (auto it = b->launches.rbegin(); it != b->launches.rend(); ++it) {
-        const ClassLaunch &cl = *it;
-        if (b->band_at && b->mode != AGX_SW_MODE_GLOBAL && b->mode != AGX_SW_MODE_EXTEND) {
-            if (agx_sw_band_at_launch_class(cl.C, b->mode, b->prm, (const uint32_t *)b->img.p, (const SwBandGroup *)b->groups.p,
-                                            (const SwWave *)b->waves.p + cl.first_wave, cl.n_waves, (int32_t *)b->scores.p,
-                                            (uint32_t *)b->band_pos.p, fan.stream(k++))) {
-                agx_set_error("sw_fill_band_at<%d, %d> launch failed: %s", cl.C, b->mode, hipGetErrorString(hipGetLastError()));
-                return AGX_E_HIP;
-            }
-            continue;
-        }
-        if (agx_sw_band_launch_class(cl.C, b->mode == AGX_SW_MODE_EXTEND, b->prm, (const uint32_t *)b->img.p, (const SwBandGroup *)b->groups.p,
-                                     (const SwWave *)b->waves.p + cl.first_wave, cl.n_waves, (int32_t *)b->scores.p, (uint32_t *)b->band_pos.p,
-                                     fan.stream(k++))) {
-            agx_set_error("sw_fill_band<%d> launch failed: %s", cl.C, hipGetErrorString(hipGetLastError()));
-            return AGX_E_HIP;
-        }
-    }
-    return fan.end();
-}
-
-// band_hits of a batch around a diagonal (include/agx.h, "Banded alignment around a diagonal"): the fill's rows are counted from
-// the pair's first row; every reported cell is checked against the matrix and the band.  begins: run the begin pass of a SPANS
-// batch in LOCAL and FIT (agx_sw_batch_scores does not need it) -- a second batch of the same kind over the reversed prefixes,
-// whose band is the mirror image of the pair's: reversed, cell (i, j) of the span of cb rows and ca columns is (cb - i, ca - j),
-// so diagonal d becomes ca - cb - d and the centre c becomes ca - cb - c, the half-width stays.
-int band_at_hits(agx_sw_batch *b, agx_sw_hit *hits, bool begins)
-{
-    int rc = agx_bind(b->ctx);
-    if (rc) return rc;
-    hipStream_t st = b->ctx->stream;
-    const int64_t n = b->n_pairs;
-    const int mode = b->mode;
-    const bool cell = mode == AGX_SW_MODE_LOCAL || mode == AGX_SW_MODE_EXTEND, column = mode == AGX_SW_MODE_FIT || mode == AGX_SW_MODE_EXTEND_QUERY;
-    if (!b->launches.empty()) {
-        AGX_HIP(hipMemcpyAsync(b->out_stage.p, b->scores.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        if (cell || column) AGX_HIP(hipMemcpyAsync(b->band_pos_stage.p, b->band_pos.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    }
-    AGX_HIP(hipStreamSynchronize(st));
-    const int32_t *sc = (const int32_t *)b->out_stage.p;
-    const uint32_t *ps = (const uint32_t *)b->band_pos_stage.p;
-    const bool spans = b->align == AGX_SW_ALIGN_SPANS;
-    const agx_sw_hit nothing{0, -1, -1, -1, -1};
-    for (int64_t p = 0; p < n; ++p) {
-        const uint32_t la = b->seq_len[(size_t)(2 * p)], lb = b->seq_len[(size_t)(2 * p + 1)];
-        const uint32_t row0 = b->band_row0[(size_t)p];
-        if (!la || !lb) {
-            hits[p] = mode == AGX_SW_MODE_LOCAL ? nothing : empty_side_hit(mode, b->align, b->scoring, la, lb);
-            continue;
-        }
-        if (row0 == kNoBandRow) { // LOCAL: the band misses the matrix
-            hits[p] = nothing;
-            continue;
-        }
-        const int64_t dlo = (int64_t)b->band_diag[(size_t)p] - b->band, dhi = (int64_t)b->band_diag[(size_t)p] + b->band;
-        agx_sw_hit h{sc[p], -1, (int32_t)la - 1, -1, (int32_t)lb - 1};
-        int64_t i = lb, j = la;
-        bool ok = true, consumed = true;
-        if (cell) {
-            if (h.score <= 0) {
-                ok = h.score == 0;
-                h = nothing;
-                consumed = false;
-            } else {
-                i = (int64_t)(ps[p] >> 16) + row0;
-                j = ps[p] & 0xffffu;
-                ok = ps[p] != 0xffffffffu && i >= 1 && j >= 1;
-            }
-        } else if (column) {
-            i = (int64_t)ps[p] + row0;
-            ok = ps[p] <= 0xffffu;
-        }
-        if (consumed) {
-            if (!ok || i > lb || j > la || j - i < dlo || j - i > dhi) {
-                agx_set_error("agx_sw_batch_hits: pair %lld (mode %d, diag %d, band %d): score %d with end cell word 0x%08x is not an in-band cell of its "
-                              "%u x %u matrix",
-                              (long long)p, mode, b->band_diag[(size_t)p], b->band, sc[p], cell || column ? ps[p] : 0u, lb, la);
-                return AGX_E_INTERNAL;
-            }
-            h.b_end = (int32_t)i - 1;
-            h.a_end = (int32_t)j - 1;
-            if (spans && mode != AGX_SW_MODE_LOCAL) h.a_begin = h.b_begin = 0; // (FIT: b_begin follows below)
-        } else if (!ok) {
-            agx_set_error("agx_sw_batch_hits: pair %lld (mode %d): the banded fill gives the negative score %d", (long long)p, mode, sc[p]);
-            return AGX_E_INTERNAL;
-        }
-        hits[p] = h;
-    }
-    if (!begins || !spans || (mode != AGX_SW_MODE_LOCAL && mode != AGX_SW_MODE_FIT)) return AGX_OK;
-    const bool fit = mode == AGX_SW_MODE_FIT;
-
-    // ---- begin pass.  LOCAL: the pairs with a score; FIT: those that consume some of b.
-    std::vector<int64_t> pick;
-    for (int64_t p = 0; p < n; ++p)
-        if (fit ? hits[p].b_end >= 0 : hits[p].score > 0) pick.push_back(p);
-    const int64_t m = (int64_t)pick.size();
-    if (m == 0) return AGX_OK;
-    std::vector<uint64_t> roff((size_t)m * 2);
-    std::vector<uint32_t> rlen((size_t)m * 2);
-    std::vector<int32_t> rdiag((size_t)m);
-    uint64_t at = 0;
-    for (int64_t k = 0; k < m; ++k) {
-        const agx_sw_hit &h = hits[pick[(size_t)k]];
-        roff[(size_t)(2 * k)] = at;
-        rlen[(size_t)(2 * k)] = (uint32_t)h.a_end + 1u;
-        at += (uint64_t)h.a_end + 1u;
-        roff[(size_t)(2 * k + 1)] = at;
-        rlen[(size_t)(2 * k + 1)] = (uint32_t)h.b_end + 1u;
-        at += (uint64_t)h.b_end + 1u;
-        rdiag[(size_t)k] = (h.a_end + 1) - (h.b_end + 1) - b->band_diag[(size_t)pick[(size_t)k]];
-    }
-    std::vector<uint8_t> rev((size_t)at);
-    agx_parallel_for(m, 64, [&](int64_t lo, int64_t hi, int) {
-        for (int64_t k = lo; k < hi; ++k) {
-            const int64_t p = pick[(size_t)k];
-            for (int side = 0; side < 2; ++side) {
-                const uint8_t *src = b->seq.data() + b->seq_off[(size_t)(2 * p + side)];
-                uint8_t *dst = rev.data() + roff[(size_t)(2 * k + side)];
-                const uint32_t l = rlen[(size_t)(2 * k + side)];
-                for (uint32_t q = 0; q < l; ++q) dst[q] = src[l - 1u - q];
-            }
-        }
-    });
-    agx_sw_batch *rb = nullptr;
-    const BandAt rat{AGX_SW_ALIGN_ENDS, rdiag.data()};
-    rc = create_band(b->ctx, &b->scoring, fit ? AGX_SW_MODE_EXTEND_QUERY : AGX_SW_MODE_LOCAL, b->band, rev.data(), roff.data(), rlen.data(), m, &rb,
-                     false, &rat);
-    if (rc) return rc;
-    struct Drop {
-        agx_sw_batch *b;
-        ~Drop()
-        {
-            (void)hipStreamSynchronize(b->ctx->stream); // an error exit may leave its fill running
-            agx_sw_batch_destroy(b);
-        }
-    } drop{rb};
-    std::vector<agx_sw_hit> rh((size_t)m);
-    rc = agx_sw_batch_launch(rb);
-    if (!rc) rc = band_at_hits(rb, rh.data(), false);
-    if (rc) return rc;
-    for (int64_t k = 0; k < m; ++k) {
-        agx_sw_hit &h = hits[pick[(size_t)k]];
-        const agx_sw_hit &r = rh[(size_t)k];
-        // (FIT: the reverse fill may consume nothing of b -- all of a in one gap along row b_end + 1 -- which is b_begin = b_end + 1)
-        if (r.score != h.score || r.a_end > h.a_end || r.b_end > h.b_end || (fit ? r.a_end != h.a_end || r.b_end < -1 : r.a_end < 0 || r.b_end < 0)) {
-            agx_set_error("agx_sw_batch_hits: pair %lld: the reverse banded fill from its end cell (a %d, b %d) gives score %d at (a %d, b %d), the forward "
-                          "fill %d",
-                          (long long)pick[(size_t)k], h.a_end, h.b_end, r.score, r.a_end, r.b_end, h.score);
-            return AGX_E_INTERNAL;
-        }
-        if (!fit) h.a_begin = h.a_end - r.a_end;
-        h.b_begin = h.b_end - r.b_end;
-    }
-    return AGX_OK;
-}
-
-// waits for the launched fill and builds the hits by the contract's rules, in the caller's pair order
-int band_hits(agx_sw_batch *b, agx_sw_hit *hits)
-{
-    if (b->band_at) return band_at_hits(b, hits, true);
-    int rc = agx_bind(b->ctx);
-    if (rc) return rc;
-    hipStream_t st = b->ctx->stream;
-    const int64_t n = b->n_pairs;
-    const bool filled = !b->launches.empty();
-    if (filled) {
-        AGX_HIP(hipMemcpyAsync(b->out_stage.p, b->scores.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        if (b->mode == AGX_SW_MODE_EXTEND)
-            AGX_HIP(hipMemcpyAsync(b->band_pos_stage.p, b->band_pos.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    }
-    AGX_HIP(hipStreamSynchronize(st));
-    const int32_t *sc = (const int32_t *)b->out_stage.p;
-    const uint32_t *ps = (const uint32_t *)b->band_pos_stage.p;
-    for (int64_t p = 0; p < n; ++p) {
-        const uint32_t la = b->seq_len[(size_t)(2 * p)], lb = b->seq_len[(size_t)(2 * p + 1)];
-        if (!la || !lb) {
-            hits[p] = empty_side_hit(b->mode, AGX_SW_ALIGN_SPANS, b->scoring, la, lb);
-            continue;
-        }
-        agx_sw_hit h{sc[p], 0, (int32_t)la - 1, 0, (int32_t)lb - 1};
-        if (b->mode == AGX_SW_MODE_EXTEND) {
-            if (h.score <= 0)
-                h = agx_sw_hit{0, -1, -1, -1, -1};
-            else {
-                const uint32_t i = ps[p] >> 16, j = ps[p] & 0xffffu;
-                if (i < 1 || i > lb || j < 1 || j > la) {
-                    agx_set_error("pair %lld: the banded fill reported the end cell (%u, %u) outside the %u x %u matrix", (long long)p, i, j, lb, la);
-                    return AGX_E_INTERNAL;
-                }
-                h.b_end = (int32_t)i - 1;
-                h.a_end = (int32_t)j - 1;
-            }
-        }
-        hits[p] = h;
-    }
-    return AGX_OK;
-}
-
-} // namespace
+} // namespace agx_sw_host
 
 extern "C" {
-
-int agx_sw_batch_create_align_band(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t band, const uint8_t *bases,
-                                   const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_batch **out)
-{
-    AGX_GUARD_BEGIN
-    return create_band(ctx, scoring, mode, band, bases, off, len, n_pairs, out);
-    AGX_GUARD_END("agx_sw_batch_create_align_band")
-}
-
-int agx_sw_align_band(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t band, const uint8_t *bases, const uint64_t *off,
-                      const uint32_t *len, int64_t n_pairs, agx_sw_hit *hits)
-{
-    agx_sw_batch *b = nullptr;
-    int rc = agx_sw_batch_create_align_band(ctx, scoring, mode, band, bases, off, len, n_pairs, &b);
-    if (rc) return rc;
-    rc = agx_sw_batch_launch(b);
-    if (!rc) rc = agx_sw_batch_hits(b, hits);
-    if (rc && b->ctx) (void)hipStreamSynchronize(b->ctx->stream); // the blocks go back to the pools: nothing may still run on them
-    agx_sw_batch_destroy(b);
-    return rc;
-}
-
-int agx_sw_batch_create_align_band_diag(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int what, int32_t band, const int32_t *diag,
-                                        const uint8_t *bases, const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_batch **out)
-{
-    AGX_GUARD_BEGIN
-    const BandAt at{what, diag};
-    return create_band(ctx, scoring, mode, band, bases, off, len, n_pairs, out, false, &at);
-    AGX_GUARD_END("agx_sw_batch_create_align_band_diag")
-}
-
-int agx_sw_align_band_diag(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int what, int32_t band, const int32_t *diag, const uint8_t *bases,
-                           const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_hit *hits)
-{
-    agx_sw_batch *b = nullptr;
-    int rc = agx_sw_batch_create_align_band_diag(ctx, scoring, mode, what, band, diag, bases, off, len, n_pairs, &b);
-    if (rc) return rc;
-    rc = agx_sw_batch_launch(b);
-    if (!rc) rc = agx_sw_batch_hits(b, hits);
-    if (rc && b->ctx) (void)hipStreamSynchronize(b->ctx->stream); // the blocks go back to the pools: nothing may still run on them
-    agx_sw_batch_destroy(b);
-    return rc;
-}
 
 int agx_sw_batch_launch(agx_sw_batch *b)
 {
@@ -2466,1167 +1758,6 @@ int agx_sw_score(agx_ctx *ctx, const uint8_t *bases, const uint64_t *off, const 
     }
     return AGX_OK;
     AGX_GUARD_END("agx_sw_score")
-}
-
-int agx_sw_batch_create_align(agx_ctx *ctx, const agx_sw_scoring *scoring, int what, const uint8_t *bases, const uint64_t *off,
-                              const uint32_t *len, int64_t n_pairs, agx_sw_batch **out)
-{
-    return agx_sw_batch_create_align_mode(ctx, scoring, AGX_SW_MODE_LOCAL, what, bases, off, len, n_pairs, out);
-}
-
-} // extern "C"
-
-namespace {
-// What a pair with an empty side answers in the modes other than LOCAL (include/agx.h, "Alignment modes"): no cell is
-// filled, the boundary formulas are the answer.  D[0][la] = all of a in one gap; GLOBAL with la = 0 the same for b.
-agx_sw_hit empty_side_hit(int mode, int what, const agx_sw_scoring &sc, uint32_t la, uint32_t lb)
-{
-    agx_sw_hit h{0, -1, -1, -1, -1};
-    const int gap_a = la ? sc.gap_open + (int)la * sc.gap_extend : 0;
-    const int gap_b = lb ? sc.gap_open + (int)lb * sc.gap_extend : 0;
-    if (mode == AGX_SW_MODE_EXTEND) return h; // D[0][0] = 0 is the maximum: nothing consumed, all four stay -1
-    h.a_end = (int32_t)la - 1;
-    if (mode == AGX_SW_MODE_GLOBAL) {
-        h.score = gap_a + gap_b; // (one of them is 0)
-        h.b_end = (int32_t)lb - 1;
-    } else
-        h.score = gap_a; // FIT, EXTEND_QUERY: max_i D[i][la] stands at i = 0 (la = 0: D[i][0] <= 0 = D[0][0]; lb = 0: i = 0 only)
-    if (what == AGX_SW_ALIGN_SPANS) h.a_begin = h.b_begin = 0;
-    return h;
-}
-
-// an align batch under match/mismatch scoring (matrix == NULL) or under a substitution matrix (scoring unused)
-int create_align(const char *who, agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matrix *matrix, int mode, int what,
-                 const uint8_t *bases, const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_batch **out, bool stats = false, bool cigar = false)
-{
-    if (mode < AGX_SW_MODE_LOCAL || mode > AGX_SW_MODE_EXTEND_QUERY) {
-        if (out) *out = nullptr;
-        agx_set_error("%s%s: mode = %d is not one of AGX_SW_MODE_LOCAL .. AGX_SW_MODE_EXTEND_QUERY (0..4)", who, matrix || stats || cigar ? "" : "_mode", mode);
-        return AGX_E_ARG;
-    }
-    if (what != AGX_SW_ALIGN_ENDS && what != AGX_SW_ALIGN_SPANS) {
-        if (out) *out = nullptr;
-        agx_set_error("%s: what = %d is neither AGX_SW_ALIGN_ENDS nor AGX_SW_ALIGN_SPANS", who, what);
-        return AGX_E_ARG;
-    }
-    AGX_GUARD_BEGIN
-    agx_sw_batch *b = nullptr;
-    // a stats batch: LOCAL and FIT keep the plain forward fill (their begin pass carries L), the pinned modes' only fill carries it
-    const int stats_kind = !stats ? 0 : (mode == AGX_SW_MODE_LOCAL || mode == AGX_SW_MODE_FIT) ? 1 : 2;
-    const int max_query = stats ? AGX_SW_STATS_MAX_QUERY_LEN : cigar ? AGX_SW_CIGAR_MAX_QUERY_LEN : AGX_SW_ALIGN_MAX_QUERY_LEN;
-    int rc = create_batch(ctx, scoring, matrix, bases, off, len, n_pairs, &b, false, what, mode, stats_kind, cigar ? 1 : 0);
-    if (rc) return rc;
-    struct Drop {
-        agx_sw_batch *b;
-        ~Drop() { agx_sw_batch_destroy(b); } // (create_batch has waited for everything it queued)
-    } drop{b};
-    if (mode != AGX_SW_MODE_LOCAL)
-        for (int64_t p = 0; p < n_pairs; ++p) { // the planner skips pairs with an empty side: their answers come from the formulas
-            const uint32_t la = len[2 * p], lb = len[2 * p + 1];
-            if (la && lb) continue;
-            if (la > (uint32_t)max_query || lb > (uint32_t)AGX_SW_ALIGN_MAX_TARGET_LEN) {
-                agx_set_error("pair %lld: lengths %u x %u exceed the supported %d x %d (query x target of an align batch)", (long long)p, la, lb,
-                              max_query, AGX_SW_ALIGN_MAX_TARGET_LEN);
-                return AGX_E_LIMIT;
-            }
-            const int32_t v = empty_side_hit(mode, what, b->scoring, la, lb).score;
-            if (ctx && v) {
-                b->fix_pair.push_back(p);
-                b->fix_score.push_back(v);
-            }
-        }
-    if (ctx && n_pairs > 0) b->seq_len.assign(len, len + 2 * n_pairs); // agx_sw_batch_hits checks every end cell against them
-    if (ctx && what == AGX_SW_ALIGN_SPANS && n_pairs > 0 && (mode == AGX_SW_MODE_LOCAL || mode == AGX_SW_MODE_FIT || cigar)) {
-        // the begin pass (and a cigar batch's traced fill of the spans) reads the sequences again, long after this call: a dense
-        // copy of the batch's own
-        b->seq_off.resize((size_t)n_pairs * 2);
-        uint64_t at = 0;
-        for (int64_t k = 0; k < 2 * n_pairs; ++k) {
-            b->seq_off[(size_t)k] = at;
-            at += len[k];
-        }
-        b->seq.resize((size_t)at);
-        agx_parallel_for(2 * n_pairs, 8192, [&](int64_t lo, int64_t hi, int) {
-            for (int64_t k = lo; k < hi; ++k)
-                if (len[k]) memcpy(b->seq.data() + b->seq_off[(size_t)k], bases + off[k], len[k]);
-        });
-    }
-    drop.b = nullptr;
-    *out = b;
-    return AGX_OK;
-    AGX_GUARD_END(who)
-}
-} // namespace
-
-extern "C" {
-
-int agx_sw_batch_create_align_mode(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int what, const uint8_t *bases,
-                                   const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_batch **out)
-{
-    return create_align("agx_sw_batch_create_align", ctx, scoring, nullptr, mode, what, bases, off, len, n_pairs, out);
-}
-
-int agx_sw_batch_create_align_matrix(agx_ctx *ctx, const agx_sw_matrix *matrix, int mode, int what, const uint8_t *bases,
-                                     const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_batch **out)
-{
-    if (!matrix) {
-        if (out) *out = nullptr;
-        agx_set_error("agx_sw_batch_create_align_matrix: matrix is NULL");
-        return AGX_E_ARG;
-    }
-    return create_align("agx_sw_batch_create_align_matrix", ctx, nullptr, matrix, mode, what, bases, off, len, n_pairs, out);
-}
-
-} // extern "C"
-
-namespace {
-// agx_sw_batch_hits; with L (agx_sw_batch_stats) also the word matches << 12 | pairs of every pair, 0 where no fill says
-// otherwise: from this batch's own fill (stats == 2), else from the begin pass, which then runs the stats build
-int hits_impl(agx_sw_batch *b, agx_sw_hit *hits, std::vector<uint32_t> *L)
-{
-    int rc = agx_bind(b->ctx);
-    if (rc) return rc;
-    hipStream_t st = b->ctx->stream;
-    const int64_t n = b->n_pairs;
-    if (n == 0) {
-        AGX_HIP(hipStreamSynchronize(st));
-        return AGX_OK;
-    }
-    const int32_t *sc = (const int32_t *)b->out_stage.p;
-    const uint32_t *en = (const uint32_t *)b->ends_stage.p;
-    const bool own_l = L && b->stats == 2;
-    AGX_HIP(hipMemcpyAsync(b->out_stage.p, b->scores.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    AGX_HIP(hipMemcpyAsync(b->ends_stage.p, b->ends.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    if (own_l) AGX_HIP(hipMemcpyAsync(b->lstat_stage.p, b->lstat.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    AGX_HIP(hipStreamSynchronize(st));
-    if (own_l) L->assign((const uint32_t *)b->lstat_stage.p, (const uint32_t *)b->lstat_stage.p + n);
-    else if (L) L->assign((size_t)n, 0u);
-    // end cells, checked against the caller's lengths: a padding cell must never be reported
-    const uint32_t *len = b->seq_len.empty() ? nullptr : b->seq_len.data(); // (the begin passes' own batches have none: checked against the end cell below)
-    const int mode = b->mode;
-    const bool spans = b->align == AGX_SW_ALIGN_SPANS;
-    std::vector<int64_t> bad((size_t)agx_host_threads(), -1);
-    agx_parallel_for(n, 16384, [&](int64_t lo, int64_t hi, int tid) {
-        for (int64_t p = lo; p < hi; ++p) {
-            agx_sw_hit h{sc[p], -1, -1, -1, -1};
-            bool ok;
-            if (mode == AGX_SW_MODE_LOCAL) {
-                if (en[p] != 0xffffffffu) {
-                    h.a_end = (int32_t)(en[p] & ((1u << kSwLocColBits) - 1u));
-                    h.b_end = (int32_t)(en[p] >> kSwLocColBits);
-                }
-                const bool located = en[p] != 0xffffffffu;
-                ok = sc[p] >= 0 && located == (sc[p] > 0);
-                if (ok && located && len) ok = (uint32_t)h.a_end < len[2 * p] && (uint32_t)h.b_end < len[2 * p + 1];
-            } else if (len && (len[2 * p] == 0 || len[2 * p + 1] == 0)) {
-                h = empty_side_hit(mode, b->align, b->scoring, len[2 * p], len[2 * p + 1]);
-                ok = sc[p] == 0 && en[p] == 0xffffffffu; // no kernel wrote there
-            } else {
-                // the anchored fill's word: (row + 1) << 12 | (column + 1); 0xffffffff = no kernel wrote the slot
-                h.a_end = (int32_t)(en[p] & ((1u << kSwLocColBits) - 1u)) - 1;
-                h.b_end = (int32_t)(en[p] >> kSwLocColBits) - 1;
-                ok = en[p] != 0xffffffffu;
-                const int64_t la = len ? (int64_t)len[2 * p] : -1, lb = len ? (int64_t)len[2 * p + 1] : -1;
-                if (mode == AGX_SW_MODE_EXTEND) {
-                    ok = ok && sc[p] >= 0 && (sc[p] > 0 ? h.a_end >= 0 && h.b_end >= 0 : h.a_end == -1 && h.b_end == -1);
-                    if (ok && len) ok = h.a_end < la && h.b_end < lb;
-                } else {
-                    ok = ok && h.a_end >= 0 && h.b_end >= -1; // all of a, whatever of b
-                    if (ok && len) ok = h.a_end == la - 1 && (mode == AGX_SW_MODE_GLOBAL ? h.b_end == lb - 1 : h.b_end < lb);
-                }
-                if (ok && spans && !(mode == AGX_SW_MODE_EXTEND && sc[p] == 0)) h.a_begin = h.b_begin = 0; // (FIT: b_begin follows below)
-            }
-            if (!ok && bad[(size_t)tid] < 0) bad[(size_t)tid] = p;
-            hits[p] = h;
-        }
-    });
-    for (int64_t p : bad)
-        if (p >= 0) {
-            agx_set_error("agx_sw_batch_hits: pair %lld (mode %d): score %d with end cell word 0x%08x is not a cell of its matrix", (long long)p, mode, sc[p], en[p]);
-            return AGX_E_INTERNAL;
-        }
-    if (!spans || (mode != AGX_SW_MODE_LOCAL && mode != AGX_SW_MODE_FIT)) return AGX_OK;
-    const bool fit = mode == AGX_SW_MODE_FIT;
-
-    // ---- begin pass.  LOCAL: the same fill over the reversed prefixes a[a_end..0], b[b_end..0] of the pairs with a score.
-    // Its end cell, by the same rule, is the latest begin in b, then in a, of an alignment of that score ending in the end
-    // cell.  FIT: all of a reversed against b[b_end..0] in mode EXTEND_QUERY -- the smallest reversed end is the latest
-    // begin in b (DESIGN.md has both arguments).
-    std::vector<int64_t> pick;
-    pick.reserve((size_t)n);
-    for (int64_t p = 0; p < n; ++p)
-        if (fit ? hits[p].b_end >= 0 : hits[p].score > 0) pick.push_back(p);
-    const int64_t m = (int64_t)pick.size();
-    if (m == 0) return AGX_OK;
-    std::vector<uint64_t> roff((size_t)m * 2);
-    std::vector<uint32_t> rlen((size_t)m * 2);
-    uint64_t at = 0;
-    for (int64_t k = 0; k < m; ++k) {
-        const agx_sw_hit &h = hits[pick[(size_t)k]];
-        roff[(size_t)(2 * k)] = at;
-        rlen[(size_t)(2 * k)] = (uint32_t)h.a_end + 1u;
-        at += (uint64_t)h.a_end + 1u;
-        roff[(size_t)(2 * k + 1)] = at;
-        rlen[(size_t)(2 * k + 1)] = (uint32_t)h.b_end + 1u;
-        at += (uint64_t)h.b_end + 1u;
-    }
-    std::vector<uint8_t> rev((size_t)at);
-    agx_parallel_for(m, 4096, [&](int64_t lo, int64_t hi, int) {
-        for (int64_t k = lo; k < hi; ++k) {
-            const int64_t p = pick[(size_t)k];
-            for (int side = 0; side < 2; ++side) {
-                const uint8_t *src = b->seq.data() + b->seq_off[(size_t)(2 * p + side)];
-                uint8_t *dst = rev.data() + roff[(size_t)(2 * k + side)];
-                const uint32_t l = rlen[(size_t)(2 * k + side)];
-                for (uint32_t i = 0; i < l; ++i) dst[i] = src[l - 1u - i];
-            }
-        }
-    });
-    agx_sw_batch *rb = nullptr;
-    // (a substitution matrix is symmetric and a stays across the lanes: the reversed problem runs under the same matrix)
-    rc = create_batch(b->ctx, &b->scoring, b->matrix ? &b->mat : nullptr, rev.data(), roff.data(), rlen.data(), m, &rb, false, AGX_SW_ALIGN_ENDS,
-                      fit ? AGX_SW_MODE_EXTEND_QUERY : AGX_SW_MODE_LOCAL, L ? 2 : 0);
-    if (rc) return rc;
-    struct Drop {
-        agx_sw_batch *b;
-        ~Drop()
-        {
-            (void)hipStreamSynchronize(b->ctx->stream); // an error exit may leave its fill running
-            agx_sw_batch_destroy(b);
-        }
-    } drop{rb};
-    std::vector<agx_sw_hit> rh((size_t)m);
-    std::vector<uint32_t> rl;
-    rc = agx_sw_batch_launch(rb);
-    if (!rc) rc = hits_impl(rb, rh.data(), L ? &rl : nullptr);
-    if (rc) return rc;
-    for (int64_t k = 0; k < m; ++k) {
-        agx_sw_hit &h = hits[pick[(size_t)k]];
-        const agx_sw_hit &r = rh[(size_t)k];
-        if (r.score != h.score || r.a_end < 0 || r.a_end > h.a_end || r.b_end < 0 || r.b_end > h.b_end || (fit && r.a_end != h.a_end)) {
-            agx_set_error("agx_sw_batch_hits: pair %lld: the reverse fill from its end cell (a %d, b %d) gives score %d at (a %d, b %d), the forward fill %d",
-                          (long long)pick[(size_t)k], h.a_end, h.b_end, r.score, r.a_end, r.b_end, h.score);
-            return AGX_E_INTERNAL;
-        }
-        if (!fit) h.a_begin = h.a_end - r.a_end;
-        h.b_begin = h.b_end - r.b_end;
-        if (L) (*L)[(size_t)pick[(size_t)k]] = rl[(size_t)k];
-    }
-    return AGX_OK;
-}
-} // namespace
-
-extern "C" {
-
-int agx_sw_batch_hits(agx_sw_batch *b, agx_sw_hit *hits)
-{
-    if (!b || (!hits && b->n_pairs)) {
-        agx_set_error("agx_sw_batch_hits: null argument");
-        return AGX_E_ARG;
-    }
-    if (!b->align) {
-        agx_set_error("agx_sw_batch_hits: a score-only batch has no hits (create it with agx_sw_batch_create_align)");
-        return AGX_E_ARG;
-    }
-    if (!b->ctx) {
-        agx_set_error("this batch was planned without a context (no device): it has no hits");
-        return AGX_E_NODEVICE;
-    }
-    AGX_GUARD_BEGIN
-    if (b->banded) return band_hits(b, hits);
-    return hits_impl(b, hits, nullptr);
-    AGX_GUARD_END("agx_sw_batch_hits")
-}
-
-int agx_sw_batch_stats(agx_sw_batch *b, agx_sw_hit *hits, agx_sw_stat *stats)
-{
-    if (!b || (!stats && b->n_pairs)) {
-        agx_set_error("agx_sw_batch_stats: null argument");
-        return AGX_E_ARG;
-    }
-    if (!b->stats || b->align != AGX_SW_ALIGN_SPANS) {
-        agx_set_error("agx_sw_batch_stats: not a stats batch (create it with agx_sw_batch_create_align_stats)");
-        return AGX_E_ARG;
-    }
-    if (!b->ctx) {
-        agx_set_error("this batch was planned without a context (no device): it has no stats");
-        return AGX_E_NODEVICE;
-    }
-    AGX_GUARD_BEGIN
-    const int64_t n = b->n_pairs;
-    std::vector<agx_sw_hit> own;
-    if (!hits && n) {
-        own.resize((size_t)n);
-        hits = own.data();
-    }
-    std::vector<uint32_t> L;
-    const int rc = hits_impl(b, hits, &L);
-    if (rc || n == 0) return rc;
-    // Every stat is checked before it leaves: 0 <= matches <= pairs <= min(columns of a, of b); under match/mismatch scoring
-    // what the score leaves after matches, mismatches and gap cells must be a whole number of gap opens, between "one if
-    // there is a gap cell" and "one per gap cell".
-    const agx_sw_scoring s = b->scoring;
-    const bool mm = !b->matrix;
-    std::vector<int64_t> bad((size_t)agx_host_threads(), -1);
-    agx_parallel_for(n, 16384, [&](int64_t lo, int64_t hi, int tid) {
-        for (int64_t p = lo; p < hi; ++p) {
-            const agx_sw_hit &h = hits[p];
-            const int64_t ca = h.a_begin >= 0 && h.a_end >= h.a_begin ? (int64_t)h.a_end - h.a_begin + 1 : 0;
-            const int64_t cb = h.b_begin >= 0 && h.b_end >= h.b_begin ? (int64_t)h.b_end - h.b_begin + 1 : 0;
-            const int64_t matches = L[(size_t)p] >> kSwStatColBits, pairs = L[(size_t)p] & ((1u << kSwStatColBits) - 1u);
-            bool ok = matches <= pairs && pairs <= std::min(ca, cb);
-            if (ok && mm && ca + cb > 0) {
-                const int64_t gaps = ca + cb - 2 * pairs;
-                const int64_t r = (int64_t)h.score - matches * s.match - (pairs - matches) * s.mismatch - gaps * s.gap_extend;
-                if (s.gap_open == 0) ok = r == 0;
-                else {
-                    const int64_t opens = r / s.gap_open;
-                    ok = r % s.gap_open == 0 && opens >= (gaps ? 1 : 0) && opens <= gaps;
-                }
-            }
-            if (!ok && bad[(size_t)tid] < 0) bad[(size_t)tid] = p;
-            stats[p] = agx_sw_stat{(int32_t)matches, (int32_t)pairs};
-        }
-    });
-    for (int64_t p : bad)
-        if (p >= 0) {
-            agx_set_error("agx_sw_batch_stats: pair %lld (mode %d): matches %u, pairs %u do not fit its score %d over the span a %d..%d, b %d..%d",
-                          (long long)p, b->mode, L[(size_t)p] >> kSwStatColBits, L[(size_t)p] & ((1u << kSwStatColBits) - 1u), hits[p].score,
-                          hits[p].a_begin, hits[p].a_end, hits[p].b_begin, hits[p].b_end);
-            return AGX_E_INTERNAL;
-        }
-    return AGX_OK;
-    AGX_GUARD_END("agx_sw_batch_stats")
-}
-
-} // extern "C"
-
-namespace {
-// What one traced pair may take of the chunk budget: its directions in the class that needs the most dwords for its length (the
-// plan is made per chunk and chooses later), plus its operation slot.  Independent of the plan, so the cut is the caller's.
-uint64_t trace_bytes_bound(uint32_t ca, uint32_t cb)
-{
-    uint64_t worst = 0;
-#define AGX_SW_BOUND(CC)                                                           \
-    if ((ca + CC - 1u) / CC <= 64u) worst = std::max(worst, sw_trace_dwords((int)((ca + CC - 1u) / CC), cb, CC));
-    AGX_SW_FOR_EACH_TRACE_CLASS(AGX_SW_BOUND)
-#undef AGX_SW_BOUND
-    return 4u * (worst + (uint64_t)ca + cb);
-}
-
-// The host's check of one CIGAR (include/agx.h, "Alignment itself"): runs well-formed and merged, exactly x and y consumed,
-// every '=' / 'X' true of the symbols, and the operations rescored give `score`.  code: the matrix's byte map, or NULL.
-bool cigar_checks(const uint32_t *ops, uint64_t n_ops, const uint8_t *x, int64_t ca, const uint8_t *y, int64_t cb, const agx_sw_scoring &s,
-                  const agx_sw_matrix *m, int64_t score)
-{
-    int64_t i = 0, j = 0, total = 0;
-    uint32_t prev = 0;
-    for (uint64_t k = 0; k < n_ops; ++k) {
-        const uint32_t op = ops[k] & 15u;
-        const int64_t len = ops[k] >> 4;
-        if (len == 0 || op == prev) return false;
-        prev = op;
-        if (op == AGX_CIGAR_EQ || op == AGX_CIGAR_DIFF) {
-            if (j + len > ca || i + len > cb) return false;
-            for (int64_t t = 0; t < len; ++t, ++i, ++j) {
-                const bool same = m ? m->code[x[j]] == m->code[y[i]] : x[j] == y[i];
-                if (same != (op == AGX_CIGAR_EQ)) return false;
-                total += m ? m->score[m->code[x[j]]][m->code[y[i]]] : same ? s.match : s.mismatch;
-            }
-        } else if (op == AGX_CIGAR_INS) {
-            j += len;
-            total += s.gap_open + len * s.gap_extend;
-        } else if (op == AGX_CIGAR_DEL) {
-            i += len;
-            total += s.gap_open + len * s.gap_extend;
-        } else
-            return false;
-    }
-    return i == cb && j == ca && total == score;
-}
-
-// agx_sw_batch_cigars: hits (SPANS), then one traced GLOBAL fill, walk and gather per chunk of spans; the answer goes into the
-// batch (cig_hits, cig_off, cig_ops).  DESIGN.md 4.1f.
-int cigars_impl(agx_sw_batch *b)
-{
-    const int64_t n = b->n_pairs;
-    b->cig_valid = false;
-    b->cig_info = agx_sw_cigar_info{};
-    b->cig_hits.assign((size_t)n, agx_sw_hit{});
-    b->cig_off.assign((size_t)n + 1, 0);
-    b->cig_ops.clear();
-    int rc = hits_impl(b, b->cig_hits.data(), nullptr);
-    if (rc || n == 0) {
-        b->cig_valid = !rc;
-        return rc;
-    }
-    agx_ctx *ctx = b->ctx;
-    const agx_sw_hit *hits = b->cig_hits.data();
-    const agx_sw_matrix *mat = b->matrix ? &b->mat : nullptr;
-    const agx_sw_scoring s = b->scoring; // (under a matrix: its gap_open and gap_extend, which is all that is read of it)
-    auto span = [&](int64_t p, int64_t &ca, int64_t &cb) {
-        const agx_sw_hit &h = hits[p];
-        ca = h.a_begin >= 0 && h.a_end >= h.a_begin ? (int64_t)h.a_end - h.a_begin + 1 : 0;
-        cb = h.b_begin >= 0 && h.b_end >= h.b_begin ? (int64_t)h.b_end - h.b_begin + 1 : 0;
-    };
-    // ---- pairs answered without a fill, and the list of the others
-    std::vector<uint32_t> count((size_t)n, 0), lone((size_t)n, 0); // operations per pair; the only one of a pair with an empty side
-    std::vector<int64_t> traced;
-    int64_t cells = 0;
-    for (int64_t p = 0; p < n; ++p) {
-        int64_t ca, cb;
-        span(p, ca, cb);
-        if (ca && cb) {
-            traced.push_back(p);
-            cells += ca * cb;
-        } else if (ca || cb) {
-            count[(size_t)p] = 1;
-            lone[(size_t)p] = (uint32_t)(ca ? ca : cb) << 4 | (uint32_t)(ca ? AGX_CIGAR_INS : AGX_CIGAR_DEL);
-        }
-    }
-    b->cig_info.n_traced = (int64_t)traced.size();
-    b->cig_info.trace_cells = cells;
-    // ---- chunks of traced pairs, in the caller's order, by the budget
-    const uint64_t budget = (uint64_t)ctx->opt_sw_trace_bytes;
-    std::vector<std::vector<uint32_t>> chunk_ops;  // every chunk's runs, dense
-    std::vector<uint64_t> where((size_t)n, 0);     // a traced pair's first run in its chunk's array
-    std::vector<uint32_t> chunk_of((size_t)n, 0);
-    hipStream_t st = ctx->stream;
-    // tuning build, AGX_TRACE_CIGAR: kernel-only times of every chunk's traced fill, walk and gather (HIP events on the stream)
-    const bool timed = agx_tune("AGX_TRACE_CIGAR") != nullptr;
-    struct Events {
-        hipEvent_t e[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-        ~Events()
-        {
-            for (hipEvent_t v : e)
-                if (v) (void)hipEventDestroy(v);
-        }
-    } ev;
-    if (timed)
-        for (hipEvent_t &v : ev.e) AGX_HIP(hipEventCreate(&v));
-    for (size_t first = 0; first < traced.size();) {
-        size_t last = first;
-        uint64_t bytes = 0;
-        while (last < traced.size()) {
-            int64_t ca, cb;
-            span(traced[last], ca, cb);
-            const uint64_t need = trace_bytes_bound((uint32_t)ca, (uint32_t)cb);
-            if (last > first && bytes + need > budget) break;
-            bytes += need;
-            ++last;
-        }
-        const int64_t m = (int64_t)(last - first);
-        // the spans as a batch of their own, not reversed
-        std::vector<uint64_t> soff((size_t)m * 2);
-        std::vector<uint32_t> slen((size_t)m * 2);
-        uint64_t at = 0;
-        for (int64_t k = 0; k < m; ++k) {
-            int64_t ca, cb;
-            span(traced[first + (size_t)k], ca, cb);
-            soff[(size_t)(2 * k)] = at;
-            slen[(size_t)(2 * k)] = (uint32_t)ca;
-            at += (uint64_t)ca;
-            soff[(size_t)(2 * k + 1)] = at;
-            slen[(size_t)(2 * k + 1)] = (uint32_t)cb;
-            at += (uint64_t)cb;
-        }
-        std::vector<uint8_t> sub((size_t)at);
-        agx_parallel_for(m, 4096, [&](int64_t lo, int64_t hi, int) {
-            for (int64_t k = lo; k < hi; ++k) {
-                const int64_t p = traced[first + (size_t)k];
-                memcpy(sub.data() + soff[(size_t)(2 * k)], b->seq.data() + b->seq_off[(size_t)(2 * p)] + hits[p].a_begin, slen[(size_t)(2 * k)]);
-                memcpy(sub.data() + soff[(size_t)(2 * k + 1)], b->seq.data() + b->seq_off[(size_t)(2 * p + 1)] + hits[p].b_begin, slen[(size_t)(2 * k + 1)]);
-            }
-        });
-        agx_sw_batch *tb = nullptr;
-        rc = create_batch(ctx, &b->scoring, mat, sub.data(), soff.data(), slen.data(), m, &tb, false, AGX_SW_ALIGN_ENDS, AGX_SW_MODE_GLOBAL, 0, 2);
-        if (rc) return rc;
-        struct Drop { // every exit: nothing may still run on the blocks when they go back to the pool
-            agx_sw_batch *b;
-            DevBuf trace, slots, runs, dst, dense;
-            PinBuf h_runs, h_dense;
-            ~Drop()
-            {
-                (void)hipStreamSynchronize(b->ctx->stream);
-                trace.release();
-                slots.release();
-                runs.release();
-                dst.release();
-                dense.release();
-                h_runs.release();
-                h_dense.release();
-                agx_sw_batch_destroy(b);
-            }
-        } d{tb, {}, {}, {}, {}, {}, {}, {}};
-        rc = d.trace.alloc(ctx, std::max<uint64_t>(tb->tr_dwords, 1) * 4);
-        if (!rc) rc = d.slots.alloc(ctx, std::max<uint64_t>(tb->tr_slot_words, 1) * 4);
-        if (!rc) rc = d.runs.alloc(ctx, (size_t)m * sizeof(uint32_t));
-        if (!rc) rc = d.dst.alloc(ctx, (size_t)m * sizeof(uint64_t));
-        if (!rc) rc = d.h_runs.alloc(ctx, (size_t)m * sizeof(uint32_t));
-        if (rc) return rc;
-        b->cig_info.trace_bytes_peak = std::max<int64_t>(b->cig_info.trace_bytes_peak, (int64_t)((tb->tr_dwords + tb->tr_slot_words) * 4));
-        ++b->cig_info.n_chunks;
-        tb->trace_p = (uint32_t *)d.trace.p;
-        if (timed) AGX_HIP(hipEventRecord(ev.e[0], st));
-        rc = agx_sw_batch_launch(tb);
-        if (rc) return rc;
-        if (timed) AGX_HIP(hipEventRecord(ev.e[1], st));
-        if (agx_sw_walk_launch((const SwWalkRec *)tb->walkrec.p, (uint32_t)m, (const uint32_t *)tb->img.p, (const uint32_t *)d.trace.p, (uint32_t *)d.slots.p,
-                               (uint32_t *)d.runs.p, st)) {
-            agx_set_error("agx_sw_batch_cigars: walk kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
-            return AGX_E_HIP;
-        }
-        if (timed) AGX_HIP(hipEventRecord(ev.e[2], st));
-        AGX_HIP(hipMemcpyAsync(d.h_runs.p, d.runs.p, (size_t)m * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        std::vector<agx_sw_hit> th((size_t)m);
-        rc = hits_impl(tb, th.data(), nullptr); // (waits for the stream: the run counts have landed too)
-        if (rc) return rc;
-        const uint32_t *runs = (const uint32_t *)d.h_runs.p;
-        std::vector<uint64_t> dst((size_t)m);
-        uint64_t total = 0;
-        for (int64_t k = 0; k < m; ++k) {
-            const int64_t p = traced[first + (size_t)k];
-            if (th[(size_t)k].score != hits[p].score || runs[k] == 0 || runs[k] > (uint64_t)slen[(size_t)(2 * k)] + slen[(size_t)(2 * k + 1)]) {
-                agx_set_error("agx_sw_batch_cigars: pair %lld (mode %d): the traced fill of its span a %d..%d, b %d..%d gives score %d in %u runs, the hit %d",
-                              (long long)p, b->mode, hits[p].a_begin, hits[p].a_end, hits[p].b_begin, hits[p].b_end, th[(size_t)k].score, runs[k],
-                              hits[p].score);
-                return AGX_E_INTERNAL;
-            }
-            dst[(size_t)k] = total;
-            where[(size_t)p] = total;
-            chunk_of[(size_t)p] = (uint32_t)chunk_ops.size();
-            count[(size_t)p] = runs[k];
-            total += runs[k];
-        }
-        rc = d.dense.alloc(ctx, (size_t)total * sizeof(uint32_t));
-        if (!rc) rc = d.h_dense.alloc(ctx, (size_t)total * sizeof(uint32_t));
-        if (rc) return rc;
-        AGX_HIP(hipMemcpyAsync(d.dst.p, dst.data(), (size_t)m * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-        if (timed) AGX_HIP(hipEventRecord(ev.e[3], st));
-        if (agx_sw_gather_launch((const SwWalkRec *)tb->walkrec.p, (uint32_t)m, (const uint32_t *)d.slots.p, (const uint32_t *)d.runs.p,
-                                 (const uint64_t *)d.dst.p, (uint32_t *)d.dense.p, st)) {
-            agx_set_error("agx_sw_batch_cigars: gather kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
-            return AGX_E_HIP;
-        }
-        if (timed) AGX_HIP(hipEventRecord(ev.e[4], st));
-        AGX_HIP(hipMemcpyAsync(d.h_dense.p, d.dense.p, (size_t)total * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        AGX_HIP(hipStreamSynchronize(st));
-        if (timed) {
-            float fill = 0, walk = 0, gather = 0;
-            AGX_HIP(hipEventElapsedTime(&gather, ev.e[3], ev.e[4]));
-            AGX_HIP(hipEventElapsedTime(&fill, ev.e[0], ev.e[1]));
-            AGX_HIP(hipEventElapsedTime(&walk, ev.e[1], ev.e[2]));
-            fprintf(stderr, "[agx_sw_batch_cigars] chunk %d: %lld pairs, %.1f MB of directions, %.1f MB of slots: traced fill %.3f ms, walk %.3f ms, gather %.3f ms, %llu runs\n",
-                    b->cig_info.n_chunks - 1, (long long)m, tb->tr_dwords * 4 / 1e6, tb->tr_slot_words * 4 / 1e6, fill, walk, gather, (unsigned long long)total);
-        }
-        chunk_ops.emplace_back((const uint32_t *)d.h_dense.p, (const uint32_t *)d.h_dense.p + total);
-        first = last;
-    } // (Drop returns the chunk's blocks before the next chunk takes its own)
-    // ---- the caller's layout, and every CIGAR checked before it leaves
-    for (int64_t p = 0; p < n; ++p) b->cig_off[(size_t)p + 1] = b->cig_off[(size_t)p] + count[(size_t)p];
-    b->cig_ops.resize((size_t)b->cig_off[(size_t)n]);
-    std::vector<int64_t> bad((size_t)agx_host_threads(), -1);
-    agx_parallel_for(n, 4096, [&](int64_t lo, int64_t hi, int tid) {
-        for (int64_t p = lo; p < hi; ++p) {
-            int64_t ca, cb;
-            span(p, ca, cb);
-            uint32_t *out = b->cig_ops.data() + b->cig_off[(size_t)p];
-            const uint32_t c = count[(size_t)p];
-            if (ca && cb) memcpy(out, chunk_ops[chunk_of[(size_t)p]].data() + where[(size_t)p], (size_t)c * sizeof(uint32_t));
-            else if (c) out[0] = lone[(size_t)p];
-            const uint8_t *x = ca ? b->seq.data() + b->seq_off[(size_t)(2 * p)] + hits[p].a_begin : nullptr;
-            const uint8_t *y = cb ? b->seq.data() + b->seq_off[(size_t)(2 * p + 1)] + hits[p].b_begin : nullptr;
-            if (!cigar_checks(out, c, x, ca, y, cb, s, mat, hits[p].score) && bad[(size_t)tid] < 0) bad[(size_t)tid] = p;
-        }
-    });
-    for (int64_t p : bad)
-        if (p >= 0) {
-            agx_set_error("agx_sw_batch_cigars: pair %lld (mode %d): its %u operations do not consume the span a %d..%d, b %d..%d, disagree with the "
-                          "symbols or do not rescore to %d",
-                          (long long)p, b->mode, count[(size_t)p], hits[p].a_begin, hits[p].a_end, hits[p].b_begin, hits[p].b_end, hits[p].score);
-            return AGX_E_INTERNAL;
-        }
-    b->cig_valid = true;
-    return AGX_OK;
-}
-
-// ---- CIGARs of banded batches (include/agx.h, "CIGARs for banded batches")
-
-// What one traced pair of a banded cigar batch may take of the chunk budget: its directions in the class that needs the most
-// dwords for its band width and its rows, plus its operation slot.  Independent of the plan, as trace_bytes_bound.
-uint64_t band_trace_bytes_bound(uint32_t width, uint32_t ca, uint32_t cb)
-{
-    uint64_t worst = 0;
-    for (int c = 0; c < kSwNumBandClasses; ++c) {
-        const uint32_t K = (uint32_t)kSwBandClasses[c], G = (width + K - 1u) / K;
-        if (G >= 1u && G <= 64u) worst = std::max(worst, sw_band_trace_dwords((int)G, cb, (int)K));
-    }
-    return 4u * (worst + (uint64_t)ca + cb);
-}
-
-// The band-aware part of the host's check: from (0, 0), after every operation dlo <= j - i <= dhi (within a run j - i moves one
-// way only, so the run's end decides).
-bool cigar_in_band(const uint32_t *ops, uint64_t n_ops, int64_t dlo, int64_t dhi)
-{
-    int64_t d = 0;
-    if (d < dlo || d > dhi) return false;
-    for (uint64_t k = 0; k < n_ops; ++k) {
-        const uint32_t op = ops[k] & 15u;
-        const int64_t len = ops[k] >> 4;
-        if (op == AGX_CIGAR_INS) d += len;
-        else if (op == AGX_CIGAR_DEL) d -= len;
-        else if (op != AGX_CIGAR_EQ && op != AGX_CIGAR_DIFF) return false;
-        if (d < dlo || d > dhi) return false;
-    }
-    return true;
-}
-
-// in-band cells (1 <= i <= cb, 1 <= j <= ca, dlo <= j - i <= dhi) of a span
-int64_t band_cells(int64_t ca, int64_t cb, int64_t dlo, int64_t dhi)
-{
-    int64_t cells = 0;
-    for (int64_t i = 1; i <= cb; ++i) {
-        const int64_t lo = std::max<int64_t>(1, i + dlo), hi = std::min<int64_t>(ca, i + dhi);
-        if (hi >= lo) cells += hi - lo + 1;
-    }
-    return cells;
-}
-
-// Where the traced fill of a span starts inside a banded batch's resident image (include/agx.h, agx_sw_band_span_record; the
-// head of agx_sw_band_diag_trace_kernel.hip has the argument).  false: the span does not lie in the image or in the band.
-bool band_span_record(uint32_t la, uint32_t rows, uint32_t row0, uint32_t fpad, int64_t dlo, int64_t dhi, int lanes, const agx_sw_hit &h,
-                      agx_sw_band_span &o)
-{
-    if (lanes < 1 || lanes > 64 || dhi < dlo) return false;
-    if (h.a_begin < 0 || h.b_begin < 0 || h.a_end < h.a_begin || h.b_end < h.b_begin) return false;
-    if ((uint32_t)h.a_end >= la || (uint32_t)h.b_begin < row0 || (uint64_t)h.b_end >= (uint64_t)row0 + rows) return false;
-    const int64_t s = (int64_t)h.b_begin - row0, shift = s - h.a_begin;
-    const int64_t ca = (int64_t)h.a_end - h.a_begin + 1, cb = (int64_t)h.b_end - h.b_begin + 1;
-    const int64_t lo = dlo + shift, hi = dhi + shift;
-    if (lo > 0 || hi < 0 || ca - cb < lo || ca - cb > hi) return false; // the begin and the end cell
-    o.ca = (uint32_t)ca;
-    o.cb = (uint32_t)cb;
-    o.x_bytes = fpad + (uint32_t)h.a_begin;
-    o.phase = (uint32_t)(s & 3);
-    o.y_dwords = (uint32_t)((s - o.phase) / 4);
-    o.dlo = (int32_t)lo;
-    o.dhi = (int32_t)hi;
-    o.steps = (uint32_t)cb + (uint32_t)lanes + o.phase;
-    return true;
-}
-
-// agx_sw_batch_cigars on a banded cigar batch: hits, then per chunk of spans one traced banded fill (corner capture, whatever the
-// mode: the span's global alignment inside the pair's band), the band-aware walk and the gather.  The fills read the batch's
-// resident image through copies of its group records that carry the span's lengths, in the tiling the batch planned.  A batch
-// around a diagonal (band_at) has spans that begin anywhere: its records are those of band_span_record, its fill and walk the
-// builds that start inside the image (agx_sw_band_diag_trace_kernel.hip); every span of the other batches begins at (0, 0).
-int band_cigars_impl(agx_sw_batch *b)
-{
-    const int64_t n = b->n_pairs;
-    b->cig_valid = false;
-    b->cig_info = agx_sw_cigar_info{};
-    b->cig_hits.assign((size_t)n, agx_sw_hit{});
-    b->cig_off.assign((size_t)n + 1, 0);
-    b->cig_ops.clear();
-    int rc = band_hits(b, b->cig_hits.data());
-    if (rc || n == 0) {
-        b->cig_valid = !rc;
-        return rc;
-    }
-    agx_ctx *ctx = b->ctx;
-    const agx_sw_hit *hits = b->cig_hits.data();
-    const agx_sw_scoring s = b->scoring;
-    const bool at = b->band_at;
-    auto span = [&](int64_t p, int64_t &ca, int64_t &cb) { // (begins are 0 unless the batch is banded around a diagonal)
-        const agx_sw_hit &h = hits[p];
-        ca = h.a_begin >= 0 && h.a_end >= h.a_begin ? (int64_t)h.a_end - h.a_begin + 1 : 0;
-        cb = h.b_begin >= 0 && h.b_end >= h.b_begin ? (int64_t)h.b_end - h.b_begin + 1 : 0;
-    };
-    auto limits = [&](int64_t p, int64_t &dlo, int64_t &dhi) { // the band the score was computed in, counted from the begin cell
-        if (!at) {
-            band_limits(b->mode, b->band, b->seq_len[(size_t)(2 * p)], b->seq_len[(size_t)(2 * p + 1)], dlo, dhi);
-            return;
-        }
-        const agx_sw_hit &h = hits[p];
-        const int64_t delta = h.a_begin >= 0 && h.b_begin >= 0 ? (int64_t)h.a_begin - h.b_begin : b->band_diag[(size_t)p]; // (no begin cell: no path)
-        dlo = (int64_t)b->band_diag[(size_t)p] - b->band - delta;
-        dhi = (int64_t)b->band_diag[(size_t)p] + b->band - delta;
-    };
-    std::vector<uint32_t> count((size_t)n, 0), lone((size_t)n, 0);
-    std::vector<int64_t> traced;
-    int64_t cells = 0;
-    for (int64_t p = 0; p < n; ++p) {
-        int64_t ca, cb;
-        span(p, ca, cb);
-        if (ca && cb) {
-            if (b->band_rec[(size_t)p] == kNoBandRec) {
-                agx_set_error("agx_sw_batch_cigars: pair %lld has a span of %lld x %lld and no fill", (long long)p, (long long)ca, (long long)cb);
-                return AGX_E_INTERNAL;
-            }
-            int64_t dlo, dhi;
-            limits(p, dlo, dhi);
-            traced.push_back(p);
-            cells += band_cells(ca, cb, dlo, dhi);
-        } else if (ca || cb) {
-            count[(size_t)p] = 1;
-            lone[(size_t)p] = (uint32_t)(ca ? ca : cb) << 4 | (uint32_t)(ca ? AGX_CIGAR_INS : AGX_CIGAR_DEL);
-        }
-    }
-    b->cig_info.n_traced = (int64_t)traced.size();
-    b->cig_info.trace_cells = cells;
-    const uint64_t budget = (uint64_t)ctx->opt_sw_trace_bytes;
-    std::vector<std::vector<uint32_t>> chunk_ops;
-    std::vector<uint64_t> where((size_t)n, 0);
-    std::vector<uint32_t> chunk_of((size_t)n, 0);
-    hipStream_t st = ctx->stream;
-    const bool timed = agx_tune("AGX_TRACE_CIGAR") != nullptr;
-    struct Events {
-        hipEvent_t e[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-        ~Events()
-        {
-            for (hipEvent_t v : e)
-                if (v) (void)hipEventDestroy(v);
-        }
-    } ev;
-    if (timed)
-        for (hipEvent_t &v : ev.e) AGX_HIP(hipEventCreate(&v));
-    auto width_of = [&](int64_t p) {
-        const SwBandGroup &g = b->band_groups[b->band_rec[(size_t)p]];
-        return (uint32_t)(g.dhi - g.dlo + 1);
-    };
-    for (size_t first = 0; first < traced.size();) {
-        size_t last = first;
-        uint64_t bytes = 0;
-        while (last < traced.size()) {
-            int64_t ca, cb;
-            span(traced[last], ca, cb);
-            const uint64_t need = band_trace_bytes_bound(width_of(traced[last]), (uint32_t)ca, (uint32_t)cb);
-            if (last > first && bytes + need > budget) break;
-            bytes += need;
-            ++last;
-        }
-        const int64_t m = (int64_t)(last - first);
-        // ---- the chunk's plan: the batch's tiling per pair, waves of one (class, lanes per group), longest span first
-        struct Item {
-            uint32_t k, rec, cb;
-            uint8_t cls, G;
-        };
-        std::vector<Item> items((size_t)m);
-        for (int64_t k = 0; k < m; ++k) {
-            const int64_t p = traced[first + (size_t)k];
-            int64_t ca, cb;
-            span(p, ca, cb);
-            const uint32_t rec = b->band_rec[(size_t)p];
-            items[(size_t)k] = Item{(uint32_t)k, rec, (uint32_t)cb, b->band_cls[rec], b->band_G[rec]};
-        }
-        std::sort(items.begin(), items.end(), [](const Item &x, const Item &y) {
-            if (x.cls != y.cls) return x.cls < y.cls;
-            if (x.G != y.G) return x.G < y.G;
-            if (x.cb != y.cb) return x.cb > y.cb;
-            return x.k < y.k;
-        });
-        std::vector<SwBandGroup> groups((size_t)m);
-        std::vector<uint64_t> goff((size_t)m);
-        std::vector<SwWalkRec> walk((size_t)m);
-        std::vector<SwBandWalkRec> bwalk((size_t)m);
-        std::vector<SwWave> waves;
-        std::vector<ClassLaunch> launches;
-        uint64_t tr_dwords = 0, slot_words = 0;
-        for (size_t k = 0; k < (size_t)m;) {
-            const Item &h = items[k];
-            const int K = kSwBandClasses[h.cls], G = h.G, per_wave = 64 / G;
-            size_t end = k;
-            while (end < (size_t)m && end - k < (size_t)per_wave && items[end].cls == h.cls && items[end].G == h.G) ++end;
-            SwWave w{};
-            w.first_group = (uint32_t)k;
-            w.n_groups = (uint16_t)(end - k);
-            w.G = (uint16_t)G;
-            w.steps = h.cb + (uint32_t)G;
-            w.reserved = (uint32_t)K;
-            if (launches.empty() || launches.back().C != K) {
-                ClassLaunch cl;
-                cl.C = K;
-                cl.first_wave = (uint32_t)waves.size();
-                launches.push_back(cl);
-            }
-            ++launches.back().n_waves;
-            waves.push_back(w);
-            for (; k < end; ++k) {
-                const Item &e = items[k];
-                const int64_t p = traced[first + e.k];
-                int64_t ca, cb;
-                span(p, ca, cb);
-                SwBandGroup g = b->band_groups[e.rec]; // image offsets, band and fpad as planned; the span's lengths
-                uint32_t phase = 0;
-                if (at) { // the span begins inside the image
-                    agx_sw_band_span sp;
-                    if (!band_span_record(g.la_lb & 0xffffu, g.la_lb >> 16, g.reserved, g.fpad, g.dlo, g.dhi, G, hits[p], sp) || sp.ca != (uint32_t)ca ||
-                        sp.cb != (uint32_t)cb) {
-                        agx_set_error("agx_sw_batch_cigars: pair %lld (mode %d, diag %d, band %d): its span a %d..%d, b %d..%d does not lie in the rows "
-                                      "%u.. of its image or its begin or end cell is outside the band",
-                                      (long long)p, b->mode, b->band_diag[(size_t)p], b->band, hits[p].a_begin, hits[p].a_end, hits[p].b_begin,
-                                      hits[p].b_end, g.reserved);
-                        return AGX_E_INTERNAL;
-                    }
-                    g.y_dw += sp.y_dwords;
-                    g.fpad = sp.x_bytes;
-                    g.dlo = sp.dlo;
-                    g.dhi = sp.dhi;
-                    g.reserved = phase = sp.phase;
-                    waves.back().steps = std::max(waves.back().steps, sp.steps);
-                }
-                g.la_lb = (uint32_t)ca | (uint32_t)cb << 16;
-                g.out = e.k;
-                groups[k] = g;
-                goff[k] = tr_dwords;
-                SwWalkRec &r = walk[e.k];
-                r.goff = tr_dwords;
-                r.slot = 0; // below, in the caller's order
-                r.x_dw = g.x_dw;
-                r.y_dw = g.y_dw;
-                r.ca = (uint32_t)ca;
-                r.cb = (uint32_t)cb;
-                r.G = (uint16_t)G;
-                r.C = (uint16_t)K;
-                r.reserved = phase;
-                int ks = 0;
-                while ((1 << ks) < K) ++ks;
-                bwalk[e.k] = SwBandWalkRec{g.dlo, g.dhi, g.fpad, (uint32_t)ks};
-                tr_dwords += sw_band_trace_dwords(G, (uint32_t)cb, K);
-            }
-        }
-        for (int64_t k = 0; k < m; ++k) {
-            walk[(size_t)k].slot = slot_words;
-            slot_words += (uint64_t)walk[(size_t)k].ca + walk[(size_t)k].cb;
-        }
-        std::vector<uint64_t> dst((size_t)m);
-        struct Drop { // every exit: nothing may still run on the blocks when they go back to the pool
-            agx_ctx *ctx;
-            DevBuf groups, waves, goff, walk, bwalk, scores, trace, slots, runs, dst, dense;
-            PinBuf h_runs, h_scores, h_dense;
-            ~Drop()
-            {
-                (void)hipStreamSynchronize(ctx->stream);
-                for (DevBuf *v : {&groups, &waves, &goff, &walk, &bwalk, &scores, &trace, &slots, &runs, &dst, &dense}) v->release();
-                for (PinBuf *v : {&h_runs, &h_scores, &h_dense}) v->release();
-            }
-        } d{ctx, {}, {}, {}, {}, {}, {}, {}, {}, {}, {}, {}, {}, {}, {}};
-        rc = d.groups.alloc(ctx, (size_t)m * sizeof(SwBandGroup));
-        if (!rc) rc = d.waves.alloc(ctx, waves.size() * sizeof(SwWave));
-        if (!rc) rc = d.goff.alloc(ctx, (size_t)m * sizeof(uint64_t));
-        if (!rc) rc = d.walk.alloc(ctx, (size_t)m * sizeof(SwWalkRec));
-        if (!rc) rc = d.bwalk.alloc(ctx, (size_t)m * sizeof(SwBandWalkRec));
-        if (!rc) rc = d.scores.alloc(ctx, (size_t)m * sizeof(int32_t));
-        if (!rc) rc = d.trace.alloc(ctx, std::max<uint64_t>(tr_dwords, 4) * 4);
-        if (!rc) rc = d.slots.alloc(ctx, std::max<uint64_t>(slot_words, 1) * 4);
-        if (!rc) rc = d.runs.alloc(ctx, (size_t)m * sizeof(uint32_t));
-        if (!rc) rc = d.dst.alloc(ctx, (size_t)m * sizeof(uint64_t));
-        if (!rc) rc = d.h_runs.alloc(ctx, (size_t)m * sizeof(uint32_t));
-        if (!rc) rc = d.h_scores.alloc(ctx, (size_t)m * sizeof(int32_t));
-        if (rc) return rc;
-        b->cig_info.trace_bytes_peak = std::max<int64_t>(b->cig_info.trace_bytes_peak, (int64_t)((tr_dwords + slot_words) * 4));
-        ++b->cig_info.n_chunks;
-        AGX_HIP(hipMemcpyAsync(d.groups.p, groups.data(), (size_t)m * sizeof(SwBandGroup), hipMemcpyHostToDevice, st));
-        AGX_HIP(hipMemcpyAsync(d.waves.p, waves.data(), waves.size() * sizeof(SwWave), hipMemcpyHostToDevice, st));
-        AGX_HIP(hipMemcpyAsync(d.goff.p, goff.data(), (size_t)m * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-        AGX_HIP(hipMemcpyAsync(d.walk.p, walk.data(), (size_t)m * sizeof(SwWalkRec), hipMemcpyHostToDevice, st));
-        AGX_HIP(hipMemcpyAsync(d.bwalk.p, bwalk.data(), (size_t)m * sizeof(SwBandWalkRec), hipMemcpyHostToDevice, st));
-        if (timed) AGX_HIP(hipEventRecord(ev.e[0], st));
-        for (auto it = launches.rbegin(); it != launches.rend(); ++it) // widest class first, one after the other on the stream
-            if ((at ? agx_sw_band_trace_at_launch_class : agx_sw_band_trace_launch_class)(
-                    it->C, b->prm, (const uint32_t *)b->img.p, (const SwBandGroup *)d.groups.p, (const SwWave *)d.waves.p + it->first_wave, it->n_waves,
-                    (int32_t *)d.scores.p, (uint32_t *)d.trace.p, (const uint64_t *)d.goff.p, st)) {
-                agx_set_error("sw_fill_band_trace%s<%d> launch failed: %s", at ? "_at" : "", it->C, hipGetErrorString(hipGetLastError()));
-                return AGX_E_HIP;
-            }
-        if (timed) AGX_HIP(hipEventRecord(ev.e[1], st));
-        if ((at ? agx_sw_band_walk_at_launch : agx_sw_band_walk_launch)((const SwWalkRec *)d.walk.p, (const SwBandWalkRec *)d.bwalk.p, (uint32_t)m,
-                                                                        (const uint32_t *)b->img.p, (const uint32_t *)d.trace.p, (uint32_t *)d.slots.p,
-                                                                        (uint32_t *)d.runs.p, st)) {
-            agx_set_error("agx_sw_batch_cigars: walk kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
-            return AGX_E_HIP;
-        }
-        if (timed) AGX_HIP(hipEventRecord(ev.e[2], st));
-        AGX_HIP(hipMemcpyAsync(d.h_runs.p, d.runs.p, (size_t)m * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        AGX_HIP(hipMemcpyAsync(d.h_scores.p, d.scores.p, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        AGX_HIP(hipStreamSynchronize(st));
-        const uint32_t *runs = (const uint32_t *)d.h_runs.p;
-        const int32_t *tsc = (const int32_t *)d.h_scores.p;
-        uint64_t total = 0;
-        for (int64_t k = 0; k < m; ++k) {
-            const int64_t p = traced[first + (size_t)k];
-            const SwWalkRec &r = walk[(size_t)k];
-            if (tsc[k] != hits[p].score || runs[k] == 0 || runs[k] > (uint64_t)r.ca + r.cb) { // (kSwWalkFailed: the walk left the band)
-                agx_set_error("agx_sw_batch_cigars: pair %lld (mode %d, band %d): the traced fill of its span a %d..%d, b %d..%d gives score %d in %u runs%s, "
-                              "the hit %d",
-                              (long long)p, b->mode, b->band, hits[p].a_begin, hits[p].a_end, hits[p].b_begin, hits[p].b_end, tsc[k], runs[k],
-                              runs[k] == kSwWalkFailed ? " (the walk left the band)" : "", hits[p].score);
-                return AGX_E_INTERNAL;
-            }
-            dst[(size_t)k] = total;
-            where[(size_t)p] = total;
-            chunk_of[(size_t)p] = (uint32_t)chunk_ops.size();
-            count[(size_t)p] = runs[k];
-            total += runs[k];
-        }
-        rc = d.dense.alloc(ctx, (size_t)total * sizeof(uint32_t));
-        if (!rc) rc = d.h_dense.alloc(ctx, (size_t)total * sizeof(uint32_t));
-        if (rc) return rc;
-        AGX_HIP(hipMemcpyAsync(d.dst.p, dst.data(), (size_t)m * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-        if (timed) AGX_HIP(hipEventRecord(ev.e[3], st));
-        if (agx_sw_gather_launch((const SwWalkRec *)d.walk.p, (uint32_t)m, (const uint32_t *)d.slots.p, (const uint32_t *)d.runs.p,
-                                 (const uint64_t *)d.dst.p, (uint32_t *)d.dense.p, st)) {
-            agx_set_error("agx_sw_batch_cigars: gather kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
-            return AGX_E_HIP;
-        }
-        if (timed) AGX_HIP(hipEventRecord(ev.e[4], st));
-        AGX_HIP(hipMemcpyAsync(d.h_dense.p, d.dense.p, (size_t)total * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        AGX_HIP(hipStreamSynchronize(st));
-        if (timed) {
-            float fill = 0, walk_ms = 0, gather = 0;
-            AGX_HIP(hipEventElapsedTime(&gather, ev.e[3], ev.e[4]));
-            AGX_HIP(hipEventElapsedTime(&fill, ev.e[0], ev.e[1]));
-            AGX_HIP(hipEventElapsedTime(&walk_ms, ev.e[1], ev.e[2]));
-            fprintf(stderr, "[agx_sw_batch_cigars] chunk %d: %lld pairs, %.1f MB of directions, %.1f MB of slots: traced fill %.3f ms, walk %.3f ms, gather %.3f ms, %llu runs\n",
-                    b->cig_info.n_chunks - 1, (long long)m, tr_dwords * 4 / 1e6, slot_words * 4 / 1e6, fill, walk_ms, gather, (unsigned long long)total);
-        }
-        chunk_ops.emplace_back((const uint32_t *)d.h_dense.p, (const uint32_t *)d.h_dense.p + total);
-        first = last;
-    } // (Drop returns the chunk's blocks before the next chunk takes its own)
-    // ---- the caller's layout, and every CIGAR checked before it leaves
-    for (int64_t p = 0; p < n; ++p) b->cig_off[(size_t)p + 1] = b->cig_off[(size_t)p] + count[(size_t)p];
-    b->cig_ops.resize((size_t)b->cig_off[(size_t)n]);
-    std::vector<int64_t> bad((size_t)agx_host_threads(), -1);
-    agx_parallel_for(n, 4096, [&](int64_t lo, int64_t hi, int tid) {
-        for (int64_t p = lo; p < hi; ++p) {
-            int64_t ca, cb, dlo, dhi;
-            span(p, ca, cb);
-            limits(p, dlo, dhi);
-            uint32_t *out = b->cig_ops.data() + b->cig_off[(size_t)p];
-            const uint32_t c = count[(size_t)p];
-            if (ca && cb) memcpy(out, chunk_ops[chunk_of[(size_t)p]].data() + where[(size_t)p], (size_t)c * sizeof(uint32_t));
-            else if (c) out[0] = lone[(size_t)p];
-            const uint8_t *x = ca ? b->seq.data() + b->seq_off[(size_t)(2 * p)] + hits[p].a_begin : nullptr;
-            const uint8_t *y = cb ? b->seq.data() + b->seq_off[(size_t)(2 * p + 1)] + hits[p].b_begin : nullptr;
-            if ((!cigar_checks(out, c, x, ca, y, cb, s, nullptr, hits[p].score) || (c && !cigar_in_band(out, c, dlo, dhi))) && bad[(size_t)tid] < 0)
-                bad[(size_t)tid] = p;
-        }
-    });
-    for (int64_t p : bad)
-        if (p >= 0) {
-            agx_set_error("agx_sw_batch_cigars: pair %lld (mode %d, band %d): its %u operations do not consume the span a %d..%d, b %d..%d, disagree "
-                          "with the symbols, leave the band or do not rescore to %d",
-                          (long long)p, b->mode, b->band, count[(size_t)p], hits[p].a_begin, hits[p].a_end, hits[p].b_begin, hits[p].b_end,
-                          hits[p].score);
-            return AGX_E_INTERNAL;
-        }
-    b->cig_valid = true;
-    return AGX_OK;
-}
-} // namespace
-
-extern "C" {
-
-uint64_t agx_sw_band_cigar_bytes_bound(int32_t width, uint32_t ca, uint32_t cb)
-{
-    if (width < 1 || width > AGX_SW_BAND_MAX_WIDTH) return 0;
-    return band_trace_bytes_bound((uint32_t)width, ca, cb);
-}
-
-int agx_sw_band_span_record(uint32_t la, uint32_t rows, uint32_t row0, uint32_t fpad, int32_t dlo, int32_t dhi, int32_t lanes,
-                            const agx_sw_hit *hit, agx_sw_band_span *out)
-{
-    agx_sw_band_span sp;
-    if (!hit || !out || !band_span_record(la, rows, row0, fpad, dlo, dhi, lanes, *hit, sp)) {
-        agx_set_error("agx_sw_band_span_record: null argument, an empty side, a span outside the image, lanes outside 1..64 or a begin or end cell "
-                      "outside the band");
-        return AGX_E_ARG;
-    }
-    *out = sp;
-    return AGX_OK;
-}
-
-int agx_sw_batch_create_align_band_diag_cigar(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t band, const int32_t *diag,
-                                              const uint8_t *bases, const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_batch **out)
-{
-    AGX_GUARD_BEGIN
-    const BandAt at{AGX_SW_ALIGN_SPANS, diag};
-    return create_band(ctx, scoring, mode, band, bases, off, len, n_pairs, out, true, &at);
-    AGX_GUARD_END("agx_sw_batch_create_align_band_diag_cigar")
-}
-
-int agx_sw_align_band_diag_cigar(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t band, const int32_t *diag, const uint8_t *bases,
-                                 const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_hit *hits, uint64_t *op_off, uint32_t *ops,
-                                 uint64_t ops_cap)
-{
-    agx_sw_batch *b = nullptr;
-    int rc = agx_sw_batch_create_align_band_diag_cigar(ctx, scoring, mode, band, diag, bases, off, len, n_pairs, &b);
-    if (rc) return rc;
-    rc = agx_sw_batch_launch(b);
-    if (!rc) rc = agx_sw_batch_cigars(b, hits, op_off, ops, ops_cap);
-    if (rc && b->ctx) (void)hipStreamSynchronize(b->ctx->stream); // the blocks go back to the pools: nothing may still run on them
-    agx_sw_batch_destroy(b);
-    return rc;
-}
-
-int agx_sw_cigar_in_band(const uint32_t *ops, uint64_t n_ops, int32_t dlo, int32_t dhi)
-{
-    if (!ops && n_ops) return 0;
-    return cigar_in_band(ops, n_ops, dlo, dhi) ? 1 : 0;
-}
-
-int agx_sw_batch_create_align_band_cigar(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t band, const uint8_t *bases,
-                                         const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_batch **out)
-{
-    AGX_GUARD_BEGIN
-    return create_band(ctx, scoring, mode, band, bases, off, len, n_pairs, out, true);
-    AGX_GUARD_END("agx_sw_batch_create_align_band_cigar")
-}
-
-int agx_sw_align_band_cigar(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t band, const uint8_t *bases, const uint64_t *off,
-                            const uint32_t *len, int64_t n_pairs, agx_sw_hit *hits, uint64_t *op_off, uint32_t *ops, uint64_t ops_cap)
-{
-    agx_sw_batch *b = nullptr;
-    int rc = agx_sw_batch_create_align_band_cigar(ctx, scoring, mode, band, bases, off, len, n_pairs, &b);
-    if (rc) return rc;
-    rc = agx_sw_batch_launch(b);
-    if (!rc) rc = agx_sw_batch_cigars(b, hits, op_off, ops, ops_cap);
-    if (rc && b->ctx) (void)hipStreamSynchronize(b->ctx->stream); // the blocks go back to the pools: nothing may still run on them
-    agx_sw_batch_destroy(b);
-    return rc;
-}
-
-int agx_sw_batch_cigars(agx_sw_batch *b, agx_sw_hit *hits, uint64_t *op_off, uint32_t *ops, uint64_t ops_cap)
-{
-    if (!b || !op_off) {
-        agx_set_error("agx_sw_batch_cigars: null argument");
-        return AGX_E_ARG;
-    }
-    if (b->cigar != 1 || b->align != AGX_SW_ALIGN_SPANS) {
-        agx_set_error("agx_sw_batch_cigars: not a cigar batch (create it with agx_sw_batch_create_align_cigar, agx_sw_batch_create_align_band_cigar or "
-                      "agx_sw_batch_create_align_band_diag_cigar)");
-        return AGX_E_ARG;
-    }
-    if (!b->ctx) {
-        agx_set_error("this batch was planned without a context (no device): it has no CIGARs");
-        return AGX_E_NODEVICE;
-    }
-    AGX_GUARD_BEGIN
-    if (!b->cig_valid) {
-        const int rc = b->banded ? band_cigars_impl(b) : cigars_impl(b);
-        if (rc) return rc;
-    }
-    const int64_t n = b->n_pairs;
-    memcpy(op_off, b->cig_off.data(), ((size_t)n + 1) * sizeof(uint64_t));
-    if (hits && n) memcpy(hits, b->cig_hits.data(), (size_t)n * sizeof(agx_sw_hit));
-    const uint64_t total = b->cig_off[(size_t)n];
-    if (!ops) return AGX_OK; // the sizing call
-    if (ops_cap < total) {
-        agx_set_error("agx_sw_batch_cigars: ops_cap = %llu, the batch has %llu operations", (unsigned long long)ops_cap, (unsigned long long)total);
-        return AGX_E_ARG;
-    }
-    if (total) memcpy(ops, b->cig_ops.data(), (size_t)total * sizeof(uint32_t));
-    return AGX_OK;
-    AGX_GUARD_END("agx_sw_batch_cigars")
-}
-
-int agx_sw_batch_cigar_info(const agx_sw_batch *b, agx_sw_cigar_info *info)
-{
-    if (!b || !info) {
-        agx_set_error("agx_sw_batch_cigar_info: null argument");
-        return AGX_E_ARG;
-    }
-    if (b->cigar != 1) {
-        agx_set_error("agx_sw_batch_cigar_info: not a cigar batch (create it with agx_sw_batch_create_align_cigar)");
-        return AGX_E_ARG;
-    }
-    *info = b->cig_info;
-    return AGX_OK;
-}
-
-int agx_sw_batch_create_align_cigar(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matrix *matrix, int mode, const uint8_t *bases,
-                                    const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_batch **out)
-{
-    if (scoring && matrix) {
-        if (out) *out = nullptr;
-        agx_set_error("agx_sw_batch_create_align_cigar: both scoring and matrix given; exactly one way of scoring");
-        return AGX_E_ARG;
-    }
-    return create_align("agx_sw_batch_create_align_cigar", ctx, scoring, matrix, mode, AGX_SW_ALIGN_SPANS, bases, off, len, n_pairs, out, false, true);
-}
-
-int agx_sw_align_cigar(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matrix *matrix, int mode, const uint8_t *bases,
-                       const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_hit *hits, uint64_t *op_off, uint32_t *ops, uint64_t ops_cap)
-{
-    agx_sw_batch *b = nullptr;
-    int rc = agx_sw_batch_create_align_cigar(ctx, scoring, matrix, mode, bases, off, len, n_pairs, &b);
-    if (rc) return rc;
-    rc = agx_sw_batch_launch(b);
-    if (!rc) rc = agx_sw_batch_cigars(b, hits, op_off, ops, ops_cap);
-    if (rc && b->ctx) (void)hipStreamSynchronize(b->ctx->stream); // the blocks go back to the pools: nothing may still run on them
-    agx_sw_batch_destroy(b);
-    return rc;
-}
-
-int agx_sw_align(agx_ctx *ctx, const agx_sw_scoring *scoring, int what, const uint8_t *bases, const uint64_t *off,
-                 const uint32_t *len, int64_t n_pairs, agx_sw_hit *hits)
-{
-    return agx_sw_align_mode(ctx, scoring, AGX_SW_MODE_LOCAL, what, bases, off, len, n_pairs, hits);
-}
-
-} // extern "C"
-
-namespace {
-int align_once(agx_sw_batch *b, agx_sw_hit *hits) // launch + hits + destroy
-{
-    int rc = agx_sw_batch_launch(b);
-    if (!rc) rc = agx_sw_batch_hits(b, hits);
-    if (rc && b->ctx) (void)hipStreamSynchronize(b->ctx->stream); // the blocks go back to the pools: nothing may still run on them
-    agx_sw_batch_destroy(b);
-    return rc;
-}
-} // namespace
-
-extern "C" {
-
-int agx_sw_align_mode(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int what, const uint8_t *bases, const uint64_t *off,
-                      const uint32_t *len, int64_t n_pairs, agx_sw_hit *hits)
-{
-    agx_sw_batch *b = nullptr;
-    const int rc = agx_sw_batch_create_align_mode(ctx, scoring, mode, what, bases, off, len, n_pairs, &b);
-    return rc ? rc : align_once(b, hits);
-}
-
-int agx_sw_align_matrix(agx_ctx *ctx, const agx_sw_matrix *matrix, int mode, int what, const uint8_t *bases, const uint64_t *off,
-                        const uint32_t *len, int64_t n_pairs, agx_sw_hit *hits)
-{
-    agx_sw_batch *b = nullptr;
-    const int rc = agx_sw_batch_create_align_matrix(ctx, matrix, mode, what, bases, off, len, n_pairs, &b);
-    return rc ? rc : align_once(b, hits);
-}
-
-int agx_sw_batch_create_align_stats(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matrix *matrix, int mode, const uint8_t *bases,
-                                    const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_batch **out)
-{
-    if (scoring && matrix) {
-        if (out) *out = nullptr;
-        agx_set_error("agx_sw_batch_create_align_stats: both scoring and matrix given; exactly one way of scoring");
-        return AGX_E_ARG;
-    }
-    return create_align("agx_sw_batch_create_align_stats", ctx, scoring, matrix, mode, AGX_SW_ALIGN_SPANS, bases, off, len, n_pairs, out, true);
-}
-
-int agx_sw_align_stats(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matrix *matrix, int mode, const uint8_t *bases,
-                       const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_hit *hits, agx_sw_stat *stats)
-{
-    agx_sw_batch *b = nullptr;
-    int rc = agx_sw_batch_create_align_stats(ctx, scoring, matrix, mode, bases, off, len, n_pairs, &b);
-    if (rc) return rc;
-    rc = agx_sw_batch_launch(b);
-    if (!rc) rc = agx_sw_batch_stats(b, hits, stats);
-    if (rc && b->ctx) (void)hipStreamSynchronize(b->ctx->stream); // the blocks go back to the pools: nothing may still run on them
-    agx_sw_batch_destroy(b);
-    return rc;
 }
 
 int agx_sw_shard_cuts(const uint32_t *len, int64_t n_pairs, int n_shards, int64_t *cut)

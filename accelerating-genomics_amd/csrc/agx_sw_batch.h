@@ -1,0 +1,159 @@
+// Private to the host side of the Smith-Waterman path -- agx_sw.cpp (plan, create, launch, scores), agx_sw_align.cpp (align
+// batches: hits, statistics), agx_sw_band.cpp (banded batches) and agx_sw_cigar.cpp (CIGARs) -- and included by nothing else:
+// the batch object and what those four files need of each other.  No kernel includes it.
+#pragma once
+#include "agx_sw.h"
+
+#include <algorithm>
+
+#include "agx_internal.h"
+
+// (hidden: what crosses a file boundary is still no export of the library)
+namespace agx_sw_host __attribute__((visibility("hidden"))) {
+
+struct ClassLaunch {
+    int C = 0;
+    uint32_t first_wave = 0, n_waves = 0;
+};
+
+} // namespace agx_sw_host
+
+struct agx_sw_batch {
+    agx_ctx *ctx = nullptr; // retained
+    int family = 0;         // 0 int32, 1 packed signed, 2 packed biased, 3 int32 on the packed plan's coded image, 4 locating int32, 5 anchored int32
+    // align batches (agx_sw_batch_create_align): 0 = a score-only batch, else AGX_SW_ALIGN_ENDS / _SPANS
+    int align = 0;
+    int mode = 0; // AGX_SW_MODE_*: anything but LOCAL runs the anchored fill (agx_sw_anch_kernel.hip)
+    // agx_sw_batch_create_align_stats: 0 = no statistics; 1 = a stats batch whose own fill is the plain one (LOCAL,
+    // FIT: the begin pass carries L); 2 = this batch's fill is the stats build and writes L = matches << 12 | pairs per pair
+    int stats = 0;
+    DevBuf lstat;       // stats == 2: L of every pair's captured cell
+    PinBuf lstat_stage; // its page-locked landing block
+    // agx_sw_batch_create_align_cigar: 0 = no CIGARs; 1 = a cigar batch (a SPANS batch that keeps its sequences
+    // and answers agx_sw_batch_cigars); 2 = the internal GLOBAL batch of one chunk of spans, whose fill is the traced build
+    int cigar = 0;
+    // cigar == 2: where every group's directions start (dwords), one walk record per pair, and the extents they add up to;
+    // the trace block itself is lent by cigars_impl for the time of one chunk
+    std::vector<uint64_t> tr_goff;
+    std::vector<SwWalkRec> tr_walk;
+    uint64_t tr_dwords = 0, tr_slot_words = 0;
+    DevBuf goff, walkrec;
+    uint32_t *trace_p = nullptr;
+    // cigar == 1: the answer of the last agx_sw_batch_cigars, kept until the next launch
+    bool cig_valid = false;
+    std::vector<agx_sw_hit> cig_hits;
+    std::vector<uint64_t> cig_off;
+    std::vector<uint32_t> cig_ops;
+    agx_sw_cigar_info cig_info{};
+    // modes other than LOCAL: pairs with an empty side whose score is not the zero the device array holds for them
+    std::vector<int64_t> fix_pair;
+    std::vector<int32_t> fix_score;
+    // agx_sw_batch_create_align_band: a banded batch -- align = SPANS, mode GLOBAL or EXTEND, its records are
+    // SwBandGroup, its image bytes, launches[].C the diagonals per lane; band_pos receives EXTEND's i << 16 | j per pair
+    bool banded = false;
+    int32_t band = 0;
+    DevBuf band_pos;
+    PinBuf band_pos_stage;
+    // agx_sw_batch_create_align_band_cigar: banded with cigar == 1.  The traced fills of agx_sw_batch_cigars read
+    // the resident image through copies of the group records with the span's lengths: the records in plan order, every pair's
+    // record (kNoBandRec: an empty side) and its tiling; seq / seq_off hold the symbols for the host's checks
+    std::vector<SwBandGroup> band_groups;
+    std::vector<uint32_t> band_rec;
+    std::vector<uint8_t> band_cls, band_G;
+    // agx_sw_batch_create_align_band_diag: banded with band_at set; align = ENDS or SPANS, any mode.  Per pair
+    // the centre diagonal and the first row the fill was given (kNoBandRow: no fill -- an empty side, or a LOCAL band that
+    // misses the matrix); the fill's rows are counted from there.  SPANS in LOCAL and FIT keep seq / seq_off for the begin pass
+    // agx_sw_batch_create_align_band_diag_cigar: band_at with cigar == 1 and align = SPANS; it keeps band_groups,
+    // band_rec, band_cls, band_G and seq like a banded cigar batch, in every mode
+    bool band_at = false;
+    std::vector<int32_t> band_diag;
+    std::vector<uint32_t> band_row0;
+    agx_sw_scoring scoring{};
+    DevBuf ends;        // per pair: row << kSwLocColBits | column of the end cell, written by the locating fill
+    PinBuf ends_stage;  // its page-locked landing block
+    // SPANS: the sequences, dense, for the begin pass (the caller's arrays need not outlive the create)
+    std::vector<uint8_t> seq;
+    std::vector<uint64_t> seq_off;
+    std::vector<uint32_t> seq_len;
+    SwParams prm{};
+    int64_t n_pairs = 0;
+    DevBuf img, groups, waves, scores;
+    DevBuf table; // substitution-matrix mode: kSwMatDim^2 int16 entries
+    int rising = 0; // biased packed fill: 1 = stored values rise by |ge| per step, 4 = and by |ge| per column in classes of four (agx_sw_pk2_kernel.hip, KC)
+    bool wide = false; // rising == 4: the column classes' period is C / 2 in the classes built that way (sw_pk2_period), not four
+    PinBuf out_stage; // page-locked landing block of the scores, taken at create: agx_sw_batch_scores allocates nothing
+                      // (a first hipHostMalloc costs milliseconds, and hipvers' timed window is launch -> scores)
+    bool matrix = false;
+    agx_sw_matrix mat{}; // ... and the caller's matrix itself: an align batch's begin pass creates its own batch from it
+    std::vector<agx_sw_host::ClassLaunch> launches;
+    agx_sw_info info{};
+    // A batch created without the closing wait (the pieces of agx_sw_score): its upload, planning and pack kernels may
+    // still be running; the temporaries they use, the event a launch has to wait for and the symbol check's verdict
+    // are held here until finish_create().
+    struct SwPending *pending = nullptr;
+    // agx_sw_batch_bind_scores: a page-locked array of the caller's that launches write their scores into themselves
+    // (only a batch planned in file order does: its waves then write consecutive bytes)
+    bool file_order = false;
+    int32_t *bound = nullptr;
+};
+
+namespace agx_sw_host __attribute__((visibility("hidden"))) {
+
+constexpr uint32_t kNoBandRec = 0xffffffffu;
+constexpr uint32_t kNoBandRow = 0xffffffffu;
+
+// The band of a pair: GLOBAL widens it by the length difference, EXTEND keeps it around the main diagonal.
+inline void band_limits(int mode, int64_t w, int64_t la, int64_t lb, int64_t &dlo, int64_t &dhi)
+{
+    const int64_t diff = mode == AGX_SW_MODE_GLOBAL ? la - lb : 0;
+    dlo = std::min<int64_t>(0, diff) - w;
+    dhi = std::max<int64_t>(0, diff) + w;
+}
+
+// agx_sw_batch_create_align_band_diag's part of create_band: what to report and the centre diagonal of every pair (NULL: 0)
+struct BandAt {
+    int what;
+    const int32_t *diag;
+};
+
+// ---- agx_sw.cpp
+int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matrix *matrix, const uint8_t *bases,
+                 const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_batch **out, bool defer = false, int align = 0, int mode = 0,
+                 int stats = 0, int cigar = 0);
+
+// ---- agx_sw_align.cpp
+agx_sw_hit empty_side_hit(int mode, int what, const agx_sw_scoring &sc, uint32_t la, uint32_t lb);
+int create_align(const char *who, agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matrix *matrix, int mode, int what,
+                 const uint8_t *bases, const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_batch **out, bool stats = false,
+                 bool cigar = false);
+int hits_impl(agx_sw_batch *b, agx_sw_hit *hits, std::vector<uint32_t> *L);
+
+// What a begin pass fills again: the pairs that have a begin to find (LOCAL: those with a score; fit: those that consume some of
+// b) and their prefixes a[a_end..0], b[b_end..0], reversed and dense, as the arrays of a batch of their own.
+struct RevPrefixes {
+    std::vector<int64_t> pick;
+    std::vector<uint64_t> off;
+    std::vector<uint32_t> len;
+    std::vector<uint8_t> bytes;
+};
+void reversed_prefixes(const agx_sw_batch *b, const agx_sw_hit *hits, bool fit, int64_t grain, RevPrefixes &r);
+
+// A one-shot call behind its create: launch, the answer (hits, stats or cigars), destroy.
+template <typename Answer>
+int align_once(agx_sw_batch *b, Answer answer)
+{
+    int rc = agx_sw_batch_launch(b);
+    if (!rc) rc = answer(b);
+    if (rc && b->ctx) (void)hipStreamSynchronize(b->ctx->stream); // the blocks go back to the pools: nothing may still run on them
+    agx_sw_batch_destroy(b);
+    return rc;
+}
+
+// ---- agx_sw_band.cpp
+int create_band(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t band, const uint8_t *bases, const uint64_t *off,
+                const uint32_t *len, int64_t n_pairs, agx_sw_batch **out, bool cigar = false, const BandAt *at = nullptr);
+int band_launch(agx_sw_batch *b);
+int band_at_hits(agx_sw_batch *b, agx_sw_hit *hits, bool begins);
+int band_hits(agx_sw_batch *b, agx_sw_hit *hits);
+
+} // namespace agx_sw_host
