@@ -32,6 +32,8 @@ SW_CIGAR_MAX_QUERY_LEN = 2048
 # banded batches (include/agx.h, "Banded alignment"): both sides up to SW_BAND_MAX_LEN, at most SW_BAND_MAX_WIDTH diagonals
 SW_BAND_MAX_LEN = 65535
 SW_BAND_MAX_WIDTH = 2048
+# z-drop termination of a banded extension (include/agx.h, "Z-drop for banded extension"): 0 <= zdrop <= SW_ZDROP_MAX, which never fires
+SW_ZDROP_MAX = 1000000000
 CIGAR_INS, CIGAR_DEL, CIGAR_EQ, CIGAR_DIFF = 1, 2, 7, 8
 _CIGAR_CHARS = {CIGAR_INS: "I", CIGAR_DEL: "D", CIGAR_EQ: "=", CIGAR_DIFF: "X"}
 OPT_SW_KERNEL = 1
@@ -58,6 +60,8 @@ SYMBOLS = [
     "agx_sw_batch_create_align_band_cigar", "agx_sw_align_band_cigar", "agx_sw_band_cigar_bytes_bound", "agx_sw_cigar_in_band",
     "agx_sw_batch_create_align_band_diag", "agx_sw_align_band_diag",
     "agx_sw_batch_create_align_band_diag_cigar", "agx_sw_align_band_diag_cigar", "agx_sw_band_span_record",
+    "agx_sw_batch_create_align_band_zdrop", "agx_sw_align_band_zdrop", "agx_sw_batch_zdrop_stops",
+    "agx_sw_batch_create_align_band_zdrop_cigar", "agx_sw_align_band_zdrop_cigar",
     "agx_sw_score", "agx_sw_score_multi", "agx_sw_score_devices", "agx_sw_shard_cuts",
     "agx_phmm_batch_create", "agx_phmm_batch_launch", "agx_phmm_batch_results", "agx_phmm_batch_bind_results", "agx_phmm_batch_info",
     "agx_phmm_batch_destroy", "agx_phmm_forward", "agx_phmm_forward_multi", "agx_phmm_forward_devices", "agx_phmm_shard_cuts",
@@ -228,6 +232,15 @@ def lib():
                                                                 C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)]
         l.agx_sw_align_band_diag_cigar.argtypes = [C.c_void_p, C.POINTER(SwScoring), C.c_int, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                                    C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
+        l.agx_sw_batch_create_align_band_zdrop.argtypes = [C.c_void_p, C.POINTER(SwScoring), C.c_int, C.c_int, C.c_int32, C.c_void_p, C.c_int32,
+                                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)]
+        l.agx_sw_align_band_zdrop.argtypes = [C.c_void_p, C.POINTER(SwScoring), C.c_int, C.c_int, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        l.agx_sw_batch_zdrop_stops.argtypes = [C.c_void_p, C.c_void_p]
+        l.agx_sw_batch_create_align_band_zdrop_cigar.argtypes = [C.c_void_p, C.POINTER(SwScoring), C.c_int, C.c_int32, C.c_void_p, C.c_int32,
+                                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)]
+        l.agx_sw_align_band_zdrop_cigar.argtypes = [C.c_void_p, C.POINTER(SwScoring), C.c_int, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
+                                                    C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
         l.agx_sw_band_span_record.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                                               C.POINTER(SwBandSpan)]
         l.agx_sw_score.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
@@ -343,26 +356,39 @@ class Context:
         return ms.value
 
     # ---- Smith-Waterman
-    def sw_batch(self, b, scoring=None, matrix=None, align=0, mode=SW_MODE_LOCAL, stats=False, cigar=False, band=None, diag=None) -> "SwBatch":
-        return SwBatch(self, b, scoring, matrix, align, mode, stats, cigar, band, diag)
+    def sw_batch(self, b, scoring=None, matrix=None, align=0, mode=SW_MODE_LOCAL, stats=False, cigar=False, band=None, diag=None,
+                 zdrop=None) -> "SwBatch":
+        return SwBatch(self, b, scoring, matrix, align, mode, stats, cigar, band, diag, zdrop)
 
-    def sw_align_band_diag(self, b, mode, band, diag=None, what=SW_ALIGN_SPANS, scoring=None) -> np.ndarray:
+    def sw_align_band_diag(self, b, mode, band, diag=None, what=SW_ALIGN_SPANS, scoring=None, zdrop=None):
         """b: synth.SWBatch -> SwHit records of the alignment inside the band diag - band <= j - i <= diag + band (include/agx.h,
-        "Banded alignment around a diagonal"), one-shot.  mode: any SW_MODE_*; diag: None (0), one int, or one per pair."""
+        "Banded alignment around a diagonal"), one-shot.  mode: any SW_MODE_*; diag: None (0), one int, or one per pair.
+        zdrop=Z (SW_MODE_EXTEND only; "Z-drop for banded extension"): -> (SwHit records, stops int32: the last row of b looked at, or -1)."""
         out = np.empty(b.n_pairs, SwHit)
         sc = C.byref(SwScoring(*scoring)) if scoring is not None else None
         d = _diag(diag, b.n_pairs)
+        if zdrop is not None:
+            stops = np.empty(b.n_pairs, np.int32)
+            _check(lib().agx_sw_align_band_zdrop(self._h, sc, mode, what, band, _ptr(d), zdrop, _ptr(b.bases), _ptr(b.off), _ptr(b.len), b.n_pairs,
+                                                 _ptr(out), _ptr(stops)))
+            return out, stops
         _check(lib().agx_sw_align_band_diag(self._h, sc, mode, what, band, _ptr(d), _ptr(b.bases), _ptr(b.off), _ptr(b.len), b.n_pairs, _ptr(out)))
         return out
 
-    def sw_align_band_diag_cigar(self, b, mode, band, diag=None, scoring=None):
+    def sw_align_band_diag_cigar(self, b, mode, band, diag=None, scoring=None, zdrop=None):
         """b: synth.SWBatch -> (SwHit records as sw_align_band_diag(what=SW_ALIGN_SPANS) gives them, op_off uint64[n + 1], ops uint32),
-        one-shot: the CIGAR of every pair inside its band around diag (include/agx.h, "CIGARs for batches banded around a diagonal")."""
+        one-shot: the CIGAR of every pair inside its band around diag (include/agx.h, "CIGARs for batches banded around a diagonal").
+        zdrop=Z (SW_MODE_EXTEND only): -> (hits, stops int32, op_off, ops) of the extension terminated by the z-drop."""
         hits, op_off = np.empty(b.n_pairs, SwHit), np.zeros(b.n_pairs + 1, np.uint64)
         cap = int(b.len.sum())  # an alignment has at most one operation per symbol
         ops = np.empty(max(cap, 1), np.uint32)
         sc = C.byref(SwScoring(*scoring)) if scoring is not None else None
         d = _diag(diag, b.n_pairs)
+        if zdrop is not None:
+            stops = np.empty(b.n_pairs, np.int32)
+            _check(lib().agx_sw_align_band_zdrop_cigar(self._h, sc, mode, band, _ptr(d), zdrop, _ptr(b.bases), _ptr(b.off), _ptr(b.len), b.n_pairs,
+                                                       _ptr(hits), _ptr(stops), _ptr(op_off), _ptr(ops), cap))
+            return hits, stops, op_off, ops[:int(op_off[b.n_pairs])].copy()
         _check(lib().agx_sw_align_band_diag_cigar(self._h, sc, mode, band, _ptr(d), _ptr(b.bases), _ptr(b.off), _ptr(b.len), b.n_pairs,
                                                   _ptr(hits), _ptr(op_off), _ptr(ops), cap))
         return hits, op_off, ops[:int(op_off[b.n_pairs])].copy()
@@ -442,7 +468,8 @@ class Context:
 class SwBatch:
     """agx_sw_batch: a scheduled batch resident in HBM (ctx=None: planned on the host only)."""
 
-    def __init__(self, ctx, b, scoring=None, matrix=None, align=0, mode=SW_MODE_LOCAL, stats=False, cigar=False, band=None, diag=None):
+    def __init__(self, ctx, b, scoring=None, matrix=None, align=0, mode=SW_MODE_LOCAL, stats=False, cigar=False, band=None, diag=None,
+                 zdrop=None):
         """scoring: None (the reference's +1/-1/-3/-1) or (match, mismatch, gap_open, gap_extend);
         matrix: an SwMatrix instead (score-only and align batches alike); align: SW_ALIGN_ENDS / SW_ALIGN_SPANS for a batch that also answers hits();
         mode: SW_MODE_* of an align batch (local, global, fit, extension); stats=True: a SPANS batch that also answers stats();
@@ -450,15 +477,26 @@ class SwBatch:
         band=w: a BANDED batch of mode SW_MODE_GLOBAL or SW_MODE_EXTEND (half-width w; it answers hits() as a SPANS batch does;
         no matrix or stats; with cigar=True a banded cigar batch, which also answers cigars());
         band=w with diag=one int or one per pair: a batch BANDED AROUND A DIAGONAL, any mode, align = SW_ALIGN_ENDS or
-        SW_ALIGN_SPANS (0: SPANS); no matrix or stats; with cigar=True (SPANS only) it also answers cigars()."""
+        SW_ALIGN_SPANS (0: SPANS); no matrix or stats; with cigar=True (SPANS only) it also answers cigars();
+        band=w with zdrop=Z (diag optional): such a batch in SW_MODE_EXTEND that terminates by the z-drop and also answers zdrop_stops()."""
         self.ctx = ctx
         self.n_pairs = b.n_pairs
         self._h = C.c_void_p()
-        if diag is not None:
+        if diag is not None or zdrop is not None:
             if band is None or matrix is not None or stats:
                 raise AgxError(E_ARG, "a batch banded around a diagonal takes band=w under match/mismatch scoring: no matrix or stats")
             sc = C.byref(SwScoring(*scoring)) if scoring is not None else None
             d = _diag(diag, b.n_pairs)
+            if zdrop is not None:
+                if cigar:
+                    if align not in (0, SW_ALIGN_SPANS):
+                        raise AgxError(E_ARG, "a cigar batch is a SW_ALIGN_SPANS batch")
+                    _check(lib().agx_sw_batch_create_align_band_zdrop_cigar(ctx._h if ctx else None, sc, mode, band, _ptr(d), zdrop, _ptr(b.bases),
+                                                                            _ptr(b.off), _ptr(b.len), b.n_pairs, C.byref(self._h)))
+                    return
+                _check(lib().agx_sw_batch_create_align_band_zdrop(ctx._h if ctx else None, sc, mode, align or SW_ALIGN_SPANS, band, _ptr(d), zdrop,
+                                                                  _ptr(b.bases), _ptr(b.off), _ptr(b.len), b.n_pairs, C.byref(self._h)))
+                return
             if cigar:
                 if align not in (0, SW_ALIGN_SPANS):
                     raise AgxError(E_ARG, "a cigar batch is a SW_ALIGN_SPANS batch")
@@ -530,6 +568,13 @@ class SwBatch:
         if out is None:
             out = np.empty(self.n_pairs, SwHit)
         _check(lib().agx_sw_batch_hits(self._h, _ptr(out)))
+        return out
+
+    def zdrop_stops(self, out=None) -> np.ndarray:
+        """agx_sw_batch_zdrop_stops: per pair the index in b of the last row looked at, -1 if the fill ran through (z-drop batches only)."""
+        if out is None:
+            out = np.empty(self.n_pairs, np.int32)
+        _check(lib().agx_sw_batch_zdrop_stops(self._h, _ptr(out)))
         return out
 
     def stats(self):

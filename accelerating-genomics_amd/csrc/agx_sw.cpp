@@ -230,6 +230,8 @@ void agx_sw_batch_destroy(agx_sw_batch *b)
     b->lstat_stage.release();
     b->band_pos.release();
     b->band_pos_stage.release();
+    b->band_stop.release();
+    b->band_stop_stage.release();
     b->goff.release();
     b->walkrec.release();
     agx_ctx_release(b->ctx); // the batch's own reference: a context outlives its batches

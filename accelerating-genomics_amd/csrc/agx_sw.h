@@ -228,6 +228,11 @@ void agx_sw_band_preload();
 int agx_sw_band_at_launch_class(int diags_per_lane, int mode, const SwParams &prm, const uint32_t *img, const SwBandGroup *groups,
                                 const SwWave *waves, uint32_t n_waves, int32_t *scores, uint32_t *pos, hipStream_t s);
 void agx_sw_band_at_preload();
+// the EXTEND build with z-drop termination (agx_sw_band_zdrop_kernel.hip): scores and pos as EXTEND writes them,
+// stops[out] = the last row looked at of a pair that terminated (counted from 0 in b), -1 of one that ran through
+int agx_sw_band_zdrop_launch_class(int diags_per_lane, const SwParams &prm, const uint32_t *img, const SwBandGroup *groups, const SwWave *waves,
+                                   uint32_t n_waves, int32_t *scores, uint32_t *pos, int32_t zdrop, int32_t *stops, hipStream_t s);
+void agx_sw_band_zdrop_preload();
 // the TRACED banded fill and its walk (agx_sw_band_trace_kernel.hip): corner capture only.  Every cell of rows
 // 0 .. lb leaves four bits at trace + goff[group] + (step * G + lane) * sw_band_trace_words(K) dwords, nibble k of the lane's K
 // diagonals; goff holds one 64-bit dword offset per group record, a multiple of four (the K = 32 build stores 16 bytes at once).

@@ -64,8 +64,10 @@ namespace agx_sw_host {
 int create_band(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t band, const uint8_t *bases, const uint64_t *off,
                 const uint32_t *len, int64_t n_pairs, agx_sw_batch **out, bool cigar, const BandAt *at)
 {
-    const char *who = at ? (cigar ? "agx_sw_batch_create_align_band_diag_cigar" : "agx_sw_batch_create_align_band_diag")
-                         : (cigar ? "agx_sw_batch_create_align_band_cigar" : "agx_sw_batch_create_align_band");
+    const bool zd = at && at->zdrop_on;
+    const char *who = zd   ? (cigar ? "agx_sw_batch_create_align_band_zdrop_cigar" : "agx_sw_batch_create_align_band_zdrop")
+                      : at ? (cigar ? "agx_sw_batch_create_align_band_diag_cigar" : "agx_sw_batch_create_align_band_diag")
+                           : (cigar ? "agx_sw_batch_create_align_band_cigar" : "agx_sw_batch_create_align_band");
     if (!out) {
         agx_set_error("%s: out is NULL", who);
         return AGX_E_ARG;
@@ -83,6 +85,14 @@ int create_band(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t b
         agx_set_error("%s: mode = %d has a free start or a column capture; a band around the main diagonal serves AGX_SW_MODE_GLOBAL and "
                       "AGX_SW_MODE_EXTEND only",
                       who, mode);
+        return AGX_E_ARG;
+    }
+    if (zd && mode != AGX_SW_MODE_EXTEND) {
+        agx_set_error("%s: mode = %d: a z-drop terminates an extension, AGX_SW_MODE_EXTEND only", who, mode);
+        return AGX_E_ARG;
+    }
+    if (zd && (at->zdrop < 0 || at->zdrop > AGX_SW_ZDROP_MAX)) {
+        agx_set_error("%s: zdrop = %d is outside 0 .. AGX_SW_ZDROP_MAX (%d)", who, at->zdrop, AGX_SW_ZDROP_MAX);
         return AGX_E_ARG;
     }
     if (band < 0) {
@@ -238,6 +248,8 @@ int create_band(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t b
     b->family = 5;
     b->align = at ? at->what : AGX_SW_ALIGN_SPANS;
     b->band_at = at != nullptr;
+    b->zdrop_on = zd;
+    b->zdrop = zd ? at->zdrop : 0;
     b->mode = mode;
     b->scoring = sc;
     b->prm.ge = sc.gap_extend;
@@ -262,6 +274,7 @@ int create_band(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t b
     if (n_pairs > 0) b->seq_len.assign(len, len + 2 * n_pairs);
     if (at) {
         agx_sw_band_at_preload();
+        if (zd) agx_sw_band_zdrop_preload();
         b->band_row0 = row0s;
         if (at->diag) b->band_diag.assign(at->diag, at->diag + n_pairs);
         else b->band_diag.assign((size_t)n_pairs, 0);
@@ -358,6 +371,8 @@ int create_band(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t b
         if (!rc) rc = b->band_pos.alloc(ctx, words);
         if (!rc) rc = b->out_stage.alloc(ctx, words);
         if (!rc) rc = b->band_pos_stage.alloc(ctx, words);
+        if (!rc && zd) rc = b->band_stop.alloc(ctx, words);
+        if (!rc && zd) rc = b->band_stop_stage.alloc(ctx, words);
         if (rc) return rc;
         AGX_HIP(hipStreamSynchronize(cs));
         drain.ok = true;
@@ -379,6 +394,15 @@ int band_launch(agx_sw_batch *b)
     // widest class first: its waves have the longest steps
     for (auto it = b->launches.rbegin(); it != b->launches.rend(); ++it) {
         const ClassLaunch &cl = *it;
+        if (b->zdrop_on) {
+            if (agx_sw_band_zdrop_launch_class(cl.C, b->prm, (const uint32_t *)b->img.p, (const SwBandGroup *)b->groups.p,
+                                               (const SwWave *)b->waves.p + cl.first_wave, cl.n_waves, (int32_t *)b->scores.p,
+                                               (uint32_t *)b->band_pos.p, b->zdrop, (int32_t *)b->band_stop.p, fan.stream(k++))) {
+                agx_set_error("sw_fill_band_zd<%d> launch failed: %s", cl.C, hipGetErrorString(hipGetLastError()));
+                return AGX_E_HIP;
+            }
+            continue;
+        }
         if (b->band_at && b->mode != AGX_SW_MODE_GLOBAL && b->mode != AGX_SW_MODE_EXTEND) {
             if (agx_sw_band_at_launch_class(cl.C, b->mode, b->prm, (const uint32_t *)b->img.p, (const SwBandGroup *)b->groups.p,
                                             (const SwWave *)b->waves.p + cl.first_wave, cl.n_waves, (int32_t *)b->scores.p,
@@ -443,7 +467,9 @@ int band_at_hits(agx_sw_batch *b, agx_sw_hit *hits, bool begins)
             } else {
                 i = (int64_t)(ps[p] >> 16) + row0;
                 j = ps[p] & 0xffffu;
-                ok = ps[p] != 0xffffffffu && i >= 1 && j >= 1;
+                // (0xffffffff, the word of a pair without a hit, is also cell (65535, 65535): with a score it is that cell, and the
+                // test below holds it against the matrix and the band like any other)
+                ok = i >= 1 && j >= 1;
             }
         } else if (column) {
             i = (int64_t)ps[p] + row0;
@@ -508,6 +534,37 @@ int band_at_hits(agx_sw_batch *b, agx_sw_hit *hits, bool begins)
         }
         if (!fit) h.a_begin = h.a_end - r.a_end;
         h.b_begin = h.b_end - r.b_end;
+    }
+    return AGX_OK;
+}
+
+// the stops of a z-drop batch (include/agx.h, "Z-drop for banded extension"): waits like band_at_hits, -1 for the pairs answered
+// without a fill; every stop is checked against its pair's rows and end cell
+int band_zdrop_stops(agx_sw_batch *b, int32_t *stops)
+{
+    const int64_t n = b->n_pairs;
+    std::vector<agx_sw_hit> hits((size_t)n);
+    int rc = band_at_hits(b, hits.data(), false);
+    if (rc) return rc;
+    hipStream_t st = b->ctx->stream;
+    if (!b->launches.empty()) {
+        AGX_HIP(hipMemcpyAsync(b->band_stop_stage.p, b->band_stop.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        AGX_HIP(hipStreamSynchronize(st));
+    }
+    const int32_t *sp = (const int32_t *)b->band_stop_stage.p;
+    for (int64_t p = 0; p < n; ++p) {
+        const uint32_t lb = b->seq_len[(size_t)(2 * p + 1)];
+        if (b->band_row0[(size_t)p] == kNoBandRow) { // an empty side: no fill
+            stops[p] = -1;
+            continue;
+        }
+        const int32_t s = sp[p];
+        if (s < -1 || s >= (int64_t)lb || (s >= 0 && s < hits[(size_t)p].b_end)) {
+            agx_set_error("agx_sw_batch_zdrop_stops: pair %lld (diag %d, band %d, zdrop %d): stop %d does not lie in -1 .. %u or lies before b_end = %d",
+                          (long long)p, b->band_diag[(size_t)p], b->band, b->zdrop, s, lb, hits[(size_t)p].b_end);
+            return AGX_E_INTERNAL;
+        }
+        stops[p] = s;
     }
     return AGX_OK;
 }
@@ -589,6 +646,47 @@ int agx_sw_align_band_diag(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode
     agx_sw_batch *b = nullptr;
     const int rc = agx_sw_batch_create_align_band_diag(ctx, scoring, mode, what, band, diag, bases, off, len, n_pairs, &b);
     return rc ? rc : align_once(b, [&](agx_sw_batch *x) { return agx_sw_batch_hits(x, hits); });
+}
+
+int agx_sw_batch_create_align_band_zdrop(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int what, int32_t band, const int32_t *diag,
+                                         int32_t zdrop, const uint8_t *bases, const uint64_t *off, const uint32_t *len, int64_t n_pairs,
+                                         agx_sw_batch **out)
+{
+    AGX_GUARD_BEGIN
+    const BandAt at{what, diag, true, zdrop};
+    return create_band(ctx, scoring, mode, band, bases, off, len, n_pairs, out, false, &at);
+    AGX_GUARD_END("agx_sw_batch_create_align_band_zdrop")
+}
+
+int agx_sw_batch_zdrop_stops(agx_sw_batch *b, int32_t *stops)
+{
+    if (!b || (!stops && b->n_pairs)) {
+        agx_set_error("agx_sw_batch_zdrop_stops: null argument");
+        return AGX_E_ARG;
+    }
+    if (!b->zdrop_on) {
+        agx_set_error("agx_sw_batch_zdrop_stops: not a z-drop batch (create it with agx_sw_batch_create_align_band_zdrop or "
+                      "agx_sw_batch_create_align_band_zdrop_cigar)");
+        return AGX_E_ARG;
+    }
+    if (!b->ctx) {
+        agx_set_error("this batch was planned without a context (no device): it has no stops");
+        return AGX_E_NODEVICE;
+    }
+    AGX_GUARD_BEGIN
+    return band_zdrop_stops(b, stops);
+    AGX_GUARD_END("agx_sw_batch_zdrop_stops")
+}
+
+int agx_sw_align_band_zdrop(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int what, int32_t band, const int32_t *diag, int32_t zdrop,
+                            const uint8_t *bases, const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_hit *hits, int32_t *stops)
+{
+    agx_sw_batch *b = nullptr;
+    const int rc = agx_sw_batch_create_align_band_zdrop(ctx, scoring, mode, what, band, diag, zdrop, bases, off, len, n_pairs, &b);
+    return rc ? rc : align_once(b, [&](agx_sw_batch *x) {
+        const int r = agx_sw_batch_hits(x, hits);
+        return r || !stops ? r : agx_sw_batch_zdrop_stops(x, stops);
+    });
 }
 
 } // extern "C"

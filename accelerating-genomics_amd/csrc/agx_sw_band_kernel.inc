@@ -86,6 +86,12 @@
 // that both still read whole dwords at t = 0 (mod 4).  That file's head has the argument and says what the bytes outside the span
 // do.  r = 0 is the plain traced build, step for step.
 //
+// ZD (agx_sw_band_zdrop_kernel.hip; include/agx.h, "Z-drop for banded extension"; DESIGN.md 4.1k): the EXTEND build that stops a
+// pair once its alignment has fallen apart.  A row's maximum and its leftmost column travel along the group's lanes one lane per
+// step, as z_last does; the group's last lane sees the rows complete and in order, keeps the running best and applies the rule.
+// Once per four steps the wave leaves when each of its groups has terminated or passed its last row.  That file's head has the
+// argument.
+//
 // (included by agx_sw_band_kernel.hip; opens an anonymous namespace that the including file closes after its launch helper)
 #include "agx_sw.h"
 
@@ -107,10 +113,11 @@ __device__ __forceinline__ int band_shl1(int old, int v)
 
 // AT: -1 for the builds above; else the mode of a build of agx_sw_band_diag_kernel.hip (LOCAL: EXT is set, it captures by the
 // ANY rule; FIT and EXTEND_QUERY capture column la).  Everything they add stands inside `if constexpr` blocks.
-template <int K, bool EXT, bool TRACE = false, int AT = -1, bool PH = false>
+template <int K, bool EXT, bool TRACE = false, int AT = -1, bool PH = false, bool ZD = false>
 __device__ __forceinline__ void band_body(const SwParams &prm, const uint32_t *__restrict__ img, const SwBandGroup *__restrict__ groups,
                                           const SwWave w, int32_t *__restrict__ scores, uint32_t *__restrict__ pos,
-                                          uint32_t *trace = nullptr, const uint64_t *goff = nullptr)
+                                          uint32_t *trace = nullptr, const uint64_t *goff = nullptr, [[maybe_unused]] int zdrop = 0,
+                                          [[maybe_unused]] int32_t *__restrict__ stops = nullptr)
 {
     static_assert(!(TRACE && EXT), "the traced build captures the corner: an EXTEND span is traced as the global alignment it is");
     static_assert(K % 4 == 0 && K >= 4 && K <= 32, "the query window is whole dwords and the cell mask one dword");
@@ -118,6 +125,7 @@ __device__ __forceinline__ void band_body(const SwParams &prm, const uint32_t *_
                                (AT == AGX_SW_MODE_LOCAL || AT == AGX_SW_MODE_FIT || AT == AGX_SW_MODE_EXTEND_QUERY)),
                   "GLOBAL and EXTEND around a diagonal run the plain builds: their boundaries and captures are the same");
     static_assert(!PH || (TRACE && AT == -1), "the start phase belongs to the traced build");
+    static_assert(!ZD || (EXT && !TRACE && AT == -1), "the z-drop belongs to the plain EXTEND build");
     constexpr bool AT_LOCAL = AT == AGX_SW_MODE_LOCAL, AT_FIT = AT == AGX_SW_MODE_FIT, AT_COL = AT_FIT || AT == AGX_SW_MODE_EXTEND_QUERY;
     constexpr int XW = K / 4;
     const int ge = prm.ge, gf = prm.gf, s_match = prm.hd, s_mis = prm.hd - prm.delta; // the diagonal move on z: score - gf
@@ -175,6 +183,9 @@ __device__ __forceinline__ void band_body(const SwParams &prm, const uint32_t *_
     const int dc = la - lb - g.dlo;       // GLOBAL: the corner's diagonal, counted from dlo
     const int kc = dc - gl * K;           // its slot here, if 0 <= kc < K
     [[maybe_unused]] int cbest = kBandNegInf, cap_i = -1; // AT_COL: the best z of column la so far and its row
+    // ZD: the carrier -- the maximum of this lane's row over the lanes up to this one and its leftmost column, as this lane left
+    // it in the step before -- and, meaningful in the group's last lane only, the running best B (as z) with its cell and the stop
+    [[maybe_unused]] int car_m = kBandNegInf, car_c = 0, zb = gf, zbi = 0, zbj = 0, zstop = -1;
 
     // TRACE: this lane's nibbles of step t go to tp + t G TW
     constexpr int TW = sw_band_trace_words(K);
@@ -293,7 +304,33 @@ __device__ __forceinline__ void band_body(const SwParams &prm, const uint32_t *_
             tp += G * TW;
         }
 
-        if constexpr (EXT) {
+        if constexpr (ZD) {
+            // the row's maximum so far arrives from the lane that finished this row one step ago; this lane's own maximum wins on
+            // a strict improvement only (the lower lanes hold the smaller columns), masked cells are minus infinity and never do
+            int rm = band_shr1(kBandNegInf, car_m);
+            int rc = band_shr1(0, car_c);
+            if (first) rm = kBandNegInf;
+            int m = z[0];
+#pragma unroll
+            for (int k = 1; k < K; ++k) m = max(m, z[k]);
+            int col = 0;
+#pragma unroll
+            for (int k = K - 1; k >= 0; --k) col = z[k] == m ? k : col; // the leftmost cell of the row that holds it
+            const bool mine = m > rm;
+            car_m = mine ? m : rm;
+            car_c = mine ? j0 + col : rc;
+            // the rule, rows 1 .. lb in order (lb is the last row with an in-band cell: the host trims the rows to the band).  Every
+            // lane runs it on what it holds; the group's last lane holds R(i) and c(i), and only its outcome is read
+            if ((uint32_t)(i - 1) < (uint32_t)lb && zstop < 0) {
+                if (car_m > zb) {
+                    zb = car_m;
+                    zbi = i;
+                    zbj = car_c;
+                } else if (zb - car_m > zdrop - ge * abs((i - zbi) - (car_c - zbj))) {
+                    zstop = i - 1;
+                }
+            }
+        } else if constexpr (EXT) {
             int m = z[0];
 #pragma unroll
             for (int k = 1; k < K; ++k) m = max(m, z[k]);
@@ -343,6 +380,13 @@ __device__ __forceinline__ void band_body(const SwParams &prm, const uint32_t *_
 
     const int quads = steps >> 2;
     for (int q = 0; q < quads; ++q) {
+        if constexpr (ZD) {
+            // leave once every group of the wave has terminated or passed its last row: the vote of a group is its last lane's
+            if (__builtin_amdgcn_ballot_w64(loader && zstop < 0 && t - gl <= lb) == 0) {
+                t = steps;
+                break;
+            }
+        }
         rows = q0;
         q0 = q1;
         q1 = q2;
@@ -359,7 +403,13 @@ __device__ __forceinline__ void band_body(const SwParams &prm, const uint32_t *_
 #pragma unroll 1
     while (t < steps) step();
 
-    if constexpr (EXT) {
+    if constexpr (ZD) {
+        if (loader) {
+            scores[g.out] = zb - gf;
+            pos[g.out] = zbi == 0 ? 0xffffffffu : ((uint32_t)zbi << 16) | (uint32_t)zbj;
+            stops[g.out] = zstop;
+        }
+    } else if constexpr (EXT) {
         best -= gf;
         uint32_t key = hit_i < 0 ? 0xffffffffu : ((uint32_t)hit_i << 16) | (uint32_t)(hit_i + d0 + hit_k);
         // over the group's lanes by the rule: score, then row, then column (G need not be a power of two)

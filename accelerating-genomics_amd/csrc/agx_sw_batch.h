@@ -65,7 +65,12 @@ struct agx_sw_batch {
     // misses the matrix); the fill's rows are counted from there.  SPANS in LOCAL and FIT keep seq / seq_off for the begin pass
     // agx_sw_batch_create_align_band_diag_cigar: band_at with cigar == 1 and align = SPANS; it keeps band_groups,
     // band_rec, band_cls, band_G and seq like a banded cigar batch, in every mode
-    bool band_at = false;
+    // agx_sw_batch_create_align_band_zdrop[_cigar]: a band_at batch in mode EXTEND whose fill is the z-drop build;
+    // band_stop receives per pair the last row looked at, or -1
+    bool band_at = false, zdrop_on = false;
+    int32_t zdrop = 0;
+    DevBuf band_stop;
+    PinBuf band_stop_stage;
     std::vector<int32_t> band_diag;
     std::vector<uint32_t> band_row0;
     agx_sw_scoring scoring{};
@@ -111,9 +116,12 @@ inline void band_limits(int mode, int64_t w, int64_t la, int64_t lb, int64_t &dl
 }
 
 // agx_sw_batch_create_align_band_diag's part of create_band: what to report and the centre diagonal of every pair (NULL: 0)
+// agx_sw_batch_create_align_band_zdrop adds its z-drop (zdrop_on; EXTEND only)
 struct BandAt {
     int what;
     const int32_t *diag;
+    bool zdrop_on = false;
+    int32_t zdrop = 0;
 };
 
 // ---- agx_sw.cpp

@@ -633,6 +633,28 @@ int agx_sw_align_band_diag_cigar(agx_ctx *ctx, const agx_sw_scoring *scoring, in
     return rc ? rc : align_once(b, [&](agx_sw_batch *x) { return agx_sw_batch_cigars(x, hits, op_off, ops, ops_cap); });
 }
 
+int agx_sw_batch_create_align_band_zdrop_cigar(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t band, const int32_t *diag,
+                                               int32_t zdrop, const uint8_t *bases, const uint64_t *off, const uint32_t *len, int64_t n_pairs,
+                                               agx_sw_batch **out)
+{
+    AGX_GUARD_BEGIN
+    const BandAt at{AGX_SW_ALIGN_SPANS, diag, true, zdrop};
+    return create_band(ctx, scoring, mode, band, bases, off, len, n_pairs, out, true, &at);
+    AGX_GUARD_END("agx_sw_batch_create_align_band_zdrop_cigar")
+}
+
+int agx_sw_align_band_zdrop_cigar(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t band, const int32_t *diag, int32_t zdrop,
+                                  const uint8_t *bases, const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_hit *hits,
+                                  int32_t *stops, uint64_t *op_off, uint32_t *ops, uint64_t ops_cap)
+{
+    agx_sw_batch *b = nullptr;
+    const int rc = agx_sw_batch_create_align_band_zdrop_cigar(ctx, scoring, mode, band, diag, zdrop, bases, off, len, n_pairs, &b);
+    return rc ? rc : align_once(b, [&](agx_sw_batch *x) {
+        const int r = agx_sw_batch_cigars(x, hits, op_off, ops, ops_cap);
+        return r || !stops ? r : agx_sw_batch_zdrop_stops(x, stops);
+    });
+}
+
 int agx_sw_cigar_in_band(const uint32_t *ops, uint64_t n_ops, int32_t dlo, int32_t dhi)
 {
     if (!ops && n_ops) return 0;

@@ -1,5 +1,5 @@
 /*
- * swAlign <file_path> [local|global|fit|extend|extend-query][+stats|+cigar|+band=W|+cigar+band=W|+band=W@D|+bandcigar=W@D]: where the best alignment of every pair ends and begins
+ * swAlign <file_path> [local|global|fit|extend|extend-query][+stats|+cigar|+band=W|+cigar+band=W|+band=W@D|+bandcigar=W@D][+zdrop=Z]: where the best alignment of every pair ends and begins
  * (default: local; the other modes are include/agx.h's "Alignment modes").
  * swAlign <file_path> <mode> <matrix_file> [gap_open gap_extend]: the same under a substitution matrix (gaps default to
  * -11 -1).  The matrix file is the usual text layout: '#' comment lines, one line of symbols, then one row per symbol
@@ -36,6 +36,9 @@
  * around the diagonal D AND its CIGAR inside that band (include/agx.h, "CIGARs for batches banded around a diagonal"): the lines
  * of "+band=W@D" with the CIGAR text appended as "+cigar" formats it, read with the line buffer of "+band=W".  W and D as in
  * "+band=W@D", both required; no matrix file.
+ * Or "+zdrop=Z" behind either of the last two on extend, in this place only (extend+band=64@0+zdrop=100,
+ * extend+bandcigar=64@0+zdrop=100): the extension terminates by the z-drop Z >= 0 (include/agx.h, "Z-drop for banded extension");
+ * the same lines as without the suffix.  Another mode, a negative or non-numeric Z, or the suffix anywhere else is a usage error.
  *   AGX_CLI_CHUNK_PAIRS   pairs per agx_sw_align call (default 262144)
  */
 #include <stdio.h>
@@ -129,8 +132,8 @@ int main(int argc, char *argv[])
 {
     static const char *const words[] = {"local", "global", "fit", "extend", "extend-query"}; /* AGX_SW_MODE_* 0..4 */
     int mode = argc == 2 ? AGX_SW_MODE_LOCAL : -1;
-    int with_stats = 0, with_cigar = 0, with_band = 0, with_diag = 0;
-    int32_t band = 0, diag = 0;
+    int with_stats = 0, with_cigar = 0, with_band = 0, with_diag = 0, with_zdrop = 0;
+    int32_t band = 0, diag = 0, zdrop = 0;
     for (int k = 0; (argc == 3 || argc == 4 || argc == 6) && k < 5; k++) {
         const size_t n = strlen(words[k]);
         if (!strcmp(argv[2], words[k])) mode = k;
@@ -156,9 +159,19 @@ int main(int argc, char *argv[])
             if (isdigit((unsigned char)*w) && *end == '@' && v <= 0x7fffffffL) {
                 const char *d = end + 1;
                 const long c = strtol(d, &end2, 10);
+                /* "+zdrop=Z" may follow on extend: digits only, up to the end of the word */
+                long z = -1;
+                if (k == AGX_SW_MODE_EXTEND && !strncmp(end2, "+zdrop=", 7) && isdigit((unsigned char)end2[7])) {
+                    char *end3;
+                    z = strtol(end2 + 7, &end3, 10);
+                    if (*end3 || z > 0x7fffffffL) z = -1;
+                    else end2 = end3;
+                }
                 if (isdigit((unsigned char)d[*d == '-']) && !*end2 && c >= -0x7fffffffL && c <= 0x7fffffffL) {
                     mode = k;
                     with_band = with_diag = 1;
+                    with_zdrop = z >= 0;
+                    zdrop = (int32_t)(z >= 0 ? z : 0);
                     with_cigar = band_cigar;
                     band = (int32_t)v;
                     diag = (int32_t)c;
@@ -187,7 +200,8 @@ int main(int argc, char *argv[])
                 "global+cigar+band=W, extend+cigar+band=W: the banded alignment with its CIGAR inside the band (in this order).\n"
                 "<mode>+band=W@D (fit+band=64@0, local+band=200@-1500): the alignment inside the band D-W <= j-i <= D+W around the\n"
                 "diagonal D, in any mode; not with +stats, +cigar or a matrix file.\n"
-                "<mode>+bandcigar=W@D (fit+bandcigar=64@-1500): the same with its CIGAR inside that band appended; no matrix file.\n",
+                "<mode>+bandcigar=W@D (fit+bandcigar=64@-1500): the same with its CIGAR inside that band appended; no matrix file.\n"
+                "extend+band=W@D+zdrop=Z, extend+bandcigar=W@D+zdrop=Z: the extension terminates by the z-drop Z >= 0; extend only.\n",
                 argv[0], argv[0]);
         return 1;
     }
@@ -259,8 +273,10 @@ int main(int argc, char *argv[])
                 if (!dg) {
                     fprintf(stderr, "swAlign: out of memory\n");
                     status = EXIT_FAILURE;
-                } else if (agx_sw_align_band_diag_cigar(ctx, NULL, mode, band, dg, t->bases, t->off, t->len, t->n_pairs, hits, op_off, ops, ops_cap) !=
-                           AGX_OK) {
+                } else if ((with_zdrop ? agx_sw_align_band_zdrop_cigar(ctx, NULL, mode, band, dg, zdrop, t->bases, t->off, t->len, t->n_pairs, hits, NULL,
+                                                                       op_off, ops, ops_cap)
+                                       : agx_sw_align_band_diag_cigar(ctx, NULL, mode, band, dg, t->bases, t->off, t->len, t->n_pairs, hits, op_off, ops,
+                                                                      ops_cap)) != AGX_OK) {
                     fprintf(stderr, "swAlign: %s\n", agx_last_error());
                     status = EXIT_FAILURE;
                 }
@@ -282,7 +298,10 @@ int main(int argc, char *argv[])
                 if (!dg) {
                     fprintf(stderr, "swAlign: out of memory\n");
                     status = EXIT_FAILURE;
-                } else if (agx_sw_align_band_diag(ctx, NULL, mode, AGX_SW_ALIGN_SPANS, band, dg, t->bases, t->off, t->len, t->n_pairs, hits) != AGX_OK) {
+                } else if ((with_zdrop ? agx_sw_align_band_zdrop(ctx, NULL, mode, AGX_SW_ALIGN_SPANS, band, dg, zdrop, t->bases, t->off, t->len,
+                                                                 t->n_pairs, hits, NULL)
+                                       : agx_sw_align_band_diag(ctx, NULL, mode, AGX_SW_ALIGN_SPANS, band, dg, t->bases, t->off, t->len, t->n_pairs,
+                                                                hits)) != AGX_OK) {
                     fprintf(stderr, "swAlign: %s\n", agx_last_error());
                     status = EXIT_FAILURE;
                 }

@@ -502,8 +502,8 @@ int agx_sw_cigar_in_band(const uint32_t *ops, uint64_t n_ops, int32_t dlo, int32
  * agx_sw_batch_hits the hits in the caller's pair order, agx_sw_batch_bind_scores is accepted and ignored, agx_sw_batch_info
  * works; agx_sw_batch_stats and agx_sw_batch_cigars return AGX_E_ARG.  ctx may be NULL: plan only.  scoring and byte 0x00 as in
  * "Banded alignment".  Unchanged: agx_sw_batch_create_align_band still refuses LOCAL, FIT and EXTEND_QUERY with AGX_E_ARG.
- * CIGARs come from "CIGARs for batches banded around a diagonal" below.  Deliberately left out: substitution matrices,
- * statistics, and a z-drop.
+ * CIGARs come from "CIGARs for batches banded around a diagonal" below, z-drop termination of EXTEND from "Z-drop for banded
+ * extension".  Deliberately left out: substitution matrices and statistics.
  */
 int agx_sw_batch_create_align_band_diag(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int what, int32_t band,
                                         const int32_t *diag /* n_pairs, or NULL = 0 for every pair */, const uint8_t *bases,
@@ -537,7 +537,7 @@ int agx_sw_align_band_diag(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode
  * beyond the budget alone in its chunk), agx_sw_cigar_info and the host's check of every CIGAR before it leaves (AGX_E_INTERNAL
  * naming the pair) are as in "CIGARs for banded batches".  ctx may be NULL: plan only.
  * Unchanged: a plain band-diag batch keeps answering agx_sw_batch_cigars with AGX_E_ARG; agx_sw_batch_stats on this batch gives
- * AGX_E_ARG.  Deliberately left out: substitution matrices, statistics, and a z-drop.
+ * AGX_E_ARG.  Deliberately left out: substitution matrices and statistics.
  */
 int agx_sw_batch_create_align_band_diag_cigar(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t band,
                                               const int32_t *diag /* n_pairs, or NULL = 0 for every pair */, const uint8_t *bases,
@@ -546,6 +546,58 @@ int agx_sw_batch_create_align_band_diag_cigar(agx_ctx *ctx, const agx_sw_scoring
 int agx_sw_align_band_diag_cigar(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t band, const int32_t *diag,
                                  const uint8_t *bases, const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_hit *hits,
                                  uint64_t *op_off, uint32_t *ops, uint64_t ops_cap);
+/*
+ * Z-drop for banded extension: AGX_SW_MODE_EXTEND inside a band around a diagonal that stops extending once the alignment has
+ * fallen apart -- a read whose tail is junk (a chimera, an adapter, the far side of a structural variant) neither pays for all of
+ * its rows nor picks up an unrelated high-scoring stretch further down the band.
+ * Everything is as in "Banded alignment around a diagonal", mode AGX_SW_MODE_EXTEND: the band dlo = c - w <= j - i <= dhi = c + w,
+ * the admission rule dlo <= 0 <= dhi, limits, scoring and the symbol rules, diag == NULL meaning 0.  One batch-wide integer
+ * `zdrop` is added.
+ * The rule: let last = min(lb, la - dlo), the last row with an in-band cell.  For row i, R(i) is the maximum of D[i][j] over the
+ * in-band j in 0..la and c(i) the smallest j that attains it.  The running best starts as B = D[0][0] = 0 at (bi, bj) = (0, 0).
+ * For i = 1, 2, .., last in order:
+ *   if R(i) > B: B = R(i), (bi, bj) = (i, c(i)); the drop test is not made in such a row;
+ *   otherwise, if B - R(i) > zdrop + |gap_extend| * |(i - bi) - (c(i) - bj)|, strictly, the extension TERMINATES AT ROW i: later
+ *   rows do not exist for this pair.
+ * This is ksw2's ksw_extz rule stated over rows; the second term forgives the extension cost of one long gap since the best cell.
+ * Reporting: the hit is B with end cell (bi - 1, bj - 1); score 0 keeps all four positions at -1; under AGX_SW_ALIGN_SPANS the
+ * begins are 0, as for EXTEND.  Per pair the library also reports stop = i - 1 for the terminating row i -- the index in b of the
+ * last row looked at -- and -1 when the fill ran through, which includes pairs with an empty side and pairs of score 0 that
+ * never dropped.
+ * Limits: 0 <= zdrop <= AGX_SW_ZDROP_MAX, AGX_E_ARG outside.  Under the supported scorings and lengths B - R(i) <= 7.9e5 + 1.32e8
+ * and the right side stays below 2^31, so nothing wraps and zdrop = AGX_SW_ZDROP_MAX never fires.
+ * Equivalences: with zdrop = AGX_SW_ZDROP_MAX the hits equal those of agx_sw_align_band_diag(AGX_SW_MODE_EXTEND) for the same
+ * band, diag, `what` and scoring, and every stop is -1; with a band that holds the whole matrix as well they equal those of
+ * agx_sw_align_mode(AGX_SW_MODE_EXTEND).  Example under the reference scoring (1, -1, -3, -1), w = 4, c = 0: a = AAAATTTTTTTT,
+ * b = AAAACCCCCCCC gives the hit (4, 0, 3, 0, 3) for every zdrop, stop = 4 + zdrop for zdrop = 0..7 and stop = -1 from 8 on.
+ * `mode` is kept in the signatures: anything but AGX_SW_MODE_EXTEND is AGX_E_ARG for now.
+ * A z-drop batch behaves like a band-diag batch in every other respect: launch and relaunch, agx_sw_batch_scores, _hits and
+ * _info, agx_sw_batch_bind_scores accepted and ignored, agx_sw_batch_stats AGX_E_ARG, ctx == NULL a plan-only batch.
+ * agx_sw_batch_zdrop_stops waits for the launched fill like agx_sw_batch_hits; on any other kind of batch it is AGX_E_ARG.  It
+ * checks -1 <= stop < lb and stop >= b_end for every pair (AGX_E_INTERNAL naming the pair).
+ * The cigar batch is a batch of "CIGARs for batches banded around a diagonal" whose hits come from the z-drop fill: the reported
+ * end cell is an in-band cell reached from (0, 0) inside the band, so the traced fill of the span, the band-aware walk and the
+ * host's checks apply unchanged.
+ * Deliberately left out: a z-drop for the unbanded EXTEND of agx_sw_align_mode, and an X-drop variant.
+ */
+#define AGX_SW_ZDROP_MAX 1000000000
+int agx_sw_batch_create_align_band_zdrop(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int what, int32_t band,
+                                         const int32_t *diag /* n_pairs, or NULL = 0 for every pair */, int32_t zdrop,
+                                         const uint8_t *bases, const uint64_t *off, const uint32_t *len, int64_t n_pairs,
+                                         agx_sw_batch **out);
+/* One-shot: create_align_band_zdrop + launch + hits + stops + destroy. */
+int agx_sw_align_band_zdrop(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int what, int32_t band, const int32_t *diag,
+                            int32_t zdrop, const uint8_t *bases, const uint64_t *off, const uint32_t *len, int64_t n_pairs,
+                            agx_sw_hit *hits, int32_t *stops /* n_pairs; may be NULL */);
+int agx_sw_batch_zdrop_stops(agx_sw_batch *b, int32_t *stops /* n_pairs */);
+int agx_sw_batch_create_align_band_zdrop_cigar(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t band, const int32_t *diag,
+                                               int32_t zdrop, const uint8_t *bases, const uint64_t *off, const uint32_t *len,
+                                               int64_t n_pairs, agx_sw_batch **out);
+/* One-shot: create_align_band_zdrop_cigar + launch + cigars + stops + destroy. */
+int agx_sw_align_band_zdrop_cigar(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t band, const int32_t *diag, int32_t zdrop,
+                                  const uint8_t *bases, const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_hit *hits,
+                                  int32_t *stops /* may be NULL */, uint64_t *op_off, uint32_t *ops, uint64_t ops_cap);
+
 /* Host only, no device.  How the traced fill of a span starts inside a banded batch's resident image.  The image holds the
  * query a behind `fpad` bytes and the rows b[row0 .. row0 + rows) behind one byte, packed for a fill from row0 in the band
  * dlo .. dhi COUNTED FROM row0 (j - (i - row0)) on `lanes` lanes per pair.  For a hit with a non-empty span on both sides the
