@@ -1389,6 +1389,18 @@ int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matri
         if (wide && ctx) agx_sw_pk2w_preload();
         if (trace) fprintf(stderr, "[agx_sw_batch_create] class period %d of %d\n", wide ? period : 4, period);
     }
+    // ---- staged wave priority of the biased packed fill (agx_sw_pk2_kernel.inc, "Staged priority"): only for a batch whose
+    // waves are ALL resident at once -- two on each of a CU's four SIMDs, the kernels' allocation (at most 256 VGPRs).  A batch
+    // that back-fills covers the tails of its waves with new ones, and there a wave near its end must not lose to a fresh one.
+    if (family == 2) {
+        const int64_t resident = ctx ? 8 * (int64_t)ctx->n_cu : 0;
+        bool stage = rising == 4 && n_waves_total > 0 && (int64_t)n_waves_total <= resident; // (the kernels with column classes have the build)
+        if (const char *e = agx_tune("AGX_SW_STAGE")) stage = stage && !(e[0] == '0' && !e[1]); // "0": no staging, for A/B
+        b->stage = stage ? 1 : 0;
+        if (trace)
+            fprintf(stderr, "[agx_sw_batch_create] staged priority %d: %lld waves, %lld resident at once\n", b->stage, (long long)n_waves_total,
+                    (long long)resident);
+    }
     b->info.n_pairs = n_pairs;
     b->info.cells = cells;
     b->info.padded_cells = padded;
@@ -1529,6 +1541,7 @@ int agx_sw_batch_launch(agx_sw_batch *b)
     if (b->pending && b->pending->ready) AGX_HIP(hipStreamWaitEvent(b->ctx->stream, b->pending->ready, 0));
     SwParams prm = b->prm;
     if (b->bound) prm.n_out = (uint32_t)b->n_pairs; // the caller's array has no spare slot
+    prm.stage = (uint32_t)b->stage;
     b->cig_valid = false; // what agx_sw_batch_cigars kept belongs to the launch before
     if (b->cigar == 2 && !b->trace_p && b->tr_dwords) {
         agx_set_error("agx_sw_batch_launch: a traced fill without its trace block");

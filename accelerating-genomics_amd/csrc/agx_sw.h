@@ -33,6 +33,9 @@ struct SwParams {
     // slots of the scores array a launch may write (packed kernels: a vacant half points at slot n_pairs, which exists in
     // the device array but not in a caller's page-locked one -- agx_sw_batch_bind_scores)
     uint32_t n_out;
+    // biased packed kernel: staged wave priority (agx_sw_pk2_kernel.inc, "Staged priority").  0 = none; 1 = a wave lowers its
+    // priority at 1/2, 3/4 and 7/8 of its quads of steps; 2 = at equal quarters (tools/sw_wave_timeline.py only)
+    uint32_t stage;
 };
 
 // Packed kernel: one group of G lanes carries two pairs (index 0 = low 16 bits, 1 = high 16 bits

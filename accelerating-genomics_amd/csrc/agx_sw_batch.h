@@ -86,6 +86,7 @@ struct agx_sw_batch {
     DevBuf table; // substitution-matrix mode: kSwMatDim^2 int16 entries
     int rising = 0; // biased packed fill: 1 = stored values rise by |ge| per step, 4 = and by |ge| per column in classes of four (agx_sw_pk2_kernel.hip, KC)
     bool wide = false; // rising == 4: the column classes' period is C / 2 in the classes built that way (sw_pk2_period), not four
+    int stage = 0; // biased packed fill: SwParams::stage of this batch's launches (set at create: all of its waves are resident at once)
     PinBuf out_stage; // page-locked landing block of the scores, taken at create: agx_sw_batch_scores allocates nothing
                       // (a first hipHostMalloc costs milliseconds, and hipvers' timed window is launch -> scores)
     bool matrix = false;

@@ -16,6 +16,36 @@ __global__ void __launch_bounds__(256) sw_fill_pk2(const SwParams prm, const uin
     pk2_body<C, KC>(prm, img, groups, waves[wave], scores);
 }
 
+// The column classes of period four (KC = 4) with the staged wave priority (SwParams::stage; agx_sw_pk2_kernel.inc, "Staged
+// priority"): kernels of their own, so that the unstaged ones stay what they are.  The host stages no other cell.
+template <int C>
+__global__ void __launch_bounds__(256) sw_fill_pk2_staged(const SwParams prm, const uint32_t *__restrict__ img,
+                                                          const SwGroup2 *__restrict__ groups,
+                                                          const SwWave *__restrict__ waves, uint32_t n_waves,
+                                                          int32_t *__restrict__ scores)
+{
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * 4u + (threadIdx.x >> 6));
+    if (wave >= n_waves) return;
+    pk2_body<C, 4, false, true>(prm, img, groups, waves[wave], scores);
+}
+
+__global__ void __launch_bounds__(256) sw_fill_pk2_any_staged(const SwParams prm, const uint32_t *__restrict__ img,
+                                                              const SwGroup2 *__restrict__ groups,
+                                                              const SwWave *__restrict__ waves, uint32_t n_waves,
+                                                              int32_t *__restrict__ scores)
+{
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * 4u + (threadIdx.x >> 6));
+    if (wave >= n_waves) return;
+    const SwWave w = waves[wave];
+    switch (__builtin_amdgcn_readfirstlane(w.reserved) & 0xffffu) { // columns per lane of this wave
+#define AGX_SW_CASE(CC) \
+    case CC: pk2_body<CC, 4, false, true>(prm, img, groups, w, scores); break;
+        AGX_SW_FOR_EACH_CLASS(AGX_SW_CASE)
+#undef AGX_SW_CASE
+    default: break;
+    }
+}
+
 // Mixed batches: ONE launch for every lane-tiling class.  Each wavefront reads its class (columns per lane)
 // from its record and runs that class's fill; the kernel is allocated the registers of the widest class
 // (214 VGPRs as its code object states them -- tools/kernel_resources.py --, two waves per SIMD: the fill is bound by
@@ -45,7 +75,10 @@ int launch(const SwParams &prm, const uint32_t *img, const SwGroup2 *groups, con
            int32_t *scores, hipStream_t s)
 {
     const uint32_t blocks = (n_waves + 3) / 4;
-    hipLaunchKernelGGL((sw_fill_pk2<C, KC>), dim3(blocks), dim3(256), 0, s, prm, img, groups, waves, n_waves, scores);
+    if (KC == 4 && prm.stage)
+        hipLaunchKernelGGL((sw_fill_pk2_staged<C>), dim3(blocks), dim3(256), 0, s, prm, img, groups, waves, n_waves, scores);
+    else
+        hipLaunchKernelGGL((sw_fill_pk2<C, KC>), dim3(blocks), dim3(256), 0, s, prm, img, groups, waves, n_waves, scores);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -57,7 +90,9 @@ int agx_sw_pk2_launch_any(int rising, bool wide, const SwParams &prm, const uint
     if (n_waves == 0) return 0;
     if (rising == 4 && wide) return agx_sw_pk2w_launch_any(prm, img, groups, waves, n_waves, scores, s);
     const uint32_t blocks = (n_waves + 3) / 4;
-    if (rising == 4)
+    if (rising == 4 && prm.stage)
+        hipLaunchKernelGGL(sw_fill_pk2_any_staged, dim3(blocks), dim3(256), 0, s, prm, img, groups, waves, n_waves, scores);
+    else if (rising == 4)
         hipLaunchKernelGGL(sw_fill_pk2_any<4>, dim3(blocks), dim3(256), 0, s, prm, img, groups, waves, n_waves, scores);
     else if (rising)
         hipLaunchKernelGGL(sw_fill_pk2_any<1>, dim3(blocks), dim3(256), 0, s, prm, img, groups, waves, n_waves, scores);

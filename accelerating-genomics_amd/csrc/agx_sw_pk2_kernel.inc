@@ -165,9 +165,20 @@ __device__ __forceinline__ void bytes_head(uint32_t &zl, uint32_t &fl, uint32_t 
 // read anyway: the chain of maxima then has the whole step to run in, not the few instructions left behind the last
 // column, where each dependent v_pk_maximum3_f16 drew an s_nop.  The tail steps (steps mod 4) run at phase 0 and
 // rotate the maxima by one place after each step; the last step's z are taken behind the loop.
-template <int C, bool FAST, int KC, bool WIDE = false>
+//
+// ST = wave stamps, for tools/sw_wave_timeline.hip alone: a diagnostic build hands in an object whose take<K>() reads the cycle
+// counter at place K of the wave -- 1 in front of the first quad of steps, 2 behind the last step, 3 in front of the result
+// store (0 and what follows the store are the diagnostic kernel's own).  The library's kernels pass none: SwNoStamps::take is
+// empty, and their code is instruction for instruction what it is without the parameter.
+struct SwNoStamps {
+    template <int K>
+    __device__ __forceinline__ void take() const {}
+};
+
+template <int C, bool FAST, int KC, bool WIDE = false, bool STAGED = false, class ST = SwNoStamps>
 __device__ __forceinline__ void pk2_fill(const SwParams &prm, const uint32_t *__restrict__ img, const SwGroup2 &g, const SwWave &w,
-                                         int32_t *__restrict__ scores, int lane, int G, int gl, bool active, bool start, bool feeder)
+                                         int32_t *__restrict__ scores, int lane, int G, int gl, bool active, bool start, bool feeder,
+                                         const ST &st = ST{})
 {
     constexpr int XW = (C + 3) / 4; // dwords holding this lane's C symbols
     constexpr bool RISE = KC > 0;
@@ -409,7 +420,33 @@ __device__ __forceinline__ void pk2_fill(const SwParams &prm, const uint32_t *__
         step(std::integral_constant<int, 3>{}, std::integral_constant<int, 3>{}, cc);
         rise4();
     };
+    // Staged priority (STAGED; DESIGN.md 4.1, profiles/sw_wave_timeline.md).  Of the two waves of a SIMD the older one takes
+    // nearly every issue slot: left alone it leaves its loop when the younger has done a tenth of its own, and the younger then
+    // runs the rest alone.  With the staging a wave lowers its own priority as it advances -- s_setprio 3, 2, 1, 0 at the
+    // boundaries of four segments of its quads -- so the wave that lags has the higher priority and the pair stays together to
+    // within a segment.  The segments shrink (boundaries at 1/2, 3/4, 7/8 of the quads; prm.stage == 2, the tool's comparison:
+    // equal quarters), which bounds what the last wave runs alone.  One uniform scalar compare and branch a quad, nothing per
+    // step; the host asks for it only for a launch whose waves are all resident at once (agx_sw.cpp): where new waves back-fill,
+    // a wave near its end must not lose to a fresh one.  It is a build of its own, in kernels of its own (sw_fill_pk2w_staged,
+    // ...): in the mixed batches' launches, which are not staged, even that compare cost 0.2 %.
+    const int quads = steps >> 2;
+    int stage_at = 0, stage_lv = 3;
+    auto staging = [&](int q) __attribute__((always_inline)) {
+        if (STAGED && q == stage_at) {
+            const bool even = prm.stage == 2;
+            int next = -1;
+            switch (stage_lv) {
+            case 3: __builtin_amdgcn_s_setprio(3); next = even ? quads >> 2 : quads >> 1; break;
+            case 2: __builtin_amdgcn_s_setprio(2); next = even ? quads >> 1 : (3 * quads) >> 2; break;
+            case 1: __builtin_amdgcn_s_setprio(1); next = even ? (3 * quads) >> 2 : (7 * quads) >> 3; break;
+            default: __builtin_amdgcn_s_setprio(0); break;
+            }
+            stage_at = stage_lv > 0 ? max(next, q + 1) : -1;
+            --stage_lv;
+        }
+    };
     auto take = [&](int q, int r) __attribute__((always_inline)) {
+        staging(q);
         rowsA = row_selA(q, nextA[r]);
         rowsB = row_selB(q, nextB[r]);
         nextA[r] = loadA(q + PF);
@@ -418,7 +455,6 @@ __device__ __forceinline__ void pk2_fill(const SwParams &prm, const uint32_t *__
         // registers (the one-launch kernel at 34 and 36 columns: 165 instructions ahead of their wait)
         if constexpr (WIDE) __builtin_amdgcn_sched_barrier(0);
     };
-    const int quads = steps >> 2;
     // FAST: the corner falls at step capA_t / capB_t of a group's last lane, so the quads before the wave's first such
     // step run without looking for it (a loop of their own: a branch around the test inside the loop is if-converted)
     int cap_first = 0x7fffffff;
@@ -430,6 +466,7 @@ __device__ __forceinline__ void pk2_fill(const SwParams &prm, const uint32_t *__
     const int quads_free = min(quads, cap_first >> 2);
     constexpr std::integral_constant<bool, false> no_cap{};
     constexpr std::integral_constant<bool, FAST> cap{};
+    st.template take<1>();
     int q = 0;
     if constexpr (PF == 1) {
         if constexpr (FAST) {
@@ -480,6 +517,7 @@ __device__ __forceinline__ void pk2_fill(const SwParams &prm, const uint32_t *__
             best[NM - 1] = b0 + (uint32_t)NM * prm.age2;
         }
     }
+    st.template take<2>();
     if constexpr (KC > 1) { // the maxima now stand at (steps + 2 + m) |ge|: all to the top one's offset, then to r(steps - 1)
 #pragma unroll
         for (int m = 0; m + 1 < NM; ++m) best[NM - 1] = umax2(best[NM - 1], best[m] + (uint32_t)(NM - 1 - m) * prm.age2);
@@ -513,6 +551,7 @@ __device__ __forceinline__ void pk2_fill(const SwParams &prm, const uint32_t *__
         const int src = (lane * G) & 63;
         const int sa = __shfl((int)(bestv & 0xffffu) - off, src), sb = __shfl((int)(bestv >> 16) - off, src);
         const uint32_t oa = (uint32_t)__shfl((int)g.out[0], src), ob = (uint32_t)__shfl((int)g.out[1], src);
+        st.template take<3>();
         if (lane < (int)w.n_groups) {
             if (ob == oa + 1u && !(oa & 1u) && ob < prm.n_out)
                 *reinterpret_cast<int2 *>(scores + oa) = make_int2(sa, sb);
@@ -524,9 +563,9 @@ __device__ __forceinline__ void pk2_fill(const SwParams &prm, const uint32_t *__
     }
 }
 
-template <int C, int KC, bool WIDE = false>
+template <int C, int KC, bool WIDE = false, bool STAGED = false, class ST = SwNoStamps>
 __device__ __forceinline__ void pk2_body(const SwParams &prm, const uint32_t *__restrict__ img, const SwGroup2 *__restrict__ groups,
-                                         const SwWave w, int32_t *__restrict__ scores)
+                                         const SwWave w, int32_t *__restrict__ scores, const ST &st = ST{})
 {
     static_assert(C % 2 == 0, "the running maximum takes two columns per instruction");
     // column classes cost ten instructions a step and save three quarters of one per column: narrow lanes do without
@@ -554,9 +593,9 @@ __device__ __forceinline__ void pk2_body(const SwParams &prm, const uint32_t *__
     }
     // bit 16 of the wave record's class word: set by the pack kernel when every pair of the wave is DNA-coded
     if (__builtin_amdgcn_readfirstlane(w.reserved >> 16) & 1u)
-        pk2_fill<C, true, KCC, W>(prm, img, g, w, scores, lane, G, gl, active, start, feeder);
+        pk2_fill<C, true, KCC, W, STAGED>(prm, img, g, w, scores, lane, G, gl, active, start, feeder, st);
     else
-        pk2_fill<C, false, KCC, W>(prm, img, g, w, scores, lane, G, gl, active, start, feeder);
+        pk2_fill<C, false, KCC, W, STAGED>(prm, img, g, w, scores, lane, G, gl, active, start, feeder, st);
 }
 
 } // namespace

@@ -17,6 +17,36 @@ __global__ void __launch_bounds__(256) sw_fill_pk2w(const SwParams prm, const ui
     pk2_body<C, 4, true>(prm, img, groups, waves[wave], scores);
 }
 
+// the same with the staged wave priority (SwParams::stage; agx_sw_pk2_kernel.inc, "Staged priority"): kernels of their own, so
+// that the unstaged ones stay what they are
+template <int C>
+__global__ void __launch_bounds__(256) sw_fill_pk2w_staged(const SwParams prm, const uint32_t *__restrict__ img,
+                                                           const SwGroup2 *__restrict__ groups,
+                                                           const SwWave *__restrict__ waves, uint32_t n_waves,
+                                                           int32_t *__restrict__ scores)
+{
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * 4u + (threadIdx.x >> 6));
+    if (wave >= n_waves) return;
+    pk2_body<C, 4, true, true>(prm, img, groups, waves[wave], scores);
+}
+
+__global__ void __launch_bounds__(256) sw_fill_pk2w_any_staged(const SwParams prm, const uint32_t *__restrict__ img,
+                                                               const SwGroup2 *__restrict__ groups,
+                                                               const SwWave *__restrict__ waves, uint32_t n_waves,
+                                                               int32_t *__restrict__ scores)
+{
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * 4u + (threadIdx.x >> 6));
+    if (wave >= n_waves) return;
+    const SwWave w = waves[wave];
+    switch (__builtin_amdgcn_readfirstlane(w.reserved) & 0xffffu) { // columns per lane of this wave
+#define AGX_SW_CASE(CC) \
+    case CC: pk2_body<CC, 4, true, true>(prm, img, groups, w, scores); break;
+        AGX_SW_FOR_EACH_CLASS(AGX_SW_CASE)
+#undef AGX_SW_CASE
+    default: break;
+    }
+}
+
 // the one launch of a mixed batch (sw_fill_pk2_any<4>): every class at its own period
 __global__ void __launch_bounds__(256) sw_fill_pk2w_any(const SwParams prm, const uint32_t *__restrict__ img,
                                                         const SwGroup2 *__restrict__ groups,
@@ -41,7 +71,10 @@ int launch(const SwParams &prm, const uint32_t *img, const SwGroup2 *groups, con
 {
     if constexpr (sw_pk2_period(C) > 4) {
         const uint32_t blocks = (n_waves + 3) / 4;
-        hipLaunchKernelGGL((sw_fill_pk2w<C>), dim3(blocks), dim3(256), 0, s, prm, img, groups, waves, n_waves, scores);
+        if (prm.stage)
+            hipLaunchKernelGGL((sw_fill_pk2w_staged<C>), dim3(blocks), dim3(256), 0, s, prm, img, groups, waves, n_waves, scores);
+        else
+            hipLaunchKernelGGL((sw_fill_pk2w<C>), dim3(blocks), dim3(256), 0, s, prm, img, groups, waves, n_waves, scores);
         return hipGetLastError() == hipSuccess ? 0 : -1;
     } else
         return -2; // no wide build of this class
@@ -54,7 +87,10 @@ int agx_sw_pk2w_launch_any(const SwParams &prm, const uint32_t *img, const SwGro
 {
     if (n_waves == 0) return 0;
     const uint32_t blocks = (n_waves + 3) / 4;
-    hipLaunchKernelGGL(sw_fill_pk2w_any, dim3(blocks), dim3(256), 0, s, prm, img, groups, waves, n_waves, scores);
+    if (prm.stage)
+        hipLaunchKernelGGL(sw_fill_pk2w_any_staged, dim3(blocks), dim3(256), 0, s, prm, img, groups, waves, n_waves, scores);
+    else
+        hipLaunchKernelGGL(sw_fill_pk2w_any, dim3(blocks), dim3(256), 0, s, prm, img, groups, waves, n_waves, scores);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
