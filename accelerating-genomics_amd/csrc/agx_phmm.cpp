@@ -976,7 +976,15 @@ int create_batch(agx_ctx *ctx, const agx_phmm_desc *d, const double *const prob[
     // gap-continuation quality of Phred 0 or below, a read base outside ACGTN or a haplotype base outside ACGT anywhere
     // in the batch keeps the plain cell
     std::atomic<bool> not_fast{false}, not_dna{false}; // not_dna: a read base outside ACGTN or a haplotype base outside ACGT
-    std::atomic<bool> wild{false};                     // a quality byte below '!' (as a signed char): no read trains
+    // wild: a read whose state can run away -- a quality byte below '!' (as a signed char: a "probability" above 1), or a row with
+    // Qi + Qd > 1 (both gap qualities of Phred 0 ... 3; 3 + 3 is over 1, 3 + 4 is not): 1 - (Qi + Qd) < 0 there, the recurrence is
+    // no longer sub-stochastic and its state alternates in sign and grows.  No read trains in such a batch.
+    std::atomic<bool> wild{false};
+    static const auto gap_prob = [] { // Q of a gap quality byte from '!' on, as build_lut() has it
+        std::array<double, 256> t{};
+        for (int c = 0; c < 128; ++c) t[c] = pow(10.0, -(c - 33.0) * 0.1);
+        return t;
+    }();
     static const auto dna_table = [] {
         std::array<uint8_t, 256> t{};
         for (const char *p = "ACGT"; *p; ++p) t[(uint8_t)*p] = 3; // bit 0: allowed in a read, bit 1: in a haplotype
@@ -990,7 +998,10 @@ int create_batch(agx_ctx *ctx, const agx_phmm_desc *d, const double *const prob[
                 for (uint64_t k = d->read_off[r]; k < d->read_off[r + 1]; ++k) {
                     zero |= packed && (int8_t)d->q_gcp[k] <= (int8_t)'!'; // signed as the reference's char: 0x80.. are "probabilities" above 1
                     other |= !(dna_table[d->read_bases[k]] & 1);
-                    low |= packed && ((int8_t)d->q_base[k] < (int8_t)'!' || (int8_t)d->q_ins[k] < (int8_t)'!' || (int8_t)d->q_del[k] < (int8_t)'!');
+                    // (a byte below '!' in either gap track, or two gap qualities whose sum can pass 1: only with one of them below Phred 4)
+                    const int8_t gap_lo = std::min((int8_t)d->q_ins[k], (int8_t)d->q_del[k]);
+                    low |= packed && ((int8_t)d->q_base[k] < (int8_t)'!' ||
+                                      (gap_lo < (int8_t)'!' + 4 && (gap_lo < (int8_t)'!' || gap_prob[d->q_ins[k]] + gap_prob[d->q_del[k]] > 1.0)));
                 }
             if (zero || other) not_fast.store(true, std::memory_order_relaxed);
             if (low) wild.store(true, std::memory_order_relaxed);
@@ -1049,8 +1060,10 @@ int create_batch(agx_ctx *ctx, const agx_phmm_desc *d, const double *const prob[
     const bool lut_prior = f64 && !probs && have_tracks && !not_dna.load() && (!lut_ring || !agx_tune("AGX_PHMM_NO_RING")) && !agx_tune("AGX_PHMM_NO_LUT");
     const size_t n_work = gen0.size(); // pairs with work (every pair of the batch, unless a read or haplotype is empty)
     PlanOut pmain;
-    // read trains: the fast cell only, and only on qualities that are probabilities (a byte below '!' is a "probability"
-    // above 1: a first read whose state ran to infinity there would hand NaN to the second through the reset row's 0 x inf)
+    // read trains: the fast cell only, and only where no read's state can run away (`wild` above: a quality byte below '!', or a
+    // row with Qi + Qd > 1 -- legal bytes, Phred 0 ... 3): a first read whose state ran to infinity would hand NaN to the second
+    // through the reset row's 0 x inf.  (Seen on the device with both gap qualities at Phred 0 and reads of 250 bases: the second
+    // read's NaN sums went to the double rescue pass, so its results stayed right but were no longer the plain schedule's bits.)
     const int trains_opt = ctx ? ctx->opt_phmm_trains : AGX_PHMM_TRAINS_AUTO;
     const bool may_train = packed && !not_fast.load() && !wild.load() && !agx_tune("AGX_PHMM_PLAIN_CELL") && !agx_tune("AGX_PHMM_NO_TRAINS");
     rc = packed ? make_plan(seed, gen0, 3, 2, false, false, trace, may_train ? (trains_opt == AGX_PHMM_TRAINS_ON ? 2 : trains_opt == AGX_PHMM_TRAINS_OFF ? 1 : 0) : 1, pmain)

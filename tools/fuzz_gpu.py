@@ -35,6 +35,9 @@ def phmm_case():
             n = int(rng.integers(0 if rng.random() < 0.05 else 1, hmax + 1))
             haps.append(rand_seq(n, ACGTN if rng.random() < 0.3 else ACGTN[:4]))
         reads = []
+        # one region in five: the whole clean quality range -- base '!' ... '~', gaps Phred 4 ... 93 (Qi + Qd <= 1 in every row: below
+        # that the reference itself gives negative sums), gap continuation 1 ... 93 (tests/phmm_range_cases.py); the others as ever
+        base_q, gap_q, gcp_q = ((0, 94), (4, 94), (1, 94)) if rng.random() < 0.2 else ((2, 42), (20, 46), (5, 20))
         rmax = int(rng.choice([3, 30, 150, 400, 1000], p=[0.2, 0.25, 0.3, 0.2, 0.05]))
         for _r in range(int(rng.integers(1, 12))):
             R = int(rng.integers(0 if rng.random() < 0.05 else 1, rmax + 1))
@@ -47,7 +50,7 @@ def phmm_case():
             else:
                 bases = rand_seq(R, ACGTN)
             q = lambda lo, hi: (rng.integers(lo, hi, size=R) + 33).astype(np.uint8).tobytes()
-            reads.append((bases, q(2, 42), q(20, 46), q(20, 46), q(5, 20)))
+            reads.append((bases, q(*base_q), q(*gap_q), q(*gap_q), q(*gcp_q)))
         regions.append((reads, haps))
     return synth.phmm_from_regions(regions)
 
