@@ -130,6 +130,127 @@ int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matri
                  const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_batch **out, bool defer = false, int align = 0, int mode = 0,
                  int stats = 0, int cigar = 0);
 
+// ---- agx_sw_plan.cpp: the host planner, stage by stage as create_batch calls it ("create pipeline")
+struct Tiling {
+    int cls; // index into kSwClasses
+    int G;
+};
+
+// The choice for one shorter length lx as a function of the longer length ly: cost_i(ly) = (ly + G_i - 1) * w_i
+// is a line per class, the best class is their lower envelope -- a handful of segments.
+struct TilingSeg {
+    uint32_t ly_from; // the segment covers [ly_from, next segment's ly_from)
+    uint8_t cls, G;
+    double w;
+};
+struct TilingTable {
+    std::vector<uint32_t> first; // index of lx's first segment; first[lx + 1] ends it (no segment = no class spans lx)
+    std::vector<TilingSeg> segs;
+    inline bool pick(uint32_t lx, uint32_t ly, Tiling *t, double *cost) const
+    {
+        const uint32_t a = first[lx], b = first[lx + 1];
+        if (a == b) return false;
+        uint32_t k = a;
+        while (k + 1 < b && segs[k + 1].ly_from <= ly) ++k;
+        const TilingSeg &s = segs[k];
+        *t = Tiling{s.cls, s.G};
+        if (cost) *cost = (double)(ly + s.G - 1) * s.w;
+        return true;
+    }
+};
+// The full tiling table of a kernel family (every class allowed, no tail term, every shorter length up to the
+// family's limit): what a device-planned batch is tiled with.  Made once per process.
+const TilingTable &full_tiling_table(int family);
+// per-class cost table of the kernel family a batch runs (relative lane time per padded cell)
+const double *class_costs(int family);
+// knobs of the tuning build that the create reads as well as the planner (each read once per process)
+double tail_beta_override(); // AGX_SW_TAIL_BETA; < 0 = none
+int max_classes_override();  // AGX_SW_MAX_CLASSES; 0 = none
+
+constexpr uint8_t kClsEmpty = 255;   // an empty side: nothing to fill
+constexpr uint8_t kClsUntiled = 254; // pass A done, no tiling yet
+struct PairPlan {                    // 12 bytes: the sorts move these
+    uint32_t pair;
+    uint32_t ly;
+    uint16_t lxo; // lx | (1 = sequence 2p+1 is the shorter one) << 15, as the group records carry it
+    uint8_t cls;
+    uint8_t G;
+    uint32_t lx() const { return lxo & 0x7fffu; }
+};
+// pair p as pass A leaves it: oriented (an align batch keeps its first sequence across the lanes), empty or not yet tiled
+inline void init_pair_plan(PairPlan &pp, int64_t p, uint32_t la, uint32_t lb, int align)
+{
+    pp = PairPlan{};
+    pp.pair = (uint32_t)p;
+    pp.cls = kClsEmpty;
+    if (la == 0 || lb == 0) return; // no interior cell: score stays 0
+    const bool second_short = !align && lb < la; // ties keep file order (antidiagonalSmithWaterman.c:229-244)
+    pp.lxo = (uint16_t)((second_short ? lb : la) | (second_short ? 0x8000u : 0u));
+    pp.ly = second_short ? la : lb;
+    pp.cls = kClsUntiled;
+}
+
+// Boyer-Moore majority vote over a sample of at most 512 pairs, every stride-th one below n_pairs.  shape_at(p, &sh): false
+// for a pair with nothing to fill.  -> the votes left (> 0: *cand may be a majority, to be counted)
+template <typename ShapeAt>
+int sampled_majority_shape(size_t n_pairs, size_t stride, ShapeAt shape_at, uint32_t *cand)
+{
+    int votes = 0;
+    for (size_t k = 0; k < 512 && k * stride < n_pairs; ++k) {
+        uint32_t sh;
+        if (!shape_at(k * stride, &sh)) continue;
+        if (votes == 0) {
+            *cand = sh;
+            votes = 1;
+        } else
+            votes += sh == *cand ? 1 : -1;
+    }
+    return votes;
+}
+
+// the kernel a batch runs and what the planner needs to know of it (choose_kernel, agx_sw.cpp)
+struct KernelChoice {
+    int family = 0, rising = 0;
+    bool packed = false;     // families 1 .. 3: two pairs per lane group
+    bool coded_plan = false; // the packed plan of the biased fill (one launch for all classes)
+    const double *costs = nullptr;
+    int slots = 1;
+};
+
+// one (class, G) run of the sorted plan: entry j of the run is slot j % slots of its group j / slots,
+// a wave takes 64 / G groups
+struct Bucket {
+    size_t first = 0, count = 0;     // entries of plan[]
+    size_t group0 = 0, n_groups = 0; // group records
+    size_t wave0 = 0, n_waves = 0;
+    int cls = 0, G = 0;
+};
+
+// what the rest of a create needs of a plan, whoever made it
+struct PlanLayout {
+    size_t n_groups = 0, n_waves_total = 0, groups_bytes = 0, waves_bytes = 0, img_dw = 0;
+    std::vector<ClassLaunch> launches;
+    uint32_t launched_classes = 0; // bit k: some wave runs kSwClasses[k]
+    int64_t padded = 0;
+    // host-made plans only: the runs of plan[], the wave records and every entry's image offsets
+    std::vector<Bucket> buckets;
+    std::vector<SwWave> waves;
+    std::vector<uint32_t> x_dw, y_dw;
+};
+
+// uniform batches: one tiling for the whole shape, file order kept.  false: no class fits, the host planner takes the batch
+bool plan_uniform(std::vector<PairPlan> &all, uint32_t shape, int n_cu, const KernelChoice &kc, bool matrix, std::vector<PairPlan> &plan);
+// passes B and C: tiling per pair, the batch-level rules, the two sorts.  Empties `all`; *t_plan: when the tiling was done
+int plan_host(std::vector<PairPlan> &all, const std::vector<uint8_t> &present, uint32_t longest_long, int n_cu, const KernelChoice &kc, bool matrix,
+              std::vector<PairPlan> &plan, double *t_plan);
+// pass D of a device-made plan: extents from the pairs per (class, G) bucket; bt receives the planner kernels' table
+// (entries before, count, first group, groups, first wave of each bucket), *entries the pairs with something to fill
+PlanLayout layout_from_buckets(const std::vector<uint32_t> &hist, int slots, uint32_t *bt, size_t *entries);
+// pass D of a host-made plan: buckets, waves in dispatch order, launches, image offsets
+int layout_from_plan(const std::vector<PairPlan> &plan, const KernelChoice &kc, size_t img0, PlanLayout &lay);
+void write_group_records(const PlanLayout &lay, const std::vector<PairPlan> &plan, const KernelChoice &kc, int64_t n_pairs, void *groups_data);
+void write_trace_records(const PlanLayout &lay, const std::vector<PairPlan> &plan, int64_t n_pairs, agx_sw_batch *b);
+
 // ---- agx_sw_align.cpp
 agx_sw_hit empty_side_hit(int mode, int what, const agx_sw_scoring &sc, uint32_t la, uint32_t lb);
 int create_align(const char *who, agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matrix *matrix, int mode, int what,

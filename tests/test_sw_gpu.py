@@ -479,3 +479,31 @@ def test_int32_kernel_with_the_coded_match_across_scorings(ctx, oracle):
                 dev.close()
     finally:
         ctx.set_option(agx.OPT_SW_KERNEL, agx.SW_KERNEL_AUTO)
+
+
+def test_plan_on_a_device_is_the_plan_only_plan():
+    """A host-made plan does not depend on whether a device is there: for the uniform 1024 x 150 x 150 batch, the mixed 300 of
+    32..512 and the 500 protein pairs under BLOSUM62 of tests/sw_plan_cases.py, created on device 0 in a child process under
+    AGX_TRACE_CREATE, the "plan digest" line (from the host copies of the records that were uploaded) equals the plan-only one
+    of tests/golden/sw_plan_digests.json.  Plan-only batches are tiled for 256 CUs and never staged; the child runs under
+    AGX_SW_STAGE=0, so that the staged-priority word of the digest is the plan-only one, and a case is compared whenever its
+    family, class-period and staged-priority lines equal the recorded ones: the matrix batch on any device (family 0, no such
+    choice), all three on a device of 256 CUs."""
+    import json
+
+    from tests import sw_plan_cases as pc
+
+    with open(os.path.join(os.path.dirname(__file__), "golden", "sw_plan_digests.json")) as f:
+        golden = json.load(f)
+    names = ["uniform_1024", "mixed_300", "matrix_500"]
+    got, err = pc.run_group("default", names=names, device=True, extra_env={"AGX_SW_STAGE": "0"})
+    assert sorted(got) == sorted(names), err[-2000:]
+    compared = []
+    for name in names:
+        want = golden[name]
+        if all(got[name].get(k) == want.get(k) for k in ("family", "period", "staged")):
+            assert got[name]["digest"] == want["digest"] and got[name]["info"] == want["info"], (name, got[name], want, err[-2000:])
+            compared.append(name)
+    assert "matrix_500" in compared, (got, err[-2000:])
+    if " 2048 resident at once" in err:  # 8 waves on each of 256 CUs
+        assert compared == names, (got, err[-2000:])
