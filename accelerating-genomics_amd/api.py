@@ -60,6 +60,8 @@ SYMBOLS = [
     "agx_sw_batch_create_align_band_cigar", "agx_sw_align_band_cigar", "agx_sw_band_cigar_bytes_bound", "agx_sw_cigar_in_band",
     "agx_sw_batch_create_align_band_diag", "agx_sw_align_band_diag",
     "agx_sw_batch_create_align_band_diag_cigar", "agx_sw_align_band_diag_cigar", "agx_sw_band_span_record",
+    "agx_sw_batch_create_align_band_diag_matrix", "agx_sw_align_band_diag_matrix",
+    "agx_sw_batch_create_align_band_diag_matrix_cigar", "agx_sw_align_band_diag_matrix_cigar",
     "agx_sw_batch_create_align_band_zdrop", "agx_sw_align_band_zdrop", "agx_sw_batch_zdrop_stops",
     "agx_sw_batch_create_align_band_zdrop_cigar", "agx_sw_align_band_zdrop_cigar",
     "agx_sw_score", "agx_sw_score_multi", "agx_sw_score_devices", "agx_sw_shard_cuts",
@@ -232,6 +234,14 @@ def lib():
                                                                 C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)]
         l.agx_sw_align_band_diag_cigar.argtypes = [C.c_void_p, C.POINTER(SwScoring), C.c_int, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                                    C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
+        l.agx_sw_batch_create_align_band_diag_matrix.argtypes = [C.c_void_p, C.POINTER(SwMatrix), C.c_int, C.c_int, C.c_int32, C.c_void_p, C.c_void_p,
+                                                                 C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)]
+        l.agx_sw_align_band_diag_matrix.argtypes = [C.c_void_p, C.POINTER(SwMatrix), C.c_int, C.c_int, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p, C.c_int64, C.c_void_p]
+        l.agx_sw_batch_create_align_band_diag_matrix_cigar.argtypes = [C.c_void_p, C.POINTER(SwMatrix), C.c_int, C.c_int32, C.c_void_p, C.c_void_p,
+                                                                       C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)]
+        l.agx_sw_align_band_diag_matrix_cigar.argtypes = [C.c_void_p, C.POINTER(SwMatrix), C.c_int, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                          C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
         l.agx_sw_batch_create_align_band_zdrop.argtypes = [C.c_void_p, C.POINTER(SwScoring), C.c_int, C.c_int, C.c_int32, C.c_void_p, C.c_int32,
                                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)]
         l.agx_sw_align_band_zdrop.argtypes = [C.c_void_p, C.POINTER(SwScoring), C.c_int, C.c_int, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
@@ -360,11 +370,18 @@ class Context:
                  zdrop=None) -> "SwBatch":
         return SwBatch(self, b, scoring, matrix, align, mode, stats, cigar, band, diag, zdrop)
 
-    def sw_align_band_diag(self, b, mode, band, diag=None, what=SW_ALIGN_SPANS, scoring=None, zdrop=None):
+    def sw_align_band_diag(self, b, mode, band, diag=None, what=SW_ALIGN_SPANS, scoring=None, zdrop=None, matrix=None):
         """b: synth.SWBatch -> SwHit records of the alignment inside the band diag - band <= j - i <= diag + band (include/agx.h,
         "Banded alignment around a diagonal"), one-shot.  mode: any SW_MODE_*; diag: None (0), one int, or one per pair.
-        zdrop=Z (SW_MODE_EXTEND only; "Z-drop for banded extension"): -> (SwHit records, stops int32: the last row of b looked at, or -1)."""
+        zdrop=Z (SW_MODE_EXTEND only; "Z-drop for banded extension"): -> (SwHit records, stops int32: the last row of b looked at, or -1).
+        matrix: an SwMatrix instead of scoring ("Banded alignment around a diagonal under a substitution matrix"); not with zdrop."""
         out = np.empty(b.n_pairs, SwHit)
+        if matrix is not None:
+            if scoring is not None or zdrop is not None:
+                raise AgxError(E_ARG, "matrix= takes the place of scoring= and does not combine with zdrop=")
+            _check(lib().agx_sw_align_band_diag_matrix(self._h, C.byref(matrix), mode, what, band, _ptr(_diag(diag, b.n_pairs)), _ptr(b.bases),
+                                                       _ptr(b.off), _ptr(b.len), b.n_pairs, _ptr(out)))
+            return out
         sc = C.byref(SwScoring(*scoring)) if scoring is not None else None
         d = _diag(diag, b.n_pairs)
         if zdrop is not None:
@@ -375,13 +392,20 @@ class Context:
         _check(lib().agx_sw_align_band_diag(self._h, sc, mode, what, band, _ptr(d), _ptr(b.bases), _ptr(b.off), _ptr(b.len), b.n_pairs, _ptr(out)))
         return out
 
-    def sw_align_band_diag_cigar(self, b, mode, band, diag=None, scoring=None, zdrop=None):
+    def sw_align_band_diag_cigar(self, b, mode, band, diag=None, scoring=None, zdrop=None, matrix=None):
         """b: synth.SWBatch -> (SwHit records as sw_align_band_diag(what=SW_ALIGN_SPANS) gives them, op_off uint64[n + 1], ops uint32),
         one-shot: the CIGAR of every pair inside its band around diag (include/agx.h, "CIGARs for batches banded around a diagonal").
-        zdrop=Z (SW_MODE_EXTEND only): -> (hits, stops int32, op_off, ops) of the extension terminated by the z-drop."""
+        zdrop=Z (SW_MODE_EXTEND only): -> (hits, stops int32, op_off, ops) of the extension terminated by the z-drop.
+        matrix: an SwMatrix instead of scoring; not with zdrop."""
         hits, op_off = np.empty(b.n_pairs, SwHit), np.zeros(b.n_pairs + 1, np.uint64)
         cap = int(b.len.sum())  # an alignment has at most one operation per symbol
         ops = np.empty(max(cap, 1), np.uint32)
+        if matrix is not None:
+            if scoring is not None or zdrop is not None:
+                raise AgxError(E_ARG, "matrix= takes the place of scoring= and does not combine with zdrop=")
+            _check(lib().agx_sw_align_band_diag_matrix_cigar(self._h, C.byref(matrix), mode, band, _ptr(_diag(diag, b.n_pairs)), _ptr(b.bases),
+                                                             _ptr(b.off), _ptr(b.len), b.n_pairs, _ptr(hits), _ptr(op_off), _ptr(ops), cap))
+            return hits, op_off, ops[:int(op_off[b.n_pairs])].copy()
         sc = C.byref(SwScoring(*scoring)) if scoring is not None else None
         d = _diag(diag, b.n_pairs)
         if zdrop is not None:
@@ -477,16 +501,30 @@ class SwBatch:
         band=w: a BANDED batch of mode SW_MODE_GLOBAL or SW_MODE_EXTEND (half-width w; it answers hits() as a SPANS batch does;
         no matrix or stats; with cigar=True a banded cigar batch, which also answers cigars());
         band=w with diag=one int or one per pair: a batch BANDED AROUND A DIAGONAL, any mode, align = SW_ALIGN_ENDS or
-        SW_ALIGN_SPANS (0: SPANS); no matrix or stats; with cigar=True (SPANS only) it also answers cigars();
+        SW_ALIGN_SPANS (0: SPANS); no stats; with cigar=True (SPANS only) it also answers cigars(); matrix=m puts it under a substitution
+        matrix (then no scoring and no zdrop);
         band=w with zdrop=Z (diag optional): such a batch in SW_MODE_EXTEND that terminates by the z-drop and also answers zdrop_stops()."""
         self.ctx = ctx
         self.n_pairs = b.n_pairs
         self._h = C.c_void_p()
         if diag is not None or zdrop is not None:
-            if band is None or matrix is not None or stats:
-                raise AgxError(E_ARG, "a batch banded around a diagonal takes band=w under match/mismatch scoring: no matrix or stats")
+            if band is None or stats:
+                raise AgxError(E_ARG, "a batch banded around a diagonal takes band=w, and no stats")
+            if matrix is not None and (scoring is not None or zdrop is not None):
+                raise AgxError(E_ARG, "a batch banded around a diagonal under a matrix takes no scoring and no zdrop")
             sc = C.byref(SwScoring(*scoring)) if scoring is not None else None
             d = _diag(diag, b.n_pairs)
+            if matrix is not None:
+                if cigar:
+                    if align not in (0, SW_ALIGN_SPANS):
+                        raise AgxError(E_ARG, "a cigar batch is a SW_ALIGN_SPANS batch")
+                    _check(lib().agx_sw_batch_create_align_band_diag_matrix_cigar(ctx._h if ctx else None, C.byref(matrix), mode, band, _ptr(d),
+                                                                                  _ptr(b.bases), _ptr(b.off), _ptr(b.len), b.n_pairs,
+                                                                                  C.byref(self._h)))
+                    return
+                _check(lib().agx_sw_batch_create_align_band_diag_matrix(ctx._h if ctx else None, C.byref(matrix), mode, align or SW_ALIGN_SPANS, band,
+                                                                        _ptr(d), _ptr(b.bases), _ptr(b.off), _ptr(b.len), b.n_pairs, C.byref(self._h)))
+                return
             if zdrop is not None:
                 if cigar:
                     if align not in (0, SW_ALIGN_SPANS):

@@ -1058,6 +1058,17 @@ void trace_times(const CreateTimes &t, int64_t n_pairs, bool with_device, bool d
 
 namespace agx_sw_host {
 
+int matrix_constants(const agx_sw_matrix *matrix, agx_sw_scoring &sc, SwParams &prm, std::vector<int16_t> &table)
+{
+    SwConstants k;
+    const int rc = make_constants(nullptr, matrix, k);
+    if (rc) return rc;
+    sc = k.sc;
+    prm = k.prm;
+    table.swap(k.table);
+    return AGX_OK;
+}
+
 // The create of every Smith-Waterman batch that is not banded: the stages above and agx_sw_plan.cpp's, top to bottom.
 int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matrix *matrix, const uint8_t *bases,
                  const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_batch **out, bool defer, int align, int mode, int stats,

@@ -266,6 +266,17 @@ int agx_sw_band_trace_at_launch_class(int diags_per_lane, const SwParams &prm, c
 int agx_sw_band_walk_at_launch(const SwWalkRec *recs, const SwBandWalkRec *band, uint32_t n, const uint32_t *img, const uint32_t *trace,
                                uint32_t *slots, uint32_t *runs, hipStream_t s);
 void agx_sw_band_trace_at_preload();
+// the builds of the banded body under a substitution matrix (agx_sw_band_diag_mat_kernel.hip, agx_sw_band_diag_trace_mat_kernel.hip;
+// DESIGN.md 4.1l): a band around a caller-given diagonal in all five modes, and the traced build with the start phase.  The image
+// holds symbol numbers 1 .. 32 (0 = padding) where the other banded builds hold bytes; table is the device copy of the
+// kSwMatDim x kSwMatDim entries of agx_sw_mat_launch_class.  Records, scores, pos, trace and goff are those of the builds above;
+// the walk of a traced span is agx_sw_band_walk_at_launch
+int agx_sw_band_mat_launch_class(int diags_per_lane, int mode, const SwParams &prm, const uint32_t *img, const SwBandGroup *groups,
+                                 const SwWave *waves, uint32_t n_waves, int32_t *scores, uint32_t *pos, const int16_t *table, hipStream_t s);
+void agx_sw_band_mat_preload();
+int agx_sw_band_trace_mat_launch_class(int diags_per_lane, const SwParams &prm, const uint32_t *img, const SwBandGroup *groups, const SwWave *waves,
+                                       uint32_t n_waves, int32_t *scores, uint32_t *trace, const uint64_t *goff, const int16_t *table, hipStream_t s);
+void agx_sw_band_trace_mat_preload();
 
 // ---- device-side planning (agx_sw_plan_kernel.hip): the O(pairs) passes of the planner as kernels
 constexpr uint32_t kSwPlanEmptyKey = 1u << 27;           // sort key of a pair with an empty side: behind every bucket

@@ -62,17 +62,28 @@ inline const char *band_at_condition(int mode, int64_t la, int64_t lb, int64_t d
 namespace agx_sw_host {
 
 int create_band(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t band, const uint8_t *bases, const uint64_t *off,
-                const uint32_t *len, int64_t n_pairs, agx_sw_batch **out, bool cigar, const BandAt *at)
+                const uint32_t *len, int64_t n_pairs, agx_sw_batch **out, bool cigar, const BandAt *at, const agx_sw_matrix *matrix)
 {
     const bool zd = at && at->zdrop_on;
-    const char *who = zd   ? (cigar ? "agx_sw_batch_create_align_band_zdrop_cigar" : "agx_sw_batch_create_align_band_zdrop")
-                      : at ? (cigar ? "agx_sw_batch_create_align_band_diag_cigar" : "agx_sw_batch_create_align_band_diag")
-                           : (cigar ? "agx_sw_batch_create_align_band_cigar" : "agx_sw_batch_create_align_band");
+    const char *who = matrix ? (cigar ? "agx_sw_batch_create_align_band_diag_matrix_cigar" : "agx_sw_batch_create_align_band_diag_matrix")
+                      : zd   ? (cigar ? "agx_sw_batch_create_align_band_zdrop_cigar" : "agx_sw_batch_create_align_band_zdrop")
+                      : at   ? (cigar ? "agx_sw_batch_create_align_band_diag_cigar" : "agx_sw_batch_create_align_band_diag")
+                             : (cigar ? "agx_sw_batch_create_align_band_cigar" : "agx_sw_batch_create_align_band");
     if (!out) {
         agx_set_error("%s: out is NULL", who);
         return AGX_E_ARG;
     }
     *out = nullptr;
+    // under a matrix (a batch around a diagonal without z-drop only: the entry points see to that) it is validated before anything
+    // else that can fail; scoring is then its gaps around a match/mismatch pair that nothing reads
+    agx_sw_scoring mat_sc{};
+    SwParams mat_prm{};
+    std::vector<int16_t> mat_table;
+    if (matrix) {
+        const int mrc = matrix_constants(matrix, mat_sc, mat_prm, mat_table);
+        if (mrc) return mrc;
+        scoring = &mat_sc;
+    }
     if (mode < AGX_SW_MODE_LOCAL || mode > AGX_SW_MODE_EXTEND_QUERY) {
         agx_set_error("%s: mode = %d is not one of AGX_SW_MODE_LOCAL .. AGX_SW_MODE_EXTEND_QUERY (0..4)", who, mode);
         return AGX_E_ARG;
@@ -252,6 +263,8 @@ int create_band(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t b
     b->zdrop = zd ? at->zdrop : 0;
     b->mode = mode;
     b->scoring = sc;
+    b->matrix = matrix != nullptr;
+    if (matrix) b->mat = *matrix;
     b->prm.ge = sc.gap_extend;
     b->prm.gf = sc.gap_open + sc.gap_extend;
     b->prm.hd = sc.match - b->prm.gf;
@@ -272,6 +285,7 @@ int create_band(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t b
     }
     agx_sw_band_preload();
     if (n_pairs > 0) b->seq_len.assign(len, len + 2 * n_pairs);
+    if (matrix) agx_sw_band_mat_preload();
     if (at) {
         agx_sw_band_at_preload();
         if (zd) agx_sw_band_zdrop_preload();
@@ -296,6 +310,7 @@ int create_band(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t b
     if (cigar) {
         agx_sw_band_trace_preload();
         if (at) agx_sw_band_trace_at_preload();
+        if (matrix) agx_sw_band_trace_mat_preload();
         agx_sw_walk_preload();
         b->band_groups = groups;
         b->band_rec.assign((size_t)n_pairs, kNoBandRec);
@@ -318,7 +333,9 @@ int create_band(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t b
         }
     };
     if (n_fill) {
-        // ---- the image, built on the host (it touches every byte once: the symbol check rides along)
+        // ---- the image, built on the host (it touches every byte once: the symbol check rides along).  Under a matrix the image
+        // holds symbol numbers, code + 1, and 0 stays the padding; a byte outside the alphabet is written as padding and fails
+        // the create below
         rc = h_img.alloc(ctx, (size_t)img_dw * 4);
         if (!rc) rc = h_groups.alloc(ctx, n_fill * sizeof(SwBandGroup));
         if (!rc) rc = h_waves.alloc(ctx, waves.size() * sizeof(SwWave));
@@ -338,14 +355,32 @@ int create_band(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t b
                 uint8_t *xa = im + (size_t)g.x_dw * 4, *ya = im + (size_t)g.y_dw * 4;
                 const size_t xbytes = ((size_t)(g.fpad + la + 3) / 4 + 1) * 4, ybytes = ((size_t)(lb + 4) / 4 + 1) * 4;
                 memset(xa, 0, g.fpad);
-                memcpy(xa + g.fpad, sa, la);
                 memset(xa + g.fpad + la, 0, xbytes - g.fpad - la);
                 ya[0] = 0;
-                memcpy(ya + 1, sb, lb);
                 memset(ya + 1 + lb, 0, ybytes - 1 - lb);
-                // (all of b, the rows a band around a diagonal leaves out included)
-                if ((memchr(sa, 0, la) || memchr(sb - g.reserved, 0, len[2 * (size_t)g.out + 1])) && (first_bad < 0 || (int64_t)g.out < first_bad))
-                    first_bad = g.out;
+                bool hit;
+                if (matrix) {
+                    const uint8_t *code = matrix->code, *b0 = sb - g.reserved;
+                    const uint32_t lb_all = len[2 * (size_t)g.out + 1];
+                    uint8_t miss = 0; // the OR of every code met: a valid one is below 32, so bit 7 says that some byte maps to 0xff
+                    for (uint32_t k = 0; k < la; ++k) {
+                        const uint8_t c = code[sa[k]];
+                        miss |= c;
+                        xa[g.fpad + k] = c == 0xff ? 0 : (uint8_t)(c + 1);
+                    }
+                    for (uint32_t k = 0; k < lb; ++k) {
+                        const uint8_t c = code[sb[k]];
+                        ya[1 + k] = c == 0xff ? 0 : (uint8_t)(c + 1);
+                    }
+                    for (uint32_t k = 0; k < lb_all; ++k) miss |= code[b0[k]]; // (all of b, as below)
+                    hit = (miss & 0x80u) != 0;
+                } else {
+                    memcpy(xa + g.fpad, sa, la);
+                    memcpy(ya + 1, sb, lb);
+                    // (all of b, the rows a band around a diagonal leaves out included)
+                    hit = memchr(sa, 0, la) || memchr(sb - g.reserved, 0, len[2 * (size_t)g.out + 1]);
+                }
+                if (hit && (first_bad < 0 || (int64_t)g.out < first_bad)) first_bad = g.out;
             }
             bad[(size_t)t] = first_bad;
         });
@@ -353,10 +388,12 @@ int create_band(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t b
         for (int64_t v : bad)
             if (v >= 0 && (first_bad < 0 || v < first_bad)) first_bad = v;
         if (first_bad >= 0) {
-            agx_set_error("pair %lld contains byte 0x00, which is reserved as the padding symbol", (long long)first_bad);
+            if (matrix) agx_set_error("pair %lld contains a byte outside the substitution matrix's alphabet", (long long)first_bad);
+            else agx_set_error("pair %lld contains byte 0x00, which is reserved as the padding symbol", (long long)first_bad);
             return AGX_E_SYMBOL;
         }
         rc = b->img.alloc(ctx, (size_t)img_dw * 4);
+        if (!rc && matrix) rc = b->table.alloc(ctx, mat_table.size() * sizeof(int16_t));
         if (!rc) rc = b->groups.alloc(ctx, n_fill * sizeof(SwBandGroup));
         if (!rc) rc = b->waves.alloc(ctx, waves.size() * sizeof(SwWave));
         if (!rc && launches.size() > 1) rc = agx_ctx_prepare_fanout(ctx);
@@ -365,6 +402,8 @@ int create_band(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t b
         AGX_HIP(hipMemcpyAsync(b->img.p, h_img.p, (size_t)img_dw * 4, hipMemcpyHostToDevice, cs));
         AGX_HIP(hipMemcpyAsync(b->groups.p, h_groups.p, n_fill * sizeof(SwBandGroup), hipMemcpyHostToDevice, cs));
         AGX_HIP(hipMemcpyAsync(b->waves.p, h_waves.p, waves.size() * sizeof(SwWave), hipMemcpyHostToDevice, cs));
+        // (pageable: the runtime stages it before the call returns; mat_table outlives the wait below in any case)
+        if (matrix) AGX_HIP(hipMemcpyAsync(b->table.p, mat_table.data(), mat_table.size() * sizeof(int16_t), hipMemcpyHostToDevice, cs));
         // results and their landing blocks (a later failure leaves behind the queued copies: `drain` waits for them)
         const size_t words = (size_t)n_pairs * sizeof(uint32_t);
         rc = b->scores.alloc(ctx, words);
@@ -399,6 +438,15 @@ int band_launch(agx_sw_batch *b)
                                                (const SwWave *)b->waves.p + cl.first_wave, cl.n_waves, (int32_t *)b->scores.p,
                                                (uint32_t *)b->band_pos.p, b->zdrop, (int32_t *)b->band_stop.p, fan.stream(k++))) {
                 agx_set_error("sw_fill_band_zd<%d> launch failed: %s", cl.C, hipGetErrorString(hipGetLastError()));
+                return AGX_E_HIP;
+            }
+            continue;
+        }
+        if (b->matrix) {
+            if (agx_sw_band_mat_launch_class(cl.C, b->mode, b->prm, (const uint32_t *)b->img.p, (const SwBandGroup *)b->groups.p,
+                                             (const SwWave *)b->waves.p + cl.first_wave, cl.n_waves, (int32_t *)b->scores.p,
+                                             (uint32_t *)b->band_pos.p, (const int16_t *)b->table.p, fan.stream(k++))) {
+                agx_set_error("sw_fill_band_mat<%d, %d> launch failed: %s", cl.C, b->mode, hipGetErrorString(hipGetLastError()));
                 return AGX_E_HIP;
             }
             continue;
@@ -508,7 +556,7 @@ int band_at_hits(agx_sw_batch *b, agx_sw_hit *hits, bool begins)
     agx_sw_batch *rb = nullptr;
     const BandAt rat{AGX_SW_ALIGN_ENDS, rdiag.data()};
     rc = create_band(b->ctx, &b->scoring, fit ? AGX_SW_MODE_EXTEND_QUERY : AGX_SW_MODE_LOCAL, b->band, rev.bytes.data(), rev.off.data(),
-                     rev.len.data(), m, &rb, false, &rat);
+                     rev.len.data(), m, &rb, false, &rat, b->matrix ? &b->mat : nullptr);
     if (rc) return rc;
     struct Drop {
         agx_sw_batch *b;
@@ -645,6 +693,28 @@ int agx_sw_align_band_diag(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode
 {
     agx_sw_batch *b = nullptr;
     const int rc = agx_sw_batch_create_align_band_diag(ctx, scoring, mode, what, band, diag, bases, off, len, n_pairs, &b);
+    return rc ? rc : align_once(b, [&](agx_sw_batch *x) { return agx_sw_batch_hits(x, hits); });
+}
+
+int agx_sw_batch_create_align_band_diag_matrix(agx_ctx *ctx, const agx_sw_matrix *matrix, int mode, int what, int32_t band, const int32_t *diag,
+                                               const uint8_t *bases, const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_batch **out)
+{
+    if (!matrix) {
+        if (out) *out = nullptr;
+        agx_set_error("agx_sw_batch_create_align_band_diag_matrix: matrix is NULL");
+        return AGX_E_ARG;
+    }
+    AGX_GUARD_BEGIN
+    const BandAt at{what, diag};
+    return create_band(ctx, nullptr, mode, band, bases, off, len, n_pairs, out, false, &at, matrix);
+    AGX_GUARD_END("agx_sw_batch_create_align_band_diag_matrix")
+}
+
+int agx_sw_align_band_diag_matrix(agx_ctx *ctx, const agx_sw_matrix *matrix, int mode, int what, int32_t band, const int32_t *diag,
+                                  const uint8_t *bases, const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_hit *hits)
+{
+    agx_sw_batch *b = nullptr;
+    const int rc = agx_sw_batch_create_align_band_diag_matrix(ctx, matrix, mode, what, band, diag, bases, off, len, n_pairs, &b);
     return rc ? rc : align_once(b, [&](agx_sw_batch *x) { return agx_sw_batch_hits(x, hits); });
 }
 

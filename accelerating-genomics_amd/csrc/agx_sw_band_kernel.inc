@@ -92,6 +92,38 @@
 // Once per four steps the wave leaves when each of its groups has terminated or passed its last row.  That file's head has the
 // argument.
 //
+// MAT (agx_sw_band_diag_mat_kernel.hip, agx_sw_band_diag_trace_mat_kernel.hip; include/agx.h, "Banded alignment around a diagonal
+// under a substitution matrix"; DESIGN.md 4.1l): the builds whose diagonal move adds a substitution-matrix entry -- the plain, AT
+// and traced-with-PH builds again, nothing else changed.  What the points above become:
+//   Symbols.  The image holds symbol numbers 1 .. 32 (the host writes code + 1) and 0 is the padding in rows and columns alike,
+//       as in the anchored matrix fill.  A row outside 1 .. lb carries 0, not kBandRowPad.  The table is the kSwMatDim x kSwMatDim
+//       int16 table of the other matrix fills: entry [y][x] = score - gf, and EVERY entry of row 0 and of column 0 is one constant
+//       P = (the matrix minimum, <= 0) - gf.  Every symbol a lane can hold -- from the image, from a neighbour by DPP, the preset
+//       of an idle lane -- is 0 .. 32, so the lookup stays inside the table's 2178 bytes.
+//   Origin and FIT injection.  The plain build sets the diagonal input to minus the mismatch score so that the move over padding
+//       gives exactly 0; here it sets -P.  Cell (0, 0) of the pinned modes reads table[0][x]: its row symbol is 0 whatever x is
+//       (the padding left of a, or under PH the stray symbol a[a_begin - 1]), and row 0 of the table is P throughout.  An in-band
+//       cell (i, 0) of FIT reads table[code(b_i)][0] -- or table[0][0] in row 0 --: its column symbol is the padding left of a
+//       (FIT has no PH build), and column 0 of the table is P throughout.  Both give -P + P = 0.
+//   LDS table.  One copy per workgroup, loaded by the kernel (the including file) before the `wave >= n_waves` return.
+//   Lookup schedule.  A step's K entries depend on the window's bytes and the row symbol only, both known at the step's head: all
+//       K reads are issued there, and the chain waits with a falling lgkmcnt, once per cell, for an entry that was asked for
+//       before the injection, the mask and the cells to its left (the K = 8 disassembly: eight ds_read_u16 in a row about fifty
+//       instructions ahead of the first use, then s_waitcnt lgkmcnt(7) .. (0); the entry is sign-extended by the SDWA add).
+//       The price is K registers a step for the entries.
+//   No wrap.  Entries are int8, so a diagonal move adds -128 .. 127 (as z: -128 - gf .. 127 - gf, within int16), over at most
+//       65 535 moves of a path; gap costs are unchanged.  True values: an in-band cell still has its path from the origin along
+//       row 0 or column 0 and then its diagonal, so a pinned H lies within [-2000 - 131070 * 1000 - 65535 * 128, 127 * 65535] =
+//       [-1.395e8, 8.33e6]; z, e and f add at most two gap costs.  A value derived from minus infinity is -2^30 plus at most one
+//       row's or one column stretch's gap costs (<= 0) plus at most one diagonal move before a masked H cuts the chain (a cell
+//       that exists and takes it has a true competitor, below): within [-2^30 - 2.05e6 - 128, -2^30 + 2127].  -1.4e8 > -2^30 +
+//       2127, so a true value still beats a derived one, and nothing comes near +-2^31.  LOCAL: the floor replaces a derived
+//       value by 0 only in cells that exist, where 0 is true, and a LOCAL H lies in [0, 127 * 65535]; FIT's H is at least the
+//       pinned one.  The traced build's argument -- every cell the walk reads has the true cell (i - 1, j - 1) on its diagonal,
+//       so its maximum is true and bits 0-1 point at a true source -- reads the same with "plus the table's entry" for "plus
+//       match or mismatch".
+//   Walk.  sw_walk_band_at compares image bytes: under MAT symbol numbers, so '=' is "identical codes", as the contract words it.
+//
 // (included by agx_sw_band_kernel.hip; opens an anonymous namespace that the including file closes after its launch helper)
 #include "agx_sw.h"
 
@@ -113,11 +145,12 @@ __device__ __forceinline__ int band_shl1(int old, int v)
 
 // AT: -1 for the builds above; else the mode of a build of agx_sw_band_diag_kernel.hip (LOCAL: EXT is set, it captures by the
 // ANY rule; FIT and EXTEND_QUERY capture column la).  Everything they add stands inside `if constexpr` blocks.
-template <int K, bool EXT, bool TRACE = false, int AT = -1, bool PH = false, bool ZD = false>
+// MAT: the builds under a substitution matrix; sub is the table in LDS.
+template <int K, bool EXT, bool TRACE = false, int AT = -1, bool PH = false, bool ZD = false, bool MAT = false>
 __device__ __forceinline__ void band_body(const SwParams &prm, const uint32_t *__restrict__ img, const SwBandGroup *__restrict__ groups,
                                           const SwWave w, int32_t *__restrict__ scores, uint32_t *__restrict__ pos,
                                           uint32_t *trace = nullptr, const uint64_t *goff = nullptr, [[maybe_unused]] int zdrop = 0,
-                                          [[maybe_unused]] int32_t *__restrict__ stops = nullptr)
+                                          [[maybe_unused]] int32_t *__restrict__ stops = nullptr, [[maybe_unused]] const int16_t *sub = nullptr)
 {
     static_assert(!(TRACE && EXT), "the traced build captures the corner: an EXTEND span is traced as the global alignment it is");
     static_assert(K % 4 == 0 && K >= 4 && K <= 32, "the query window is whole dwords and the cell mask one dword");
@@ -126,9 +159,15 @@ __device__ __forceinline__ void band_body(const SwParams &prm, const uint32_t *_
                   "GLOBAL and EXTEND around a diagonal run the plain builds: their boundaries and captures are the same");
     static_assert(!PH || (TRACE && AT == -1), "the start phase belongs to the traced build");
     static_assert(!ZD || (EXT && !TRACE && AT == -1), "the z-drop belongs to the plain EXTEND build");
+    static_assert(!MAT || !ZD, "no z-drop under a matrix");
     constexpr bool AT_LOCAL = AT == AGX_SW_MODE_LOCAL, AT_FIT = AT == AGX_SW_MODE_FIT, AT_COL = AT_FIT || AT == AGX_SW_MODE_EXTEND_QUERY;
     constexpr int XW = K / 4;
     const int ge = prm.ge, gf = prm.gf, s_match = prm.hd, s_mis = prm.hd - prm.delta; // the diagonal move on z: score - gf
+    // what a row outside 1 .. lb carries, and the diagonal input that the move over padding turns into exactly 0 (MAT: minus the
+    // table's padding entry, which every entry of row 0 and of column 0 holds)
+    constexpr int kRowPad = MAT ? 0 : kBandRowPad;
+    [[maybe_unused]] int inject = 0;
+    if constexpr (MAT) inject = -(int)sub[0];
     const int lane = threadIdx.x & 63;
     const int G = w.G;
     const int grp = lane / G;
@@ -177,7 +216,7 @@ __device__ __forceinline__ void band_body(const SwParams &prm, const uint32_t *_
     int z[K], e[K];
 #pragma unroll
     for (int k = 0; k < K; ++k) z[k] = e[k] = kBandNegInf;
-    int z_last = kBandNegInf, f_last = kBandNegInf, yc_prev = kBandRowPad;
+    int z_last = kBandNegInf, f_last = kBandNegInf, yc_prev = kRowPad;
     int best = gf, hit_i = -1, hit_k = 0; // EXTEND: H(0, 0) = 0 as z
     int corner = 0;                       // GLOBAL
     const int dc = la - lb - g.dlo;       // GLOBAL: the corner's diagonal, counted from dlo
@@ -204,7 +243,7 @@ __device__ __forceinline__ void band_body(const SwParams &prm, const uint32_t *_
     auto step = [&]() __attribute__((always_inline)) {
         const int i = t - (PH ? glp : gl);
         // (PH: 1 <= t' <= lb is 1 <= i <= lb in a group's first lane, and no other lane's `fresh` is read)
-        const int fresh = (PH ? (uint32_t)(i - 1) < (uint32_t)lb : (t >= 1 && t <= lb)) ? (int)(rows & 0xffu) : kBandRowPad;
+        const int fresh = (PH ? (uint32_t)(i - 1) < (uint32_t)lb : (t >= 1 && t <= lb)) ? (int)(rows & 0xffu) : kRowPad;
         rows >>= 8;
         const uint32_t xin = xrows & 0xffu;
         xrows >>= 8;
@@ -216,6 +255,18 @@ __device__ __forceinline__ void band_body(const SwParams &prm, const uint32_t *_
             fl = kBandNegInf;
             yc = fresh;
         }
+        // MAT: the K entries of this step -- row yc of the table, the columns of the window's bytes -- depend on nothing the cell
+        // chain computes: all K reads are issued here, ahead of the injection, the mask and the chain, which then waits for
+        // each entry once it needs it and not for one LDS round trip per cell
+        [[maybe_unused]] int sc[MAT ? K : 1];
+        if constexpr (MAT) {
+            const char *row = reinterpret_cast<const char *>(sub) + yc * (kSwMatDim * 2);
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                const int xs = (int)((xw[k >> 2] >> (8 * (k & 3))) & 0xffu);
+                sc[k] = *reinterpret_cast<const int16_t *>(row + xs * 2);
+            }
+        }
         if constexpr (AT_FIT) {
             // column 0 of this lane's row: the diagonal input that makes H(i, 0) = 0 in every row 0 .. lb.  The slot moves down by
             // one per step and crosses the lanes; the branch is taken only while column 0 is inside the band (2w + 1 rows).
@@ -223,7 +274,7 @@ __device__ __forceinline__ void band_body(const SwParams &prm, const uint32_t *_
             if ((uint32_t)slot < (uint32_t)K && (uint32_t)i <= (uint32_t)lb) {
                 asm volatile("" : "+v"(slot));
 #pragma unroll
-                for (int k = 0; k < K; ++k) z[k] = k == slot ? -s_mis : z[k];
+                for (int k = 0; k < K; ++k) z[k] = k == slot ? (MAT ? inject : -s_mis) : z[k];
             }
         } else if constexpr (AT_LOCAL) {
             // no injection: a diagonal input of minus infinity under the zero floor gives H = 0 on row 0 and in column 0
@@ -232,7 +283,7 @@ __device__ __forceinline__ void band_body(const SwParams &prm, const uint32_t *_
             int slot = k0;
             asm volatile("" : "+v"(slot));
 #pragma unroll
-            for (int k = 0; k < K; ++k) z[k] = k == slot ? -s_mis : z[k];
+            for (int k = 0; k < K; ++k) z[k] = k == slot ? (MAT ? inject : -s_mis) : z[k];
         }
         // which of this step's cells exist
         const int j0 = i + d0;
@@ -260,8 +311,12 @@ __device__ __forceinline__ void band_body(const SwParams &prm, const uint32_t *_
         {
             const int ev = max(z[1], e[1] + ge);
             f = max(zl, fl + ge);
-            const int xs = (int)(xw[0] & 0xffu);
-            const int s = z[0] + (xs == yc ? s_match : s_mis);
+            int s;
+            if constexpr (MAT) s = z[0] + sc[0];
+            else {
+                const int xs = (int)(xw[0] & 0xffu);
+                s = z[0] + (xs == yc ? s_match : s_mis);
+            }
             if constexpr (AT_LOCAL) zleft = keep(max(max(max(ev, f), s), 0) + gf, 0); // the zero floor: z >= gf
             else zleft = keep(max(max(ev, f), s) + gf, 0);
             if constexpr (TRACE) {
@@ -283,8 +338,12 @@ __device__ __forceinline__ void band_body(const SwParams &prm, const uint32_t *_
             const int ue = k + 1 < K ? e[k + 1] : re;
             const int ev = max(uz, ue + ge);
             f = max(zleft, f + ge);
-            const int xs = (int)((xw[k >> 2] >> (8 * (k & 3))) & 0xffu);
-            const int s = z[k] + (xs == yc ? s_match : s_mis);
+            int s;
+            if constexpr (MAT) s = z[k] + sc[k];
+            else {
+                const int xs = (int)((xw[k >> 2] >> (8 * (k & 3))) & 0xffu);
+                s = z[k] + (xs == yc ? s_match : s_mis);
+            }
             if constexpr (AT_LOCAL) zleft = keep(max(max(max(ev, f), s), 0) + gf, k);
             else zleft = keep(max(max(ev, f), s) + gf, k);
             if constexpr (TRACE) {

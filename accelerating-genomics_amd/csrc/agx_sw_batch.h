@@ -129,6 +129,9 @@ struct BandAt {
 int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matrix *matrix, const uint8_t *bases,
                  const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_batch **out, bool defer = false, int align = 0, int mode = 0,
                  int stats = 0, int cigar = 0);
+// make_constants for a batch under a matrix that create_batch does not make (create_band): the matrix validated as every matrix
+// batch validates it, sc = {1, 0, gap_open, gap_extend}, the kernel constants and the kSwMatDim x kSwMatDim table
+int matrix_constants(const agx_sw_matrix *matrix, agx_sw_scoring &sc, SwParams &prm, std::vector<int16_t> &table);
 
 // ---- agx_sw_plan.cpp: the host planner, stage by stage as create_batch calls it ("create pipeline")
 struct Tiling {
@@ -281,7 +284,8 @@ int align_once(agx_sw_batch *b, Answer answer)
 
 // ---- agx_sw_band.cpp
 int create_band(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t band, const uint8_t *bases, const uint64_t *off,
-                const uint32_t *len, int64_t n_pairs, agx_sw_batch **out, bool cigar = false, const BandAt *at = nullptr);
+                const uint32_t *len, int64_t n_pairs, agx_sw_batch **out, bool cigar = false, const BandAt *at = nullptr,
+                const agx_sw_matrix *matrix = nullptr);
 int band_launch(agx_sw_batch *b);
 int band_at_hits(agx_sw_batch *b, agx_sw_hit *hits, bool begins);
 int band_hits(agx_sw_batch *b, agx_sw_hit *hits);

@@ -414,13 +414,20 @@ int band_trace(agx_sw_batch *b, const int64_t *pairs, int64_t m, CigarChunk &c, 
     AGX_HIP(hipMemcpyAsync(c.walk.p, walk.data(), (size_t)m * sizeof(SwWalkRec), hipMemcpyHostToDevice, st));
     AGX_HIP(hipMemcpyAsync(c.bwalk.p, bwalk.data(), (size_t)m * sizeof(SwBandWalkRec), hipMemcpyHostToDevice, st));
     if (ev) AGX_HIP(hipEventRecord(ev[0], st));
-    for (auto it = launches.rbegin(); it != launches.rend(); ++it) // widest class first, one after the other on the stream
-        if ((at ? agx_sw_band_trace_at_launch_class : agx_sw_band_trace_launch_class)(
-                it->C, b->prm, (const uint32_t *)b->img.p, (const SwBandGroup *)c.groups.p, (const SwWave *)c.waves.p + it->first_wave, it->n_waves,
-                (int32_t *)c.scores.p, (uint32_t *)c.trace.p, (const uint64_t *)c.goff.p, st)) {
-            agx_set_error("sw_fill_band_trace%s<%d> launch failed: %s", at ? "_at" : "", it->C, hipGetErrorString(hipGetLastError()));
+    for (auto it = launches.rbegin(); it != launches.rend(); ++it) { // widest class first, one after the other on the stream
+        // (a batch under a matrix is banded around a diagonal: its spans run the traced build with the start phase and the table)
+        const int bad = b->matrix ? agx_sw_band_trace_mat_launch_class(it->C, b->prm, (const uint32_t *)b->img.p, (const SwBandGroup *)c.groups.p,
+                                                                       (const SwWave *)c.waves.p + it->first_wave, it->n_waves, (int32_t *)c.scores.p,
+                                                                       (uint32_t *)c.trace.p, (const uint64_t *)c.goff.p, (const int16_t *)b->table.p, st)
+                                  : (at ? agx_sw_band_trace_at_launch_class : agx_sw_band_trace_launch_class)(
+                                        it->C, b->prm, (const uint32_t *)b->img.p, (const SwBandGroup *)c.groups.p,
+                                        (const SwWave *)c.waves.p + it->first_wave, it->n_waves, (int32_t *)c.scores.p, (uint32_t *)c.trace.p,
+                                        (const uint64_t *)c.goff.p, st);
+        if (bad) {
+            agx_set_error("sw_fill_band_trace%s<%d> launch failed: %s", b->matrix ? "_mat" : at ? "_at" : "", it->C, hipGetErrorString(hipGetLastError()));
             return AGX_E_HIP;
         }
+    }
     if (ev) AGX_HIP(hipEventRecord(ev[1], st));
     if ((at ? agx_sw_band_walk_at_launch : agx_sw_band_walk_launch)(c.walkrec, (const SwBandWalkRec *)c.bwalk.p, (uint32_t)m, (const uint32_t *)b->img.p,
                                                                     (const uint32_t *)c.trace.p, (uint32_t *)c.slots.p, (uint32_t *)c.runs.p, st)) {
@@ -633,6 +640,30 @@ int agx_sw_align_band_diag_cigar(agx_ctx *ctx, const agx_sw_scoring *scoring, in
     return rc ? rc : align_once(b, [&](agx_sw_batch *x) { return agx_sw_batch_cigars(x, hits, op_off, ops, ops_cap); });
 }
 
+int agx_sw_batch_create_align_band_diag_matrix_cigar(agx_ctx *ctx, const agx_sw_matrix *matrix, int mode, int32_t band, const int32_t *diag,
+                                                     const uint8_t *bases, const uint64_t *off, const uint32_t *len, int64_t n_pairs,
+                                                     agx_sw_batch **out)
+{
+    if (!matrix) {
+        if (out) *out = nullptr;
+        agx_set_error("agx_sw_batch_create_align_band_diag_matrix_cigar: matrix is NULL");
+        return AGX_E_ARG;
+    }
+    AGX_GUARD_BEGIN
+    const BandAt at{AGX_SW_ALIGN_SPANS, diag};
+    return create_band(ctx, nullptr, mode, band, bases, off, len, n_pairs, out, true, &at, matrix);
+    AGX_GUARD_END("agx_sw_batch_create_align_band_diag_matrix_cigar")
+}
+
+int agx_sw_align_band_diag_matrix_cigar(agx_ctx *ctx, const agx_sw_matrix *matrix, int mode, int32_t band, const int32_t *diag,
+                                        const uint8_t *bases, const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_hit *hits,
+                                        uint64_t *op_off, uint32_t *ops, uint64_t ops_cap)
+{
+    agx_sw_batch *b = nullptr;
+    const int rc = agx_sw_batch_create_align_band_diag_matrix_cigar(ctx, matrix, mode, band, diag, bases, off, len, n_pairs, &b);
+    return rc ? rc : align_once(b, [&](agx_sw_batch *x) { return agx_sw_batch_cigars(x, hits, op_off, ops, ops_cap); });
+}
+
 int agx_sw_batch_create_align_band_zdrop_cigar(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t band, const int32_t *diag,
                                                int32_t zdrop, const uint8_t *bases, const uint64_t *off, const uint32_t *len, int64_t n_pairs,
                                                agx_sw_batch **out)
@@ -684,8 +715,8 @@ int agx_sw_batch_cigars(agx_sw_batch *b, agx_sw_hit *hits, uint64_t *op_off, uin
         return AGX_E_ARG;
     }
     if (b->cigar != 1 || b->align != AGX_SW_ALIGN_SPANS) {
-        agx_set_error("agx_sw_batch_cigars: not a cigar batch (create it with agx_sw_batch_create_align_cigar, agx_sw_batch_create_align_band_cigar or "
-                      "agx_sw_batch_create_align_band_diag_cigar)");
+        agx_set_error("agx_sw_batch_cigars: not a cigar batch (create it with agx_sw_batch_create_align_cigar, agx_sw_batch_create_align_band_cigar, "
+                      "agx_sw_batch_create_align_band_diag_cigar or agx_sw_batch_create_align_band_diag_matrix_cigar)");
         return AGX_E_ARG;
     }
     if (!b->ctx) {

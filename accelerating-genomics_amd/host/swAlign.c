@@ -1,5 +1,6 @@
 /*
- * swAlign <file_path> [local|global|fit|extend|extend-query][+stats|+cigar|+band=W|+cigar+band=W|+band=W@D|+bandcigar=W@D][+zdrop=Z]: where the best alignment of every pair ends and begins
+ * swAlign <file_path> [local|global|fit|extend|extend-query][+stats|+cigar|+band=W|+cigar+band=W|+band=W@D|+bandcigar=W@D][+zdrop=Z]
+ * (and, with a matrix file, +matband=W@D|+matbandcigar=W@D): where the best alignment of every pair ends and begins
  * (default: local; the other modes are include/agx.h's "Alignment modes").
  * swAlign <file_path> <mode> <matrix_file> [gap_open gap_extend]: the same under a substitution matrix (gaps default to
  * -11 -1).  The matrix file is the usual text layout: '#' comment lines, one line of symbols, then one row per symbol
@@ -39,6 +40,12 @@
  * Or "+zdrop=Z" behind either of the last two on extend, in this place only (extend+band=64@0+zdrop=100,
  * extend+bandcigar=64@0+zdrop=100): the extension terminates by the z-drop Z >= 0 (include/agx.h, "Z-drop for banded extension");
  * the same lines as without the suffix.  Another mode, a negative or non-numeric Z, or the suffix anywhere else is a usage error.
+ * swAlign <file_path> <mode>+matband=W@D <matrix_file> [gap_open gap_extend]: the lines of "+band=W@D" under the substitution
+ * matrix (include/agx.h, "Banded alignment around a diagonal under a substitution matrix"), and
+ * swAlign <file_path> <mode>+matbandcigar=W@D <matrix_file> [gap_open gap_extend]: the lines of "+bandcigar=W@D" under it.  Any
+ * mode; W and D as in "+band=W@D", both required; read with the line buffer of "+band=W", the line ends stripped as with every
+ * matrix file.  Either word without a matrix file, or with +stats, +cigar or +zdrop, is a usage error; so is a matrix file behind
+ * "+band=W@D" or "+bandcigar=W@D".
  *   AGX_CLI_CHUNK_PAIRS   pairs per agx_sw_align call (default 262144)
  */
 #include <stdio.h>
@@ -132,7 +139,7 @@ int main(int argc, char *argv[])
 {
     static const char *const words[] = {"local", "global", "fit", "extend", "extend-query"}; /* AGX_SW_MODE_* 0..4 */
     int mode = argc == 2 ? AGX_SW_MODE_LOCAL : -1;
-    int with_stats = 0, with_cigar = 0, with_band = 0, with_diag = 0, with_zdrop = 0;
+    int with_stats = 0, with_cigar = 0, with_band = 0, with_diag = 0, with_zdrop = 0, with_matband = 0;
     int32_t band = 0, diag = 0, zdrop = 0;
     for (int k = 0; (argc == 3 || argc == 4 || argc == 6) && k < 5; k++) {
         const size_t n = strlen(words[k]);
@@ -178,6 +185,24 @@ int main(int argc, char *argv[])
                 }
             }
         }
+        const int mat_cigar = !strncmp(argv[2], words[k], n) && !strncmp(argv[2] + n, "+matbandcigar=", 14);
+        if (!strncmp(argv[2], words[k], n) && (mat_cigar || !strncmp(argv[2] + n, "+matband=", 9)) && (argc == 4 || argc == 6)) {
+            /* W@D as above, up to the end of the word (no further suffix); any mode, and only with a matrix file */
+            const char *w = argv[2] + n + (mat_cigar ? 14 : 9);
+            char *end, *end2;
+            const long v = strtol(w, &end, 10);
+            if (isdigit((unsigned char)*w) && *end == '@' && v <= 0x7fffffffL) {
+                const char *d = end + 1;
+                const long c = strtol(d, &end2, 10);
+                if (isdigit((unsigned char)d[*d == '-']) && !*end2 && c >= -0x7fffffffL && c <= 0x7fffffffL) {
+                    mode = k;
+                    with_band = with_diag = with_matband = 1;
+                    with_cigar = mat_cigar;
+                    band = (int32_t)v;
+                    diag = (int32_t)c;
+                }
+            }
+        }
         if (!strncmp(argv[2], words[k], n) && !strcmp(argv[2] + n, "+stats")) {
             mode = k;
             with_stats = 1;
@@ -201,7 +226,10 @@ int main(int argc, char *argv[])
                 "<mode>+band=W@D (fit+band=64@0, local+band=200@-1500): the alignment inside the band D-W <= j-i <= D+W around the\n"
                 "diagonal D, in any mode; not with +stats, +cigar or a matrix file.\n"
                 "<mode>+bandcigar=W@D (fit+bandcigar=64@-1500): the same with its CIGAR inside that band appended; no matrix file.\n"
-                "extend+band=W@D+zdrop=Z, extend+bandcigar=W@D+zdrop=Z: the extension terminates by the z-drop Z >= 0; extend only.\n",
+                "extend+band=W@D+zdrop=Z, extend+bandcigar=W@D+zdrop=Z: the extension terminates by the z-drop Z >= 0; extend only.\n"
+                "<mode>+matband=W@D <matrix_file> [gap_open gap_extend], <mode>+matbandcigar=W@D <matrix_file> [gap_open gap_extend]:\n"
+                "the lines of +band=W@D and of +bandcigar=W@D under the substitution matrix; a matrix file is required, and no\n"
+                "+stats, +cigar or +zdrop.\n",
                 argv[0], argv[0]);
         return 1;
     }
@@ -273,9 +301,11 @@ int main(int argc, char *argv[])
                 if (!dg) {
                     fprintf(stderr, "swAlign: out of memory\n");
                     status = EXIT_FAILURE;
-                } else if ((with_zdrop ? agx_sw_align_band_zdrop_cigar(ctx, NULL, mode, band, dg, zdrop, t->bases, t->off, t->len, t->n_pairs, hits, NULL,
-                                                                       op_off, ops, ops_cap)
-                                       : agx_sw_align_band_diag_cigar(ctx, NULL, mode, band, dg, t->bases, t->off, t->len, t->n_pairs, hits, op_off, ops,
+                } else if ((with_matband ? agx_sw_align_band_diag_matrix_cigar(ctx, &matrix, mode, band, dg, t->bases, t->off, t->len, t->n_pairs, hits,
+                                                                               op_off, ops, ops_cap)
+                            : with_zdrop ? agx_sw_align_band_zdrop_cigar(ctx, NULL, mode, band, dg, zdrop, t->bases, t->off, t->len, t->n_pairs, hits, NULL,
+                                                                         op_off, ops, ops_cap)
+                                         : agx_sw_align_band_diag_cigar(ctx, NULL, mode, band, dg, t->bases, t->off, t->len, t->n_pairs, hits, op_off, ops,
                                                                       ops_cap)) != AGX_OK) {
                     fprintf(stderr, "swAlign: %s\n", agx_last_error());
                     status = EXIT_FAILURE;
@@ -298,9 +328,11 @@ int main(int argc, char *argv[])
                 if (!dg) {
                     fprintf(stderr, "swAlign: out of memory\n");
                     status = EXIT_FAILURE;
-                } else if ((with_zdrop ? agx_sw_align_band_zdrop(ctx, NULL, mode, AGX_SW_ALIGN_SPANS, band, dg, zdrop, t->bases, t->off, t->len,
-                                                                 t->n_pairs, hits, NULL)
-                                       : agx_sw_align_band_diag(ctx, NULL, mode, AGX_SW_ALIGN_SPANS, band, dg, t->bases, t->off, t->len, t->n_pairs,
+                } else if ((with_matband ? agx_sw_align_band_diag_matrix(ctx, &matrix, mode, AGX_SW_ALIGN_SPANS, band, dg, t->bases, t->off, t->len,
+                                                                         t->n_pairs, hits)
+                            : with_zdrop ? agx_sw_align_band_zdrop(ctx, NULL, mode, AGX_SW_ALIGN_SPANS, band, dg, zdrop, t->bases, t->off, t->len,
+                                                                   t->n_pairs, hits, NULL)
+                                         : agx_sw_align_band_diag(ctx, NULL, mode, AGX_SW_ALIGN_SPANS, band, dg, t->bases, t->off, t->len, t->n_pairs,
                                                                 hits)) != AGX_OK) {
                     fprintf(stderr, "swAlign: %s\n", agx_last_error());
                     status = EXIT_FAILURE;

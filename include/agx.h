@@ -393,8 +393,9 @@ int agx_sw_align_cigar(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw
  * around the main diagonal means nothing for them without a diagonal offset: AGX_E_ARG, as for a mode outside 0..4 (they are
  * served by "Banded alignment around a diagonal" below).
  * scoring: agx_sw_scoring with its limits, NULL = the reference's constants.  Byte 0x00 is refused (AGX_E_SYMBOL) as elsewhere.
- * Deliberately left out: no substitution matrix and no statistics; CIGARs come from a banded cigar batch ("CIGARs for banded
- * batches" below), not from this one.
+ * Deliberately left out: no substitution matrix (a band under a matrix is "Banded alignment around a diagonal under a
+ * substitution matrix" below, whose EXTEND with diag == NULL is this entry's EXTEND band; GLOBAL with the widening is not offered
+ * under a matrix) and no statistics; CIGARs come from a banded cigar batch ("CIGARs for banded batches" below), not from this one.
  * The batch behaves like the other align batches: agx_sw_batch_launch (re)launches, agx_sw_batch_scores returns the mode's
  * score, agx_sw_batch_hits the hits in the caller's pair order, agx_sw_batch_bind_scores is accepted and ignored;
  * agx_sw_batch_stats and agx_sw_batch_cigars return AGX_E_ARG.  ctx may be NULL: plan only.  In agx_sw_info, cells stays
@@ -503,7 +504,8 @@ int agx_sw_cigar_in_band(const uint32_t *ops, uint64_t n_ops, int32_t dlo, int32
  * works; agx_sw_batch_stats and agx_sw_batch_cigars return AGX_E_ARG.  ctx may be NULL: plan only.  scoring and byte 0x00 as in
  * "Banded alignment".  Unchanged: agx_sw_batch_create_align_band still refuses LOCAL, FIT and EXTEND_QUERY with AGX_E_ARG.
  * CIGARs come from "CIGARs for batches banded around a diagonal" below, z-drop termination of EXTEND from "Z-drop for banded
- * extension".  Deliberately left out: substitution matrices and statistics.
+ * extension", substitution matrices from "Banded alignment around a diagonal under a substitution matrix".  Deliberately left
+ * out: statistics.
  */
 int agx_sw_batch_create_align_band_diag(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int what, int32_t band,
                                         const int32_t *diag /* n_pairs, or NULL = 0 for every pair */, const uint8_t *bases,
@@ -537,7 +539,8 @@ int agx_sw_align_band_diag(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode
  * beyond the budget alone in its chunk), agx_sw_cigar_info and the host's check of every CIGAR before it leaves (AGX_E_INTERNAL
  * naming the pair) are as in "CIGARs for banded batches".  ctx may be NULL: plan only.
  * Unchanged: a plain band-diag batch keeps answering agx_sw_batch_cigars with AGX_E_ARG; agx_sw_batch_stats on this batch gives
- * AGX_E_ARG.  Deliberately left out: substitution matrices and statistics.
+ * AGX_E_ARG.  Substitution matrices come from "Banded alignment around a diagonal under a substitution matrix" below.
+ * Deliberately left out: statistics.
  */
 int agx_sw_batch_create_align_band_diag_cigar(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t band,
                                               const int32_t *diag /* n_pairs, or NULL = 0 for every pair */, const uint8_t *bases,
@@ -546,6 +549,58 @@ int agx_sw_batch_create_align_band_diag_cigar(agx_ctx *ctx, const agx_sw_scoring
 int agx_sw_align_band_diag_cigar(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t band, const int32_t *diag,
                                  const uint8_t *bases, const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_hit *hits,
                                  uint64_t *op_off, uint32_t *ops, uint64_t ops_cap);
+
+/*
+ * Banded alignment around a diagonal under a substitution matrix: protein extension around a seed diagonal under BLOSUM62, DNA
+ * under an IUPAC or transition/transversion matrix, any query beyond AGX_SW_ALIGN_MAX_QUERY_LEN under a matrix -- the batches of
+ * "Banded alignment around a diagonal" and of "CIGARs for batches banded around a diagonal" with an agx_sw_matrix in place of
+ * the agx_sw_scoring.
+ * Base contract: everything is as in those two sections -- the band c - w <= j - i <= c + w per pair (never widened), the table
+ * of what the band must hold per mode, boundaries, result and tie rules, the begin pass of LOCAL and FIT under
+ * AGX_SW_ALIGN_SPANS, trimmed rows, limits (la, lb <= AGX_SW_BAND_MAX_LEN, w <= 1023, |c| <= AGX_SW_BAND_MAX_LEN + w), error
+ * codes and messages, the empty-side formulas, plan-only batches with ctx == NULL, launch and relaunch, agx_sw_batch_scores,
+ * _hits, _info, bind_scores accepted and ignored, and on the cigar batch agx_sw_batch_cigars and _cigar_info with their chunking
+ * under AGX_OPT_SW_TRACE_BYTES and agx_sw_band_cigar_bytes_bound.  The one difference: the diagonal move adds
+ * score[code[a_j]][code[b_i]], and the gap costs are the matrix's gap_open and gap_extend.
+ * Matrix: validated as agx_sw_batch_create_align_matrix validates it -- NULL, n_symbols outside 1..32, an asymmetric matrix or a
+ * code that is neither 0xff nor below n_symbols: AGX_E_ARG; a gap cost outside -1000..0: AGX_E_LIMIT -- and before anything
+ * else that can fail (mode, what, band, the pairs), also when ctx == NULL.
+ * Symbols: a byte outside the alphabet (code 0xff) fails the create with AGX_E_SYMBOL naming the lowest such pair among the
+ * pairs that are filled; all of b is checked, the rows the band leaves out included.  Byte 0x00 is a symbol like any other if
+ * the matrix maps it.  As in the base contract the check belongs to the image build, so a plan-only batch does not make it.
+ * Score zero: as in "Align batches under a substitution matrix" a diagonal score may be <= 0 even for identical symbols, so a
+ * LOCAL or EXTEND score of 0 means "nothing consumed" -- all four positions -1, no operations -- whatever the sequences hold;
+ * GLOBAL, FIT and EXTEND_QUERY scores may be negative.
+ * CIGARs: '=' means identical symbol CODES, whatever that entry scores -- two bytes mapped to one code, such as upper and lower
+ * case, are '=' -- and 'X' any other aligned pair.  The host's check of every CIGAR rescores under the matrix.
+ * Range: entries are int8 and a path has at most 65 535 diagonal moves, so every score lies within -1.4e8 .. 8.4e6 (DESIGN.md
+ * 4.1l has the bound for the intermediate values).
+ * Equivalences:
+ *   a band that holds the whole matrix (c - w <= -lb and c + w >= la) reports what agx_sw_align_matrix reports in the same mode
+ *       and `what`, and its cigar batch what agx_sw_align_cigar reports with the matrix;
+ *   a matrix over ACGT whose entries restate a supported scoring -- `match` on the diagonal, `mismatch` elsewhere, the scoring's
+ *       gaps -- reports, on sequences over the bytes it maps to those four codes, what agx_sw_align_band_diag and
+ *       agx_sw_align_band_diag_cigar report under that scoring on the same sequences with identical bytes for identical codes,
+ *       hit for hit and operation for operation.
+ * Both kinds of batch return AGX_E_ARG from agx_sw_batch_stats and agx_sw_batch_zdrop_stops, the batch without CIGARs also from
+ * agx_sw_batch_cigars.
+ * Deliberately left out: statistics on banded batches, z-drop under a matrix, and a matrix for agx_sw_batch_create_align_band
+ * (EXTEND with diag == NULL here is its EXTEND band; its GLOBAL band, widened by the length difference, is not offered).
+ */
+int agx_sw_batch_create_align_band_diag_matrix(agx_ctx *ctx, const agx_sw_matrix *matrix, int mode, int what, int32_t band,
+                                               const int32_t *diag /* n_pairs, or NULL = 0 for every pair */, const uint8_t *bases,
+                                               const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_batch **out);
+/* One-shot: create_align_band_diag_matrix + launch + hits + destroy. */
+int agx_sw_align_band_diag_matrix(agx_ctx *ctx, const agx_sw_matrix *matrix, int mode, int what, int32_t band, const int32_t *diag,
+                                  const uint8_t *bases, const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_hit *hits);
+int agx_sw_batch_create_align_band_diag_matrix_cigar(agx_ctx *ctx, const agx_sw_matrix *matrix, int mode, int32_t band,
+                                                     const int32_t *diag /* n_pairs, or NULL = 0 for every pair */, const uint8_t *bases,
+                                                     const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_batch **out);
+/* One-shot: create_align_band_diag_matrix_cigar + launch + cigars + destroy.  ops_cap >= sum(len) always suffices. */
+int agx_sw_align_band_diag_matrix_cigar(agx_ctx *ctx, const agx_sw_matrix *matrix, int mode, int32_t band, const int32_t *diag,
+                                        const uint8_t *bases, const uint64_t *off, const uint32_t *len, int64_t n_pairs,
+                                        agx_sw_hit *hits /* may be NULL */, uint64_t *op_off, uint32_t *ops, uint64_t ops_cap);
+
 /*
  * Z-drop for banded extension: AGX_SW_MODE_EXTEND inside a band around a diagonal that stops extending once the alignment has
  * fallen apart -- a read whose tail is junk (a chimera, an adapter, the far side of a structural variant) neither pays for all of
@@ -578,7 +633,8 @@ int agx_sw_align_band_diag_cigar(agx_ctx *ctx, const agx_sw_scoring *scoring, in
  * The cigar batch is a batch of "CIGARs for batches banded around a diagonal" whose hits come from the z-drop fill: the reported
  * end cell is an in-band cell reached from (0, 0) inside the band, so the traced fill of the span, the band-aware walk and the
  * host's checks apply unchanged.
- * Deliberately left out: a z-drop for the unbanded EXTEND of agx_sw_align_mode, and an X-drop variant.
+ * Deliberately left out: a z-drop for the unbanded EXTEND of agx_sw_align_mode, a z-drop under a substitution matrix, and an
+ * X-drop variant.
  */
 #define AGX_SW_ZDROP_MAX 1000000000
 int agx_sw_batch_create_align_band_zdrop(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int what, int32_t band,

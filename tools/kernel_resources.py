@@ -20,7 +20,7 @@ def demangle(names):
 
 
 def kernel_resources(lib=None):
-    """-> {demangled kernel name (up to its argument list): dict(vgpr, agpr, sgpr, lds, scratch, wg)}"""
+    """-> {demangled kernel name (up to its argument list): dict(vgpr, agpr, sgpr, lds, scratch, wg, vgpr_spill, sgpr_spill)}"""
     lib = lib or os.path.join(ROOT, "accelerating-genomics_amd", "libagx.so")
     res = {}
     with tempfile.TemporaryDirectory(dir="/tmp") as d:
@@ -38,7 +38,8 @@ def kernel_resources(lib=None):
                     continue
                 res[name] = dict(vgpr=int(get("vgpr_count") or 0), agpr=int(get("agpr_count") or 0), sgpr=int(get("sgpr_count") or 0),
                                  lds=int(get("group_segment_fixed_size") or 0), scratch=int(get("private_segment_fixed_size") or 0),
-                                 wg=int(get("max_flat_workgroup_size") or 0))
+                                 wg=int(get("max_flat_workgroup_size") or 0), vgpr_spill=int(get("vgpr_spill_count") or 0),
+                                 sgpr_spill=int(get("sgpr_spill_count") or 0))
     names = list(res)
     return {dm.split("(")[0]: res[n] for n, dm in zip(names, demangle(names))}
 
