@@ -376,14 +376,14 @@ class Context:
         zdrop=Z (SW_MODE_EXTEND only; "Z-drop for banded extension"): -> (SwHit records, stops int32: the last row of b looked at, or -1).
         matrix: an SwMatrix instead of scoring ("Banded alignment around a diagonal under a substitution matrix"); not with zdrop."""
         out = np.empty(b.n_pairs, SwHit)
+        d = _diag(diag, b.n_pairs)  # (named: the array must outlive the call that reads it through its address)
         if matrix is not None:
             if scoring is not None or zdrop is not None:
                 raise AgxError(E_ARG, "matrix= takes the place of scoring= and does not combine with zdrop=")
-            _check(lib().agx_sw_align_band_diag_matrix(self._h, C.byref(matrix), mode, what, band, _ptr(_diag(diag, b.n_pairs)), _ptr(b.bases),
+            _check(lib().agx_sw_align_band_diag_matrix(self._h, C.byref(matrix), mode, what, band, _ptr(d), _ptr(b.bases),
                                                        _ptr(b.off), _ptr(b.len), b.n_pairs, _ptr(out)))
             return out
         sc = C.byref(SwScoring(*scoring)) if scoring is not None else None
-        d = _diag(diag, b.n_pairs)
         if zdrop is not None:
             stops = np.empty(b.n_pairs, np.int32)
             _check(lib().agx_sw_align_band_zdrop(self._h, sc, mode, what, band, _ptr(d), zdrop, _ptr(b.bases), _ptr(b.off), _ptr(b.len), b.n_pairs,
@@ -400,14 +400,14 @@ class Context:
         hits, op_off = np.empty(b.n_pairs, SwHit), np.zeros(b.n_pairs + 1, np.uint64)
         cap = int(b.len.sum())  # an alignment has at most one operation per symbol
         ops = np.empty(max(cap, 1), np.uint32)
+        d = _diag(diag, b.n_pairs)
         if matrix is not None:
             if scoring is not None or zdrop is not None:
                 raise AgxError(E_ARG, "matrix= takes the place of scoring= and does not combine with zdrop=")
-            _check(lib().agx_sw_align_band_diag_matrix_cigar(self._h, C.byref(matrix), mode, band, _ptr(_diag(diag, b.n_pairs)), _ptr(b.bases),
+            _check(lib().agx_sw_align_band_diag_matrix_cigar(self._h, C.byref(matrix), mode, band, _ptr(d), _ptr(b.bases),
                                                              _ptr(b.off), _ptr(b.len), b.n_pairs, _ptr(hits), _ptr(op_off), _ptr(ops), cap))
             return hits, op_off, ops[:int(op_off[b.n_pairs])].copy()
         sc = C.byref(SwScoring(*scoring)) if scoring is not None else None
-        d = _diag(diag, b.n_pairs)
         if zdrop is not None:
             stops = np.empty(b.n_pairs, np.int32)
             _check(lib().agx_sw_align_band_zdrop_cigar(self._h, sc, mode, band, _ptr(d), zdrop, _ptr(b.bases), _ptr(b.off), _ptr(b.len), b.n_pairs,

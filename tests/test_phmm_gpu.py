@@ -741,3 +741,40 @@ def test_a_quality_byte_below_the_phred_range_keeps_trains_out(ctx, oracle):
     assert ok.sum() >= ref.size - 5  # (the byte sits in one read: at most its five pairs)
     for opt in (agx.PHMM_TRAINS_OFF, agx.PHMM_TRAINS_ON):
         assert relerr(res[("wild", opt)][1][ok], ref[ok]) <= 1e-6
+
+
+def test_plan_on_a_device_is_the_plan_only_plan():
+    """A plan does not depend on whether a device is there: one small case of tests/phmm_plan_cases.py per kernel family -- F64
+    with looked-up priors, F32, F32_FMA -- created on device 0 in a child process under AGX_TRACE_CREATE prints the main and
+    image digests, the flags and the info fields of tests/golden/phmm_plan_digests.json.  Plan-only batches are tiled for 256
+    CUs, an MI355X's count; on a device of another count the test skips.
+    The same child launches the packed mismatch ladder of tests/phmm_range_cases.py, which crosses the rescue threshold
+    (tests/test_phmm_range_gpu.py: n_rescued > 0): its rescue plan, made at that first underflow, prints the digest that the
+    same batch planned as F64 under AGX_PHMM_NO_LUT has as its main one."""
+    import json
+    import re
+
+    from tests import phmm_plan_cases as pc
+
+    with open(os.path.join(os.path.dirname(__file__), "golden", "phmm_plan_digests.json")) as f:
+        golden = json.load(f)
+    names = ["jitter_f64", "corpus_f32", "jitter_pk", "ladder_pk"]
+    got, err = pc.run_group("default", names=names, device=True, run=("ladder_pk",), timeout=120)
+    assert sorted(got) == sorted(names), err[-2000:]
+    n_cu = set(re.findall(r"^\[agx_phmm_batch_create\] planned for (\d+) CUs$", err, flags=re.M))
+    if n_cu != {"256"}:
+        pytest.skip("the context reports %s CUs: its plans are tiled for that count, the fixture's for 256" % sorted(n_cu))
+    for name in names:
+        want = golden[name]
+        for k in ("main", "image", "flags"):
+            assert got[name][k] == want[k], (name, k, got[name], want, err[-2000:])
+        assert {k: v for k, v in got[name]["info"].items() if k != "n_rescued"} == {k: v for k, v in want["info"].items() if k != "n_rescued"}, name
+    assert _flags_of(golden["jitter_f64"])["lut_prior"] == 1
+    assert got["ladder_pk"]["info"]["n_rescued"] > 0, got["ladder_pk"]
+    assert got["ladder_pk"]["rescue"] == golden["ladder_f64_no_lut"]["main"], (got["ladder_pk"], err[-2000:])
+    assert all("rescue" not in got[n] for n in names[:3])
+
+
+def _flags_of(entry):
+    words = entry["flags"].split()
+    return dict(zip(words[0::2], (int(v) for v in words[1::2])))
