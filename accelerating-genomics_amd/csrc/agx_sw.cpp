@@ -20,6 +20,7 @@
 #include <cmath>
 #include <memory>
 #include <mutex>
+#include <string>
 #include <thread>
 
 #include "agx_parallel.h"
@@ -443,30 +444,58 @@ int launch_device_plan(agx_ctx *ctx, DevPlan &dp, agx_sw_batch *b, uint32_t n_pa
 // AGX_TRACE_CREATE: a host-made plan as one number, 64-bit FNV-1a over the kernel choice (family, rising, wide, stage as
 // int32), the launches (C, first_wave, n_waves), the wave and group records as they go to the device and, for the traced fill,
 // its offsets and walk records field by field (no struct padding).  tests/test_sw_plan_digest_cpu.py pins it per kind of batch.
-uint64_t plan_digest(const agx_sw_batch *b, const std::vector<SwWave> &waves, const void *groups, size_t groups_bytes)
-{
+struct Fnv1a {
     uint64_t h = 0xcbf29ce484222325ull;
-    auto bytes = [&h](const void *p, size_t n) {
+    void bytes(const void *p, size_t n)
+    {
         for (size_t k = 0; k < n; ++k) h = (h ^ ((const uint8_t *)p)[k]) * 0x100000001b3ull;
-    };
-    auto field = [&bytes](auto v) { bytes(&v, sizeof v); };
-    for (int32_t v : {(int32_t)b->family, (int32_t)b->rising, (int32_t)b->wide, (int32_t)b->stage}) field(v);
-    for (const ClassLaunch &cl : b->launches) {
-        field((int32_t)cl.C);
-        field(cl.first_wave);
-        field(cl.n_waves);
     }
-    bytes(waves.data(), waves.size() * sizeof(SwWave));
-    bytes(groups, groups_bytes);
-    if (b->cigar == 2) {
-        bytes(b->tr_goff.data(), b->tr_goff.size() * sizeof(uint64_t));
-        field(b->tr_dwords);
-        field(b->tr_slot_words);
-        for (const SwWalkRec &r : b->tr_walk) {
-            field(r.goff), field(r.x_dw), field(r.y_dw), field(r.ca), field(r.cb), field(r.G), field(r.C), field(r.slot);
+    template <typename T> void field(T v) { bytes(&v, sizeof v); }
+    // the kernel choice and the launches: what a plan says before its records
+    void head(const agx_sw_batch *b)
+    {
+        for (int32_t v : {(int32_t)b->family, (int32_t)b->rising, (int32_t)b->wide, (int32_t)b->stage}) field(v);
+        for (const ClassLaunch &cl : b->launches) {
+            field((int32_t)cl.C);
+            field(cl.first_wave);
+            field(cl.n_waves);
         }
     }
-    return h;
+};
+uint64_t plan_digest(const agx_sw_batch *b, const std::vector<SwWave> &waves, const void *groups, size_t groups_bytes)
+{
+    Fnv1a f;
+    f.head(b);
+    f.bytes(waves.data(), waves.size() * sizeof(SwWave));
+    f.bytes(groups, groups_bytes);
+    if (b->cigar == 2) {
+        f.bytes(b->tr_goff.data(), b->tr_goff.size() * sizeof(uint64_t));
+        f.field(b->tr_dwords);
+        f.field(b->tr_slot_words);
+        for (const SwWalkRec &r : b->tr_walk) {
+            f.field(r.goff), f.field(r.x_dw), f.field(r.y_dw), f.field(r.ca), f.field(r.cb), f.field(r.G), f.field(r.C), f.field(r.slot);
+        }
+    }
+    return f.h;
+}
+
+// AGX_TRACE_CREATE: the same plan part by part, each hashed afresh, so that two digests that differ say where: the head (kernel
+// choice and launches), the wave records, the group records; then the groups, how many of them have a vacant second half (a
+// packed plan's group whose second score slot is the spare one, n_pairs) and the columns per lane of every launch.
+void trace_plan_parts(const agx_sw_batch *b, bool packed, const std::vector<SwWave> &waves, const void *groups, size_t groups_bytes)
+{
+    Fnv1a head, wv, gr;
+    head.head(b);
+    wv.bytes(waves.data(), waves.size() * sizeof(SwWave));
+    gr.bytes(groups, groups_bytes);
+    const size_t n_groups = groups_bytes / (packed ? sizeof(SwGroup2) : sizeof(SwGroup));
+    size_t vacant = 0;
+    if (packed)
+        for (size_t g = 0; g < n_groups; ++g) vacant += ((const SwGroup2 *)groups)[g].out[1] == (uint32_t)b->n_pairs;
+    std::string cs;
+    for (const ClassLaunch &cl : b->launches) cs += " " + std::to_string(cl.C);
+    fprintf(stderr, "[agx_sw_batch_create] plan parts: head %016llx waves %016llx groups %016llx; %zu groups, %zu vacant halves; launch C%s\n",
+            (unsigned long long)head.h, (unsigned long long)wv.h, (unsigned long long)gr.h, n_groups, vacant, cs.empty() ? " none" : cs.c_str());
 }
 
 // ---- the stages of create_batch, in the order it calls them.  Each reads what it is given and fills a result of its own.
@@ -1014,14 +1043,29 @@ int queue_device_image(agx_ctx *ctx, agx_sw_batch *b, SwPending &tmp, const Plan
 }
 
 // AGX_TRACE_CREATE: what was chosen once the plan was known, and the plan's digest (tests parse these lines)
-void trace_plan(const agx_sw_batch *b, const KernelChoice &kc, const PeriodAndStage &ps, const PlanLayout &lay, bool device_plan, const void *groups_data)
+// A device-made plan's records never reach the host otherwise: the trace waits for the planning kernels (dp.done) and copies the
+// wave and group records back, before the pack kernel marks the waves, and hashes them as it does a host-made plan's.
+int trace_plan(const agx_sw_batch *b, const KernelChoice &kc, const PeriodAndStage &ps, const PlanLayout &lay, const DevPlan *dp, const void *groups_data)
 {
     if (kc.family == 2 && kc.rising == 4) fprintf(stderr, "[agx_sw_batch_create] class period %d of %d\n", ps.wide ? ps.period : 4, ps.period);
     if (kc.family == 2)
         fprintf(stderr, "[agx_sw_batch_create] staged priority %d: %lld waves, %lld resident at once\n", ps.stage, (long long)lay.n_waves_total,
                 (long long)ps.resident);
-    if (device_plan) fprintf(stderr, "[agx_sw_batch_create] plan digest: on device\n");
-    else fprintf(stderr, "[agx_sw_batch_create] plan digest %016llx\n", (unsigned long long)plan_digest(b, lay.waves, groups_data, lay.groups_bytes));
+    if (!dp) {
+        fprintf(stderr, "[agx_sw_batch_create] plan digest %016llx\n", (unsigned long long)plan_digest(b, lay.waves, groups_data, lay.groups_bytes));
+        trace_plan_parts(b, kc.packed, lay.waves, groups_data, lay.groups_bytes);
+        return AGX_OK;
+    }
+    fprintf(stderr, "[agx_sw_batch_create] plan digest: on device\n");
+    std::vector<SwWave> waves(lay.n_waves_total);
+    std::vector<SwGroup2> groups(lay.n_groups);
+    const size_t groups_bytes = lay.n_groups * sizeof(SwGroup2);
+    AGX_HIP(hipEventSynchronize(dp->done));
+    if (!waves.empty()) AGX_HIP(hipMemcpy(waves.data(), b->waves.p, waves.size() * sizeof(SwWave), hipMemcpyDeviceToHost));
+    if (!groups.empty()) AGX_HIP(hipMemcpy(groups.data(), b->groups.p, groups_bytes, hipMemcpyDeviceToHost));
+    fprintf(stderr, "[agx_sw_batch_create] device plan digest %016llx\n", (unsigned long long)plan_digest(b, waves, groups.data(), groups_bytes));
+    trace_plan_parts(b, true, waves, groups.data(), groups_bytes);
+    return AGX_OK;
 }
 
 // what agx_sw_batch_info answers (a device-made plan's padded cells arrive with the verdict)
@@ -1155,7 +1199,7 @@ int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matri
     b->wide = ps.wide;
     b->stage = ps.stage;
     if (ps.wide && ctx) agx_sw_pk2w_preload();
-    if (trace) trace_plan(b, kc, ps, lay, device_plan, groups_data);
+    if (trace && (rc = trace_plan(b, kc, ps, lay, device_plan ? &tmp->dp : nullptr, groups_data))) return rc;
     set_info(b, a.cells, lay, device_plan);
     if (!ctx) { // planning only
         if (trace) trace_times(t, n_pairs, false, false, 0);

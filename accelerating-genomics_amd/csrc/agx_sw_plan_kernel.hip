@@ -5,7 +5,9 @@
 // wavefronts, give every pair its place in the image, write the group and wave records, order the waves longest
 // first -- as kernels behind the upload of len[], so that the host is left with one reduction pass over len[] / off[]
 // and the batch-level rules.  The records are the ones the host planner writes, byte for byte (same keys, stable
-// sorts): tests/test_sw_gpu.py compares the two planners through agx_sw_batch_info and the scores.
+// sorts): tests/test_sw_devplan_gpu.py holds the digest of the records copied back from the device (AGX_TRACE_CREATE,
+// "device plan digest") equal to the host-made plan's; tests/test_sw_gpu.py compares agx_sw_batch_info and the scores.
+// sw_plan_records<1> cannot be reached: a device plan requires family 2, and every packed family has two slots.
 //
 //   sw_plan_keys     pair -> sort key (class << 22 | (64 - G) << 16 | longest - ly), value = pair number
 //   [radix sort]     rocprim::radix_sort_pairs, 28 bits, stable (pairs with an empty side sort last)

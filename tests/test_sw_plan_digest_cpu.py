@@ -9,7 +9,8 @@ A change that is meant to alter plans records the fixture again with that tool.
 
 Not pinned here: cigar == 2 batches (the traced fill's chunk batches, whose walk records the digest also covers) are made by
 agx_sw_batch_cigars on a device only -- no plan-only route reaches them, the GPU CIGAR tests are their check -- and
-device-planned batches, whose records never reach the host (tests/test_sw_gpu.py compares their scores)."""
+device-planned batches, which need a device: under the trace their records are copied back and hashed the same way ("device
+plan digest"), and tests/test_sw_devplan_gpu.py holds that digest equal to the host-made plan's of the same batch."""
 import json
 import os
 
