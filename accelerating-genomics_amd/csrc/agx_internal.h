@@ -79,6 +79,22 @@ static inline double agx_now_ms()
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
+// AGX_TRACE_CREATE: a plan (or an image) as one number, 64-bit FNV-1a field by field -- never over struct padding; a float or
+// a double goes in by its bit pattern.  tests/test_sw_plan_digest_cpu.py, tests/test_sw_band_plan_digest_cpu.py and
+// tests/test_phmm_plan_digest_cpu.py pin the digests per kind of batch.
+struct Fnv1a {
+    uint64_t h = 0xcbf29ce484222325ull;
+    void bytes(const void *p, size_t n)
+    {
+        for (size_t k = 0; k < n; ++k) h = (h ^ ((const uint8_t *)p)[k]) * 0x100000001b3ull;
+    }
+    template <typename T>
+    void field(T v)
+    {
+        bytes(&v, sizeof v);
+    }
+};
+
 constexpr int kAuxStreams = 3;
 
 struct PoolBlock {

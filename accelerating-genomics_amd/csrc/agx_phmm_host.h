@@ -78,21 +78,7 @@ PhGroup make_group(uint32_t hap_dw, const Plan &p, uint32_t tab);
 // AGX_E_LIMIT with the message naming `named` when a launch's tables of `largest` bytes are beyond the LDS of a CU
 int check_lds(size_t largest, size_t named);
 
-// AGX_TRACE_CREATE: a plan (or the image) as one number, 64-bit FNV-1a field by field -- never over struct padding; a float or
-// a double goes in by its bit pattern.  tests/test_phmm_plan_digest_cpu.py pins the digests per kind of batch.
-struct Fnv1a {
-    uint64_t h = 0xcbf29ce484222325ull;
-    void bytes(const void *p, size_t n)
-    {
-        for (size_t k = 0; k < n; ++k) h = (h ^ ((const uint8_t *)p)[k]) * 0x100000001b3ull;
-    }
-    template <typename T>
-    void field(T v)
-    {
-        bytes(&v, sizeof v);
-    }
-};
-// kind and slots as make_plan takes them, the flags, the padded cells, the launches and every record as it goes to the device
+// AGX_TRACE_CREATE (Fnv1a, agx_internal.h; tests/test_phmm_plan_digest_cpu.py pins the digests per kind of batch): kind and slots as make_plan takes them, the flags, the padded cells, the launches and every record as it goes to the device
 Fnv1a plan_hash(int kind, int slots, const PlanOut &po, const std::vector<ClassLaunch> &launches);
 
 } // namespace agx_phmm_host

@@ -441,31 +441,19 @@ int launch_device_plan(agx_ctx *ctx, DevPlan &dp, agx_sw_batch *b, uint32_t n_pa
     return AGX_OK;
 }
 
-// AGX_TRACE_CREATE: a host-made plan as one number, 64-bit FNV-1a over the kernel choice (family, rising, wide, stage as
-// int32), the launches (C, first_wave, n_waves), the wave and group records as they go to the device and, for the traced fill,
-// its offsets and walk records field by field (no struct padding).  tests/test_sw_plan_digest_cpu.py pins it per kind of batch.
-struct Fnv1a {
-    uint64_t h = 0xcbf29ce484222325ull;
-    void bytes(const void *p, size_t n)
-    {
-        for (size_t k = 0; k < n; ++k) h = (h ^ ((const uint8_t *)p)[k]) * 0x100000001b3ull;
-    }
-    template <typename T> void field(T v) { bytes(&v, sizeof v); }
-    // the kernel choice and the launches: what a plan says before its records
-    void head(const agx_sw_batch *b)
-    {
-        for (int32_t v : {(int32_t)b->family, (int32_t)b->rising, (int32_t)b->wide, (int32_t)b->stage}) field(v);
-        for (const ClassLaunch &cl : b->launches) {
-            field((int32_t)cl.C);
-            field(cl.first_wave);
-            field(cl.n_waves);
-        }
-    }
-};
+// AGX_TRACE_CREATE: a host-made plan as one number, 64-bit FNV-1a (agx_internal.h) over the kernel choice (family, rising, wide,
+// stage as int32), the launches (C, first_wave, n_waves), the wave and group records as they go to the device and, for the traced
+// fill, its offsets and walk records field by field (no struct padding).  tests/test_sw_plan_digest_cpu.py pins it per kind of
+// batch.  hash_head: the kernel choice and the launches, what a plan says before its records
+void hash_head(Fnv1a &f, const agx_sw_batch *b)
+{
+    for (int32_t v : {(int32_t)b->family, (int32_t)b->rising, (int32_t)b->wide, (int32_t)b->stage}) f.field(v);
+    hash_launches(f, b->launches);
+}
 uint64_t plan_digest(const agx_sw_batch *b, const std::vector<SwWave> &waves, const void *groups, size_t groups_bytes)
 {
     Fnv1a f;
-    f.head(b);
+    hash_head(f, b);
     f.bytes(waves.data(), waves.size() * sizeof(SwWave));
     f.bytes(groups, groups_bytes);
     if (b->cigar == 2) {
@@ -485,7 +473,7 @@ uint64_t plan_digest(const agx_sw_batch *b, const std::vector<SwWave> &waves, co
 void trace_plan_parts(const agx_sw_batch *b, bool packed, const std::vector<SwWave> &waves, const void *groups, size_t groups_bytes)
 {
     Fnv1a head, wv, gr;
-    head.head(b);
+    hash_head(head, b);
     wv.bytes(waves.data(), waves.size() * sizeof(SwWave));
     gr.bytes(groups, groups_bytes);
     const size_t n_groups = groups_bytes / (packed ? sizeof(SwGroup2) : sizeof(SwGroup));

@@ -1,7 +1,10 @@
 // ------------------------------------------------------------------ banded batches (include/agx.h, "Banded alignment")
-// Their plan and create (around the main diagonal or a given one), launch and hits; the CIGARs of banded batches are in
-// agx_sw_cigar.cpp.
+// Their create (around the main diagonal or a given one) as a driver over stages -- the planner's are in agx_sw_band_plan.cpp,
+// the ones that fill the batch object and the device are here -- their launch and their hits; the CIGARs of banded batches are
+// in agx_sw_cigar.cpp.
 #include "agx_sw_batch.h"
+
+#include <string>
 
 #include "agx_parallel.h"
 
@@ -9,58 +12,237 @@ using namespace agx_sw_host;
 
 namespace {
 
-// Lane tiling of a band of `width` diagonals over lb rows: K diagonals per lane, G = ceil(width / K) lanes per group, 64 / G
-// groups per wave.  A wave step costs about kBandStepCells cells' worth of instructions besides its K cells (the exchanges, the
-// cell mask, the window shift, the loop: counted in the K = 8 disassembly) and a group runs lb + G steps; the
-// class with the least lane time per pair wins, ties go to the wider one (fewer steps).
-constexpr int kBandStepCells = 5;
-inline void band_tiling(int width, uint32_t lb, int &cls, int &G)
+// ---- AGX_TRACE_CREATE: the banded plan and its image as numbers (Fnv1a, field by field), in lines that
+// tests/test_sw_band_plan_digest_cpu.py pins per kind of batch (tests/sw_band_plan_cases.py)
+
+// what a banded plan says before its records: the kind, the kernel constants, the launches
+void hash_band_head(Fnv1a &f, const agx_sw_batch *b)
 {
-    double best = 0;
-    cls = -1;
-    for (int c = kSwNumBandClasses - 1; c >= 0; --c) {
-        const int K = kSwBandClasses[c], g = (width + K - 1) / K;
-        if (g > 64) continue;
-        const double cost = ((double)lb + g) * (kBandStepCells + K) / (double)(64 / g);
-        if (cls < 0 || cost < best) {
-            best = cost;
-            cls = c;
-            G = g;
+    for (int32_t v : {(int32_t)b->mode, b->band, (int32_t)b->align, (int32_t)b->band_at, b->zdrop_on ? b->zdrop : -1, (int32_t)b->cigar,
+                      (int32_t)b->matrix, b->prm.ge, b->prm.gf, b->prm.hd, b->prm.delta})
+        f.field(v);
+    f.field(b->prm.n_out);
+    hash_launches(f, b->launches);
+}
+void hash_band_waves(Fnv1a &f, const std::vector<SwWave> &waves)
+{
+    for (const SwWave &w : waves) f.field(w.first_group), f.field(w.n_groups), f.field(w.G), f.field(w.steps), f.field(w.reserved);
+}
+void hash_band_groups(Fnv1a &f, const std::vector<SwBandGroup> &groups)
+{
+    for (const SwBandGroup &g : groups)
+        f.field(g.x_dw), f.field(g.y_dw), f.field(g.la_lb), f.field(g.dlo), f.field(g.dhi), f.field(g.out), f.field(g.fpad), f.field(g.reserved);
+}
+
+// The kind line, the digest and the parts line.  The digest covers the head, every wave and group record, the first rows, the
+// centre diagonals of a batch around a diagonal and the tables a cigar batch keeps for its traced fills (band_rec, band_cls,
+// band_G) -- made here from the plan itself, since a plan-only batch does not keep them.  The parts line hashes head, waves and
+// groups afresh, so that two digests that differ say where, and counts what shows that a case reached its branch: the groups,
+// how many have each fpad, the rows of b the fills are not given, the diagonals per lane of every launch.
+void trace_band_plan(const agx_sw_batch *b, const std::vector<SwWave> &waves, const std::vector<SwBandGroup> &groups,
+                     const std::vector<uint32_t> &row0s, const int32_t *diag, const uint32_t *len)
+{
+    fprintf(stderr, "[agx_sw_batch_create_band] kind: mode %d band %d align %d at %d zdrop %d cigar %d matrix %d\n", b->mode, b->band, b->align,
+            (int)b->band_at, b->zdrop_on ? b->zdrop : -1, b->cigar, (int)b->matrix);
+    Fnv1a all, head, wv, gr;
+    hash_band_head(all, b), hash_band_head(head, b);
+    hash_band_waves(all, waves), hash_band_waves(wv, waves);
+    hash_band_groups(all, groups), hash_band_groups(gr, groups);
+    for (uint32_t r : row0s) all.field(r);
+    if (b->band_at)
+        for (int64_t p = 0; p < b->n_pairs; ++p) all.field(diag ? diag[p] : (int32_t)0);
+    if (b->cigar) {
+        std::vector<uint32_t> rec((size_t)b->n_pairs, kNoBandRec);
+        for (size_t k = 0; k < groups.size(); ++k) rec[groups[k].out] = (uint32_t)k;
+        for (uint32_t r : rec) all.field(r);
+        for (int tab = 0; tab < 2; ++tab) // band_cls, then band_G: every group has its wave's
+            for (const SwWave &w : waves) {
+                const int cls = (int)(std::find(kSwBandClasses, kSwBandClasses + kSwNumBandClasses, (int)w.reserved) - kSwBandClasses);
+                for (uint32_t k = 0; k < w.n_groups; ++k) all.field((uint8_t)(tab ? w.G : cls));
+            }
+    }
+    size_t fpad[4] = {0, 0, 0, 0};
+    unsigned long long trimmed = 0;
+    for (const SwBandGroup &g : groups) {
+        ++fpad[g.fpad & 3u];
+        trimmed += len[2 * (size_t)g.out + 1] - (g.la_lb >> 16);
+    }
+    std::string ks;
+    for (const ClassLaunch &cl : b->launches) ks += " " + std::to_string(cl.C);
+    fprintf(stderr, "[agx_sw_batch_create_band] plan digest %016llx\n", (unsigned long long)all.h);
+    fprintf(stderr,
+            "[agx_sw_batch_create_band] plan parts: head %016llx waves %016llx groups %016llx; %zu groups; fpad %zu/%zu/%zu/%zu; trimmed rows %llu; "
+            "launch K%s\n",
+            (unsigned long long)head.h, (unsigned long long)wv.h, (unsigned long long)gr.h, groups.size(), fpad[0], fpad[1], fpad[2], fpad[3], trimmed,
+            ks.empty() ? " none" : ks.c_str());
+}
+
+// the image as the fills read it (the pinned block that is uploaded; plan only: a block built for this line alone)
+void trace_band_image(const void *img, size_t bytes, int64_t first_bad)
+{
+    Fnv1a f;
+    f.bytes(img, bytes);
+    fprintf(stderr, "[agx_sw_batch_create_band] image digest %016llx, first bad pair %lld\n", (unsigned long long)f.h, (long long)first_bad);
+}
+
+// ---- the device side of a create, in the order create_band calls it
+
+// the batch object of a banded create, before its plan: the kind's flags and the kernel constants
+agx_sw_batch *init_band_batch(agx_ctx *ctx, const BandKind &kind, const agx_sw_scoring &sc, int64_t n_pairs)
+{
+    const BandAt *at = kind.at;
+    agx_sw_batch *b = new agx_sw_batch();
+    agx_ctx_retain(ctx);
+    b->ctx = ctx;
+    b->n_pairs = n_pairs;
+    b->banded = true;
+    b->band = kind.band;
+    b->cigar = kind.cigar ? 1 : 0;
+    b->family = 5;
+    b->align = at ? at->what : AGX_SW_ALIGN_SPANS;
+    b->band_at = at != nullptr;
+    b->zdrop_on = at && at->zdrop_on;
+    b->zdrop = b->zdrop_on ? at->zdrop : 0;
+    b->mode = kind.mode;
+    b->scoring = sc;
+    b->matrix = kind.matrix != nullptr;
+    if (kind.matrix) b->mat = *kind.matrix;
+    b->prm.ge = sc.gap_extend;
+    b->prm.gf = sc.gap_open + sc.gap_extend;
+    b->prm.hd = sc.match - b->prm.gf;
+    b->prm.delta = sc.match - sc.mismatch;
+    b->prm.n_out = (uint32_t)n_pairs;
+    return b;
+}
+
+// what agx_sw_batch_info answers
+void set_band_info(agx_sw_batch *b, int64_t cells, int64_t padded, uint64_t img_dw, size_t n_waves)
+{
+    b->info.n_pairs = b->n_pairs;
+    b->info.cells = cells;
+    b->info.padded_cells = padded;
+    b->info.input_bytes = (int64_t)(img_dw * 4);
+    b->info.n_launches = (int32_t)b->launches.size();
+    b->info.n_waves = (int32_t)n_waves;
+}
+
+// the whole image into dst, a range of groups per host thread -> the first pair that breaks the symbol rule, or -1
+int64_t build_band_image_all(const std::vector<SwBandGroup> &groups, const agx_sw_matrix *matrix, const uint8_t *bases, const uint64_t *off,
+                             const uint32_t *len, uint8_t *dst)
+{
+    std::vector<int64_t> bad((size_t)agx_host_threads(), -1);
+    agx_parallel_for((int64_t)groups.size(), 64, [&](int64_t lo, int64_t hi, int t) {
+        bad[(size_t)t] = build_band_image(groups, lo, hi, bases, off, len, matrix ? matrix->code : nullptr, dst);
+    });
+    int64_t first_bad = -1;
+    for (int64_t v : bad)
+        if (v >= 0 && (first_bad < 0 || v < first_bad)) first_bad = v;
+    return first_bad;
+}
+
+// What a batch on a device keeps on the host long after the create: the kernels it will launch, loaded now; the lengths; around
+// a diagonal the first rows and the centres; the sequences where the begin pass, the traced fills of the spans or the host's
+// checks need them; for a cigar batch the group records, every pair's record and its tiling.
+void keep_band_host_state(agx_sw_batch *b, const BandKind &kind, const BandPairs &pairs, const std::vector<SwBandGroup> &groups,
+                          const uint8_t *bases, const uint64_t *off, const uint32_t *len)
+{
+    const BandAt *at = kind.at;
+    const int64_t n_pairs = b->n_pairs;
+    agx_sw_band_preload();
+    if (n_pairs > 0) b->seq_len.assign(len, len + 2 * n_pairs);
+    if (kind.matrix) agx_sw_band_mat_preload();
+    if (at) {
+        agx_sw_band_at_preload();
+        if (at->zdrop_on) agx_sw_band_zdrop_preload();
+        b->band_row0 = pairs.row0s;
+        if (at->diag) b->band_diag.assign(at->diag, at->diag + n_pairs);
+        else b->band_diag.assign((size_t)n_pairs, 0);
+    }
+    if (kind.cigar || (at && at->what == AGX_SW_ALIGN_SPANS && (kind.mode == AGX_SW_MODE_LOCAL || kind.mode == AGX_SW_MODE_FIT))) {
+        b->seq_off.resize((size_t)n_pairs * 2);
+        uint64_t at_byte = 0;
+        for (int64_t k = 0; k < 2 * n_pairs; ++k) {
+            b->seq_off[(size_t)k] = at_byte;
+            at_byte += len[k];
         }
+        b->seq.resize((size_t)at_byte);
+        agx_parallel_for(2 * n_pairs, 8192, [&](int64_t lo, int64_t hi, int) {
+            for (int64_t k = lo; k < hi; ++k)
+                if (len[k] && bases) memcpy(b->seq.data() + b->seq_off[(size_t)k], bases + off[k], len[k]);
+        }); // (bases == NULL: every pair has an empty side, and a lone run of I or D reads no symbol)
+    }
+    if (!kind.cigar) return;
+    agx_sw_band_trace_preload();
+    if (at) agx_sw_band_trace_at_preload();
+    if (kind.matrix) agx_sw_band_trace_mat_preload();
+    agx_sw_walk_preload();
+    const std::vector<BandPlan> &plan = pairs.plan;
+    b->band_groups = groups;
+    b->band_rec.assign((size_t)n_pairs, kNoBandRec);
+    b->band_cls.resize(plan.size());
+    b->band_G.resize(plan.size());
+    for (size_t k = 0; k < plan.size(); ++k) {
+        b->band_rec[plan[k].pair] = (uint32_t)k;
+        b->band_cls[k] = plan[k].cls;
+        b->band_G[k] = plan[k].G;
     }
 }
 
-struct BandPlan { // one pair with work, as the sort moves it
-    uint32_t pair, la, lb;
-    int32_t dlo, dhi;
-    uint8_t cls, G;
-    uint32_t row0; // a band around a diagonal: the fill is given b[row0 .. row0 + lb) and the band shifted by row0; else 0
-};
-
-// What the band dlo .. dhi must hold in `mode` (include/agx.h, "Banded alignment around a diagonal"): nullptr if it does, else
-// the words of the error message.
-inline const char *band_at_condition(int mode, int64_t la, int64_t lb, int64_t dlo, int64_t dhi)
+// The image, built on the host in page-locked memory, and everything a batch with fills has on the device: the records, the
+// image, the matrix's table, the results and their landing blocks.  Returns when the copies have landed.  Every exit releases
+// the page-locked temporaries, an error exit behind a queued copy only once the copy stream has drained: `drain` does both.
+int upload_band(agx_ctx *ctx, agx_sw_batch *b, const BandKind &kind, const std::vector<SwBandGroup> &groups, const std::vector<SwWave> &waves,
+                uint64_t img_dw, const std::vector<int16_t> &mat_table, const uint8_t *bases, const uint64_t *off, const uint32_t *len, bool trace)
 {
-    const bool origin = dlo <= 0 && 0 <= dhi;
-    switch (mode) {
-    case AGX_SW_MODE_GLOBAL:
-        if (!origin) return "does not hold the origin (diagonal 0)";
-        return dlo <= la - lb && la - lb <= dhi ? nullptr : "does not hold the corner (diagonal la - lb)";
-    case AGX_SW_MODE_EXTEND: return origin ? nullptr : "does not hold the origin (diagonal 0)";
-    case AGX_SW_MODE_EXTEND_QUERY:
-        if (!origin) return "does not hold the origin (diagonal 0)";
-        return dhi >= la - lb ? nullptr : "holds no cell of column la (dhi < la - lb)";
-    case AGX_SW_MODE_FIT:
-        if (dlo > 0) return "holds no cell of column 0 (dlo > 0)";
-        return dhi >= la - lb ? nullptr : "holds no cell of column la (dhi < la - lb)";
-    default: return nullptr; // LOCAL: a band that misses the matrix scores 0
+    const size_t img_bytes = (size_t)img_dw * 4, groups_bytes = groups.size() * sizeof(SwBandGroup), waves_bytes = waves.size() * sizeof(SwWave);
+    PinBuf h_img, h_groups, h_waves;
+    DrainOnError drain(ctx, [&] {
+        for (PinBuf *v : {&h_img, &h_groups, &h_waves}) v->release();
+    });
+    int rc = h_img.alloc(ctx, img_bytes);
+    if (!rc) rc = h_groups.alloc(ctx, groups_bytes);
+    if (!rc) rc = h_waves.alloc(ctx, waves_bytes);
+    if (rc) return rc;
+    memcpy(h_groups.p, groups.data(), groups_bytes);
+    memcpy(h_waves.p, waves.data(), waves_bytes);
+    const int64_t first_bad = build_band_image_all(groups, kind.matrix, bases, off, len, (uint8_t *)h_img.p);
+    if (trace) trace_band_image(h_img.p, img_bytes, first_bad);
+    if (first_bad >= 0) {
+        if (kind.matrix) agx_set_error("pair %lld contains a byte outside the substitution matrix's alphabet", (long long)first_bad);
+        else agx_set_error("pair %lld contains byte 0x00, which is reserved as the padding symbol", (long long)first_bad);
+        return AGX_E_SYMBOL;
     }
+    rc = b->img.alloc(ctx, img_bytes);
+    if (!rc && kind.matrix) rc = b->table.alloc(ctx, mat_table.size() * sizeof(int16_t));
+    if (!rc) rc = b->groups.alloc(ctx, groups_bytes);
+    if (!rc) rc = b->waves.alloc(ctx, waves_bytes);
+    if (!rc && b->launches.size() > 1) rc = agx_ctx_prepare_fanout(ctx);
+    if (rc) return rc;
+    hipStream_t cs = ctx->copy;
+    AGX_HIP(hipMemcpyAsync(b->img.p, h_img.p, img_bytes, hipMemcpyHostToDevice, cs));
+    AGX_HIP(hipMemcpyAsync(b->groups.p, h_groups.p, groups_bytes, hipMemcpyHostToDevice, cs));
+    AGX_HIP(hipMemcpyAsync(b->waves.p, h_waves.p, waves_bytes, hipMemcpyHostToDevice, cs));
+    // (pageable: the runtime stages it before the call returns; mat_table outlives the wait below in any case)
+    if (kind.matrix) AGX_HIP(hipMemcpyAsync(b->table.p, mat_table.data(), mat_table.size() * sizeof(int16_t), hipMemcpyHostToDevice, cs));
+    // results and their landing blocks
+    const size_t words = (size_t)b->n_pairs * sizeof(uint32_t);
+    rc = b->scores.alloc(ctx, words);
+    if (!rc) rc = b->band_pos.alloc(ctx, words);
+    if (!rc) rc = b->out_stage.alloc(ctx, words);
+    if (!rc) rc = b->band_pos_stage.alloc(ctx, words);
+    if (!rc && b->zdrop_on) rc = b->band_stop.alloc(ctx, words);
+    if (!rc && b->zdrop_on) rc = b->band_stop_stage.alloc(ctx, words);
+    if (rc) return rc;
+    AGX_HIP(hipStreamSynchronize(cs));
+    drain.ok = true;
+    return AGX_OK;
 }
 
 } // namespace
 
 namespace agx_sw_host {
 
+// The create of every banded batch: the stages of agx_sw_band_plan.cpp and the ones above, top to bottom.
 int create_band(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t band, const uint8_t *bases, const uint64_t *off,
                 const uint32_t *len, int64_t n_pairs, agx_sw_batch **out, bool cigar, const BandAt *at, const agx_sw_matrix *matrix)
 {
@@ -74,347 +256,45 @@ int create_band(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t b
         return AGX_E_ARG;
     }
     *out = nullptr;
+    const BandKind kind{mode, band, cigar, at, matrix, who};
     // under a matrix (a batch around a diagonal without z-drop only: the entry points see to that) it is validated before anything
     // else that can fail; scoring is then its gaps around a match/mismatch pair that nothing reads
-    agx_sw_scoring mat_sc{};
+    agx_sw_scoring mat_sc{}, sc{};
     SwParams mat_prm{};
     std::vector<int16_t> mat_table;
-    if (matrix) {
-        const int mrc = matrix_constants(matrix, mat_sc, mat_prm, mat_table);
-        if (mrc) return mrc;
-        scoring = &mat_sc;
-    }
-    if (mode < AGX_SW_MODE_LOCAL || mode > AGX_SW_MODE_EXTEND_QUERY) {
-        agx_set_error("%s: mode = %d is not one of AGX_SW_MODE_LOCAL .. AGX_SW_MODE_EXTEND_QUERY (0..4)", who, mode);
-        return AGX_E_ARG;
-    }
-    if (at && at->what != AGX_SW_ALIGN_ENDS && at->what != AGX_SW_ALIGN_SPANS) {
-        agx_set_error("%s: what = %d is neither AGX_SW_ALIGN_ENDS nor AGX_SW_ALIGN_SPANS", who, at->what);
-        return AGX_E_ARG;
-    }
-    if (!at && mode != AGX_SW_MODE_GLOBAL && mode != AGX_SW_MODE_EXTEND) {
-        agx_set_error("%s: mode = %d has a free start or a column capture; a band around the main diagonal serves AGX_SW_MODE_GLOBAL and "
-                      "AGX_SW_MODE_EXTEND only",
-                      who, mode);
-        return AGX_E_ARG;
-    }
-    if (zd && mode != AGX_SW_MODE_EXTEND) {
-        agx_set_error("%s: mode = %d: a z-drop terminates an extension, AGX_SW_MODE_EXTEND only", who, mode);
-        return AGX_E_ARG;
-    }
-    if (zd && (at->zdrop < 0 || at->zdrop > AGX_SW_ZDROP_MAX)) {
-        agx_set_error("%s: zdrop = %d is outside 0 .. AGX_SW_ZDROP_MAX (%d)", who, at->zdrop, AGX_SW_ZDROP_MAX);
-        return AGX_E_ARG;
-    }
-    if (band < 0) {
-        agx_set_error("%s: band = %d is negative", who, band);
-        return AGX_E_ARG;
-    }
-    if (at && 2 * (int64_t)band + 1 > AGX_SW_BAND_MAX_WIDTH) {
-        agx_set_error("%s: band = %d needs %lld diagonals, supported %d", who, band, 2 * (long long)band + 1, AGX_SW_BAND_MAX_WIDTH);
-        return AGX_E_LIMIT;
-    }
-    int rc = ctx ? agx_bind(ctx) : AGX_OK;
+    int rc = matrix ? matrix_constants(matrix, mat_sc, mat_prm, mat_table) : AGX_OK;
     if (rc) return rc;
-    if (n_pairs < 0 || (n_pairs > 0 && (!off || !len))) {
-        agx_set_error("%s: bad arguments (n_pairs=%lld)", who, (long long)n_pairs);
-        return AGX_E_ARG;
-    }
-    if (n_pairs > 0x7fffffffLL / 2) {
-        agx_set_error("%s: more than 2^30 pairs in one batch", who);
-        return AGX_E_LIMIT;
-    }
-    const agx_sw_scoring ref_scoring = AGX_SW_SCORING_REFERENCE;
-    const agx_sw_scoring sc = scoring ? *scoring : ref_scoring;
-    if (sc.match < 1 || sc.match > 12 || sc.mismatch > 0 || sc.mismatch < sc.match - 128 || sc.gap_open > 0 || sc.gap_open < -1000 ||
-        sc.gap_extend > 0 || sc.gap_extend < -1000) {
-        agx_set_error("scoring {match %d, mismatch %d, open %d, extend %d} outside the supported range", sc.match, sc.mismatch, sc.gap_open,
-                      sc.gap_extend);
-        return AGX_E_LIMIT;
-    }
+    if ((rc = check_band_kind(kind))) return rc;
+    // ctx == NULL: plan only (no device needed) -- the batch answers agx_sw_batch_info() and nothing else
+    if ((rc = ctx ? agx_bind(ctx) : AGX_OK)) return rc;
+    if ((rc = check_band_arrays(kind, matrix ? &mat_sc : scoring, off, len, n_pairs, sc))) return rc;
 
-    // ---- pass A: limits, band, lane tiling
-    std::vector<BandPlan> plan;
-    std::vector<uint32_t> row0s; // (at) per pair, for the batch
-    if (at) row0s.assign((size_t)n_pairs, kNoBandRow);
-    int64_t cells = 0;
-    for (int64_t p = 0; p < n_pairs; ++p) {
-        const uint32_t la = len[2 * p], lb = len[2 * p + 1];
-        if (la > (uint32_t)AGX_SW_BAND_MAX_LEN || lb > (uint32_t)AGX_SW_BAND_MAX_LEN) {
-            agx_set_error("pair %lld: lengths %u x %u exceed the supported %d on either side of a banded batch", (long long)p, la, lb,
-                          AGX_SW_BAND_MAX_LEN);
-            return AGX_E_LIMIT;
-        }
-        int64_t dlo, dhi, row0 = 0, rows = lb;
-        if (at) {
-            // exactly c - w .. c + w, never widened.  The band touches the rows max(0, -dhi) .. min(lb, la - dlo) only: the fill is
-            // given those rows of b and the band shifted by the first.  The shifted problem has the same boundary values: the
-            // pinned modes hold the origin, so their first row is 0; in FIT and LOCAL a first row > 0 means dhi < 0, the row above
-            // it holds no in-band cell with j >= 0, and the only in-band cell of the first row is (row0, 0), whose value (0) is
-            // what the fill gives the origin of its own matrix.
-            const int64_t c = at->diag ? at->diag[p] : 0;
-            if (c > (int64_t)AGX_SW_BAND_MAX_LEN + band || -c > (int64_t)AGX_SW_BAND_MAX_LEN + band) {
-                agx_set_error("pair %lld: diag = %lld lies beyond the supported %d + band on either side", (long long)p, (long long)c, AGX_SW_BAND_MAX_LEN);
-                return AGX_E_ARG;
-            }
-            dlo = c - band;
-            dhi = c + band;
-            if (const char *why = band_at_condition(mode, la, lb, dlo, dhi)) {
-                agx_set_error("pair %lld: lengths %u x %u in mode %d: the band %lld .. %lld (diag %lld, band %d) %s", (long long)p, la, lb, mode,
-                              (long long)dlo, (long long)dhi, (long long)c, band, why);
-                return AGX_E_ARG;
-            }
-            if (mode == AGX_SW_MODE_LOCAL && (dlo > (int64_t)la - 1 || dhi < 1 - (int64_t)lb)) { // no in-band cell with i, j >= 1: scores 0
-                cells += (int64_t)la * lb;
-                continue;
-            }
-            row0 = std::max<int64_t>(0, -dhi);
-            rows = std::min<int64_t>(lb, (int64_t)la - dlo) - row0;
-            dlo += row0;
-            dhi += row0;
-        } else
-            band_limits(mode, band, la, lb, dlo, dhi);
-        if (dhi - dlo + 1 > AGX_SW_BAND_MAX_WIDTH) {
-            agx_set_error("pair %lld: lengths %u x %u at band %d need %lld diagonals, supported %d", (long long)p, la, lb, band,
-                          (long long)(dhi - dlo + 1), AGX_SW_BAND_MAX_WIDTH);
-            return AGX_E_LIMIT;
-        }
-        cells += (int64_t)la * lb;
-        if (!la || !lb) continue; // answered by the formulas
-        if (!bases) {
-            agx_set_error("%s: bases is NULL", who);
-            return AGX_E_ARG;
-        }
-        BandPlan e{(uint32_t)p, la, (uint32_t)rows, (int32_t)dlo, (int32_t)dhi, 0, 0, (uint32_t)row0};
-        if (at) row0s[(size_t)p] = (uint32_t)row0;
-        int cls = 0, G = 1;
-        band_tiling((int)(dhi - dlo + 1), e.lb, cls, G);
-        e.cls = (uint8_t)cls;
-        e.G = (uint8_t)G;
-        plan.push_back(e);
-    }
-    // ---- sort: class, lanes per group, then rows falling -- the groups of a wave step alike (lb + G)
-    std::sort(plan.begin(), plan.end(), [](const BandPlan &x, const BandPlan &y) {
-        if (x.cls != y.cls) return x.cls < y.cls;
-        if (x.G != y.G) return x.G < y.G;
-        if (x.lb != y.lb) return x.lb > y.lb;
-        return x.pair < y.pair;
-    });
-    // ---- waves, group records, image offsets
-    const size_t n_fill = plan.size();
-    std::vector<SwBandGroup> groups(n_fill);
+    // ---- the plan: per pair, sorted, in waves, as records
+    BandPairs pairs;
+    if ((rc = plan_band_pairs(kind, bases, len, n_pairs, pairs))) return rc;
+    sort_band_plan(pairs.plan);
     std::vector<SwWave> waves;
     std::vector<ClassLaunch> launches;
+    const int64_t padded = layout_band_waves(pairs.plan, waves, launches);
+    std::vector<SwBandGroup> groups;
     uint64_t img_dw = 0;
-    int64_t padded = 0;
-    for (size_t k = 0; k < n_fill;) {
-        const BandPlan &h = plan[k];
-        const int K = kSwBandClasses[h.cls], G = h.G, per_wave = 64 / G;
-        size_t end = k;
-        while (end < n_fill && end - k < (size_t)per_wave && plan[end].cls == h.cls && plan[end].G == h.G) ++end;
-        SwWave w{};
-        w.first_group = (uint32_t)k;
-        w.n_groups = (uint16_t)(end - k);
-        w.G = (uint16_t)G;
-        w.steps = h.lb + (uint32_t)G; // the wave's longest target comes first
-        w.reserved = (uint32_t)K;
-        if (launches.empty() || launches.back().C != K) {
-            ClassLaunch cl;
-            cl.C = K;
-            cl.first_wave = (uint32_t)waves.size();
-            launches.push_back(cl);
-        }
-        ++launches.back().n_waves;
-        waves.push_back(w);
-        padded += (int64_t)w.steps * 64 * K;
-        for (; k < end; ++k) {
-            const BandPlan &e = plan[k];
-            SwBandGroup &g = groups[k];
-            const int q0 = e.dlo + G * K - G;
-            g.fpad = (uint32_t)(((-q0) % 4 + 4) % 4);
-            g.x_dw = (uint32_t)img_dw;
-            img_dw += (g.fpad + e.la + 3) / 4 + 1;
-            g.y_dw = (uint32_t)img_dw;
-            img_dw += (e.lb + 4) / 4 + 1;
-            g.la_lb = e.la | e.lb << 16;
-            g.dlo = e.dlo;
-            g.dhi = e.dhi;
-            g.out = e.pair;
-            g.reserved = e.row0; // (the kernels do not read it: the image build below does)
-            if (img_dw > 0xffffffffull) {
-                agx_set_error("pair %u: the batch's sequences exceed the 16 GiB a banded batch's image may take", e.pair);
-                return AGX_E_LIMIT;
-            }
-        }
-    }
+    if ((rc = write_band_groups(pairs.plan, groups, img_dw))) return rc;
 
-    agx_sw_batch *b = new agx_sw_batch();
-    DrainOnError done(ctx, [&] { agx_sw_batch_destroy(b); }); // (an error exit behind a queued copy drains the copy stream first)
-    agx_ctx_retain(ctx);
-    b->ctx = ctx;
-    b->n_pairs = n_pairs;
-    b->banded = true;
-    b->band = band;
-    b->cigar = cigar ? 1 : 0;
-    b->family = 5;
-    b->align = at ? at->what : AGX_SW_ALIGN_SPANS;
-    b->band_at = at != nullptr;
-    b->zdrop_on = zd;
-    b->zdrop = zd ? at->zdrop : 0;
-    b->mode = mode;
-    b->scoring = sc;
-    b->matrix = matrix != nullptr;
-    if (matrix) b->mat = *matrix;
-    b->prm.ge = sc.gap_extend;
-    b->prm.gf = sc.gap_open + sc.gap_extend;
-    b->prm.hd = sc.match - b->prm.gf;
-    b->prm.delta = sc.match - sc.mismatch;
-    b->prm.n_out = (uint32_t)n_pairs;
+    // ---- the batch.  Every exit from here: on an error the copy stream drained (upload_band has seen to its own temporaries),
+    // then the half-built batch destroyed
+    agx_sw_batch *b = init_band_batch(ctx, kind, sc, n_pairs);
+    DrainOnError done(ctx, [&] { agx_sw_batch_destroy(b); });
     b->launches = launches;
-    b->info.n_pairs = n_pairs;
-    b->info.cells = cells;
-    b->info.padded_cells = padded;
-    b->info.input_bytes = (int64_t)(img_dw * 4);
-    b->info.n_launches = (int32_t)launches.size();
-    b->info.n_waves = (int32_t)waves.size();
-    if (!ctx) {
-        *out = b;
-        b = nullptr;
-        done.ok = true;
-        return AGX_OK;
-    }
-    agx_sw_band_preload();
-    if (n_pairs > 0) b->seq_len.assign(len, len + 2 * n_pairs);
-    if (matrix) agx_sw_band_mat_preload();
-    if (at) {
-        agx_sw_band_at_preload();
-        if (zd) agx_sw_band_zdrop_preload();
-        b->band_row0 = row0s;
-        if (at->diag) b->band_diag.assign(at->diag, at->diag + n_pairs);
-        else b->band_diag.assign((size_t)n_pairs, 0);
-    }
-    if (cigar || (at && at->what == AGX_SW_ALIGN_SPANS && (mode == AGX_SW_MODE_LOCAL || mode == AGX_SW_MODE_FIT))) {
-        // what the traced fills of the spans and the host's checks, or the begin pass, need long after this call
-        b->seq_off.resize((size_t)n_pairs * 2);
-        uint64_t at_byte = 0;
-        for (int64_t k = 0; k < 2 * n_pairs; ++k) {
-            b->seq_off[(size_t)k] = at_byte;
-            at_byte += len[k];
-        }
-        b->seq.resize((size_t)at_byte);
-        agx_parallel_for(2 * n_pairs, 8192, [&](int64_t lo, int64_t hi, int) {
-            for (int64_t k = lo; k < hi; ++k)
-                if (len[k] && bases) memcpy(b->seq.data() + b->seq_off[(size_t)k], bases + off[k], len[k]);
-        }); // (bases == NULL: every pair has an empty side, and a lone run of I or D reads no symbol)
-    }
-    if (cigar) {
-        agx_sw_band_trace_preload();
-        if (at) agx_sw_band_trace_at_preload();
-        if (matrix) agx_sw_band_trace_mat_preload();
-        agx_sw_walk_preload();
-        b->band_groups = groups;
-        b->band_rec.assign((size_t)n_pairs, kNoBandRec);
-        b->band_cls.resize(n_fill);
-        b->band_G.resize(n_fill);
-        for (size_t k = 0; k < n_fill; ++k) {
-            b->band_rec[plan[k].pair] = (uint32_t)k;
-            b->band_cls[k] = plan[k].cls;
-            b->band_G[k] = plan[k].G;
-        }
-    }
-    PinBuf h_img, h_groups, h_waves;
-    struct Temps {
-        PinBuf *a, *b, *c;
-        ~Temps()
-        {
-            a->release();
-            b->release();
-            c->release();
-        }
-    };
-    if (n_fill) {
-        // ---- the image, built on the host (it touches every byte once: the symbol check rides along).  Under a matrix the image
-        // holds symbol numbers, code + 1, and 0 stays the padding; a byte outside the alphabet is written as padding and fails
-        // the create below
-        rc = h_img.alloc(ctx, (size_t)img_dw * 4);
-        if (!rc) rc = h_groups.alloc(ctx, n_fill * sizeof(SwBandGroup));
-        if (!rc) rc = h_waves.alloc(ctx, waves.size() * sizeof(SwWave));
-        Temps temps{&h_img, &h_groups, &h_waves}; // released after `done` below has drained (it is declared later, so runs first)
-        DrainOnError drain(ctx, [] {});
-        if (rc) return rc;
-        memcpy(h_groups.p, groups.data(), n_fill * sizeof(SwBandGroup));
-        memcpy(h_waves.p, waves.data(), waves.size() * sizeof(SwWave));
-        std::vector<int64_t> bad((size_t)agx_host_threads(), -1);
-        uint8_t *im = (uint8_t *)h_img.p;
-        agx_parallel_for((int64_t)n_fill, 64, [&](int64_t lo, int64_t hi, int t) {
-            int64_t first_bad = -1;
-            for (int64_t k = lo; k < hi; ++k) {
-                const SwBandGroup &g = groups[(size_t)k];
-                const uint32_t la = g.la_lb & 0xffffu, lb = g.la_lb >> 16;
-                const uint8_t *sa = bases + off[2 * (size_t)g.out], *sb = bases + off[2 * (size_t)g.out + 1] + g.reserved; // (row0)
-                uint8_t *xa = im + (size_t)g.x_dw * 4, *ya = im + (size_t)g.y_dw * 4;
-                const size_t xbytes = ((size_t)(g.fpad + la + 3) / 4 + 1) * 4, ybytes = ((size_t)(lb + 4) / 4 + 1) * 4;
-                memset(xa, 0, g.fpad);
-                memset(xa + g.fpad + la, 0, xbytes - g.fpad - la);
-                ya[0] = 0;
-                memset(ya + 1 + lb, 0, ybytes - 1 - lb);
-                bool hit;
-                if (matrix) {
-                    const uint8_t *code = matrix->code, *b0 = sb - g.reserved;
-                    const uint32_t lb_all = len[2 * (size_t)g.out + 1];
-                    uint8_t miss = 0; // the OR of every code met: a valid one is below 32, so bit 7 says that some byte maps to 0xff
-                    for (uint32_t k = 0; k < la; ++k) {
-                        const uint8_t c = code[sa[k]];
-                        miss |= c;
-                        xa[g.fpad + k] = c == 0xff ? 0 : (uint8_t)(c + 1);
-                    }
-                    for (uint32_t k = 0; k < lb; ++k) {
-                        const uint8_t c = code[sb[k]];
-                        ya[1 + k] = c == 0xff ? 0 : (uint8_t)(c + 1);
-                    }
-                    for (uint32_t k = 0; k < lb_all; ++k) miss |= code[b0[k]]; // (all of b, as below)
-                    hit = (miss & 0x80u) != 0;
-                } else {
-                    memcpy(xa + g.fpad, sa, la);
-                    memcpy(ya + 1, sb, lb);
-                    // (all of b, the rows a band around a diagonal leaves out included)
-                    hit = memchr(sa, 0, la) || memchr(sb - g.reserved, 0, len[2 * (size_t)g.out + 1]);
-                }
-                if (hit && (first_bad < 0 || (int64_t)g.out < first_bad)) first_bad = g.out;
-            }
-            bad[(size_t)t] = first_bad;
-        });
-        int64_t first_bad = -1;
-        for (int64_t v : bad)
-            if (v >= 0 && (first_bad < 0 || v < first_bad)) first_bad = v;
-        if (first_bad >= 0) {
-            if (matrix) agx_set_error("pair %lld contains a byte outside the substitution matrix's alphabet", (long long)first_bad);
-            else agx_set_error("pair %lld contains byte 0x00, which is reserved as the padding symbol", (long long)first_bad);
-            return AGX_E_SYMBOL;
-        }
-        rc = b->img.alloc(ctx, (size_t)img_dw * 4);
-        if (!rc && matrix) rc = b->table.alloc(ctx, mat_table.size() * sizeof(int16_t));
-        if (!rc) rc = b->groups.alloc(ctx, n_fill * sizeof(SwBandGroup));
-        if (!rc) rc = b->waves.alloc(ctx, waves.size() * sizeof(SwWave));
-        if (!rc && launches.size() > 1) rc = agx_ctx_prepare_fanout(ctx);
-        if (rc) return rc;
-        hipStream_t cs = ctx->copy;
-        AGX_HIP(hipMemcpyAsync(b->img.p, h_img.p, (size_t)img_dw * 4, hipMemcpyHostToDevice, cs));
-        AGX_HIP(hipMemcpyAsync(b->groups.p, h_groups.p, n_fill * sizeof(SwBandGroup), hipMemcpyHostToDevice, cs));
-        AGX_HIP(hipMemcpyAsync(b->waves.p, h_waves.p, waves.size() * sizeof(SwWave), hipMemcpyHostToDevice, cs));
-        // (pageable: the runtime stages it before the call returns; mat_table outlives the wait below in any case)
-        if (matrix) AGX_HIP(hipMemcpyAsync(b->table.p, mat_table.data(), mat_table.size() * sizeof(int16_t), hipMemcpyHostToDevice, cs));
-        // results and their landing blocks (a later failure leaves behind the queued copies: `drain` waits for them)
-        const size_t words = (size_t)n_pairs * sizeof(uint32_t);
-        rc = b->scores.alloc(ctx, words);
-        if (!rc) rc = b->band_pos.alloc(ctx, words);
-        if (!rc) rc = b->out_stage.alloc(ctx, words);
-        if (!rc) rc = b->band_pos_stage.alloc(ctx, words);
-        if (!rc && zd) rc = b->band_stop.alloc(ctx, words);
-        if (!rc && zd) rc = b->band_stop_stage.alloc(ctx, words);
-        if (rc) return rc;
-        AGX_HIP(hipStreamSynchronize(cs));
-        drain.ok = true;
+    set_band_info(b, pairs.cells, padded, img_dw, waves.size());
+    const bool trace = agx_tune("AGX_TRACE_CREATE") != nullptr;
+    if (trace) trace_band_plan(b, waves, groups, pairs.row0s, at ? at->diag : nullptr, len);
+    if (ctx) {
+        keep_band_host_state(b, kind, pairs, groups, bases, off, len);
+        if (!groups.empty() && (rc = upload_band(ctx, b, kind, groups, waves, img_dw, mat_table, bases, off, len, trace))) return rc;
+        if (groups.empty() && trace) trace_band_image(nullptr, 0, -1);
+    } else if (trace) { // plan only: no image and no symbol check, but for the image digest
+        std::vector<uint8_t> im((size_t)img_dw * 4);
+        trace_band_image(im.data(), im.size(), groups.empty() ? -1 : build_band_image_all(groups, matrix, bases, off, len, im.data()));
     }
     *out = b;
     b = nullptr;
@@ -426,48 +306,43 @@ int band_launch(agx_sw_batch *b)
 {
     b->cig_valid = false; // what agx_sw_batch_cigars kept belongs to the launch before
     if (b->launches.empty()) return AGX_OK;
-    FanOut fan(b->ctx, (int)b->launches.size());
-    int rc = fan.begin();
-    if (rc) return rc;
-    int k = 0;
-    // widest class first: its waves have the longest steps
-    for (auto it = b->launches.rbegin(); it != b->launches.rend(); ++it) {
-        const ClassLaunch &cl = *it;
-        if (b->zdrop_on) {
-            if (agx_sw_band_zdrop_launch_class(cl.C, b->prm, (const uint32_t *)b->img.p, (const SwBandGroup *)b->groups.p,
-                                               (const SwWave *)b->waves.p + cl.first_wave, cl.n_waves, (int32_t *)b->scores.p,
-                                               (uint32_t *)b->band_pos.p, b->zdrop, (int32_t *)b->band_stop.p, fan.stream(k++))) {
-                agx_set_error("sw_fill_band_zd<%d> launch failed: %s", cl.C, hipGetErrorString(hipGetLastError()));
-                return AGX_E_HIP;
-            }
-            continue;
-        }
-        if (b->matrix) {
-            if (agx_sw_band_mat_launch_class(cl.C, b->mode, b->prm, (const uint32_t *)b->img.p, (const SwBandGroup *)b->groups.p,
-                                             (const SwWave *)b->waves.p + cl.first_wave, cl.n_waves, (int32_t *)b->scores.p,
-                                             (uint32_t *)b->band_pos.p, (const int16_t *)b->table.p, fan.stream(k++))) {
-                agx_set_error("sw_fill_band_mat<%d, %d> launch failed: %s", cl.C, b->mode, hipGetErrorString(hipGetLastError()));
-                return AGX_E_HIP;
-            }
-            continue;
-        }
-        if (b->band_at && b->mode != AGX_SW_MODE_GLOBAL && b->mode != AGX_SW_MODE_EXTEND) {
-            if (agx_sw_band_at_launch_class(cl.C, b->mode, b->prm, (const uint32_t *)b->img.p, (const SwBandGroup *)b->groups.p,
-                                            (const SwWave *)b->waves.p + cl.first_wave, cl.n_waves, (int32_t *)b->scores.p,
-                                            (uint32_t *)b->band_pos.p, fan.stream(k++))) {
-                agx_set_error("sw_fill_band_at<%d, %d> launch failed: %s", cl.C, b->mode, hipGetErrorString(hipGetLastError()));
-                return AGX_E_HIP;
-            }
-            continue;
-        }
-        if (agx_sw_band_launch_class(cl.C, b->mode == AGX_SW_MODE_EXTEND, b->prm, (const uint32_t *)b->img.p, (const SwBandGroup *)b->groups.p,
-                                     (const SwWave *)b->waves.p + cl.first_wave, cl.n_waves, (int32_t *)b->scores.p, (uint32_t *)b->band_pos.p,
-                                     fan.stream(k++))) {
-            agx_set_error("sw_fill_band<%d> launch failed: %s", cl.C, hipGetErrorString(hipGetLastError()));
+    const uint32_t *img = (const uint32_t *)b->img.p;
+    const SwBandGroup *groups = (const SwBandGroup *)b->groups.p;
+    const SwWave *waves = (const SwWave *)b->waves.p;
+    int32_t *scores = (int32_t *)b->scores.p;
+    uint32_t *pos = (uint32_t *)b->band_pos.p;
+    // every class through `launch`, the batch's kernel (`name`; with_mode: a build per mode, which the message names too)
+    const auto launch_classes = [&](const char *name, bool with_mode, auto launch) -> int {
+        FanOut fan(b->ctx, (int)b->launches.size());
+        int rc = fan.begin();
+        if (rc) return rc;
+        int k = 0;
+        // widest class first: its waves have the longest steps
+        for (auto it = b->launches.rbegin(); it != b->launches.rend(); ++it) {
+            if (!launch(*it, fan.stream(k++))) continue;
+            if (with_mode) agx_set_error("%s<%d, %d> launch failed: %s", name, it->C, b->mode, hipGetErrorString(hipGetLastError()));
+            else agx_set_error("%s<%d> launch failed: %s", name, it->C, hipGetErrorString(hipGetLastError()));
             return AGX_E_HIP;
         }
-    }
-    return fan.end();
+        return fan.end();
+    };
+    if (b->zdrop_on)
+        return launch_classes("sw_fill_band_zd", false, [&](const ClassLaunch &cl, hipStream_t s) {
+            return agx_sw_band_zdrop_launch_class(cl.C, b->prm, img, groups, waves + cl.first_wave, cl.n_waves, scores, pos, b->zdrop,
+                                                  (int32_t *)b->band_stop.p, s);
+        });
+    if (b->matrix)
+        return launch_classes("sw_fill_band_mat", true, [&](const ClassLaunch &cl, hipStream_t s) {
+            return agx_sw_band_mat_launch_class(cl.C, b->mode, b->prm, img, groups, waves + cl.first_wave, cl.n_waves, scores, pos,
+                                                (const int16_t *)b->table.p, s);
+        });
+    if (b->band_at && b->mode != AGX_SW_MODE_GLOBAL && b->mode != AGX_SW_MODE_EXTEND)
+        return launch_classes("sw_fill_band_at", true, [&](const ClassLaunch &cl, hipStream_t s) {
+            return agx_sw_band_at_launch_class(cl.C, b->mode, b->prm, img, groups, waves + cl.first_wave, cl.n_waves, scores, pos, s);
+        });
+    return launch_classes("sw_fill_band", false, [&](const ClassLaunch &cl, hipStream_t s) {
+        return agx_sw_band_launch_class(cl.C, b->mode == AGX_SW_MODE_EXTEND, b->prm, img, groups, waves + cl.first_wave, cl.n_waves, scores, pos, s);
+    });
 }
 
 // band_hits of a batch around a diagonal (include/agx.h, "Banded alignment around a diagonal"): the fill's rows are counted from

@@ -1,6 +1,7 @@
-// Private to the host side of the Smith-Waterman path -- agx_sw.cpp (plan, create, launch, scores), agx_sw_align.cpp (align
-// batches: hits, statistics), agx_sw_band.cpp (banded batches) and agx_sw_cigar.cpp (CIGARs) -- and included by nothing else:
-// the batch object and what those four files need of each other.  No kernel includes it.
+// Private to the host side of the Smith-Waterman path -- agx_sw.cpp (create, launch, scores), agx_sw_plan.cpp (its planner),
+// agx_sw_align.cpp (align batches: hits, statistics), agx_sw_band.cpp (banded batches: create, launch, hits),
+// agx_sw_band_plan.cpp (their planner) and agx_sw_cigar.cpp (CIGARs) -- and included by nothing else: the batch object and what
+// those files need of each other.  No kernel includes it.
 #pragma once
 #include "agx_sw.h"
 
@@ -104,6 +105,16 @@ struct agx_sw_batch {
 };
 
 namespace agx_sw_host __attribute__((visibility("hidden"))) {
+
+// AGX_TRACE_CREATE: the launches as every plan digest takes them
+inline void hash_launches(Fnv1a &f, const std::vector<ClassLaunch> &launches)
+{
+    for (const ClassLaunch &cl : launches) {
+        f.field((int32_t)cl.C);
+        f.field(cl.first_wave);
+        f.field(cl.n_waves);
+    }
+}
 
 constexpr uint32_t kNoBandRec = 0xffffffffu;
 constexpr uint32_t kNoBandRow = 0xffffffffu;
@@ -281,6 +292,72 @@ int align_once(agx_sw_batch *b, Answer answer)
     agx_sw_batch_destroy(b);
     return rc;
 }
+
+// ---- agx_sw_band_plan.cpp: the planner of banded batches, stage by stage as create_band calls it ("create
+// pipeline"); none of it touches the device
+// what kind of banded batch a create makes: the arguments of create_band that select checks, kernels and limits, and the entry
+// point's name for the messages
+struct BandKind {
+    int mode;
+    int32_t band;
+    bool cigar;
+    const BandAt *at;
+    const agx_sw_matrix *matrix;
+    const char *who;
+};
+struct BandPlan { // one pair with work, as the sort moves it
+    uint32_t pair, la, lb;
+    int32_t dlo, dhi;
+    uint8_t cls, G;
+    uint32_t row0; // a band around a diagonal: the fill is given b[row0 .. row0 + lb) and the band shifted by row0; else 0
+};
+// pass A's result: the pairs with work, (around a diagonal) every pair's first row or kNoBandRow, the cells of every matrix
+struct BandPairs {
+    std::vector<BandPlan> plan;
+    std::vector<uint32_t> row0s;
+    int64_t cells = 0;
+};
+// every check that runs before pass A; create_band binds the context between the two.  sc: what the batch is scored with
+int check_band_kind(const BandKind &kind);
+int check_band_arrays(const BandKind &kind, const agx_sw_scoring *scoring, const uint64_t *off, const uint32_t *len, int64_t n_pairs,
+                      agx_sw_scoring &sc);
+int plan_band_pairs(const BandKind &kind, const uint8_t *bases, const uint32_t *len, int64_t n_pairs, BandPairs &out);
+void sort_band_plan(std::vector<BandPlan> &plan);
+// The one wave builder of the banded plans, for create_band's pairs and for the spans of a cigar chunk (band_trace,
+// agx_sw_cigar.cpp): waves of 64 / G groups of one (class, lanes per group), a launch per class.  sorted: by class, lanes per
+// group, then rows falling; E has cls, G and lb (its rows).  -> the padded cells
+template <typename E>
+int64_t layout_band_waves(const std::vector<E> &sorted, std::vector<SwWave> &waves, std::vector<ClassLaunch> &launches)
+{
+    int64_t padded = 0;
+    for (size_t k = 0, end = 0, n = sorted.size(); k < n; k = end) {
+        const E &h = sorted[k];
+        const int K = kSwBandClasses[h.cls], G = h.G, per_wave = 64 / G;
+        while (end < n && end - k < (size_t)per_wave && sorted[end].cls == h.cls && sorted[end].G == h.G) ++end;
+        SwWave w{};
+        w.first_group = (uint32_t)k;
+        w.n_groups = (uint16_t)(end - k);
+        w.G = (uint16_t)G;
+        w.steps = h.lb + (uint32_t)G; // the wave's longest target comes first
+        w.reserved = (uint32_t)K;
+        if (launches.empty() || launches.back().C != K) {
+            ClassLaunch cl;
+            cl.C = K;
+            cl.first_wave = (uint32_t)waves.size();
+            launches.push_back(cl);
+        }
+        ++launches.back().n_waves;
+        waves.push_back(w);
+        padded += (int64_t)w.steps * 64 * K;
+    }
+    return padded;
+}
+// the group records in plan order and the image's extent; AGX_E_LIMIT beyond the 16 GiB an image may take
+int write_band_groups(const std::vector<BandPlan> &plan, std::vector<SwBandGroup> &groups, uint64_t &img_dw);
+// the image bytes of groups [lo, hi) into dst (code: a matrix's byte map, or NULL) -> the first pair of the range that breaks the
+// symbol rule, or -1
+int64_t build_band_image(const std::vector<SwBandGroup> &groups, int64_t lo, int64_t hi, const uint8_t *bases, const uint64_t *off,
+                         const uint32_t *len, const uint8_t *code, uint8_t *dst);
 
 // ---- agx_sw_band.cpp
 int create_band(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t band, const uint8_t *bases, const uint64_t *off,

@@ -1,6 +1,6 @@
 // CIGARs of the Smith-Waterman path (include/agx.h, "Alignment itself", "CIGARs for banded batches"):
 // the bounds and the host's checks, one driver (cigars_impl) for every kind of cigar batch with a tracer per kind, and the entry
-// points.
+// points.  (The chunks of a banded cigar batch are laid out in waves by the banded planner's builder, layout_band_waves.)
 #include "agx_sw_batch.h"
 
 #include "agx_parallel.h"
@@ -299,9 +299,9 @@ int band_trace(agx_sw_batch *b, const int64_t *pairs, int64_t m, CigarChunk &c, 
     hipStream_t st = ctx->stream;
     const agx_sw_hit *hits = b->cig_hits.data();
     const bool at = b->band_at;
-    // ---- the chunk's plan: the batch's tiling per pair, waves of one (class, lanes per group), longest span first
+    // ---- the chunk's plan: the batch's tiling per pair, longest span first, in waves by the wave builder of the batch's own plan
     struct Item {
-        uint32_t k, rec, cb;
+        uint32_t k, rec, lb; // the pair's place in the chunk, its record, the span's rows
         uint8_t cls, G;
     };
     std::vector<Item> items((size_t)m);
@@ -314,7 +314,7 @@ int band_trace(agx_sw_batch *b, const int64_t *pairs, int64_t m, CigarChunk &c, 
     std::sort(items.begin(), items.end(), [](const Item &x, const Item &y) {
         if (x.cls != y.cls) return x.cls < y.cls;
         if (x.G != y.G) return x.G < y.G;
-        if (x.cb != y.cb) return x.cb > y.cb;
+        if (x.lb != y.lb) return x.lb > y.lb;
         return x.k < y.k;
     });
     std::vector<SwBandGroup> &groups = c.plan_groups;
@@ -327,27 +327,11 @@ int band_trace(agx_sw_batch *b, const int64_t *pairs, int64_t m, CigarChunk &c, 
     walk.resize((size_t)m);
     bwalk.resize((size_t)m);
     std::vector<ClassLaunch> launches;
+    layout_band_waves(items, waves, launches);
     uint64_t tr_dwords = 0, slot_words = 0;
-    for (size_t k = 0; k < (size_t)m;) {
-        const Item &h = items[k];
-        const int K = kSwBandClasses[h.cls], G = h.G, per_wave = 64 / G;
-        size_t end = k;
-        while (end < (size_t)m && end - k < (size_t)per_wave && items[end].cls == h.cls && items[end].G == h.G) ++end;
-        SwWave w{};
-        w.first_group = (uint32_t)k;
-        w.n_groups = (uint16_t)(end - k);
-        w.G = (uint16_t)G;
-        w.steps = h.cb + (uint32_t)G;
-        w.reserved = (uint32_t)K;
-        if (launches.empty() || launches.back().C != K) {
-            ClassLaunch cl;
-            cl.C = K;
-            cl.first_wave = (uint32_t)waves.size();
-            launches.push_back(cl);
-        }
-        ++launches.back().n_waves;
-        waves.push_back(w);
-        for (; k < end; ++k) {
+    for (SwWave &w : waves) {
+        const int K = (int)w.reserved, G = w.G;
+        for (size_t k = w.first_group, end = k + w.n_groups; k < end; ++k) {
             const Item &e = items[k];
             const int64_t p = pairs[e.k];
             int64_t ca, cb;
@@ -369,7 +353,7 @@ int band_trace(agx_sw_batch *b, const int64_t *pairs, int64_t m, CigarChunk &c, 
                 g.dlo = sp.dlo;
                 g.dhi = sp.dhi;
                 g.reserved = phase = sp.phase;
-                waves.back().steps = std::max(waves.back().steps, sp.steps);
+                w.steps = std::max(w.steps, sp.steps);
             }
             g.la_lb = (uint32_t)ca | (uint32_t)cb << 16;
             g.out = e.k;

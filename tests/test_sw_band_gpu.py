@@ -364,3 +364,23 @@ def test_swalign_prints_what_the_api_returns(ctx, tmp_path, word, mode, w):
     for bad_word in ("fit+band=3", "global+band=x", "global+band=3+cigar"):
         bad = subprocess.run([exe, str(long), bad_word], capture_output=True, timeout=60)
         assert bad.returncode != 0 and b"Usage" in bad.stderr and not bad.stdout, bad_word
+
+
+# ---- 10. what a device is given is what the plan fixture pins
+
+
+def test_device_creates_upload_the_pinned_plan_and_image():
+    """Three cases of tests/sw_band_plan_cases.py -- plain GLOBAL, FIT windows around diagonals (trimmed rows) and a cigar batch
+    under a matrix -- created on device 0 in one child process under the tuning build's AGX_TRACE_CREATE: the plan digest, the
+    digest of the page-locked image that is uploaded, and the info equal tests/golden/sw_band_plan_digests.json, which the CPU
+    test holds the plan-only creates to.  A banded plan reads nothing of the device, so the equality is unconditional."""
+    import json
+
+    from tests import sw_band_plan_cases as bc
+
+    with open(os.path.join(ROOT, "tests", "golden", "sw_band_plan_digests.json")) as f:
+        golden = json.load(f)
+    got, err = bc.run_group("default", names=list(bc.DEVICE_CASES), device=True)
+    assert sorted(got) == sorted(bc.DEVICE_CASES), err[-2000:]
+    for name in bc.DEVICE_CASES:
+        assert got[name] == golden[name], name
