@@ -107,6 +107,10 @@ struct agx_ctx {
     hipStream_t stream = nullptr;
     bool own_stream = false;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    // Work the library has put on `stream`, counted (agx_enqueue_stream): a Smith-Waterman launch that carries its batch's done
+    // event notes the count it leaves behind, and agx_sw_batch_scores waits for that event only while the count still stands
+    // there -- after anything else it waits for the stream, as every other fetch does (agx_sw.cpp, "Completion on the dispatch")
+    uint64_t enqueued = 0;
     int n_cu = 0;
     // Uploads run on their own stream so that building batch k+1 overlaps the fill of batch k.
     hipStream_t copy = nullptr;
@@ -206,6 +210,14 @@ static inline int agx_bind(const agx_ctx *c)
     }
     AGX_HIP(hipSetDevice(c->device));
     return AGX_OK;
+}
+
+// The context's stream for a call that is about to put work on it -- a kernel, a copy, an event record, a wait for an event:
+// every such site takes the stream here, so that agx_ctx::enqueued counts them all.  (Waiting for the stream takes c->stream.)
+static inline hipStream_t agx_enqueue_stream(agx_ctx *c)
+{
+    ++c->enqueued;
+    return c->stream;
 }
 
 // memcpy with streaming stores, for staging copies into page-locked memory (agx_runtime.cpp)

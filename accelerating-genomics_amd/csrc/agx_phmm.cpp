@@ -772,7 +772,7 @@ int agx_phmm_batch_launch(agx_phmm_batch *b)
     }
     int rc = agx_bind(b->ctx);
     if (rc) return rc;
-    hipStream_t s = b->ctx->stream;
+    hipStream_t s = agx_enqueue_stream(b->ctx);
     const LutPtrs lut = lut_ptrs(b->lut.p);
     const bool f32 = f32_family(b->precision);
     // The two counters are zero at creation and are reset by whoever reads them (the log10 kernel of agx_phmm_batch_results; a
@@ -944,7 +944,7 @@ int agx_phmm_batch_results(agx_phmm_batch *b, double *log10_lik, double *raw_sum
     char *const stage = (char *)b->out_stage.p; // [two counters][logs (float modes)][sums (when wanted)]
     volatile unsigned long long *host_counter = (volatile unsigned long long *)stage; // written by the log10 kernel itself
     double *s = nullptr, *dev_logs = nullptr;                                         // (float modes; the double modes have no rescue pass)
-    hipStream_t st = b->ctx->stream;
+    hipStream_t st = agx_enqueue_stream(b->ctx);
     for (int round = 0; round < 2; ++round) {
         host_counter[0] = host_counter[1] = 0;
         char *at = stage + 16;

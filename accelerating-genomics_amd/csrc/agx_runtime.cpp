@@ -426,7 +426,7 @@ int FanOut::begin()
     if (n <= 1) return AGX_OK;
     const int rc = agx_ctx_prepare_fanout(c); // normally done at batch creation already
     if (rc) return rc;
-    AGX_HIP(hipEventRecord(c->fork, c->stream));
+    AGX_HIP(hipEventRecord(c->fork, agx_enqueue_stream(c)));
     return AGX_OK;
 }
 
@@ -453,9 +453,9 @@ int agx_ctx_prepare_plan(agx_ctx *c)
 
 hipStream_t FanOut::stream(int k)
 {
-    if (n <= 1) return c->stream;
+    if (n <= 1) return agx_enqueue_stream(c);
     const int lane = k % (kAuxStreams + 1);
-    if (lane == 0) return c->stream;
+    if (lane == 0) return agx_enqueue_stream(c);
     if (!used[lane - 1]) {
         (void)hipStreamWaitEvent(c->aux[lane - 1], c->fork, 0);
         used[lane - 1] = true;
@@ -468,7 +468,7 @@ int FanOut::end()
     for (int k = 0; k < kAuxStreams; ++k)
         if (used[k]) {
             AGX_HIP(hipEventRecord(c->join[k], c->aux[k]));
-            AGX_HIP(hipStreamWaitEvent(c->stream, c->join[k], 0));
+            AGX_HIP(hipStreamWaitEvent(agx_enqueue_stream(c), c->join[k], 0));
         }
     return AGX_OK;
 }
@@ -741,6 +741,7 @@ int agx_ctx_set_stream(agx_ctx *c, void *s)
         (void)hipStreamDestroy(c->stream);
     }
     c->stream = (hipStream_t)s;
+    ++c->enqueued; // another stream: no launch noted on the old one is this one's last
     c->own_stream = false;
     return AGX_OK;
 }
@@ -786,7 +787,7 @@ int agx_ctx_timer_start(agx_ctx *c)
 {
     int rc = agx_bind(c);
     if (rc) return rc;
-    AGX_HIP(hipEventRecord(c->ev0, c->stream));
+    AGX_HIP(hipEventRecord(c->ev0, agx_enqueue_stream(c)));
     return AGX_OK;
 }
 
@@ -794,7 +795,7 @@ int agx_ctx_timer_stop(agx_ctx *c, float *ms)
 {
     int rc = agx_bind(c);
     if (rc) return rc;
-    AGX_HIP(hipEventRecord(c->ev1, c->stream));
+    AGX_HIP(hipEventRecord(c->ev1, agx_enqueue_stream(c)));
     AGX_HIP(hipEventSynchronize(c->ev1));
     float t = 0;
     AGX_HIP(hipEventElapsedTime(&t, c->ev0, c->ev1));
@@ -806,7 +807,7 @@ int agx_ctx_timer_mark(agx_ctx *c)
 {
     int rc = agx_bind(c);
     if (rc) return rc;
-    AGX_HIP(hipEventRecord(c->ev1, c->stream));
+    AGX_HIP(hipEventRecord(c->ev1, agx_enqueue_stream(c)));
     return AGX_OK;
 }
 

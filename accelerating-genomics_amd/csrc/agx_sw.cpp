@@ -46,6 +46,17 @@ int tuned_kernel() // AGX_SW_KERNEL; 0 = no override
 // AGX_SW_PIECE_MB, AGX_SW_PIECE_MIN_PAIRS
 inline uint64_t piece_bytes() { static const uint64_t v = (uint64_t)agx_knob_int(agx_tune("AGX_SW_PIECE_MB"), 32, positive) << 20; return v; }
 inline int64_t piece_min_pairs() { static const int64_t v = agx_knob_int(agx_tune("AGX_SW_PIECE_MIN_PAIRS"), 32768, positive); return v; }
+// completion on the dispatch (ensure_done_event), taken off for an A/B: AGX_SW_DONE_EVENT=0
+inline bool done_event_on()
+{
+    static const bool v = [] {
+        const char *e = agx_tune("AGX_SW_DONE_EVENT");
+        return !(e && e[0] == '0' && !e[1]);
+    }();
+    return v;
+}
+// AGX_TRACE_FETCH: a line for every bind_scores (was the array taken?) and every fetch from a bound array (what it waited for)
+inline bool trace_fetch() { static const bool v = agx_tune("AGX_TRACE_FETCH") != nullptr; return v; }
 constexpr size_t kRawPad = 64;       // bytes in front of and behind the uploaded sequences (16-byte aligned pieces, agx_sw_pack_kernel.hip)
 
 } // namespace
@@ -53,6 +64,7 @@ constexpr size_t kRawPad = 64;       // bytes in front of and behind the uploade
 namespace {
 int finish_create(agx_sw_batch *b);
 void drop_pending(agx_sw_batch *b);
+int ensure_done_event(agx_sw_batch *b);
 }
 
 extern "C" {
@@ -62,6 +74,7 @@ void agx_sw_batch_destroy(agx_sw_batch *b)
     if (!b) return;
     if (b->ctx) (void)hipSetDevice(b->ctx->device);
     drop_pending(b);
+    if (b->done) (void)hipEventDestroy(b->done);
     b->img.release();
     b->groups.release();
     b->waves.release();
@@ -1217,6 +1230,8 @@ int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matri
         return AGX_OK;
     }
     if ((rc = wait_for_verdict(b, *tmp, ts))) return rc; // blocking by contract; the staging buffers are free again
+    if ((rc = ensure_done_event(b))) return rc;
+    if (trace) fprintf(stderr, "[agx_sw_batch_create] done event %d\n", b->done ? 1 : 0);
     if (trace) trace_times(t, n_pairs, true, device_plan, tmp->up.raw_bytes);
     *out = b;
     b = nullptr;
@@ -1225,6 +1240,24 @@ int create_batch(agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matri
 }
 
 } // namespace agx_sw_host
+
+namespace {
+
+// ---- Completion on the dispatch.  A launch carries no completion signal of its own, so a stream wait makes the runtime queue a
+// marker packet with a signal behind the fill, and the command processor must take that packet, after the last wave has retired,
+// before the host's poll sees anything.  A batch of the biased packed fill with ONE launch therefore owns an event, and its launch
+// -- while the batch is bound: nothing else waits for the event -- hands it to the runtime as the kernel's stop event (hipExtLaunchKernelGGL): the fill's own packet then carries the signal.
+// agx_sw_batch_scores waits for that event instead of the stream -- in its bound branch, where nothing else is queued behind
+// the fill -- while the launch is still the last thing the library put on the stream (agx_ctx::enqueued), and for the stream
+// otherwise.  The kind of wait is the runtime's in both cases.  profiles/sw_step_boundary.md: bench.py's config-2 step 156.2-156.9 -> 153.8-154.2 us.
+int ensure_done_event(agx_sw_batch *b)
+{
+    const bool one_fill = b->ctx && b->family == 2 && !b->banded && !b->matrix && !b->align && b->launches.size() == 1;
+    if (one_fill && done_event_on() && !b->done) AGX_HIP(hipEventCreateWithFlags(&b->done, hipEventDisableTiming));
+    return AGX_OK;
+}
+
+} // namespace
 
 extern "C" {
 
@@ -1240,9 +1273,10 @@ int agx_sw_batch_launch(agx_sw_batch *b)
     }
     int rc = agx_bind(b->ctx);
     if (rc) return rc;
+    b->rebound = false; // what this launch writes is what the next fetch reads
     if (b->banded) return band_launch(b);
     // a batch whose create was not finished: its fill waits for the pack kernel on the device, not on the host
-    if (b->pending && b->pending->ready) AGX_HIP(hipStreamWaitEvent(b->ctx->stream, b->pending->ready, 0));
+    if (b->pending && b->pending->ready) AGX_HIP(hipStreamWaitEvent(agx_enqueue_stream(b->ctx), b->pending->ready, 0));
     SwParams prm = b->prm;
     if (b->bound) prm.n_out = (uint32_t)b->n_pairs; // the caller's array has no spare slot
     prm.stage = (uint32_t)b->stage;
@@ -1254,6 +1288,9 @@ int agx_sw_batch_launch(agx_sw_batch *b)
     FanOut fan(b->ctx, (int)b->launches.size());
     rc = fan.begin();
     if (rc) return rc;
+    // (ensure_done_event: the biased packed fill only; only a fetch from the bound array waits for the event, so only a bound
+    // batch's launch carries it -- every other launch is the plain one)
+    hipEvent_t stop = b->bound && b->launches.size() == 1 ? b->done : nullptr;
     int k = 0;
     // widest class first: its waves have the longest rows-times-columns chain, so they should not be the tail
     for (auto it = b->launches.rbegin(); it != b->launches.rend(); ++it) {
@@ -1299,10 +1336,13 @@ int agx_sw_batch_launch(agx_sw_batch *b)
         else if (b->family == 3)
             r = cl.C == 0 ? agx_sw_i32d_launch_any(prm, img, (const SwGroup2 *)b->groups.p, wv, cl.n_waves, scores, st)
                           : agx_sw_i32d_launch_class(cl.C, prm, img, (const SwGroup2 *)b->groups.p, wv, cl.n_waves, scores, st);
-        else if (b->family == 2 && cl.C == 0)
-            r = agx_sw_pk2_launch_any(b->rising, b->wide, prm, img, (const SwGroup2 *)b->groups.p, wv, cl.n_waves, scores, st);
-        else if (b->family == 2)
-            r = agx_sw_pk2_launch_class(cl.C, b->rising, b->wide, prm, img, (const SwGroup2 *)b->groups.p, wv, cl.n_waves, scores, st);
+        else if (b->family == 2) {
+            r = cl.C == 0 ? agx_sw_pk2_launch_any(b->rising, b->wide, prm, img, (const SwGroup2 *)b->groups.p, wv, cl.n_waves, scores, st, stop)
+                          : agx_sw_pk2_launch_class(cl.C, b->rising, b->wide, prm, img, (const SwGroup2 *)b->groups.p, wv, cl.n_waves, scores, st, stop);
+            // only these launchers take the event.  This launch is the stream's last, and its event will arrive:
+            // agx_sw_batch_scores may wait for it alone
+            if (!r && stop && cl.n_waves) b->done_at = b->ctx->enqueued;
+        }
         else if (b->family == 1)
             r = agx_sw_pk_launch_class(cl.C, prm, img, (const SwGroup2 *)b->groups.p, wv, cl.n_waves, scores, st);
         else
@@ -1336,6 +1376,10 @@ int agx_sw_batch_scores(agx_sw_batch *b, int32_t *scores)
         return rc;
         AGX_GUARD_END("agx_sw_batch_scores")
     }
+    if (b->rebound) {
+        agx_set_error("agx_sw_batch_scores: agx_sw_batch_bind_scores changed where this batch's scores go and no launch has run since; launch first");
+        return AGX_E_ARG;
+    }
     if (b->pending) { // (the pieces of agx_sw_score finish before they fetch; kept for safety)
         rc = finish_create(b);
         if (rc) return rc;
@@ -1346,7 +1390,14 @@ int agx_sw_batch_scores(agx_sw_batch *b, int32_t *scores)
     }
     const size_t bytes = (size_t)b->n_pairs * sizeof(int32_t);
     if (b->bound && scores == b->bound) { // the launches wrote them there themselves: nothing to copy
-        AGX_HIP(hipStreamSynchronize(b->ctx->stream));
+        // completion on the dispatch (ensure_done_event): while this batch's launch is the last thing the library put on the
+        // stream, its own stop event says all a stream wait would -- and the runtime queues no marker behind the fill to learn it
+        const bool own = b->done && b->done_at && b->done_at == b->ctx->enqueued;
+        if (trace_fetch()) fprintf(stderr, "[agx_sw_batch_scores] wait: %s\n", own ? "event" : "stream");
+        if (own)
+            AGX_HIP(hipEventSynchronize(b->done));
+        else
+            AGX_HIP(hipStreamSynchronize(b->ctx->stream));
         return AGX_OK;
     }
     if (b->bound) { // bound elsewhere: the device array was not written by the last launch
@@ -1357,7 +1408,7 @@ int agx_sw_batch_scores(agx_sw_batch *b, int32_t *scores)
     // one copy kernel right behind the last fill on the launch stream: straight into the caller's array when that is
     // page-locked (agx_host_alloc), else into pinned staging and a host copy from there
     int32_t *dst = agx_is_pinned_host(scores, bytes) ? scores : (int32_t *)b->out_stage.p;
-    if (agx_copy_out_launch(b->scores.p, dst, bytes, b->ctx->stream)) {
+    if (agx_copy_out_launch(b->scores.p, dst, bytes, agx_enqueue_stream(b->ctx))) {
         agx_set_error("agx_sw_batch_scores: copy kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
         return AGX_E_HIP;
     }
@@ -1386,7 +1437,10 @@ int agx_sw_batch_bind_scores(agx_sw_batch *b, int32_t *scores)
     AGX_HIP(hipStreamSynchronize(b->ctx->stream)); // launches in flight still write the old destination
     // only a batch whose records are in file order takes the binding (a sorted batch's waves would scatter 4-byte
     // writes over PCIe: measured slower than the copy kernel behind the fill); the call is a hint otherwise
-    b->bound = (scores && b->file_order && b->n_pairs > 0 && !b->matrix && !b->align) ? scores : nullptr;
+    int32_t *const bound = (scores && b->file_order && b->n_pairs > 0 && !b->matrix && !b->align) ? scores : nullptr;
+    if (bound != b->bound) b->rebound = true; // the last launch wrote elsewhere: agx_sw_batch_scores refuses until the next one
+    b->bound = bound;
+    if (trace_fetch()) fprintf(stderr, "[agx_sw_batch_bind_scores] bound %d\n", bound ? 1 : 0);
     return AGX_OK;
 }
 

@@ -104,19 +104,29 @@ int agx_sw_pk_launch_class(int cols_per_lane, const SwParams &prm, const uint32_
 // (their wide build passes 256 VGPRs or spills).
 #define AGX_SW_PK2_KEEP_NARROW(C) (false)
 constexpr int sw_pk2_period(int C) { return C >= 14 && !AGX_SW_PK2_KEEP_NARROW(C) ? C / 2 : 4; }
+// stop (the biased fill's launchers only): an event the dispatch itself carries as its stop event, so that the batch's fetch can wait
+// for this launch alone (agx_sw.cpp, "Completion on the dispatch"); NULL: a plain launch
 int agx_sw_pk2_launch_class(int cols_per_lane, int rising, bool wide, const SwParams &prm, const uint32_t *img, const SwGroup2 *groups,
-                            const SwWave *waves, uint32_t n_waves, int32_t *scores, hipStream_t s);
+                            const SwWave *waves, uint32_t n_waves, int32_t *scores, hipStream_t s, hipEvent_t stop = nullptr);
 int agx_sw_pk2w_launch_class(int cols_per_lane, const SwParams &prm, const uint32_t *img, const SwGroup2 *groups, const SwWave *waves,
-                             uint32_t n_waves, int32_t *scores, hipStream_t s);
+                             uint32_t n_waves, int32_t *scores, hipStream_t s, hipEvent_t stop = nullptr);
 int agx_sw_pk2w_launch_any(const SwParams &prm, const uint32_t *img, const SwGroup2 *groups, const SwWave *waves, uint32_t n_waves,
-                           int32_t *scores, hipStream_t s);
+                           int32_t *scores, hipStream_t s, hipEvent_t stop = nullptr);
+// one launch of 256-thread workgroups: with stop, hipExtLaunchKernelGGL binds that event to the kernel's own packet
+#define AGX_SW_PK2_LAUNCH(kernel, blocks, s, stop, ...)                                                            \
+    do {                                                                                                           \
+        if (stop)                                                                                                  \
+            hipExtLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, s, nullptr, stop, 0, __VA_ARGS__);           \
+        else                                                                                                       \
+            hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, s, __VA_ARGS__);                                \
+    } while (0)
 void agx_sw_pk2w_preload();
 // every class of a mixed batch in one launch: waves[].reserved holds each wave's columns per lane
 void agx_sw_pk2_preload();
 void agx_sw_pack_preload();
 void agx_sw_i32_preload();
 int agx_sw_pk2_launch_any(int rising, bool wide, const SwParams &prm, const uint32_t *img, const SwGroup2 *groups, const SwWave *waves,
-                          uint32_t n_waves, int32_t *scores, hipStream_t s);
+                          uint32_t n_waves, int32_t *scores, hipStream_t s, hipEvent_t stop = nullptr);
 // the 32-bit fill with the DNA-coded match: the packed plan's records and image, one pair of a lane group at a time
 int agx_sw_i32d_launch_any(const SwParams &prm, const uint32_t *img, const SwGroup2 *groups, const SwWave *waves, uint32_t n_waves, int32_t *scores,
                            hipStream_t s);

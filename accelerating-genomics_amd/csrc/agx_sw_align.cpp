@@ -158,7 +158,7 @@ int hits_impl(agx_sw_batch *b, agx_sw_hit *hits, std::vector<uint32_t> *L)
 {
     int rc = agx_bind(b->ctx);
     if (rc) return rc;
-    hipStream_t st = b->ctx->stream;
+    hipStream_t st = agx_enqueue_stream(b->ctx);
     const int64_t n = b->n_pairs;
     if (n == 0) {
         AGX_HIP(hipStreamSynchronize(st));

@@ -354,7 +354,7 @@ int band_at_hits(agx_sw_batch *b, agx_sw_hit *hits, bool begins)
 {
     int rc = agx_bind(b->ctx);
     if (rc) return rc;
-    hipStream_t st = b->ctx->stream;
+    hipStream_t st = agx_enqueue_stream(b->ctx);
     const int64_t n = b->n_pairs;
     const int mode = b->mode;
     const bool cell = mode == AGX_SW_MODE_LOCAL || mode == AGX_SW_MODE_EXTEND, column = mode == AGX_SW_MODE_FIT || mode == AGX_SW_MODE_EXTEND_QUERY;
@@ -469,7 +469,7 @@ int band_zdrop_stops(agx_sw_batch *b, int32_t *stops)
     std::vector<agx_sw_hit> hits((size_t)n);
     int rc = band_at_hits(b, hits.data(), false);
     if (rc) return rc;
-    hipStream_t st = b->ctx->stream;
+    hipStream_t st = agx_enqueue_stream(b->ctx);
     if (!b->launches.empty()) {
         AGX_HIP(hipMemcpyAsync(b->band_stop_stage.p, b->band_stop.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
         AGX_HIP(hipStreamSynchronize(st));
@@ -498,7 +498,7 @@ int band_hits(agx_sw_batch *b, agx_sw_hit *hits)
     if (b->band_at) return band_at_hits(b, hits, true);
     int rc = agx_bind(b->ctx);
     if (rc) return rc;
-    hipStream_t st = b->ctx->stream;
+    hipStream_t st = agx_enqueue_stream(b->ctx);
     const int64_t n = b->n_pairs;
     const bool filled = !b->launches.empty();
     if (filled) {

@@ -102,6 +102,13 @@ struct agx_sw_batch {
     // (only a batch planned in file order does: its waves then write consecutive bytes)
     bool file_order = false;
     int32_t *bound = nullptr;
+    // bind_scores changed `bound` and no launch has run since: neither the caller's array nor the device array holds what a
+    // fetch would promise, so agx_sw_batch_scores refuses until the next launch
+    bool rebound = false;
+    // Completion on the dispatch (agx_sw.cpp, ensure_done_event): the event this batch's one launch carries as its stop event
+    // (null: none), and agx_ctx::enqueued as that launch left it (0: no such launch yet)
+    hipEvent_t done = nullptr;
+    uint64_t done_at = 0;
 };
 
 namespace agx_sw_host __attribute__((visibility("hidden"))) {

@@ -201,7 +201,7 @@ int plain_admit(const agx_sw_batch *, int64_t, int64_t ca, int64_t cb, uint64_t 
 int plain_trace(agx_sw_batch *b, const int64_t *pairs, int64_t m, CigarChunk &c, hipEvent_t *ev)
 {
     agx_ctx *ctx = b->ctx;
-    hipStream_t st = ctx->stream;
+    hipStream_t st = agx_enqueue_stream(ctx);
     const agx_sw_hit *hits = b->cig_hits.data();
     // the spans as a batch of their own, not reversed
     std::vector<uint64_t> &soff = c.span_off;
@@ -296,7 +296,7 @@ int band_admit(const agx_sw_batch *b, int64_t p, int64_t ca, int64_t cb, uint64_
 int band_trace(agx_sw_batch *b, const int64_t *pairs, int64_t m, CigarChunk &c, hipEvent_t *ev)
 {
     agx_ctx *ctx = b->ctx;
-    hipStream_t st = ctx->stream;
+    hipStream_t st = agx_enqueue_stream(ctx);
     const agx_sw_hit *hits = b->cig_hits.data();
     const bool at = b->band_at;
     // ---- the chunk's plan: the batch's tiling per pair, longest span first, in waves by the wave builder of the batch's own plan
@@ -485,7 +485,7 @@ int cigars_impl(agx_sw_batch *b)
     std::vector<std::vector<uint32_t>> chunk_ops;  // every chunk's runs, dense
     std::vector<uint64_t> where((size_t)n, 0);     // a traced pair's first run in its chunk's array
     std::vector<uint32_t> chunk_of((size_t)n, 0);
-    hipStream_t st = ctx->stream;
+    hipStream_t st = agx_enqueue_stream(ctx);
     // tuning build, AGX_TRACE_CIGAR: kernel-only times of every chunk's traced fill, walk and gather (HIP events on the stream)
     const bool timed = agx_tune("AGX_TRACE_CIGAR") != nullptr;
     struct Events {

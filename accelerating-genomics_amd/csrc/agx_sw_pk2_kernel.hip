@@ -3,6 +3,8 @@
 // agx_sw_pk2w_kernel.hip.
 #include "agx_sw_pk2_kernel.inc"
 
+#include <hip/hip_ext.h>
+
 namespace {
 
 template <int C, int KC>
@@ -72,45 +74,45 @@ __global__ void __launch_bounds__(256) sw_fill_pk2_any(const SwParams prm, const
 
 template <int C, int KC>
 int launch(const SwParams &prm, const uint32_t *img, const SwGroup2 *groups, const SwWave *waves, uint32_t n_waves,
-           int32_t *scores, hipStream_t s)
+           int32_t *scores, hipStream_t s, hipEvent_t stop)
 {
     const uint32_t blocks = (n_waves + 3) / 4;
     if (KC == 4 && prm.stage)
-        hipLaunchKernelGGL((sw_fill_pk2_staged<C>), dim3(blocks), dim3(256), 0, s, prm, img, groups, waves, n_waves, scores);
+        AGX_SW_PK2_LAUNCH((sw_fill_pk2_staged<C>), blocks, s, stop, prm, img, groups, waves, n_waves, scores);
     else
-        hipLaunchKernelGGL((sw_fill_pk2<C, KC>), dim3(blocks), dim3(256), 0, s, prm, img, groups, waves, n_waves, scores);
+        AGX_SW_PK2_LAUNCH((sw_fill_pk2<C, KC>), blocks, s, stop, prm, img, groups, waves, n_waves, scores);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
 } // namespace
 
 int agx_sw_pk2_launch_any(int rising, bool wide, const SwParams &prm, const uint32_t *img, const SwGroup2 *groups, const SwWave *waves,
-                          uint32_t n_waves, int32_t *scores, hipStream_t s)
+                          uint32_t n_waves, int32_t *scores, hipStream_t s, hipEvent_t stop)
 {
     if (n_waves == 0) return 0;
-    if (rising == 4 && wide) return agx_sw_pk2w_launch_any(prm, img, groups, waves, n_waves, scores, s);
+    if (rising == 4 && wide) return agx_sw_pk2w_launch_any(prm, img, groups, waves, n_waves, scores, s, stop);
     const uint32_t blocks = (n_waves + 3) / 4;
     if (rising == 4 && prm.stage)
-        hipLaunchKernelGGL(sw_fill_pk2_any_staged, dim3(blocks), dim3(256), 0, s, prm, img, groups, waves, n_waves, scores);
+        AGX_SW_PK2_LAUNCH(sw_fill_pk2_any_staged, blocks, s, stop, prm, img, groups, waves, n_waves, scores);
     else if (rising == 4)
-        hipLaunchKernelGGL(sw_fill_pk2_any<4>, dim3(blocks), dim3(256), 0, s, prm, img, groups, waves, n_waves, scores);
+        AGX_SW_PK2_LAUNCH(sw_fill_pk2_any<4>, blocks, s, stop, prm, img, groups, waves, n_waves, scores);
     else if (rising)
-        hipLaunchKernelGGL(sw_fill_pk2_any<1>, dim3(blocks), dim3(256), 0, s, prm, img, groups, waves, n_waves, scores);
+        AGX_SW_PK2_LAUNCH(sw_fill_pk2_any<1>, blocks, s, stop, prm, img, groups, waves, n_waves, scores);
     else
-        hipLaunchKernelGGL(sw_fill_pk2_any<0>, dim3(blocks), dim3(256), 0, s, prm, img, groups, waves, n_waves, scores);
+        AGX_SW_PK2_LAUNCH(sw_fill_pk2_any<0>, blocks, s, stop, prm, img, groups, waves, n_waves, scores);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
 int agx_sw_pk2_launch_class(int cols_per_lane, int rising, bool wide, const SwParams &prm, const uint32_t *img, const SwGroup2 *groups,
-                            const SwWave *waves, uint32_t n_waves, int32_t *scores, hipStream_t s)
+                            const SwWave *waves, uint32_t n_waves, int32_t *scores, hipStream_t s, hipEvent_t stop)
 {
     if (n_waves == 0) return 0;
     // (a class without a wide build -- sw_pk2_period -- runs the period of four: the host's rule then holds all the more)
     if (rising == 4 && wide && sw_pk2_period(cols_per_lane) > 4)
-        return agx_sw_pk2w_launch_class(cols_per_lane, prm, img, groups, waves, n_waves, scores, s);
+        return agx_sw_pk2w_launch_class(cols_per_lane, prm, img, groups, waves, n_waves, scores, s, stop);
     switch (cols_per_lane) {
 #define AGX_SW_CASE(CC) \
-    case CC: return rising == 4 ? launch<CC, 4>(prm, img, groups, waves, n_waves, scores, s) : rising ? launch<CC, 1>(prm, img, groups, waves, n_waves, scores, s) : launch<CC, 0>(prm, img, groups, waves, n_waves, scores, s);
+    case CC: return rising == 4 ? launch<CC, 4>(prm, img, groups, waves, n_waves, scores, s, stop) : rising ? launch<CC, 1>(prm, img, groups, waves, n_waves, scores, s, stop) : launch<CC, 0>(prm, img, groups, waves, n_waves, scores, s, stop);
         AGX_SW_FOR_EACH_CLASS(AGX_SW_CASE)
 #undef AGX_SW_CASE
     default: return -2;

@@ -4,6 +4,8 @@
 // batch whose values stay in range with the larger class offsets (agx_sw.cpp, "class period"), the period of four otherwise.
 #include "agx_sw_pk2_kernel.inc"
 
+#include <hip/hip_ext.h>
+
 namespace {
 
 template <int C>
@@ -67,14 +69,14 @@ __global__ void __launch_bounds__(256) sw_fill_pk2w_any(const SwParams prm, cons
 
 template <int C>
 int launch(const SwParams &prm, const uint32_t *img, const SwGroup2 *groups, const SwWave *waves, uint32_t n_waves,
-           int32_t *scores, hipStream_t s)
+           int32_t *scores, hipStream_t s, hipEvent_t stop)
 {
     if constexpr (sw_pk2_period(C) > 4) {
         const uint32_t blocks = (n_waves + 3) / 4;
         if (prm.stage)
-            hipLaunchKernelGGL((sw_fill_pk2w_staged<C>), dim3(blocks), dim3(256), 0, s, prm, img, groups, waves, n_waves, scores);
+            AGX_SW_PK2_LAUNCH((sw_fill_pk2w_staged<C>), blocks, s, stop, prm, img, groups, waves, n_waves, scores);
         else
-            hipLaunchKernelGGL((sw_fill_pk2w<C>), dim3(blocks), dim3(256), 0, s, prm, img, groups, waves, n_waves, scores);
+            AGX_SW_PK2_LAUNCH((sw_fill_pk2w<C>), blocks, s, stop, prm, img, groups, waves, n_waves, scores);
         return hipGetLastError() == hipSuccess ? 0 : -1;
     } else
         return -2; // no wide build of this class
@@ -83,24 +85,24 @@ int launch(const SwParams &prm, const uint32_t *img, const SwGroup2 *groups, con
 } // namespace
 
 int agx_sw_pk2w_launch_any(const SwParams &prm, const uint32_t *img, const SwGroup2 *groups, const SwWave *waves, uint32_t n_waves,
-                           int32_t *scores, hipStream_t s)
+                           int32_t *scores, hipStream_t s, hipEvent_t stop)
 {
     if (n_waves == 0) return 0;
     const uint32_t blocks = (n_waves + 3) / 4;
     if (prm.stage)
-        hipLaunchKernelGGL(sw_fill_pk2w_any_staged, dim3(blocks), dim3(256), 0, s, prm, img, groups, waves, n_waves, scores);
+        AGX_SW_PK2_LAUNCH(sw_fill_pk2w_any_staged, blocks, s, stop, prm, img, groups, waves, n_waves, scores);
     else
-        hipLaunchKernelGGL(sw_fill_pk2w_any, dim3(blocks), dim3(256), 0, s, prm, img, groups, waves, n_waves, scores);
+        AGX_SW_PK2_LAUNCH(sw_fill_pk2w_any, blocks, s, stop, prm, img, groups, waves, n_waves, scores);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
 int agx_sw_pk2w_launch_class(int cols_per_lane, const SwParams &prm, const uint32_t *img, const SwGroup2 *groups, const SwWave *waves,
-                             uint32_t n_waves, int32_t *scores, hipStream_t s)
+                             uint32_t n_waves, int32_t *scores, hipStream_t s, hipEvent_t stop)
 {
     if (n_waves == 0) return 0;
     switch (cols_per_lane) {
 #define AGX_SW_CASE(CC) \
-    case CC: return launch<CC>(prm, img, groups, waves, n_waves, scores, s);
+    case CC: return launch<CC>(prm, img, groups, waves, n_waves, scores, s, stop);
         AGX_SW_FOR_EACH_CLASS(AGX_SW_CASE)
 #undef AGX_SW_CASE
     default: return -2;

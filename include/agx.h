@@ -172,12 +172,17 @@ int agx_sw_batch_create_matrix(agx_ctx *ctx, const agx_sw_matrix *matrix, const 
                                const uint32_t *len, int64_t n_pairs, agx_sw_batch **out);
 /* Enqueue the fill on the context's stream; scores stay in HBM.  Asynchronous. */
 int agx_sw_batch_launch(agx_sw_batch *b);
-/* Wait for the stream and copy the scores out in the caller's pair order. */
+/* Wait for the batch's last launch -- and for everything the library queued on the context's stream behind it -- and copy the
+ * scores out in the caller's pair order.  After agx_sw_batch_bind_scores has changed where the scores go (an array bound,
+ * unbound or replaced by another), the call fails with AGX_E_ARG until the batch has been launched again: the last launch wrote
+ * to the place named before, so neither the caller's array nor the batch's own holds what this call would promise. */
 int agx_sw_batch_scores(agx_sw_batch *b, int32_t *scores);
 /* Optional: name the page-locked array (agx_host_alloc, n_pairs ints) the scores are wanted in BEFORE launching.  A batch
  * whose records are in file order (a uniform batch: fixed-length reads) then lets every launch write its scores there
  * itself -- one PCIe write per wavefront, no copy kernel behind the fill -- and agx_sw_batch_scores(b, the same pointer)
- * only waits.  Other batches keep the copy; scores == NULL unbinds.  The array must stay valid while it is bound. */
+ * only waits.  Other batches keep the copy; scores == NULL unbinds.  The array must stay valid while it is bound.
+ * Bind, then launch, then fetch: a change of the binding after a launch leaves that launch's scores where they were, and
+ * agx_sw_batch_scores refuses (AGX_E_ARG) until the next launch.  Binding the array that is bound already changes nothing. */
 int agx_sw_batch_bind_scores(agx_sw_batch *b, int32_t *scores);
 int agx_sw_batch_info(const agx_sw_batch *b, agx_sw_info *info);
 void agx_sw_batch_destroy(agx_sw_batch *b);
