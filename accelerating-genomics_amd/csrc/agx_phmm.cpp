@@ -1160,9 +1160,6 @@ void agx_pairHMM(double *likelihood, double *M, double *X, double *Y, char *R, c
     (void)M;
     (void)X;
     (void)Y; // the reference's rolling anti-diagonal scratch (antidiagsPairHMM.c:452-455): unused here
-    static std::mutex mu;
-    agx_ctx *ctx = nullptr;
-    std::lock_guard<std::mutex> lock(mu);
     if (!likelihood) return;
     *likelihood = NAN;
     if (read_len < 0 || haplotype_len < 0 || !R || !H || !Qr || !Qi || !Qd || !Qg) {
@@ -1170,7 +1167,11 @@ void agx_pairHMM(double *likelihood, double *M, double *X, double *Y, char *R, c
         return;
     }
     try {
-    if (agx_shared_ctx(0, 0, &ctx) != AGX_OK) return; // process-wide, created on first use (this function's own mutex covers its use)
+    agx_ctx *ctx = nullptr;
+    std::mutex *busy = nullptr;
+    if (agx_shared_ctx(0, 0, &ctx, &busy) != AGX_OK) return; // process-wide, created on first use
+    // the context's own mutex, the one a shard of agx_*_devices on (device 0, slot 0) holds: calls take turns with those too
+    std::lock_guard<std::mutex> turn(*busy);
     const uint64_t roff[2] = {0, (uint64_t)read_len}, hoff[2] = {0, (uint64_t)haplotype_len};
     const uint32_t reg[2] = {0, 1};
     agx_phmm_desc d{};

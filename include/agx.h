@@ -775,6 +775,9 @@ int agx_phmm_shard_cuts(const agx_phmm_desc *d, int n_shards, uint32_t *cut);
  * Qr/Qi/Qd/Qg are probabilities, not Phred characters.  Runs one pair on
  * device 0 through a process-wide lazily created context; returns nothing, as
  * the reference does: on failure *likelihood = NaN and agx_last_error() is set.
+ * Callable from several host threads at once: calls take turns with each other
+ * and with the shards of agx_*_devices / agx_*_multi on (device 0, slot 0),
+ * whose context this is.
  */
 void agx_pairHMM(double *likelihood, double *M, double *X, double *Y, char *R, char *H, int read_len,
                  int haplotype_len, double *Qr, double *Qi, double *Qd, double *Qg);
