@@ -64,6 +64,7 @@ SYMBOLS = [
     "agx_sw_batch_create_align_band_diag_matrix_cigar", "agx_sw_align_band_diag_matrix_cigar",
     "agx_sw_batch_create_align_band_zdrop", "agx_sw_align_band_zdrop", "agx_sw_batch_zdrop_stops",
     "agx_sw_batch_create_align_band_zdrop_cigar", "agx_sw_align_band_zdrop_cigar",
+    "agx_sw_batch_create_align_band_diag_stats", "agx_sw_align_band_diag_stats",
     "agx_sw_score", "agx_sw_score_multi", "agx_sw_score_devices", "agx_sw_shard_cuts",
     "agx_phmm_batch_create", "agx_phmm_batch_launch", "agx_phmm_batch_results", "agx_phmm_batch_bind_results", "agx_phmm_batch_info",
     "agx_phmm_batch_destroy", "agx_phmm_forward", "agx_phmm_forward_multi", "agx_phmm_forward_devices", "agx_phmm_shard_cuts",
@@ -251,6 +252,10 @@ def lib():
                                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)]
         l.agx_sw_align_band_zdrop_cigar.argtypes = [C.c_void_p, C.POINTER(SwScoring), C.c_int, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
                                                     C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
+        l.agx_sw_batch_create_align_band_diag_stats.argtypes = [C.c_void_p, C.POINTER(SwScoring), C.c_int, C.c_int32, C.c_void_p, C.c_void_p,
+                                                                C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        l.agx_sw_align_band_diag_stats.argtypes = [C.c_void_p, C.POINTER(SwScoring), C.c_int, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                   C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         l.agx_sw_band_span_record.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                                               C.POINTER(SwBandSpan)]
         l.agx_sw_score.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
@@ -367,8 +372,19 @@ class Context:
 
     # ---- Smith-Waterman
     def sw_batch(self, b, scoring=None, matrix=None, align=0, mode=SW_MODE_LOCAL, stats=False, cigar=False, band=None, diag=None,
-                 zdrop=None) -> "SwBatch":
-        return SwBatch(self, b, scoring, matrix, align, mode, stats, cigar, band, diag, zdrop)
+                 zdrop=None, band_stats=False) -> "SwBatch":
+        return SwBatch(self, b, scoring, matrix, align, mode, stats, cigar, band, diag, zdrop, band_stats)
+
+    def sw_align_band_diag_stats(self, b, mode, band, diag=None, scoring=None):
+        """b: synth.SWBatch -> (SwHit records as sw_align_band_diag(what=SW_ALIGN_SPANS) gives them, SwStat records), one-shot: matches
+        and aligned pairs of the alignment inside the band around diag, no traceback (include/agx.h, "Statistics for batches banded
+        around a diagonal")."""
+        hits, stats = np.empty(b.n_pairs, SwHit), np.empty(b.n_pairs, SwStat)
+        sc = C.byref(SwScoring(*scoring)) if scoring is not None else None
+        d = _diag(diag, b.n_pairs)
+        _check(lib().agx_sw_align_band_diag_stats(self._h, sc, mode, band, _ptr(d), _ptr(b.bases), _ptr(b.off), _ptr(b.len), b.n_pairs, _ptr(hits),
+                                                  _ptr(stats)))
+        return hits, stats
 
     def sw_align_band_diag(self, b, mode, band, diag=None, what=SW_ALIGN_SPANS, scoring=None, zdrop=None, matrix=None):
         """b: synth.SWBatch -> SwHit records of the alignment inside the band diag - band <= j - i <= diag + band (include/agx.h,
@@ -493,7 +509,7 @@ class SwBatch:
     """agx_sw_batch: a scheduled batch resident in HBM (ctx=None: planned on the host only)."""
 
     def __init__(self, ctx, b, scoring=None, matrix=None, align=0, mode=SW_MODE_LOCAL, stats=False, cigar=False, band=None, diag=None,
-                 zdrop=None):
+                 zdrop=None, band_stats=False):
         """scoring: None (the reference's +1/-1/-3/-1) or (match, mismatch, gap_open, gap_extend);
         matrix: an SwMatrix instead (score-only and align batches alike); align: SW_ALIGN_ENDS / SW_ALIGN_SPANS for a batch that also answers hits();
         mode: SW_MODE_* of an align batch (local, global, fit, extension); stats=True: a SPANS batch that also answers stats();
@@ -503,10 +519,20 @@ class SwBatch:
         band=w with diag=one int or one per pair: a batch BANDED AROUND A DIAGONAL, any mode, align = SW_ALIGN_ENDS or
         SW_ALIGN_SPANS (0: SPANS); no stats; with cigar=True (SPANS only) it also answers cigars(); matrix=m puts it under a substitution
         matrix (then no scoring and no zdrop);
-        band=w with zdrop=Z (diag optional): such a batch in SW_MODE_EXTEND that terminates by the z-drop and also answers zdrop_stops()."""
+        band=w with zdrop=Z (diag optional): such a batch in SW_MODE_EXTEND that terminates by the z-drop and also answers zdrop_stops();
+        band=w with band_stats=True (diag optional): a SPANS batch banded around a diagonal that also answers stats() (no matrix, cigar or
+        zdrop; stats=True stays the unbanded stats batch and does not combine with band=)."""
         self.ctx = ctx
         self.n_pairs = b.n_pairs
         self._h = C.c_void_p()
+        if band_stats:
+            if band is None or stats or cigar or matrix is not None or zdrop is not None or align not in (0, SW_ALIGN_SPANS):
+                raise AgxError(E_ARG, "band_stats=True takes band=w (and diag=) on a SW_ALIGN_SPANS batch: no stats=, cigar, matrix or zdrop")
+            sc = C.byref(SwScoring(*scoring)) if scoring is not None else None
+            d = _diag(diag, b.n_pairs)
+            _check(lib().agx_sw_batch_create_align_band_diag_stats(ctx._h if ctx else None, sc, mode, band, _ptr(d), _ptr(b.bases), _ptr(b.off),
+                                                                   _ptr(b.len), b.n_pairs, C.byref(self._h)))
+            return
         if diag is not None or zdrop is not None:
             if band is None or stats:
                 raise AgxError(E_ARG, "a batch banded around a diagonal takes band=w, and no stats")

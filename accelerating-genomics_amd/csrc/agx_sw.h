@@ -246,6 +246,14 @@ void agx_sw_band_at_preload();
 int agx_sw_band_zdrop_launch_class(int diags_per_lane, const SwParams &prm, const uint32_t *img, const SwBandGroup *groups, const SwWave *waves,
                                    uint32_t n_waves, int32_t *scores, uint32_t *pos, int32_t zdrop, int32_t *stops, hipStream_t s);
 void agx_sw_band_zdrop_preload();
+// the builds WITH alignment statistics (agx_sw_band_stats_kernel.hip): mode GLOBAL, EXTEND, LOCAL or EXTEND_QUERY (the
+// last two are also the begin passes of LOCAL and FIT); records, scores and pos as the plain builds of that mode write them, and
+// lstat[out] = matches << kSwBandStatBits | pairs of the captured cell's best path.  Every class of AGX_SW_FOR_EACH_BAND_CLASS is
+// built: none spills or takes scratch, AGPRs or LDS (DESIGN.md 4.1m has the table), so a stats batch is tiled like a plain one.
+constexpr int kSwBandStatBits = 16; // L = matches << 16 | pairs: both up to 65 535
+int agx_sw_band_stats_launch_class(int diags_per_lane, int mode, const SwParams &prm, const uint32_t *img, const SwBandGroup *groups,
+                                   const SwWave *waves, uint32_t n_waves, int32_t *scores, uint32_t *pos, uint32_t *lstat, hipStream_t s);
+void agx_sw_band_stats_preload();
 // the TRACED banded fill and its walk (agx_sw_band_trace_kernel.hip): corner capture only.  Every cell of rows
 // 0 .. lb leaves four bits at trace + goff[group] + (step * G + lane) * sw_band_trace_words(K) dwords, nibble k of the lane's K
 // diagonals; goff holds one 64-bit dword offset per group record, a multiple of four (the K = 32 build stores 16 bytes at once).

@@ -292,7 +292,8 @@ int agx_sw_batch_stats(agx_sw_batch *b, agx_sw_hit *hits, agx_sw_stat *stats)
         return AGX_E_ARG;
     }
     if (!b->stats || b->align != AGX_SW_ALIGN_SPANS) {
-        agx_set_error("agx_sw_batch_stats: not a stats batch (create it with agx_sw_batch_create_align_stats)");
+        agx_set_error("agx_sw_batch_stats: not a stats batch (create it with agx_sw_batch_create_align_stats or "
+                      "agx_sw_batch_create_align_band_diag_stats)");
         return AGX_E_ARG;
     }
     if (!b->ctx) {
@@ -307,8 +308,10 @@ int agx_sw_batch_stats(agx_sw_batch *b, agx_sw_hit *hits, agx_sw_stat *stats)
         hits = own.data();
     }
     std::vector<uint32_t> L;
-    const int rc = hits_impl(b, hits, &L);
+    // (a batch banded around a diagonal: DESIGN.md 4.1m -- its L has wider fields, both lengths reach 65 535)
+    const int rc = b->banded ? band_at_hits(b, hits, true, &L) : hits_impl(b, hits, &L);
     if (rc || n == 0) return rc;
+    const int bits = b->banded ? kSwBandStatBits : kSwStatColBits;
     // Every stat is checked before it leaves: 0 <= matches <= pairs <= min(columns of a, of b); under match/mismatch scoring
     // what the score leaves after matches, mismatches and gap cells must be a whole number of gap opens, between "one if
     // there is a gap cell" and "one per gap cell".
@@ -320,7 +323,7 @@ int agx_sw_batch_stats(agx_sw_batch *b, agx_sw_hit *hits, agx_sw_stat *stats)
             const agx_sw_hit &h = hits[p];
             const int64_t ca = h.a_begin >= 0 && h.a_end >= h.a_begin ? (int64_t)h.a_end - h.a_begin + 1 : 0;
             const int64_t cb = h.b_begin >= 0 && h.b_end >= h.b_begin ? (int64_t)h.b_end - h.b_begin + 1 : 0;
-            const int64_t matches = L[(size_t)p] >> kSwStatColBits, pairs = L[(size_t)p] & ((1u << kSwStatColBits) - 1u);
+            const int64_t matches = L[(size_t)p] >> bits, pairs = L[(size_t)p] & ((1u << bits) - 1u);
             bool ok = matches <= pairs && pairs <= std::min(ca, cb);
             if (ok && mm && ca + cb > 0) {
                 const int64_t gaps = ca + cb - 2 * pairs;
@@ -338,7 +341,7 @@ int agx_sw_batch_stats(agx_sw_batch *b, agx_sw_hit *hits, agx_sw_stat *stats)
     for (int64_t p : bad)
         if (p >= 0) {
             agx_set_error("agx_sw_batch_stats: pair %lld (mode %d): matches %u, pairs %u do not fit its score %d over the span a %d..%d, b %d..%d",
-                          (long long)p, b->mode, L[(size_t)p] >> kSwStatColBits, L[(size_t)p] & ((1u << kSwStatColBits) - 1u), hits[p].score,
+                          (long long)p, b->mode, L[(size_t)p] >> bits, L[(size_t)p] & ((1u << bits) - 1u), hits[p].score,
                           hits[p].a_begin, hits[p].a_end, hits[p].b_begin, hits[p].b_end);
             return AGX_E_INTERNAL;
         }

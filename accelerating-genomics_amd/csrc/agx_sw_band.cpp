@@ -22,6 +22,7 @@ void hash_band_head(Fnv1a &f, const agx_sw_batch *b)
                       (int32_t)b->matrix, b->prm.ge, b->prm.gf, b->prm.hd, b->prm.delta})
         f.field(v);
     f.field(b->prm.n_out);
+    if (b->stats) f.field((int32_t)b->stats); // (the other kinds keep the digests they have)
     hash_launches(f, b->launches);
 }
 void hash_band_waves(Fnv1a &f, const std::vector<SwWave> &waves)
@@ -42,8 +43,8 @@ void hash_band_groups(Fnv1a &f, const std::vector<SwBandGroup> &groups)
 void trace_band_plan(const agx_sw_batch *b, const std::vector<SwWave> &waves, const std::vector<SwBandGroup> &groups,
                      const std::vector<uint32_t> &row0s, const int32_t *diag, const uint32_t *len)
 {
-    fprintf(stderr, "[agx_sw_batch_create_band] kind: mode %d band %d align %d at %d zdrop %d cigar %d matrix %d\n", b->mode, b->band, b->align,
-            (int)b->band_at, b->zdrop_on ? b->zdrop : -1, b->cigar, (int)b->matrix);
+    fprintf(stderr, "[agx_sw_batch_create_band] kind: mode %d band %d align %d at %d zdrop %d cigar %d matrix %d%s\n", b->mode, b->band, b->align,
+            (int)b->band_at, b->zdrop_on ? b->zdrop : -1, b->cigar, (int)b->matrix, b->stats == 2 ? " stats 2" : b->stats ? " stats 1" : "");
     Fnv1a all, head, wv, gr;
     hash_band_head(all, b), hash_band_head(head, b);
     hash_band_waves(all, waves), hash_band_waves(wv, waves);
@@ -103,6 +104,7 @@ agx_sw_batch *init_band_batch(agx_ctx *ctx, const BandKind &kind, const agx_sw_s
     b->band_at = at != nullptr;
     b->zdrop_on = at && at->zdrop_on;
     b->zdrop = b->zdrop_on ? at->zdrop : 0;
+    b->stats = at ? at->stats : 0;
     b->mode = kind.mode;
     b->scoring = sc;
     b->matrix = kind.matrix != nullptr;
@@ -154,6 +156,7 @@ void keep_band_host_state(agx_sw_batch *b, const BandKind &kind, const BandPairs
     if (at) {
         agx_sw_band_at_preload();
         if (at->zdrop_on) agx_sw_band_zdrop_preload();
+        if (at->stats) agx_sw_band_stats_preload();
         b->band_row0 = pairs.row0s;
         if (at->diag) b->band_diag.assign(at->diag, at->diag + n_pairs);
         else b->band_diag.assign((size_t)n_pairs, 0);
@@ -232,7 +235,10 @@ int upload_band(agx_ctx *ctx, agx_sw_batch *b, const BandKind &kind, const std::
     if (!rc) rc = b->band_pos_stage.alloc(ctx, words);
     if (!rc && b->zdrop_on) rc = b->band_stop.alloc(ctx, words);
     if (!rc && b->zdrop_on) rc = b->band_stop_stage.alloc(ctx, words);
+    if (!rc && b->stats == 2) rc = b->lstat.alloc(ctx, words);
+    if (!rc && b->stats == 2) rc = b->lstat_stage.alloc(ctx, words);
     if (rc) return rc;
+    if (b->stats == 2) AGX_HIP(hipMemsetAsync(b->lstat.p, 0, words, cs)); // a pair no wave writes reads {0, 0}
     AGX_HIP(hipStreamSynchronize(cs));
     drain.ok = true;
     return AGX_OK;
@@ -247,7 +253,8 @@ int create_band(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t b
                 const uint32_t *len, int64_t n_pairs, agx_sw_batch **out, bool cigar, const BandAt *at, const agx_sw_matrix *matrix)
 {
     const bool zd = at && at->zdrop_on;
-    const char *who = matrix ? (cigar ? "agx_sw_batch_create_align_band_diag_matrix_cigar" : "agx_sw_batch_create_align_band_diag_matrix")
+    const char *who = at && at->stats ? "agx_sw_batch_create_align_band_diag_stats"
+                      : matrix      ? (cigar ? "agx_sw_batch_create_align_band_diag_matrix_cigar" : "agx_sw_batch_create_align_band_diag_matrix")
                       : zd   ? (cigar ? "agx_sw_batch_create_align_band_zdrop_cigar" : "agx_sw_batch_create_align_band_zdrop")
                       : at   ? (cigar ? "agx_sw_batch_create_align_band_diag_cigar" : "agx_sw_batch_create_align_band_diag")
                              : (cigar ? "agx_sw_batch_create_align_band_cigar" : "agx_sw_batch_create_align_band");
@@ -326,6 +333,11 @@ int band_launch(agx_sw_batch *b)
         }
         return fan.end();
     };
+    if (b->stats == 2)
+        return launch_classes("sw_fill_band_stats", true, [&](const ClassLaunch &cl, hipStream_t s) {
+            return agx_sw_band_stats_launch_class(cl.C, b->mode, b->prm, img, groups, waves + cl.first_wave, cl.n_waves, scores, pos,
+                                                  (uint32_t *)b->lstat.p, s);
+        });
     if (b->zdrop_on)
         return launch_classes("sw_fill_band_zd", false, [&](const ClassLaunch &cl, hipStream_t s) {
             return agx_sw_band_zdrop_launch_class(cl.C, b->prm, img, groups, waves + cl.first_wave, cl.n_waves, scores, pos, b->zdrop,
@@ -350,7 +362,9 @@ int band_launch(agx_sw_batch *b)
 // batch in LOCAL and FIT (agx_sw_batch_scores does not need it) -- a second batch of the same kind over the reversed prefixes,
 // whose band is the mirror image of the pair's: reversed, cell (i, j) of the span of cb rows and ca columns is (cb - i, ca - j),
 // so diagonal d becomes ca - cb - d and the centre c becomes ca - cb - c, the half-width stays.
-int band_at_hits(agx_sw_batch *b, agx_sw_hit *hits, bool begins)
+// L: also every pair's word matches << kSwBandStatBits | pairs -- from this batch's own fill (stats == 2), else from the begin pass,
+// which then runs the stats builds; 0 for the pairs answered without a fill and for those whose alignment consumes nothing
+int band_at_hits(agx_sw_batch *b, agx_sw_hit *hits, bool begins, std::vector<uint32_t> *L)
 {
     int rc = agx_bind(b->ctx);
     if (rc) return rc;
@@ -362,7 +376,11 @@ int band_at_hits(agx_sw_batch *b, agx_sw_hit *hits, bool begins)
         AGX_HIP(hipMemcpyAsync(b->out_stage.p, b->scores.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
         if (cell || column) AGX_HIP(hipMemcpyAsync(b->band_pos_stage.p, b->band_pos.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     }
+    const bool own_l = L && b->stats == 2 && !b->launches.empty();
+    if (own_l) AGX_HIP(hipMemcpyAsync(b->lstat_stage.p, b->lstat.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     AGX_HIP(hipStreamSynchronize(st));
+    if (own_l) L->assign((const uint32_t *)b->lstat_stage.p, (const uint32_t *)b->lstat_stage.p + n);
+    else if (L) L->assign((size_t)n, 0u);
     const int32_t *sc = (const int32_t *)b->out_stage.p;
     const uint32_t *ps = (const uint32_t *)b->band_pos_stage.p;
     const bool spans = b->align == AGX_SW_ALIGN_SPANS;
@@ -429,7 +447,7 @@ int band_at_hits(agx_sw_batch *b, agx_sw_hit *hits, bool begins)
         rdiag[(size_t)k] = (h.a_end + 1) - (h.b_end + 1) - b->band_diag[(size_t)pick[(size_t)k]];
     }
     agx_sw_batch *rb = nullptr;
-    const BandAt rat{AGX_SW_ALIGN_ENDS, rdiag.data()};
+    const BandAt rat{AGX_SW_ALIGN_ENDS, rdiag.data(), false, 0, L ? 2 : 0};
     rc = create_band(b->ctx, &b->scoring, fit ? AGX_SW_MODE_EXTEND_QUERY : AGX_SW_MODE_LOCAL, b->band, rev.bytes.data(), rev.off.data(),
                      rev.len.data(), m, &rb, false, &rat, b->matrix ? &b->mat : nullptr);
     if (rc) return rc;
@@ -442,8 +460,9 @@ int band_at_hits(agx_sw_batch *b, agx_sw_hit *hits, bool begins)
         }
     } drop{rb};
     std::vector<agx_sw_hit> rh((size_t)m);
+    std::vector<uint32_t> rl;
     rc = agx_sw_batch_launch(rb);
-    if (!rc) rc = band_at_hits(rb, rh.data(), false);
+    if (!rc) rc = band_at_hits(rb, rh.data(), false, L ? &rl : nullptr);
     if (rc) return rc;
     for (int64_t k = 0; k < m; ++k) {
         agx_sw_hit &h = hits[pick[(size_t)k]];
@@ -457,6 +476,7 @@ int band_at_hits(agx_sw_batch *b, agx_sw_hit *hits, bool begins)
         }
         if (!fit) h.a_begin = h.a_end - r.a_end;
         h.b_begin = h.b_end - r.b_end;
+        if (L) (*L)[(size_t)pick[(size_t)k]] = rl[(size_t)k];
     }
     return AGX_OK;
 }
@@ -569,6 +589,24 @@ int agx_sw_align_band_diag(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode
     agx_sw_batch *b = nullptr;
     const int rc = agx_sw_batch_create_align_band_diag(ctx, scoring, mode, what, band, diag, bases, off, len, n_pairs, &b);
     return rc ? rc : align_once(b, [&](agx_sw_batch *x) { return agx_sw_batch_hits(x, hits); });
+}
+
+int agx_sw_batch_create_align_band_diag_stats(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t band, const int32_t *diag,
+                                              const uint8_t *bases, const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_batch **out)
+{
+    AGX_GUARD_BEGIN
+    // LOCAL and FIT keep the plain forward fill (their begin pass carries L), the pinned modes' only fill carries it
+    const BandAt at{AGX_SW_ALIGN_SPANS, diag, false, 0, mode == AGX_SW_MODE_LOCAL || mode == AGX_SW_MODE_FIT ? 1 : 2};
+    return create_band(ctx, scoring, mode, band, bases, off, len, n_pairs, out, false, &at);
+    AGX_GUARD_END("agx_sw_batch_create_align_band_diag_stats")
+}
+
+int agx_sw_align_band_diag_stats(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t band, const int32_t *diag, const uint8_t *bases,
+                                 const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_hit *hits, agx_sw_stat *stats)
+{
+    agx_sw_batch *b = nullptr;
+    const int rc = agx_sw_batch_create_align_band_diag_stats(ctx, scoring, mode, band, diag, bases, off, len, n_pairs, &b);
+    return rc ? rc : align_once(b, [&](agx_sw_batch *x) { return agx_sw_batch_stats(x, hits, stats); });
 }
 
 int agx_sw_batch_create_align_band_diag_matrix(agx_ctx *ctx, const agx_sw_matrix *matrix, int mode, int what, int32_t band, const int32_t *diag,

@@ -124,6 +124,13 @@
 //       match or mismatch".
 //   Walk.  sw_walk_band_at compares image bytes: under MAT symbol numbers, so '=' is "identical codes", as the contract words it.
 //
+// STATS (agx_sw_band_stats_kernel.hip; include/agx.h, "Statistics for batches banded around a diagonal"; DESIGN.md 4.1m): the
+// builds whose states are tuples (score, L), L = matches << 16 | pairs of the state's best path, held as one int64
+// score << 32 | L: the plain GLOBAL and EXTEND builds and the AT builds of LOCAL and EXTEND_QUERY again.  Max is a 64-bit compare,
+// gaps add to the score word only, a diagonal move also counts its pair unless it runs over padding, a masked cell is (minus
+// infinity, 0), every hand-over between lanes carries both words, and capture reads the score word alone: lstat[out] receives L
+// of the cell the plain build would have captured.  That file's head has the argument, for the low word above all.
+//
 // (included by agx_sw_band_kernel.hip; opens an anonymous namespace that the including file closes after its launch helper)
 #include "agx_sw.h"
 
@@ -143,14 +150,52 @@ __device__ __forceinline__ int band_shl1(int old, int v)
     return __builtin_amdgcn_update_dpp(old, v, 0x130, 0xf, 0xf, false);
 }
 
+// A state: the score (int) or, in the STATS builds, the tuple score << 32 | L (long long).  One set of operations for both; on
+// int they are the plain build's expressions.
+template <bool STATS>
+struct BandState {
+    using type = int;
+};
+template <>
+struct BandState<true> {
+    using type = long long;
+};
+__device__ __forceinline__ int band_gap(int v, int c) { return v + c; }
+__device__ __forceinline__ int band_max(int x, int y) { return max(x, y); }
+__device__ __forceinline__ int band_score(int v) { return v; }
+__device__ __forceinline__ uint32_t band_low(int) { return 0u; }
+__device__ __forceinline__ long long band_tuple(int score, uint32_t l) { return (long long)(((unsigned long long)(uint32_t)score << 32) | l); }
+__device__ __forceinline__ int band_score(long long v) { return (int)(v >> 32); }
+__device__ __forceinline__ uint32_t band_low(long long v) { return (uint32_t)v; }
+// the two words are added apart: nothing carries from L into the score
+__device__ __forceinline__ long long band_gap(long long v, int c) { return band_tuple(band_score(v) + c, band_low(v)); }
+__device__ __forceinline__ long long band_max(long long x, long long y) { return x > y ? x : y; }
+// The diagonal move of a cell with window byte xs and row symbol yc.  A match is never over padding (kBandRowPad equals no byte,
+// and the padding byte 0 no symbol); a mismatch counts its pair only in a row 1 .. lb (pair1) and a column 1 .. la (xs != 0).
+__device__ __forceinline__ long long band_pair_move(long long zd, int xs, int yc, int s_match, int s_mis, uint32_t pair1)
+{
+    const bool same = xs == yc;
+    return band_tuple(band_score(zd) + (same ? s_match : s_mis), band_low(zd) + (same ? 0x10001u : xs ? pair1 : 0u));
+}
+__device__ __forceinline__ long long band_shr1(long long old, long long v)
+{
+    return band_tuple(band_shr1(band_score(old), band_score(v)), (uint32_t)band_shr1((int)band_low(old), (int)band_low(v)));
+}
+__device__ __forceinline__ long long band_shl1(long long old, long long v)
+{
+    return band_tuple(band_shl1(band_score(old), band_score(v)), (uint32_t)band_shl1((int)band_low(old), (int)band_low(v)));
+}
+
 // AT: -1 for the builds above; else the mode of a build of agx_sw_band_diag_kernel.hip (LOCAL: EXT is set, it captures by the
 // ANY rule; FIT and EXTEND_QUERY capture column la).  Everything they add stands inside `if constexpr` blocks.
 // MAT: the builds under a substitution matrix; sub is the table in LDS.
-template <int K, bool EXT, bool TRACE = false, int AT = -1, bool PH = false, bool ZD = false, bool MAT = false>
+// STATS: the builds on tuples; lstat receives L of the captured cell.
+template <int K, bool EXT, bool TRACE = false, int AT = -1, bool PH = false, bool ZD = false, bool MAT = false, bool STATS = false>
 __device__ __forceinline__ void band_body(const SwParams &prm, const uint32_t *__restrict__ img, const SwBandGroup *__restrict__ groups,
                                           const SwWave w, int32_t *__restrict__ scores, uint32_t *__restrict__ pos,
                                           uint32_t *trace = nullptr, const uint64_t *goff = nullptr, [[maybe_unused]] int zdrop = 0,
-                                          [[maybe_unused]] int32_t *__restrict__ stops = nullptr, [[maybe_unused]] const int16_t *sub = nullptr)
+                                          [[maybe_unused]] int32_t *__restrict__ stops = nullptr, [[maybe_unused]] const int16_t *sub = nullptr,
+                                          [[maybe_unused]] uint32_t *__restrict__ lstat = nullptr)
 {
     static_assert(!(TRACE && EXT), "the traced build captures the corner: an EXTEND span is traced as the global alignment it is");
     static_assert(K % 4 == 0 && K >= 4 && K <= 32, "the query window is whole dwords and the cell mask one dword");
@@ -160,6 +205,10 @@ __device__ __forceinline__ void band_body(const SwParams &prm, const uint32_t *_
     static_assert(!PH || (TRACE && AT == -1), "the start phase belongs to the traced build");
     static_assert(!ZD || (EXT && !TRACE && AT == -1), "the z-drop belongs to the plain EXTEND build");
     static_assert(!MAT || !ZD, "no z-drop under a matrix");
+    static_assert(!STATS || (!TRACE && !PH && !ZD && !MAT && AT != AGX_SW_MODE_FIT),
+                  "statistics ride on the plain GLOBAL and EXTEND builds and on the LOCAL and EXTEND_QUERY builds around a diagonal");
+    using V = typename BandState<STATS>::type;
+    constexpr V kNeg = STATS ? (V)((unsigned long long)(uint32_t)kBandNegInf << 32) : (V)kBandNegInf; // STATS: (minus infinity, 0)
     constexpr bool AT_LOCAL = AT == AGX_SW_MODE_LOCAL, AT_FIT = AT == AGX_SW_MODE_FIT, AT_COL = AT_FIT || AT == AGX_SW_MODE_EXTEND_QUERY;
     constexpr int XW = K / 4;
     const int ge = prm.ge, gf = prm.gf, s_match = prm.hd, s_mis = prm.hd - prm.delta; // the diagonal move on z: score - gf
@@ -213,10 +262,13 @@ __device__ __forceinline__ void band_body(const SwParams &prm, const uint32_t *_
     const int nxd = ((int)g.fpad + la + 3) >> 2;
     auto col_quad = [&](int q) -> uint32_t { return (loader && (uint32_t)(rel0 + q) < (uint32_t)nxd) ? xp[rel0 + q] : 0u; };
 
-    int z[K], e[K];
+    V z[K], e[K];
 #pragma unroll
-    for (int k = 0; k < K; ++k) z[k] = e[k] = kBandNegInf;
-    int z_last = kBandNegInf, f_last = kBandNegInf, yc_prev = kRowPad;
+    for (int k = 0; k < K; ++k) z[k] = e[k] = kNeg;
+    V z_last = kNeg, f_last = kNeg;
+    int yc_prev = kRowPad;
+    // STATS: L of the cell that `best` / `corner` / `cbest` was read from
+    [[maybe_unused]] uint32_t hit_l = 0;
     int best = gf, hit_i = -1, hit_k = 0; // EXTEND: H(0, 0) = 0 as z
     int corner = 0;                       // GLOBAL
     const int dc = la - lb - g.dlo;       // GLOBAL: the corner's diagonal, counted from dlo
@@ -247,12 +299,12 @@ __device__ __forceinline__ void band_body(const SwParams &prm, const uint32_t *_
         rows >>= 8;
         const uint32_t xin = xrows & 0xffu;
         xrows >>= 8;
-        int zl = band_shr1(kBandNegInf, z_last);
-        int fl = band_shr1(kBandNegInf, f_last);
+        V zl = band_shr1(kNeg, z_last);
+        V fl = band_shr1(kNeg, f_last);
         int yc = band_shr1(fresh, yc_prev);
         if (first) {
-            zl = kBandNegInf;
-            fl = kBandNegInf;
+            zl = kNeg;
+            fl = kNeg;
             yc = fresh;
         }
         // MAT: the K entries of this step -- row yc of the table, the columns of the window's bytes -- depend on nothing the cell
@@ -283,17 +335,24 @@ __device__ __forceinline__ void band_body(const SwParams &prm, const uint32_t *_
             int slot = k0;
             asm volatile("" : "+v"(slot));
 #pragma unroll
-            for (int k = 0; k < K; ++k) z[k] = k == slot ? (MAT ? inject : -s_mis) : z[k];
+            for (int k = 0; k < K; ++k) {
+                if constexpr (STATS) z[k] = k == slot ? band_tuple(-s_mis, 0u) : z[k]; // the move over padding adds nothing to L
+                else z[k] = k == slot ? (MAT ? inject : -s_mis) : z[k];
+            }
         }
         // which of this step's cells exist
         const int j0 = i + d0;
         const int klo = max(0, -j0), khi = min(kmax, la - j0);
         const bool any = (uint32_t)i <= (uint32_t)lb && khi >= klo;
         const uint32_t mask = any ? ((2u << (khi & 31)) - 1u) & (~0u << (klo & 31)) : 0u;
-        auto keep = [&](int v, int k) -> int {
+        auto keep = [&](V v, int k) -> V {
             const int m = (int)(mask << (31 - k)) >> 31; // all ones where cell k exists
-            return (v & m) | (kBandNegInf & ~m);
+            if constexpr (STATS) return band_tuple((band_score(v) & m) | (kBandNegInf & ~m), band_low(v) & (uint32_t)m); // (minus infinity, 0)
+            else return (v & m) | (kBandNegInf & ~m);
         };
+        // STATS: what a mismatch adds to L in this step's row: its pair, unless the row lies outside 1 .. lb
+        [[maybe_unused]] uint32_t pair1 = 0;
+        if constexpr (STATS) pair1 = yc != kRowPad ? 1u : 0u;
 
         // TRACE, per cell: where H came from (diagonal, then E, then F) | E extended << 2 | F extended << 3, both strictly:
         // ue + ge > uz is ev > uz, and f + ge > zleft is the new f > the left cell's z, which z[k - 1] still holds.  Everything
@@ -307,18 +366,19 @@ __device__ __forceinline__ void band_body(const SwParams &prm, const uint32_t *_
         };
 
         // phase 1: the first cell
-        int f, zleft;
+        V f, zleft;
         {
-            const int ev = max(z[1], e[1] + ge);
-            f = max(zl, fl + ge);
-            int s;
+            const V ev = band_max(z[1], band_gap(e[1], ge));
+            f = band_max(zl, band_gap(fl, ge));
+            V s;
             if constexpr (MAT) s = z[0] + sc[0];
             else {
                 const int xs = (int)(xw[0] & 0xffu);
-                s = z[0] + (xs == yc ? s_match : s_mis);
+                if constexpr (STATS) s = band_pair_move(z[0], xs, yc, s_match, s_mis, pair1);
+                else s = z[0] + (xs == yc ? s_match : s_mis);
             }
-            if constexpr (AT_LOCAL) zleft = keep(max(max(max(ev, f), s), 0) + gf, 0); // the zero floor: z >= gf
-            else zleft = keep(max(max(ev, f), s) + gf, 0);
+            if constexpr (AT_LOCAL) zleft = keep(band_gap(band_max(band_max(band_max(ev, f), s), (V)0), gf), 0); // the zero floor: z >= gf
+            else zleft = keep(band_gap(band_max(band_max(ev, f), s), gf), 0);
             if constexpr (TRACE) {
                 tw[0] = dirs(s, ev, f, ev > z[1], f > zl);
 #pragma unroll
@@ -329,23 +389,24 @@ __device__ __forceinline__ void band_body(const SwParams &prm, const uint32_t *_
             z[0] = zleft;
         }
         // phase 2: it is the up input of the left neighbour's last diagonal
-        int rz = band_shl1(kBandNegInf, z[0]);
-        int re = band_shl1(kBandNegInf, e[0]);
-        if (last) rz = re = kBandNegInf;
+        V rz = band_shl1(kNeg, z[0]);
+        V re = band_shl1(kNeg, e[0]);
+        if (last) rz = re = kNeg;
 #pragma unroll
         for (int k = 1; k < K; ++k) {
-            const int uz = k + 1 < K ? z[k + 1] : rz;
-            const int ue = k + 1 < K ? e[k + 1] : re;
-            const int ev = max(uz, ue + ge);
-            f = max(zleft, f + ge);
-            int s;
+            const V uz = k + 1 < K ? z[k + 1] : rz;
+            const V ue = k + 1 < K ? e[k + 1] : re;
+            const V ev = band_max(uz, band_gap(ue, ge));
+            f = band_max(zleft, band_gap(f, ge));
+            V s;
             if constexpr (MAT) s = z[k] + sc[k];
             else {
                 const int xs = (int)((xw[k >> 2] >> (8 * (k & 3))) & 0xffu);
-                s = z[k] + (xs == yc ? s_match : s_mis);
+                if constexpr (STATS) s = band_pair_move(z[k], xs, yc, s_match, s_mis, pair1);
+                else s = z[k] + (xs == yc ? s_match : s_mis);
             }
-            if constexpr (AT_LOCAL) zleft = keep(max(max(max(ev, f), s), 0) + gf, k);
-            else zleft = keep(max(max(ev, f), s) + gf, k);
+            if constexpr (AT_LOCAL) zleft = keep(band_gap(band_max(band_max(band_max(ev, f), s), (V)0), gf), k);
+            else zleft = keep(band_gap(band_max(band_max(ev, f), s), gf), k);
             if constexpr (TRACE) {
                 tw[k >> 3] |= dirs(s, ev, f, ev > uz, f > z[k - 1]) << (4 * (k & 7));
                 asm volatile("" : "+v"(tw[k >> 3]), "+v"(zleft));
@@ -390,13 +451,17 @@ __device__ __forceinline__ void band_body(const SwParams &prm, const uint32_t *_
                 }
             }
         } else if constexpr (EXT) {
-            int m = z[0];
+            int m = band_score(z[0]);
 #pragma unroll
-            for (int k = 1; k < K; ++k) m = max(m, z[k]);
+            for (int k = 1; k < K; ++k) m = max(m, band_score(z[k]));
             if (m > best) { // a higher score than in any earlier row of this lane's diagonals
                 int col = 0;
 #pragma unroll
-                for (int k = K - 1; k >= 0; --k) col = z[k] == m ? k : col; // the leftmost cell of the row that holds it
+                for (int k = K - 1; k >= 0; --k) col = band_score(z[k]) == m ? k : col; // the leftmost cell of the row that holds it
+                if constexpr (STATS) { // ... chosen by its score alone; L is read there
+#pragma unroll
+                    for (int k = K - 1; k >= 0; --k) hit_l = band_score(z[k]) == m ? band_low(z[k]) : hit_l;
+                }
                 best = m;
                 hit_i = i;
                 hit_k = col;
@@ -407,12 +472,13 @@ __device__ __forceinline__ void band_body(const SwParams &prm, const uint32_t *_
             int slot = la - i - d0;
             if ((uint32_t)slot < (uint32_t)K && (uint32_t)i <= (uint32_t)lb) {
                 asm volatile("" : "+v"(slot));
-                int v = kBandNegInf;
+                V v = kNeg;
 #pragma unroll
                 for (int k = 0; k < K; ++k) v = k == slot ? z[k] : v;
-                if (v > cbest) {
-                    cbest = v;
+                if (band_score(v) > cbest) {
+                    cbest = band_score(v);
                     cap_i = i;
+                    if constexpr (STATS) hit_l = band_low(v);
                 }
             }
         } else {
@@ -420,7 +486,11 @@ __device__ __forceinline__ void band_body(const SwParams &prm, const uint32_t *_
                 int slot = kc; // (as above)
                 asm volatile("" : "+v"(slot));
 #pragma unroll
-                for (int k = 0; k < K; ++k) corner = k == slot ? z[k] : corner;
+                for (int k = 0; k < K; ++k) corner = k == slot ? band_score(z[k]) : corner;
+                if constexpr (STATS) {
+#pragma unroll
+                    for (int k = 0; k < K; ++k) hit_l = k == slot ? band_low(z[k]) : hit_l;
+                }
             }
         }
 
@@ -475,14 +545,18 @@ __device__ __forceinline__ void band_body(const SwParams &prm, const uint32_t *_
         for (int o = 1; o < G; o <<= 1) {
             const int ob = __shfl_down(best, o);
             const uint32_t ok = (uint32_t)__shfl_down((int)key, o);
+            [[maybe_unused]] uint32_t ol = 0;
+            if constexpr (STATS) ol = (uint32_t)__shfl_down((int)hit_l, o);
             if (gl + o < G && (ob > best || (ob == best && ok < key))) {
                 best = ob;
                 key = ok;
+                if constexpr (STATS) hit_l = ol; // L travels with the winner
             }
         }
         if (feeder) {
             scores[g.out] = best;
             pos[g.out] = key;
+            if constexpr (STATS) lstat[g.out] = hit_l; // (0 where no cell beat H(0, 0) = 0: nothing consumed)
         }
     } else if constexpr (AT_COL) {
         // over the group's lanes: score, then row (no lane of an admitted pair's group is without a cell of column la)
@@ -490,17 +564,24 @@ __device__ __forceinline__ void band_body(const SwParams &prm, const uint32_t *_
         for (int o = 1; o < G; o <<= 1) {
             const int ob = __shfl_down(cbest, o);
             const uint32_t ok = (uint32_t)__shfl_down((int)key, o);
+            [[maybe_unused]] uint32_t ol = 0;
+            if constexpr (STATS) ol = (uint32_t)__shfl_down((int)hit_l, o);
             if (gl + o < G && (ob > cbest || (ob == cbest && ok < key))) {
                 cbest = ob;
                 key = ok;
+                if constexpr (STATS) hit_l = ol;
             }
         }
         if (feeder) {
             scores[g.out] = cbest - gf;
             pos[g.out] = key;
+            if constexpr (STATS) lstat[g.out] = hit_l;
         }
     } else {
-        if (active && kc >= 0 && kc < K) scores[g.out] = corner - gf;
+        if (active && kc >= 0 && kc < K) {
+            scores[g.out] = corner - gf;
+            if constexpr (STATS) lstat[g.out] = hit_l;
+        }
     }
 }
 

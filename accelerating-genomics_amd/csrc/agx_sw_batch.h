@@ -27,6 +27,8 @@ struct agx_sw_batch {
     int mode = 0; // AGX_SW_MODE_*: anything but LOCAL runs the anchored fill (agx_sw_anch_kernel.hip)
     // agx_sw_batch_create_align_stats: 0 = no statistics; 1 = a stats batch whose own fill is the plain one (LOCAL,
     // FIT: the begin pass carries L); 2 = this batch's fill is the stats build and writes L = matches << 12 | pairs per pair
+    // agx_sw_batch_create_align_band_diag_stats: the same on a batch banded around a diagonal, whose L is
+    // matches << 16 | pairs (kSwBandStatBits); lstat is zeroed at create, so a pair without a fill reads 0
     int stats = 0;
     DevBuf lstat;       // stats == 2: L of every pair's captured cell
     PinBuf lstat_stage; // its page-locked landing block
@@ -136,11 +138,14 @@ inline void band_limits(int mode, int64_t w, int64_t la, int64_t lb, int64_t &dl
 
 // agx_sw_batch_create_align_band_diag's part of create_band: what to report and the centre diagonal of every pair (NULL: 0)
 // agx_sw_batch_create_align_band_zdrop adds its z-drop (zdrop_on; EXTEND only)
+// agx_sw_batch_create_align_band_diag_stats its statistics (stats: agx_sw_batch::stats -- 1 = answers agx_sw_batch_stats from its
+// begin pass, 2 = its own fill is the stats build)
 struct BandAt {
     int what;
     const int32_t *diag;
     bool zdrop_on = false;
     int32_t zdrop = 0;
+    int stats = 0;
 };
 
 // ---- agx_sw.cpp
@@ -371,7 +376,8 @@ int create_band(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t b
                 const uint32_t *len, int64_t n_pairs, agx_sw_batch **out, bool cigar = false, const BandAt *at = nullptr,
                 const agx_sw_matrix *matrix = nullptr);
 int band_launch(agx_sw_batch *b);
-int band_at_hits(agx_sw_batch *b, agx_sw_hit *hits, bool begins);
+// L (agx_sw_batch_stats): also the word matches << kSwBandStatBits | pairs of every pair, 0 where no fill says otherwise
+int band_at_hits(agx_sw_batch *b, agx_sw_hit *hits, bool begins, std::vector<uint32_t> *L = nullptr);
 int band_hits(agx_sw_batch *b, agx_sw_hit *hits);
 
 } // namespace agx_sw_host

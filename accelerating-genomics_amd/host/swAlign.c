@@ -1,5 +1,5 @@
 /*
- * swAlign <file_path> [local|global|fit|extend|extend-query][+stats|+cigar|+band=W|+cigar+band=W|+band=W@D|+bandcigar=W@D][+zdrop=Z]
+ * swAlign <file_path> [local|global|fit|extend|extend-query][+stats|+cigar|+band=W|+cigar+band=W|+band=W@D|+bandcigar=W@D|+bandstats=W@D][+zdrop=Z]
  * (and, with a matrix file, +matband=W@D|+matbandcigar=W@D): where the best alignment of every pair ends and begins
  * (default: local; the other modes are include/agx.h's "Alignment modes").
  * swAlign <file_path> <mode> <matrix_file> [gap_open gap_extend]: the same under a substitution matrix (gaps default to
@@ -40,6 +40,10 @@
  * Or "+zdrop=Z" behind either of the last two on extend, in this place only (extend+band=64@0+zdrop=100,
  * extend+bandcigar=64@0+zdrop=100): the extension terminates by the z-drop Z >= 0 (include/agx.h, "Z-drop for banded extension");
  * the same lines as without the suffix.  Another mode, a negative or non-numeric Z, or the suffix anywhere else is a usage error.
+ * Or the suffix "+bandstats=W@D" on any mode (fit+bandstats=64@-1500, global+bandstats=128@0): the alignment inside the band around
+ * the diagonal D AND its matches and aligned pairs, with no traceback (include/agx.h, "Statistics for batches banded around a
+ * diagonal"): the lines of "+band=W@D" with the two numbers appended as "+stats" appends them, read with the line buffer of
+ * "+band=W".  W and D as in "+band=W@D", both required; no matrix file, and no +cigar or +zdrop behind it.
  * swAlign <file_path> <mode>+matband=W@D <matrix_file> [gap_open gap_extend]: the lines of "+band=W@D" under the substitution
  * matrix (include/agx.h, "Banded alignment around a diagonal under a substitution matrix"), and
  * swAlign <file_path> <mode>+matbandcigar=W@D <matrix_file> [gap_open gap_extend]: the lines of "+bandcigar=W@D" under it.  Any
@@ -185,6 +189,22 @@ int main(int argc, char *argv[])
                 }
             }
         }
+        if (!strncmp(argv[2], words[k], n) && !strncmp(argv[2] + n, "+bandstats=", 11) && argc == 3) {
+            /* W@D as above, up to the end of the word (no further suffix); any mode, no matrix file */
+            const char *w = argv[2] + n + 11;
+            char *end, *end2;
+            const long v = strtol(w, &end, 10);
+            if (isdigit((unsigned char)*w) && *end == '@' && v <= 0x7fffffffL) {
+                const char *d = end + 1;
+                const long c = strtol(d, &end2, 10);
+                if (isdigit((unsigned char)d[*d == '-']) && !*end2 && c >= -0x7fffffffL && c <= 0x7fffffffL) {
+                    mode = k;
+                    with_band = with_diag = with_stats = 1;
+                    band = (int32_t)v;
+                    diag = (int32_t)c;
+                }
+            }
+        }
         const int mat_cigar = !strncmp(argv[2], words[k], n) && !strncmp(argv[2] + n, "+matbandcigar=", 14);
         if (!strncmp(argv[2], words[k], n) && (mat_cigar || !strncmp(argv[2] + n, "+matband=", 9)) && (argc == 4 || argc == 6)) {
             /* W@D as above, up to the end of the word (no further suffix); any mode, and only with a matrix file */
@@ -227,6 +247,8 @@ int main(int argc, char *argv[])
                 "diagonal D, in any mode; not with +stats, +cigar or a matrix file.\n"
                 "<mode>+bandcigar=W@D (fit+bandcigar=64@-1500): the same with its CIGAR inside that band appended; no matrix file.\n"
                 "extend+band=W@D+zdrop=Z, extend+bandcigar=W@D+zdrop=Z: the extension terminates by the z-drop Z >= 0; extend only.\n"
+                "<mode>+bandstats=W@D (fit+bandstats=64@-1500): the lines of +band=W@D with matches and aligned pairs appended, no\n"
+                "traceback; no matrix file, +cigar or +zdrop.\n"
                 "<mode>+matband=W@D <matrix_file> [gap_open gap_extend], <mode>+matbandcigar=W@D <matrix_file> [gap_open gap_extend]:\n"
                 "the lines of +band=W@D and of +bandcigar=W@D under the substitution matrix; a matrix file is required, and no\n"
                 "+stats, +cigar or +zdrop.\n",
@@ -290,7 +312,18 @@ int main(int argc, char *argv[])
                     if (t->len[k] && t->bases[t->off[k] + t->len[k] - 1] == '\n') t->len[k]--;
                     if (t->len[k] && t->bases[t->off[k] + t->len[k] - 1] == '\r') t->len[k]--;
                 }
-            if (!status && with_stats) {
+            if (!status && with_stats && with_diag) {
+                int32_t *dg = (int32_t *)malloc(sizeof(int32_t) * (size_t)t->n_pairs);
+                for (int64_t p = 0; dg && p < t->n_pairs; p++) dg[p] = diag;
+                if (!dg) {
+                    fprintf(stderr, "swAlign: out of memory\n");
+                    status = EXIT_FAILURE;
+                } else if (agx_sw_align_band_diag_stats(ctx, NULL, mode, band, dg, t->bases, t->off, t->len, t->n_pairs, hits, stats) != AGX_OK) {
+                    fprintf(stderr, "swAlign: %s\n", agx_last_error());
+                    status = EXIT_FAILURE;
+                }
+                free(dg);
+            } else if (!status && with_stats) {
                 if (agx_sw_align_stats(ctx, NULL, with_matrix ? &matrix : NULL, mode, t->bases, t->off, t->len, t->n_pairs, hits, stats) != AGX_OK) {
                     fprintf(stderr, "swAlign: %s\n", agx_last_error());
                     status = EXIT_FAILURE;

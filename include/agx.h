@@ -509,8 +509,8 @@ int agx_sw_cigar_in_band(const uint32_t *ops, uint64_t n_ops, int32_t dlo, int32
  * works; agx_sw_batch_stats and agx_sw_batch_cigars return AGX_E_ARG.  ctx may be NULL: plan only.  scoring and byte 0x00 as in
  * "Banded alignment".  Unchanged: agx_sw_batch_create_align_band still refuses LOCAL, FIT and EXTEND_QUERY with AGX_E_ARG.
  * CIGARs come from "CIGARs for batches banded around a diagonal" below, z-drop termination of EXTEND from "Z-drop for banded
- * extension", substitution matrices from "Banded alignment around a diagonal under a substitution matrix".  Deliberately left
- * out: statistics.
+ * extension", substitution matrices from "Banded alignment around a diagonal under a substitution matrix", matches and aligned
+ * pairs from "Statistics for batches banded around a diagonal".
  */
 int agx_sw_batch_create_align_band_diag(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int what, int32_t band,
                                         const int32_t *diag /* n_pairs, or NULL = 0 for every pair */, const uint8_t *bases,
@@ -544,8 +544,8 @@ int agx_sw_align_band_diag(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode
  * beyond the budget alone in its chunk), agx_sw_cigar_info and the host's check of every CIGAR before it leaves (AGX_E_INTERNAL
  * naming the pair) are as in "CIGARs for banded batches".  ctx may be NULL: plan only.
  * Unchanged: a plain band-diag batch keeps answering agx_sw_batch_cigars with AGX_E_ARG; agx_sw_batch_stats on this batch gives
- * AGX_E_ARG.  Substitution matrices come from "Banded alignment around a diagonal under a substitution matrix" below.
- * Deliberately left out: statistics.
+ * AGX_E_ARG.  Substitution matrices come from "Banded alignment around a diagonal under a substitution matrix" below; matches
+ * and aligned pairs without a traceback from "Statistics for batches banded around a diagonal".
  */
 int agx_sw_batch_create_align_band_diag_cigar(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t band,
                                               const int32_t *diag /* n_pairs, or NULL = 0 for every pair */, const uint8_t *bases,
@@ -589,7 +589,7 @@ int agx_sw_align_band_diag_cigar(agx_ctx *ctx, const agx_sw_scoring *scoring, in
  *       hit for hit and operation for operation.
  * Both kinds of batch return AGX_E_ARG from agx_sw_batch_stats and agx_sw_batch_zdrop_stops, the batch without CIGARs also from
  * agx_sw_batch_cigars.
- * Deliberately left out: statistics on banded batches, z-drop under a matrix, and a matrix for agx_sw_batch_create_align_band
+ * Deliberately left out: statistics on banded batches under a matrix, z-drop under a matrix, and a matrix for agx_sw_batch_create_align_band
  * (EXTEND with diag == NULL here is its EXTEND band; its GLOBAL band, widened by the length difference, is not offered).
  */
 int agx_sw_batch_create_align_band_diag_matrix(agx_ctx *ctx, const agx_sw_matrix *matrix, int mode, int what, int32_t band,
@@ -658,6 +658,39 @@ int agx_sw_batch_create_align_band_zdrop_cigar(agx_ctx *ctx, const agx_sw_scorin
 int agx_sw_align_band_zdrop_cigar(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t band, const int32_t *diag, int32_t zdrop,
                                   const uint8_t *bases, const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_hit *hits,
                                   int32_t *stops /* may be NULL */, uint64_t *op_off, uint32_t *ops, uint64_t ops_cap);
+
+/*
+ * Statistics for batches banded around a diagonal: matches and aligned pairs of a banded alignment without a traceback -- the
+ * identity filter for long reads ("keep reads above 90 %"), which an unbanded stats batch cannot serve beyond
+ * AGX_SW_STATS_MAX_QUERY_LEN and a cigar batch serves only at the price of a traced fill and a walk.
+ * For a pair, let score, a_begin..a_end, b_begin..b_end be exactly what an AGX_SW_ALIGN_SPANS batch of
+ * agx_sw_batch_create_align_band_diag reports for the same mode, scoring, band and diag.  Consider the alignments that run
+ * through IN-BAND CELLS ONLY (dlo = c - w <= j - i <= dhi = c + w of the full matrix, after every operation), attain `score`, and
+ * consume exactly a[a_begin..a_end] and b[b_begin..b_end].  Among these take the one with the most matches, and among those the
+ * one with the most pairs; pairs, matches and the caller's arithmetic (columns, mismatches, gap cells, identity) are those of
+ * "Alignment statistics".  Nothing consumed gives {0, 0}: a LOCAL or EXTEND score of 0 (a LOCAL band that misses the matrix
+ * included), an empty side, b_end = -1, and FIT's empty range b_begin = b_end + 1 (all of a in one gap).
+ * The CIGAR of "CIGARs for batches banded around a diagonal" is ONE of these alignments, the one its tie rule picks; its count of
+ * '=' and of '=' + 'X' is therefore lexicographically <= (matches, pairs), with equality where the optimal in-band path is unique.
+ * The batch: an AGX_SW_ALIGN_SPANS batch of "Banded alignment around a diagonal" -- the same band conditions per mode, limits,
+ * trimmed rows and errors naming the pair; agx_sw_batch_launch, _scores, _hits and _info behave the same,
+ * agx_sw_batch_bind_scores is accepted and ignored, ctx may be NULL: plan only -- that also answers agx_sw_batch_stats(b, hits,
+ * stats).  Every stat is checked before it is returned by the rule of agx_sw_batch_stats (0 <= matches <= pairs <= min(ca, cb);
+ * the score minus matches, mismatches and gap cells is a whole number of gap opens within its bounds): AGX_E_INTERNAL naming the
+ * pair otherwise.
+ * No new limit: every lane class of the banded fill is built with statistics, so the widest band stays AGX_SW_BAND_MAX_WIDTH.
+ * Unchanged: agx_sw_batch_stats on a plain band-diag, cigar, z-drop or matrix batch keeps returning AGX_E_ARG, and this batch
+ * returns AGX_E_ARG from agx_sw_batch_cigars and agx_sw_batch_zdrop_stops.
+ * Deliberately left out: statistics under a substitution matrix, with a z-drop, and for agx_sw_batch_create_align_band with its
+ * GLOBAL widening; the number of gap opens, as in "Alignment statistics".
+ */
+int agx_sw_batch_create_align_band_diag_stats(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t band,
+                                              const int32_t *diag /* n_pairs, or NULL = 0 for every pair */, const uint8_t *bases,
+                                              const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_batch **out);
+/* One-shot: create_align_band_diag_stats + launch + stats + destroy. */
+int agx_sw_align_band_diag_stats(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t band, const int32_t *diag,
+                                 const uint8_t *bases, const uint64_t *off, const uint32_t *len, int64_t n_pairs,
+                                 agx_sw_hit *hits /* may be NULL */, agx_sw_stat *stats);
 
 /* Host only, no device.  How the traced fill of a span starts inside a banded batch's resident image.  The image holds the
  * query a behind `fpad` bytes and the rows b[row0 .. row0 + rows) behind one byte, packed for a fill from row0 in the band
