@@ -65,6 +65,7 @@ SYMBOLS = [
     "agx_sw_batch_create_align_band_zdrop", "agx_sw_align_band_zdrop", "agx_sw_batch_zdrop_stops",
     "agx_sw_batch_create_align_band_zdrop_cigar", "agx_sw_align_band_zdrop_cigar",
     "agx_sw_batch_create_align_band_diag_stats", "agx_sw_align_band_diag_stats",
+    "agx_sw_batch_create_align_band_diag_dual", "agx_sw_align_band_diag_dual",
     "agx_sw_score", "agx_sw_score_multi", "agx_sw_score_devices", "agx_sw_shard_cuts",
     "agx_phmm_batch_create", "agx_phmm_batch_launch", "agx_phmm_batch_results", "agx_phmm_batch_bind_results", "agx_phmm_batch_info",
     "agx_phmm_batch_destroy", "agx_phmm_forward", "agx_phmm_forward_multi", "agx_phmm_forward_devices", "agx_phmm_shard_cuts",
@@ -105,6 +106,12 @@ def cigar_string(ops) -> str:
 
 class SwScoring(C.Structure):
     _fields_ = [("match", C.c_int32), ("mismatch", C.c_int32), ("gap_open", C.c_int32), ("gap_extend", C.c_int32)]
+
+
+class SwScoringDual(C.Structure):
+    """agx_sw_scoring_dual: two-piece affine gap costs -- a gap of L costs max(gap_open + L gap_extend, gap_open2 + L gap_extend2)."""
+    _fields_ = [("match", C.c_int32), ("mismatch", C.c_int32), ("gap_open", C.c_int32), ("gap_extend", C.c_int32),
+                ("gap_open2", C.c_int32), ("gap_extend2", C.c_int32)]
 
 
 class SwMatrix(C.Structure):
@@ -256,6 +263,10 @@ def lib():
                                                                 C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
         l.agx_sw_align_band_diag_stats.argtypes = [C.c_void_p, C.POINTER(SwScoring), C.c_int, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                                    C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        l.agx_sw_batch_create_align_band_diag_dual.argtypes = [C.c_void_p, C.POINTER(SwScoringDual), C.c_int, C.c_int, C.c_int32, C.c_void_p,
+                                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        l.agx_sw_align_band_diag_dual.argtypes = [C.c_void_p, C.POINTER(SwScoringDual), C.c_int, C.c_int, C.c_int32, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
         l.agx_sw_band_span_record.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                                               C.POINTER(SwBandSpan)]
         l.agx_sw_score.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
@@ -372,8 +383,19 @@ class Context:
 
     # ---- Smith-Waterman
     def sw_batch(self, b, scoring=None, matrix=None, align=0, mode=SW_MODE_LOCAL, stats=False, cigar=False, band=None, diag=None,
-                 zdrop=None, band_stats=False) -> "SwBatch":
-        return SwBatch(self, b, scoring, matrix, align, mode, stats, cigar, band, diag, zdrop, band_stats)
+                 zdrop=None, band_stats=False, dual=None) -> "SwBatch":
+        return SwBatch(self, b, scoring, matrix, align, mode, stats, cigar, band, diag, zdrop, band_stats, dual)
+
+    def sw_align_band_diag_dual(self, b, mode, band, diag=None, what=SW_ALIGN_SPANS, scoring6=None):
+        """b: synth.SWBatch -> SwHit records of the alignment inside the band around diag under two-piece gap costs, one-shot
+        (include/agx.h, "Banded alignment around a diagonal under two-piece gap costs").  scoring6: (match, mismatch, gap_open,
+        gap_extend, gap_open2, gap_extend2), required."""
+        out = np.empty(b.n_pairs, SwHit)
+        sc = C.byref(SwScoringDual(*scoring6)) if scoring6 is not None else None
+        d = _diag(diag, b.n_pairs)
+        _check(lib().agx_sw_align_band_diag_dual(self._h, sc, mode, what, band, _ptr(d), _ptr(b.bases), _ptr(b.off), _ptr(b.len), b.n_pairs,
+                                                 _ptr(out)))
+        return out
 
     def sw_align_band_diag_stats(self, b, mode, band, diag=None, scoring=None):
         """b: synth.SWBatch -> (SwHit records as sw_align_band_diag(what=SW_ALIGN_SPANS) gives them, SwStat records), one-shot: matches
@@ -509,7 +531,7 @@ class SwBatch:
     """agx_sw_batch: a scheduled batch resident in HBM (ctx=None: planned on the host only)."""
 
     def __init__(self, ctx, b, scoring=None, matrix=None, align=0, mode=SW_MODE_LOCAL, stats=False, cigar=False, band=None, diag=None,
-                 zdrop=None, band_stats=False):
+                 zdrop=None, band_stats=False, dual=None):
         """scoring: None (the reference's +1/-1/-3/-1) or (match, mismatch, gap_open, gap_extend);
         matrix: an SwMatrix instead (score-only and align batches alike); align: SW_ALIGN_ENDS / SW_ALIGN_SPANS for a batch that also answers hits();
         mode: SW_MODE_* of an align batch (local, global, fit, extension); stats=True: a SPANS batch that also answers stats();
@@ -521,10 +543,21 @@ class SwBatch:
         matrix (then no scoring and no zdrop);
         band=w with zdrop=Z (diag optional): such a batch in SW_MODE_EXTEND that terminates by the z-drop and also answers zdrop_stops();
         band=w with band_stats=True (diag optional): a SPANS batch banded around a diagonal that also answers stats() (no matrix, cigar or
-        zdrop; stats=True stays the unbanded stats batch and does not combine with band=)."""
+        zdrop; stats=True stays the unbanded stats batch and does not combine with band=);
+        band=w with dual=(match, mismatch, gap_open, gap_extend, gap_open2, gap_extend2) (diag optional): a batch banded around a diagonal
+        under two-piece gap costs, any mode, align = SW_ALIGN_ENDS or SW_ALIGN_SPANS (0: SPANS); it answers hits() and scores() (no
+        scoring, matrix, stats, cigar, zdrop or band_stats)."""
         self.ctx = ctx
         self.n_pairs = b.n_pairs
         self._h = C.c_void_p()
+        if dual is not None:
+            if band is None or scoring is not None or matrix is not None or stats or cigar or zdrop is not None or band_stats:
+                raise AgxError(E_ARG, "dual= takes band=w (and diag=): no scoring, matrix, stats, cigar, zdrop or band_stats")
+            d = _diag(diag, b.n_pairs)
+            _check(lib().agx_sw_batch_create_align_band_diag_dual(ctx._h if ctx else None, C.byref(SwScoringDual(*dual)), mode,
+                                                                  align or SW_ALIGN_SPANS, band, _ptr(d), _ptr(b.bases), _ptr(b.off), _ptr(b.len),
+                                                                  b.n_pairs, C.byref(self._h)))
+            return
         if band_stats:
             if band is None or stats or cigar or matrix is not None or zdrop is not None or align not in (0, SW_ALIGN_SPANS):
                 raise AgxError(E_ARG, "band_stats=True takes band=w (and diag=) on a SW_ALIGN_SPANS batch: no stats=, cigar, matrix or zdrop")

@@ -254,6 +254,19 @@ constexpr int kSwBandStatBits = 16; // L = matches << 16 | pairs: both up to 65 
 int agx_sw_band_stats_launch_class(int diags_per_lane, int mode, const SwParams &prm, const uint32_t *img, const SwBandGroup *groups,
                                    const SwWave *waves, uint32_t n_waves, int32_t *scores, uint32_t *pos, uint32_t *lstat, hipStream_t s);
 void agx_sw_band_stats_preload();
+// the builds under TWO-PIECE gap costs (agx_sw_band_dual_kernel.hip): the GLOBAL and EXTEND builds and the three
+// builds around a diagonal again; records, scores and pos as the plain builds of that mode write them.  prm holds the first piece
+// exactly as a plain batch's does; the second travels beside it.  Every class is built without scratch, AGPRs or LDS.
+struct SwDualGap {
+    int32_t ge2; // the second piece's gap_extend
+    int32_t dgf; // (gap_open2 + gap_extend2) - prm.gf: what piece 2 adds to the stored z = H + gf
+};
+int agx_sw_band_dual_launch_class(int diags_per_lane, int extend, const SwParams &prm, const SwDualGap &dg, const uint32_t *img,
+                                  const SwBandGroup *groups, const SwWave *waves, uint32_t n_waves, int32_t *scores, uint32_t *pos, hipStream_t s);
+int agx_sw_band_dual_at_launch_class(int diags_per_lane, int mode, const SwParams &prm, const SwDualGap &dg, const uint32_t *img,
+                                     const SwBandGroup *groups, const SwWave *waves, uint32_t n_waves, int32_t *scores, uint32_t *pos,
+                                     hipStream_t s);
+void agx_sw_band_dual_preload();
 // the TRACED banded fill and its walk (agx_sw_band_trace_kernel.hip): corner capture only.  Every cell of rows
 // 0 .. lb leaves four bits at trace + goff[group] + (step * G + lane) * sw_band_trace_words(K) dwords, nibble k of the lane's K
 // diagonals; goff holds one 64-bit dword offset per group record, a multiple of four (the K = 32 build stores 16 bytes at once).

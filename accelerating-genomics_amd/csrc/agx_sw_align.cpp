@@ -35,6 +35,15 @@ agx_sw_hit empty_side_hit(int mode, int what, const agx_sw_scoring &sc, uint32_t
     return h;
 }
 
+// The same under two-piece gap costs (include/agx.h, "Banded alignment around a diagonal under two-piece gap costs"): every formula
+// holds one gap, whose cost is the larger of the two pieces' -- the hit of the piece that scores higher; the ends are the same.
+agx_sw_hit empty_side_hit_dual(int mode, int what, const agx_sw_scoring_dual &sc, uint32_t la, uint32_t lb)
+{
+    const agx_sw_hit h1 = empty_side_hit(mode, what, agx_sw_scoring{sc.match, sc.mismatch, sc.gap_open, sc.gap_extend}, la, lb);
+    const agx_sw_hit h2 = empty_side_hit(mode, what, agx_sw_scoring{sc.match, sc.mismatch, sc.gap_open2, sc.gap_extend2}, la, lb);
+    return h2.score > h1.score ? h2 : h1;
+}
+
 // an align batch under match/mismatch scoring (matrix == NULL) or under a substitution matrix (scoring unused)
 int create_align(const char *who, agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matrix *matrix, int mode, int what,
                  const uint8_t *bases, const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_batch **out, bool stats, bool cigar)

@@ -44,7 +44,8 @@ void trace_band_plan(const agx_sw_batch *b, const std::vector<SwWave> &waves, co
                      const std::vector<uint32_t> &row0s, const int32_t *diag, const uint32_t *len)
 {
     fprintf(stderr, "[agx_sw_batch_create_band] kind: mode %d band %d align %d at %d zdrop %d cigar %d matrix %d%s\n", b->mode, b->band, b->align,
-            (int)b->band_at, b->zdrop_on ? b->zdrop : -1, b->cigar, (int)b->matrix, b->stats == 2 ? " stats 2" : b->stats ? " stats 1" : "");
+            (int)b->band_at, b->zdrop_on ? b->zdrop : -1, b->cigar, (int)b->matrix,
+            b->dual ? " dual" : b->stats == 2 ? " stats 2" : b->stats ? " stats 1" : "");
     Fnv1a all, head, wv, gr;
     hash_band_head(all, b), hash_band_head(head, b);
     hash_band_waves(all, waves), hash_band_waves(wv, waves);
@@ -114,6 +115,12 @@ agx_sw_batch *init_band_batch(agx_ctx *ctx, const BandKind &kind, const agx_sw_s
     b->prm.hd = sc.match - b->prm.gf;
     b->prm.delta = sc.match - sc.mismatch;
     b->prm.n_out = (uint32_t)n_pairs;
+    if (at && at->dual) { // (sc is its first piece: prm, and with it the plan's digest, are the plain batch's)
+        b->dual = true;
+        b->dual_sc = *at->dual;
+        b->dual_gap.ge2 = at->dual->gap_extend2;
+        b->dual_gap.dgf = at->dual->gap_open2 + at->dual->gap_extend2 - b->prm.gf;
+    }
     return b;
 }
 
@@ -157,6 +164,7 @@ void keep_band_host_state(agx_sw_batch *b, const BandKind &kind, const BandPairs
         agx_sw_band_at_preload();
         if (at->zdrop_on) agx_sw_band_zdrop_preload();
         if (at->stats) agx_sw_band_stats_preload();
+        if (at->dual) agx_sw_band_dual_preload();
         b->band_row0 = pairs.row0s;
         if (at->diag) b->band_diag.assign(at->diag, at->diag + n_pairs);
         else b->band_diag.assign((size_t)n_pairs, 0);
@@ -253,7 +261,8 @@ int create_band(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t b
                 const uint32_t *len, int64_t n_pairs, agx_sw_batch **out, bool cigar, const BandAt *at, const agx_sw_matrix *matrix)
 {
     const bool zd = at && at->zdrop_on;
-    const char *who = at && at->stats ? "agx_sw_batch_create_align_band_diag_stats"
+    const char *who = at && at->dual  ? "agx_sw_batch_create_align_band_diag_dual"
+                      : at && at->stats ? "agx_sw_batch_create_align_band_diag_stats"
                       : matrix      ? (cigar ? "agx_sw_batch_create_align_band_diag_matrix_cigar" : "agx_sw_batch_create_align_band_diag_matrix")
                       : zd   ? (cigar ? "agx_sw_batch_create_align_band_zdrop_cigar" : "agx_sw_batch_create_align_band_zdrop")
                       : at   ? (cigar ? "agx_sw_batch_create_align_band_diag_cigar" : "agx_sw_batch_create_align_band_diag")
@@ -333,6 +342,17 @@ int band_launch(agx_sw_batch *b)
         }
         return fan.end();
     };
+    if (b->dual) {
+        if (b->mode != AGX_SW_MODE_GLOBAL && b->mode != AGX_SW_MODE_EXTEND)
+            return launch_classes("sw_fill_band_dual_at", true, [&](const ClassLaunch &cl, hipStream_t s) {
+                return agx_sw_band_dual_at_launch_class(cl.C, b->mode, b->prm, b->dual_gap, img, groups, waves + cl.first_wave, cl.n_waves, scores,
+                                                        pos, s);
+            });
+        return launch_classes("sw_fill_band_dual", false, [&](const ClassLaunch &cl, hipStream_t s) {
+            return agx_sw_band_dual_launch_class(cl.C, b->mode == AGX_SW_MODE_EXTEND, b->prm, b->dual_gap, img, groups, waves + cl.first_wave,
+                                                 cl.n_waves, scores, pos, s);
+        });
+    }
     if (b->stats == 2)
         return launch_classes("sw_fill_band_stats", true, [&](const ClassLaunch &cl, hipStream_t s) {
             return agx_sw_band_stats_launch_class(cl.C, b->mode, b->prm, img, groups, waves + cl.first_wave, cl.n_waves, scores, pos,
@@ -389,7 +409,9 @@ int band_at_hits(agx_sw_batch *b, agx_sw_hit *hits, bool begins, std::vector<uin
         const uint32_t la = b->seq_len[(size_t)(2 * p)], lb = b->seq_len[(size_t)(2 * p + 1)];
         const uint32_t row0 = b->band_row0[(size_t)p];
         if (!la || !lb) {
-            hits[p] = mode == AGX_SW_MODE_LOCAL ? nothing : empty_side_hit(mode, b->align, b->scoring, la, lb);
+            hits[p] = mode == AGX_SW_MODE_LOCAL ? nothing
+                      : b->dual                 ? empty_side_hit_dual(mode, b->align, b->dual_sc, la, lb)
+                                                : empty_side_hit(mode, b->align, b->scoring, la, lb);
             continue;
         }
         if (row0 == kNoBandRow) { // LOCAL: the band misses the matrix
@@ -447,7 +469,7 @@ int band_at_hits(agx_sw_batch *b, agx_sw_hit *hits, bool begins, std::vector<uin
         rdiag[(size_t)k] = (h.a_end + 1) - (h.b_end + 1) - b->band_diag[(size_t)pick[(size_t)k]];
     }
     agx_sw_batch *rb = nullptr;
-    const BandAt rat{AGX_SW_ALIGN_ENDS, rdiag.data(), false, 0, L ? 2 : 0};
+    const BandAt rat{AGX_SW_ALIGN_ENDS, rdiag.data(), false, 0, L ? 2 : 0, b->dual ? &b->dual_sc : nullptr}; // (under the same two pieces)
     rc = create_band(b->ctx, &b->scoring, fit ? AGX_SW_MODE_EXTEND_QUERY : AGX_SW_MODE_LOCAL, b->band, rev.bytes.data(), rev.off.data(),
                      rev.len.data(), m, &rb, false, &rat, b->matrix ? &b->mat : nullptr);
     if (rc) return rc;
@@ -607,6 +629,30 @@ int agx_sw_align_band_diag_stats(agx_ctx *ctx, const agx_sw_scoring *scoring, in
     agx_sw_batch *b = nullptr;
     const int rc = agx_sw_batch_create_align_band_diag_stats(ctx, scoring, mode, band, diag, bases, off, len, n_pairs, &b);
     return rc ? rc : align_once(b, [&](agx_sw_batch *x) { return agx_sw_batch_stats(x, hits, stats); });
+}
+
+int agx_sw_batch_create_align_band_diag_dual(agx_ctx *ctx, const agx_sw_scoring_dual *scoring, int mode, int what, int32_t band,
+                                             const int32_t *diag, const uint8_t *bases, const uint64_t *off, const uint32_t *len, int64_t n_pairs,
+                                             agx_sw_batch **out)
+{
+    if (!scoring) { // (there is no reference default for a second piece)
+        if (out) *out = nullptr;
+        agx_set_error("agx_sw_batch_create_align_band_diag_dual: scoring is NULL");
+        return AGX_E_ARG;
+    }
+    AGX_GUARD_BEGIN
+    const BandAt at{what, diag, false, 0, 0, scoring};
+    const agx_sw_scoring piece1{scoring->match, scoring->mismatch, scoring->gap_open, scoring->gap_extend};
+    return create_band(ctx, &piece1, mode, band, bases, off, len, n_pairs, out, false, &at);
+    AGX_GUARD_END("agx_sw_batch_create_align_band_diag_dual")
+}
+
+int agx_sw_align_band_diag_dual(agx_ctx *ctx, const agx_sw_scoring_dual *scoring, int mode, int what, int32_t band, const int32_t *diag,
+                                const uint8_t *bases, const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_hit *hits)
+{
+    agx_sw_batch *b = nullptr;
+    const int rc = agx_sw_batch_create_align_band_diag_dual(ctx, scoring, mode, what, band, diag, bases, off, len, n_pairs, &b);
+    return rc ? rc : align_once(b, [&](agx_sw_batch *x) { return agx_sw_batch_hits(x, hits); });
 }
 
 int agx_sw_batch_create_align_band_diag_matrix(agx_ctx *ctx, const agx_sw_matrix *matrix, int mode, int what, int32_t band, const int32_t *diag,

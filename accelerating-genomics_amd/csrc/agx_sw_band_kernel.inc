@@ -131,6 +131,12 @@
 // infinity, 0), every hand-over between lanes carries both words, and capture reads the score word alone: lstat[out] receives L
 // of the cell the plain build would have captured.  That file's head has the argument, for the low word above all.
 //
+// DUAL (agx_sw_band_dual_kernel.hip; include/agx.h, "Banded alignment around a diagonal under two-piece gap costs"; DESIGN.md
+// 4.1n): the builds whose gaps cost the cheaper of two affine pieces -- the plain GLOBAL and EXTEND builds and the three AT builds
+// again.  A second pair of gap states, e2 per diagonal and f2 along the chain, runs beside e and f under the second piece's
+// extension cost ge2; both read the one stored z = H + gf of the first piece plus dgf = gf2 - gf, and H takes the maximum over
+// all five.  Every hand-over between lanes carries the second piece as well.  That file's head has the argument.
+//
 // (included by agx_sw_band_kernel.hip; opens an anonymous namespace that the including file closes after its launch helper)
 #include "agx_sw.h"
 
@@ -190,12 +196,15 @@ __device__ __forceinline__ long long band_shl1(long long old, long long v)
 // ANY rule; FIT and EXTEND_QUERY capture column la).  Everything they add stands inside `if constexpr` blocks.
 // MAT: the builds under a substitution matrix; sub is the table in LDS.
 // STATS: the builds on tuples; lstat receives L of the captured cell.
-template <int K, bool EXT, bool TRACE = false, int AT = -1, bool PH = false, bool ZD = false, bool MAT = false, bool STATS = false>
+// DUAL: the builds under two-piece gap costs; ge2 is the second piece's extension cost and dgf its first-cell cost less gf.
+template <int K, bool EXT, bool TRACE = false, int AT = -1, bool PH = false, bool ZD = false, bool MAT = false, bool STATS = false,
+          bool DUAL = false>
 __device__ __forceinline__ void band_body(const SwParams &prm, const uint32_t *__restrict__ img, const SwBandGroup *__restrict__ groups,
                                           const SwWave w, int32_t *__restrict__ scores, uint32_t *__restrict__ pos,
                                           uint32_t *trace = nullptr, const uint64_t *goff = nullptr, [[maybe_unused]] int zdrop = 0,
                                           [[maybe_unused]] int32_t *__restrict__ stops = nullptr, [[maybe_unused]] const int16_t *sub = nullptr,
-                                          [[maybe_unused]] uint32_t *__restrict__ lstat = nullptr)
+                                          [[maybe_unused]] uint32_t *__restrict__ lstat = nullptr, [[maybe_unused]] int ge2 = 0,
+                                          [[maybe_unused]] int dgf = 0)
 {
     static_assert(!(TRACE && EXT), "the traced build captures the corner: an EXTEND span is traced as the global alignment it is");
     static_assert(K % 4 == 0 && K >= 4 && K <= 32, "the query window is whole dwords and the cell mask one dword");
@@ -207,6 +216,7 @@ __device__ __forceinline__ void band_body(const SwParams &prm, const uint32_t *_
     static_assert(!MAT || !ZD, "no z-drop under a matrix");
     static_assert(!STATS || (!TRACE && !PH && !ZD && !MAT && AT != AGX_SW_MODE_FIT),
                   "statistics ride on the plain GLOBAL and EXTEND builds and on the LOCAL and EXTEND_QUERY builds around a diagonal");
+    static_assert(!DUAL || (!TRACE && !PH && !ZD && !MAT && !STATS), "two-piece gap costs: scores, ends and spans only");
     using V = typename BandState<STATS>::type;
     constexpr V kNeg = STATS ? (V)((unsigned long long)(uint32_t)kBandNegInf << 32) : (V)kBandNegInf; // STATS: (minus infinity, 0)
     constexpr bool AT_LOCAL = AT == AGX_SW_MODE_LOCAL, AT_FIT = AT == AGX_SW_MODE_FIT, AT_COL = AT_FIT || AT == AGX_SW_MODE_EXTEND_QUERY;
@@ -266,6 +276,13 @@ __device__ __forceinline__ void band_body(const SwParams &prm, const uint32_t *_
 #pragma unroll
     for (int k = 0; k < K; ++k) z[k] = e[k] = kNeg;
     V z_last = kNeg, f_last = kNeg;
+    // DUAL: the second piece's E per diagonal and its F as the step's last cell left it
+    [[maybe_unused]] V e2[DUAL ? K : 1];
+    [[maybe_unused]] V f2_last = kNeg;
+    if constexpr (DUAL) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) e2[k] = kNeg;
+    }
     int yc_prev = kRowPad;
     // STATS: L of the cell that `best` / `corner` / `cbest` was read from
     [[maybe_unused]] uint32_t hit_l = 0;
@@ -302,10 +319,13 @@ __device__ __forceinline__ void band_body(const SwParams &prm, const uint32_t *_
         V zl = band_shr1(kNeg, z_last);
         V fl = band_shr1(kNeg, f_last);
         int yc = band_shr1(fresh, yc_prev);
+        [[maybe_unused]] V fl2 = kNeg;
+        if constexpr (DUAL) fl2 = band_shr1(kNeg, f2_last);
         if (first) {
             zl = kNeg;
             fl = kNeg;
             yc = fresh;
+            if constexpr (DUAL) fl2 = kNeg;
         }
         // MAT: the K entries of this step -- row yc of the table, the columns of the window's bytes -- depend on nothing the cell
         // chain computes: all K reads are issued here, ahead of the injection, the mask and the chain, which then waits for
@@ -367,9 +387,15 @@ __device__ __forceinline__ void band_body(const SwParams &prm, const uint32_t *_
 
         // phase 1: the first cell
         V f, zleft;
+        [[maybe_unused]] V f2 = kNeg;
         {
             const V ev = band_max(z[1], band_gap(e[1], ge));
             f = band_max(zl, band_gap(fl, ge));
+            [[maybe_unused]] V ev2 = kNeg;
+            if constexpr (DUAL) {
+                ev2 = band_max(band_gap(z[1], dgf), band_gap(e2[1], ge2));
+                f2 = band_max(band_gap(zl, dgf), band_gap(fl2, ge2));
+            }
             V s;
             if constexpr (MAT) s = z[0] + sc[0];
             else {
@@ -377,6 +403,7 @@ __device__ __forceinline__ void band_body(const SwParams &prm, const uint32_t *_
                 if constexpr (STATS) s = band_pair_move(z[0], xs, yc, s_match, s_mis, pair1);
                 else s = z[0] + (xs == yc ? s_match : s_mis);
             }
+            if constexpr (DUAL) s = band_max(s, band_max(ev2, f2)); // H over all five: the diagonal move and both pieces' E and F
             if constexpr (AT_LOCAL) zleft = keep(band_gap(band_max(band_max(band_max(ev, f), s), (V)0), gf), 0); // the zero floor: z >= gf
             else zleft = keep(band_gap(band_max(band_max(ev, f), s), gf), 0);
             if constexpr (TRACE) {
@@ -386,18 +413,30 @@ __device__ __forceinline__ void band_body(const SwParams &prm, const uint32_t *_
                 asm volatile("" : "+v"(tw[0]), "+v"(zleft));
             }
             e[0] = ev;
+            if constexpr (DUAL) e2[0] = ev2;
             z[0] = zleft;
         }
         // phase 2: it is the up input of the left neighbour's last diagonal
         V rz = band_shl1(kNeg, z[0]);
         V re = band_shl1(kNeg, e[0]);
-        if (last) rz = re = kNeg;
+        [[maybe_unused]] V re2 = kNeg;
+        if constexpr (DUAL) re2 = band_shl1(kNeg, e2[0]);
+        if (last) {
+            rz = re = kNeg;
+            if constexpr (DUAL) re2 = kNeg;
+        }
 #pragma unroll
         for (int k = 1; k < K; ++k) {
             const V uz = k + 1 < K ? z[k + 1] : rz;
             const V ue = k + 1 < K ? e[k + 1] : re;
             const V ev = band_max(uz, band_gap(ue, ge));
             f = band_max(zleft, band_gap(f, ge));
+            [[maybe_unused]] V ev2 = kNeg;
+            if constexpr (DUAL) {
+                const V ue2 = k + 1 < K ? e2[k + 1] : re2;
+                ev2 = band_max(band_gap(uz, dgf), band_gap(ue2, ge2));
+                f2 = band_max(band_gap(zleft, dgf), band_gap(f2, ge2));
+            }
             V s;
             if constexpr (MAT) s = z[k] + sc[k];
             else {
@@ -405,6 +444,7 @@ __device__ __forceinline__ void band_body(const SwParams &prm, const uint32_t *_
                 if constexpr (STATS) s = band_pair_move(z[k], xs, yc, s_match, s_mis, pair1);
                 else s = z[k] + (xs == yc ? s_match : s_mis);
             }
+            if constexpr (DUAL) s = band_max(s, band_max(ev2, f2));
             if constexpr (AT_LOCAL) zleft = keep(band_gap(band_max(band_max(band_max(ev, f), s), (V)0), gf), k);
             else zleft = keep(band_gap(band_max(band_max(ev, f), s), gf), k);
             if constexpr (TRACE) {
@@ -412,6 +452,7 @@ __device__ __forceinline__ void band_body(const SwParams &prm, const uint32_t *_
                 asm volatile("" : "+v"(tw[k >> 3]), "+v"(zleft));
             }
             e[k] = ev;
+            if constexpr (DUAL) e2[k] = ev2;
             z[k] = zleft;
         }
 
@@ -503,6 +544,7 @@ __device__ __forceinline__ void band_body(const SwParams &prm, const uint32_t *_
 
         z_last = zleft;
         f_last = f;
+        if constexpr (DUAL) f2_last = f2;
         yc_prev = yc;
         ++t;
     };

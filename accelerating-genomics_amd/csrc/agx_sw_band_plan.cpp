@@ -112,6 +112,12 @@ int check_band_arrays(const BandKind &kind, const agx_sw_scoring *scoring, const
                       sc.gap_extend);
         return AGX_E_LIMIT;
     }
+    if (const agx_sw_scoring_dual *d = kind.at ? kind.at->dual : nullptr) // the second piece: the limits of the first
+        if (d->gap_open2 > 0 || d->gap_open2 < -1000 || d->gap_extend2 > 0 || d->gap_extend2 < -1000) {
+            agx_set_error("scoring {match %d, mismatch %d, open %d, extend %d, open2 %d, extend2 %d} outside the supported range", d->match, d->mismatch,
+                          d->gap_open, d->gap_extend, d->gap_open2, d->gap_extend2);
+            return AGX_E_LIMIT;
+        }
     return AGX_OK;
 }
 

@@ -76,6 +76,12 @@ struct agx_sw_batch {
     PinBuf band_stop_stage;
     std::vector<int32_t> band_diag;
     std::vector<uint32_t> band_row0;
+    // agx_sw_batch_create_align_band_diag_dual: a band_at batch under two-piece gap costs.  scoring and prm hold
+    // the first piece exactly as the plain batch on the same pairs would (its plan is that batch's); dual_sc all six numbers,
+    // dual_gap what the fills take beside prm
+    bool dual = false;
+    agx_sw_scoring_dual dual_sc{};
+    SwDualGap dual_gap{};
     agx_sw_scoring scoring{};
     DevBuf ends;        // per pair: row << kSwLocColBits | column of the end cell, written by the locating fill
     PinBuf ends_stage;  // its page-locked landing block
@@ -146,6 +152,7 @@ struct BandAt {
     bool zdrop_on = false;
     int32_t zdrop = 0;
     int stats = 0;
+    const agx_sw_scoring_dual *dual = nullptr; // agx_sw_batch_create_align_band_diag_dual: all six numbers (scoring is then unused)
 };
 
 // ---- agx_sw.cpp
@@ -279,6 +286,8 @@ void write_trace_records(const PlanLayout &lay, const std::vector<PairPlan> &pla
 
 // ---- agx_sw_align.cpp
 agx_sw_hit empty_side_hit(int mode, int what, const agx_sw_scoring &sc, uint32_t la, uint32_t lb);
+// ... under two-piece gap costs: the lone gap costs the cheaper piece
+agx_sw_hit empty_side_hit_dual(int mode, int what, const agx_sw_scoring_dual &sc, uint32_t la, uint32_t lb);
 int create_align(const char *who, agx_ctx *ctx, const agx_sw_scoring *scoring, const agx_sw_matrix *matrix, int mode, int what,
                  const uint8_t *bases, const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_batch **out, bool stats = false,
                  bool cigar = false);

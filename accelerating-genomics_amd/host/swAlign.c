@@ -1,6 +1,6 @@
 /*
  * swAlign <file_path> [local|global|fit|extend|extend-query][+stats|+cigar|+band=W|+cigar+band=W|+band=W@D|+bandcigar=W@D|+bandstats=W@D][+zdrop=Z]
- * (and, with a matrix file, +matband=W@D|+matbandcigar=W@D): where the best alignment of every pair ends and begins
+ * (and, with a matrix file, +matband=W@D|+matbandcigar=W@D; with six scoring numbers, +dualband=W@D): where the best alignment of every pair ends and begins
  * (default: local; the other modes are include/agx.h's "Alignment modes").
  * swAlign <file_path> <mode> <matrix_file> [gap_open gap_extend]: the same under a substitution matrix (gaps default to
  * -11 -1).  The matrix file is the usual text layout: '#' comment lines, one line of symbols, then one row per symbol
@@ -50,6 +50,11 @@
  * mode; W and D as in "+band=W@D", both required; read with the line buffer of "+band=W", the line ends stripped as with every
  * matrix file.  Either word without a matrix file, or with +stats, +cigar or +zdrop, is a usage error; so is a matrix file behind
  * "+band=W@D" or "+bandcigar=W@D".
+ * swAlign <file_path> <mode>+dualband=W@D <match> <mismatch> <gap_open> <gap_extend> <gap_open2> <gap_extend2>: the lines of
+ * "+band=W@D" under two-piece gap costs -- a gap of L symbols scores max(gap_open + L gap_extend, gap_open2 + L gap_extend2), as in
+ * minimap2's -O4,24 -E2,1 (include/agx.h, "Banded alignment around a diagonal under two-piece gap costs").  Any mode; W and D as in
+ * "+band=W@D", both required; read with the line buffer of "+band=W".  All six numbers are required and must be integers: any
+ * other count of arguments, a number that is not one, or a further suffix (+stats, +cigar, +zdrop) is a usage error.
  *   AGX_CLI_CHUNK_PAIRS   pairs per agx_sw_align call (default 262144)
  */
 #include <stdio.h>
@@ -143,10 +148,36 @@ int main(int argc, char *argv[])
 {
     static const char *const words[] = {"local", "global", "fit", "extend", "extend-query"}; /* AGX_SW_MODE_* 0..4 */
     int mode = argc == 2 ? AGX_SW_MODE_LOCAL : -1;
-    int with_stats = 0, with_cigar = 0, with_band = 0, with_diag = 0, with_zdrop = 0, with_matband = 0;
+    int with_stats = 0, with_cigar = 0, with_band = 0, with_diag = 0, with_zdrop = 0, with_matband = 0, with_dual = 0;
     int32_t band = 0, diag = 0, zdrop = 0;
-    for (int k = 0; (argc == 3 || argc == 4 || argc == 6) && k < 5; k++) {
+    agx_sw_scoring_dual dual = {0, 0, 0, 0, 0, 0};
+    for (int k = 0; (argc == 3 || argc == 4 || argc == 6 || argc == 9) && k < 5; k++) {
         const size_t n = strlen(words[k]);
+        if (argc == 9) { /* six numbers behind the mode word: "+dualband=W@D" and nothing else */
+            if (strncmp(argv[2], words[k], n) || strncmp(argv[2] + n, "+dualband=", 10)) continue;
+            /* W@D as for "+band=W@D", up to the end of the word (no further suffix); any mode; every number a whole integer */
+            const char *w = argv[2] + n + 10;
+            char *end, *end2;
+            const long v = strtol(w, &end, 10);
+            if (!isdigit((unsigned char)*w) || *end != '@' || v > 0x7fffffffL) continue;
+            const char *d = end + 1;
+            const long c = strtol(d, &end2, 10);
+            if (!isdigit((unsigned char)d[*d == '-']) || *end2 || c < -0x7fffffffL || c > 0x7fffffffL) continue;
+            int32_t *const six[6] = {&dual.match, &dual.mismatch, &dual.gap_open, &dual.gap_extend, &dual.gap_open2, &dual.gap_extend2};
+            int good = 1;
+            for (int a = 0; a < 6; a++) {
+                char *e;
+                const long x = strtol(argv[3 + a], &e, 10);
+                if (e == argv[3 + a] || *e || x < -0x7fffffffL || x > 0x7fffffffL) good = 0;
+                *six[a] = (int32_t)x;
+            }
+            if (!good) continue;
+            mode = k;
+            with_band = with_diag = with_dual = 1;
+            band = (int32_t)v;
+            diag = (int32_t)c;
+            continue;
+        }
         if (!strcmp(argv[2], words[k])) mode = k;
         const int cigar_band = !strncmp(argv[2], words[k], n) && !strncmp(argv[2] + n, "+cigar+band=", 12); /* in this order only */
         if (!strncmp(argv[2], words[k], n) && (cigar_band || !strncmp(argv[2] + n, "+band=", 6))) {
@@ -251,12 +282,15 @@ int main(int argc, char *argv[])
                 "traceback; no matrix file, +cigar or +zdrop.\n"
                 "<mode>+matband=W@D <matrix_file> [gap_open gap_extend], <mode>+matbandcigar=W@D <matrix_file> [gap_open gap_extend]:\n"
                 "the lines of +band=W@D and of +bandcigar=W@D under the substitution matrix; a matrix file is required, and no\n"
-                "+stats, +cigar or +zdrop.\n",
-                argv[0], argv[0]);
+                "+stats, +cigar or +zdrop.\n"
+                "       %s <file_path> <mode>+dualband=W@D <match> <mismatch> <gap_open> <gap_extend> <gap_open2> <gap_extend2>\n"
+                "the lines of +band=W@D under two-piece gap costs: a gap of L scores max(gap_open + L gap_extend, gap_open2 + L gap_extend2);\n"
+                "all six integers are required, and no +stats, +cigar or +zdrop.\n",
+                argv[0], argv[0], argv[0]);
         return 1;
     }
     static agx_sw_matrix matrix;
-    const int with_matrix = argc >= 4;
+    const int with_matrix = argc >= 4 && !with_dual;
     if (with_matrix) {
         char err[512];
         if (read_matrix(argv[3], &matrix, err, sizeof err)) {
@@ -361,7 +395,9 @@ int main(int argc, char *argv[])
                 if (!dg) {
                     fprintf(stderr, "swAlign: out of memory\n");
                     status = EXIT_FAILURE;
-                } else if ((with_matband ? agx_sw_align_band_diag_matrix(ctx, &matrix, mode, AGX_SW_ALIGN_SPANS, band, dg, t->bases, t->off, t->len,
+                } else if ((with_dual ? agx_sw_align_band_diag_dual(ctx, &dual, mode, AGX_SW_ALIGN_SPANS, band, dg, t->bases, t->off, t->len, t->n_pairs,
+                                                                    hits)
+                            : with_matband ? agx_sw_align_band_diag_matrix(ctx, &matrix, mode, AGX_SW_ALIGN_SPANS, band, dg, t->bases, t->off, t->len,
                                                                          t->n_pairs, hits)
                             : with_zdrop ? agx_sw_align_band_zdrop(ctx, NULL, mode, AGX_SW_ALIGN_SPANS, band, dg, zdrop, t->bases, t->off, t->len,
                                                                    t->n_pairs, hits, NULL)

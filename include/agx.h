@@ -692,6 +692,43 @@ int agx_sw_align_band_diag_stats(agx_ctx *ctx, const agx_sw_scoring *scoring, in
                                  const uint8_t *bases, const uint64_t *off, const uint32_t *len, int64_t n_pairs,
                                  agx_sw_hit *hits /* may be NULL */, agx_sw_stat *stats);
 
+/*
+ * Banded alignment around a diagonal under two-piece gap costs: the gap model of long-read aligners (minimap2's -O4,24 -E2,1,
+ * the recurrence of its ksw2_extd2).  A gap of L >= 1 symbols scores
+ *     max(gap_open + L gap_extend, gap_open2 + L gap_extend2)
+ * -- one piece steep for short gaps, one shallow for long ones; no setting of one piece gives both.  As a recurrence over the
+ * in-band cells: E1 and F1 use piece 1, E2 and F2 piece 2, each exactly like E and F of "Banded alignment around a diagonal";
+ * H = max(diagonal move, E1, F1, E2, F2), and LOCAL adds the zero floor.
+ * Scoring: match, mismatch as agx_sw_scoring; each of the four gap numbers lies in -1000 .. 0 (AGX_E_LIMIT otherwise, as
+ * agx_sw_scoring).  No ordering between the pieces is required.  scoring == NULL is AGX_E_ARG: a second piece has no reference
+ * default.
+ * Everything else is "Banded alignment around a diagonal", verbatim: the band c - w <= j - i <= c + w, never widened; the table
+ * "what the band must hold"; the boundaries per mode, where the gap-initialised row 0 and column 0 carry the two-piece cost of
+ * their gap; the limits; the result and tie rules (they depend on scores only: which piece a gap was scored by never enters);
+ * the SPANS rules -- begins of LOCAL and FIT from a second banded fill of the reversed prefixes around the mirrored diagonal,
+ * under the same two pieces, whose score must equal the forward one, AGX_E_INTERNAL naming the pair otherwise --; byte 0x00
+ * refused (AGX_E_SYMBOL naming the pair); ctx == NULL: plan only.  The plan (lane tiling, waves, records, image) is that of the
+ * agx_sw_batch_create_align_band_diag batch on the same pairs, band and diag.
+ * Pairs with an empty side are answered without a fill by the mode's formulas with the two-piece cost: GLOBAL with la = 0 scores
+ * max(gap_open + lb gap_extend, gap_open2 + lb gap_extend2).
+ * The batch behaves like a batch banded around a diagonal for agx_sw_batch_launch, _scores, _hits and _info;
+ * agx_sw_batch_bind_scores is accepted and ignored; agx_sw_batch_stats, _cigars and _zdrop_stops return AGX_E_ARG.
+ * Equivalences: if piece 2 never beats piece 1 for any L >= 1 (identical pieces; gap_open2 <= gap_open and gap_extend2 <=
+ * gap_extend), the hits are exactly those of agx_sw_align_band_diag under {match, mismatch, gap_open, gap_extend}; the same
+ * with the pieces swapped.  A band that holds the whole matrix, under such pieces, therefore reports what agx_sw_align_mode does.
+ * Deliberately left out: CIGARs under two pieces (the trace needs more than four bits per cell), a z-drop, a substitution matrix
+ * and statistics under two pieces, and a two-piece agx_sw_batch_create_align_band with its GLOBAL widening.
+ */
+typedef struct agx_sw_scoring_dual {
+    int32_t match, mismatch, gap_open, gap_extend, gap_open2, gap_extend2;
+} agx_sw_scoring_dual;
+int agx_sw_batch_create_align_band_diag_dual(agx_ctx *ctx, const agx_sw_scoring_dual *scoring, int mode, int what, int32_t band,
+                                             const int32_t *diag /* n_pairs, or NULL = 0 for every pair */, const uint8_t *bases,
+                                             const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_batch **out);
+/* One-shot: create_align_band_diag_dual + launch + hits + destroy. */
+int agx_sw_align_band_diag_dual(agx_ctx *ctx, const agx_sw_scoring_dual *scoring, int mode, int what, int32_t band, const int32_t *diag,
+                                const uint8_t *bases, const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_hit *hits);
+
 /* Host only, no device.  How the traced fill of a span starts inside a banded batch's resident image.  The image holds the
  * query a behind `fpad` bytes and the rows b[row0 .. row0 + rows) behind one byte, packed for a fill from row0 in the band
  * dlo .. dhi COUNTED FROM row0 (j - (i - row0)) on `lanes` lanes per pair.  For a hit with a non-empty span on both sides the
