@@ -140,6 +140,15 @@ static int one_hit(const matrix_t *m, int mode, int what, int64_t w, int64_t c, 
         *out = h;
         return 0;
     }
+    if (mode == FIT && la == 0) {
+        /* a pair with an empty side is answered by the formulas of "Alignment modes", whatever the band: max_i D[i][0] = 0 at
+         * i = 0, also where the band leaves row 0 out (dhi < 0) and a fill would find its first in-band cell of column 0 further
+         * down.  (Every other mode's fill gives its formula: the band holds the cells the formula names.) */
+        h.a_end = h.b_end = -1;
+        if (what == SPANS) h.a_begin = h.b_begin = 0;
+        *out = h;
+        return 0;
+    }
     int rc = fill(m, mode, a, la, b, lb, dlo, dhi, 0, &sc, &i, &j);
     if (rc) return rc;
     h.score = (int32_t)sc;

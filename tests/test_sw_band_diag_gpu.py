@@ -441,3 +441,20 @@ def test_swalign_prints_what_the_api_returns(ctx, tmp_path, word, mode, w, c):
     # the mode's condition is the library's: a band that does not reach column 0 in FIT names the pair
     bad = subprocess.run([exe, str(long), "fit+band=8@100"], capture_output=True, timeout=60)
     assert bad.returncode != 0 and b"pair 0" in bad.stderr and not bad.stdout
+
+
+# ---- every byte
+
+
+def test_every_byte_but_zero_is_a_symbol(ctx):
+    """The twin of tests/test_sw_gpu.py::test_all_byte_values_are_symbols for batches banded around a diagonal: cases of the seeded sweep
+    (tests/sw_fuzz_cases.py, family "band_diag") drawn over 0x01 .. 0xff, one per mode -- 0x01, 0x7f / 0x80 and 0xff among them, bytes that
+    no other test of this file feeds in -- held to everything tests/test_fuzz_align_gpu.py holds a case to, exactly."""
+    from tests import sw_fuzz_cases as fc
+
+    cases = fc.byte_cases("band_diag")
+    assert {c.kw["mode"] for c in cases} == set(fc.MODES_OF.get("band_diag", fc.MODES))
+    for case in cases:
+        seen = set(case.batch.bases.tolist())
+        assert 0 not in seen and {0x01, 0x7f, 0x80, 0xff} <= seen
+        assert fc.check_case(ctx, case) >= 4

@@ -384,3 +384,20 @@ def test_device_creates_upload_the_pinned_plan_and_image():
     assert sorted(got) == sorted(bc.DEVICE_CASES), err[-2000:]
     for name in bc.DEVICE_CASES:
         assert got[name] == golden[name], name
+
+
+# ---- every byte
+
+
+def test_every_byte_but_zero_is_a_symbol(ctx):
+    """The twin of tests/test_sw_gpu.py::test_all_byte_values_are_symbols for banded batches: cases of the seeded sweep
+    (tests/sw_fuzz_cases.py, family "band") drawn over 0x01 .. 0xff, one per mode -- 0x01, 0x7f / 0x80 and 0xff among them, bytes that
+    no other test of this file feeds in -- held to everything tests/test_fuzz_align_gpu.py holds a case to, exactly."""
+    from tests import sw_fuzz_cases as fc
+
+    cases = fc.byte_cases("band")
+    assert {c.kw["mode"] for c in cases} == set(fc.MODES_OF.get("band", fc.MODES))
+    for case in cases:
+        seen = set(case.batch.bases.tolist())
+        assert 0 not in seen and {0x01, 0x7f, 0x80, 0xff} <= seen
+        assert fc.check_case(ctx, case) >= 4

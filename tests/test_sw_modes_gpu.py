@@ -250,3 +250,20 @@ def test_swalign_prints_what_the_api_returns(ctx, word, mode):
     _same(hits, ref.align(b, mode, ref.SPANS), word)
     bad = subprocess.run([exe, path, "sideways"], capture_output=True, timeout=60)
     assert bad.returncode != 0 and b"Usage" in bad.stderr and not bad.stdout
+
+
+# ---- every byte
+
+
+def test_every_byte_but_zero_is_a_symbol(ctx):
+    """The twin of tests/test_sw_gpu.py::test_all_byte_values_are_symbols for the alignment modes: cases of the seeded sweep
+    (tests/sw_fuzz_cases.py, family "align_mode") drawn over 0x01 .. 0xff, one per mode -- 0x01, 0x7f / 0x80 and 0xff among them, bytes that
+    no other test of this file feeds in -- held to everything tests/test_fuzz_align_gpu.py holds a case to, exactly."""
+    from tests import sw_fuzz_cases as fc
+
+    cases = fc.byte_cases("align_mode")
+    assert {c.kw["mode"] for c in cases} == set(fc.MODES_OF.get("align_mode", fc.MODES))
+    for case in cases:
+        seen = set(case.batch.bases.tolist())
+        assert 0 not in seen and {0x01, 0x7f, 0x80, 0xff} <= seen
+        assert fc.check_case(ctx, case) >= 4
