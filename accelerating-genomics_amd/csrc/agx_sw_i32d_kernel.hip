@@ -86,9 +86,10 @@ __device__ __forceinline__ int i32d_half(const SwParams &prm, const uint32_t *__
     const uint32_t kv = (uint32_t)(prm.delta & 0xff) << 24;
 
     // FAST: the step after which the group's last lane holds H[lx'][ly'] in its last column (bit 13 of the record: both
-    // sequences ended with the sentinel the pack kernel stripped)
-    const bool both_nl = FAST && active && gl == G - 1 && ((lx_ly >> 13) & 1u) && lx > 0 && ly > 0;
-    const int cap_t = both_nl ? ly + G - 2 : -1;
+    // sequences ended with the sentinel the pack kernel stripped); a stripped side that is empty leaves the corner at H = 0,
+    // its initial value at r(-1), and the two newlines still align: the pair scores one match (agx_sw_pk2_kernel.inc does the same)
+    const bool both_nl = FAST && active && gl == G - 1 && ((lx_ly >> 13) & 1u);
+    const int cap_t = (both_nl && lx > 0 && ly > 0) ? ly + G - 2 : -1;
     int corner = gf - age;
 
     uint32_t q0 = row_quad(0), q1 = row_quad(1), q2 = row_quad(2);
