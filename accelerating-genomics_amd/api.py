@@ -66,6 +66,8 @@ SYMBOLS = [
     "agx_sw_batch_create_align_band_zdrop_cigar", "agx_sw_align_band_zdrop_cigar",
     "agx_sw_batch_create_align_band_diag_stats", "agx_sw_align_band_diag_stats",
     "agx_sw_batch_create_align_band_diag_dual", "agx_sw_align_band_diag_dual",
+    "agx_sw_batch_create_align_band_diag_dual_cigar", "agx_sw_align_band_diag_dual_cigar", "agx_sw_band_dual_cigar_bytes_bound",
+    "agx_sw_cigar_rescore_dual",
     "agx_sw_score", "agx_sw_score_multi", "agx_sw_score_devices", "agx_sw_shard_cuts",
     "agx_phmm_batch_create", "agx_phmm_batch_launch", "agx_phmm_batch_results", "agx_phmm_batch_bind_results", "agx_phmm_batch_info",
     "agx_phmm_batch_destroy", "agx_phmm_forward", "agx_phmm_forward_multi", "agx_phmm_forward_devices", "agx_phmm_shard_cuts",
@@ -267,6 +269,14 @@ def lib():
                                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
         l.agx_sw_align_band_diag_dual.argtypes = [C.c_void_p, C.POINTER(SwScoringDual), C.c_int, C.c_int, C.c_int32, C.c_void_p, C.c_void_p,
                                                   C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        l.agx_sw_batch_create_align_band_diag_dual_cigar.argtypes = [C.c_void_p, C.POINTER(SwScoringDual), C.c_int, C.c_int32, C.c_void_p,
+                                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        l.agx_sw_align_band_diag_dual_cigar.argtypes = [C.c_void_p, C.POINTER(SwScoringDual), C.c_int, C.c_int32, C.c_void_p, C.c_void_p,
+                                                        C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
+        l.agx_sw_band_dual_cigar_bytes_bound.argtypes = [C.c_int32, C.c_uint32, C.c_uint32]
+        l.agx_sw_band_dual_cigar_bytes_bound.restype = C.c_uint64
+        l.agx_sw_cigar_rescore_dual.argtypes = [C.POINTER(SwScoringDual), C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
+                                                C.c_int32]
         l.agx_sw_band_span_record.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                                               C.POINTER(SwBandSpan)]
         l.agx_sw_score.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
@@ -383,8 +393,21 @@ class Context:
 
     # ---- Smith-Waterman
     def sw_batch(self, b, scoring=None, matrix=None, align=0, mode=SW_MODE_LOCAL, stats=False, cigar=False, band=None, diag=None,
-                 zdrop=None, band_stats=False, dual=None) -> "SwBatch":
-        return SwBatch(self, b, scoring, matrix, align, mode, stats, cigar, band, diag, zdrop, band_stats, dual)
+                 zdrop=None, band_stats=False, dual=None, dual_cigar=None) -> "SwBatch":
+        return SwBatch(self, b, scoring, matrix, align, mode, stats, cigar, band, diag, zdrop, band_stats, dual, dual_cigar)
+
+    def sw_align_band_diag_dual_cigar(self, b, mode, band, diag=None, scoring6=None):
+        """b: synth.SWBatch -> (SwHit records as sw_align_band_diag_dual(what=SW_ALIGN_SPANS) gives them, op_off uint64[n + 1], ops
+        uint32), one-shot: the CIGAR of every pair inside its band around diag under two-piece gap costs (include/agx.h, "CIGARs for
+        batches banded around a diagonal under two-piece gap costs").  scoring6: all six numbers, required."""
+        hits, op_off = np.empty(b.n_pairs, SwHit), np.zeros(b.n_pairs + 1, np.uint64)
+        cap = int(b.len.sum())  # an alignment has at most one operation per symbol
+        ops = np.empty(max(cap, 1), np.uint32)
+        sc = C.byref(SwScoringDual(*scoring6)) if scoring6 is not None else None
+        d = _diag(diag, b.n_pairs)
+        _check(lib().agx_sw_align_band_diag_dual_cigar(self._h, sc, mode, band, _ptr(d), _ptr(b.bases), _ptr(b.off), _ptr(b.len), b.n_pairs,
+                                                       _ptr(hits), _ptr(op_off), _ptr(ops), cap))
+        return hits, op_off, ops[:int(op_off[b.n_pairs])].copy()
 
     def sw_align_band_diag_dual(self, b, mode, band, diag=None, what=SW_ALIGN_SPANS, scoring6=None):
         """b: synth.SWBatch -> SwHit records of the alignment inside the band around diag under two-piece gap costs, one-shot
@@ -531,7 +554,7 @@ class SwBatch:
     """agx_sw_batch: a scheduled batch resident in HBM (ctx=None: planned on the host only)."""
 
     def __init__(self, ctx, b, scoring=None, matrix=None, align=0, mode=SW_MODE_LOCAL, stats=False, cigar=False, band=None, diag=None,
-                 zdrop=None, band_stats=False, dual=None):
+                 zdrop=None, band_stats=False, dual=None, dual_cigar=None):
         """scoring: None (the reference's +1/-1/-3/-1) or (match, mismatch, gap_open, gap_extend);
         matrix: an SwMatrix instead (score-only and align batches alike); align: SW_ALIGN_ENDS / SW_ALIGN_SPANS for a batch that also answers hits();
         mode: SW_MODE_* of an align batch (local, global, fit, extension); stats=True: a SPANS batch that also answers stats();
@@ -546,10 +569,22 @@ class SwBatch:
         zdrop; stats=True stays the unbanded stats batch and does not combine with band=);
         band=w with dual=(match, mismatch, gap_open, gap_extend, gap_open2, gap_extend2) (diag optional): a batch banded around a diagonal
         under two-piece gap costs, any mode, align = SW_ALIGN_ENDS or SW_ALIGN_SPANS (0: SPANS); it answers hits() and scores() (no
-        scoring, matrix, stats, cigar, zdrop or band_stats)."""
+        scoring, matrix, stats, cigar, zdrop or band_stats);
+        band=w with dual_cigar=(the same six numbers) (diag optional): the SPANS batch under two-piece gap costs that also answers
+        cigars() (no dual=, scoring, matrix, stats, cigar, zdrop or band_stats; align 0 or SW_ALIGN_SPANS)."""
         self.ctx = ctx
         self.n_pairs = b.n_pairs
         self._h = C.c_void_p()
+        if dual_cigar is not None:
+            if (band is None or dual is not None or scoring is not None or matrix is not None or stats or cigar or zdrop is not None or band_stats
+                    or align not in (0, SW_ALIGN_SPANS)):
+                raise AgxError(E_ARG, "dual_cigar= takes band=w (and diag=) on a SW_ALIGN_SPANS batch: no dual=, scoring, matrix, stats, cigar, "
+                                      "zdrop or band_stats")
+            d = _diag(diag, b.n_pairs)
+            _check(lib().agx_sw_batch_create_align_band_diag_dual_cigar(ctx._h if ctx else None, C.byref(SwScoringDual(*dual_cigar)), mode, band,
+                                                                        _ptr(d), _ptr(b.bases), _ptr(b.off), _ptr(b.len), b.n_pairs,
+                                                                        C.byref(self._h)))
+            return
         if dual is not None:
             if band is None or scoring is not None or matrix is not None or stats or cigar or zdrop is not None or band_stats:
                 raise AgxError(E_ARG, "dual= takes band=w (and diag=): no scoring, matrix, stats, cigar, zdrop or band_stats")

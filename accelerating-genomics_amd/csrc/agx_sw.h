@@ -297,6 +297,21 @@ int agx_sw_band_trace_at_launch_class(int diags_per_lane, const SwParams &prm, c
 int agx_sw_band_walk_at_launch(const SwWalkRec *recs, const SwBandWalkRec *band, uint32_t n, const uint32_t *img, const uint32_t *trace,
                                uint32_t *slots, uint32_t *runs, hipStream_t s);
 void agx_sw_band_trace_at_preload();
+// the traced build and the walk UNDER TWO-PIECE gap costs (agx_sw_band_dual_trace_kernel.hip): the span records,
+// the start phase, scores and goff of agx_sw_band_trace_at_launch_class; every cell leaves EIGHT bits -- bits 0-1 where H came
+// from, bit 2 "of piece 2", bits 4-7 E1, F1, E2, F2 extended -- at trace + goff[group] + (step * G + lane) *
+// sw_band_dual_trace_words(K) dwords, byte k of the lane's K diagonals (K = 32: two stores of 16 bytes)
+constexpr int sw_band_dual_trace_words(int K) { return K / 4; }
+inline uint64_t sw_band_dual_trace_dwords(int G, uint32_t lb, int K)
+{
+    return (((uint64_t)lb + (uint64_t)G) * (uint64_t)G * (uint64_t)sw_band_dual_trace_words(K) + 3u) & ~(uint64_t)3u;
+}
+int agx_sw_band_trace_dual_launch_class(int diags_per_lane, const SwParams &prm, const SwDualGap &dg, const uint32_t *img, const SwBandGroup *groups,
+                                        const SwWave *waves, uint32_t n_waves, int32_t *scores, uint32_t *trace, const uint64_t *goff,
+                                        hipStream_t s);
+int agx_sw_band_walk_dual_launch(const SwWalkRec *recs, const SwBandWalkRec *band, uint32_t n, const uint32_t *img, const uint32_t *trace,
+                                 uint32_t *slots, uint32_t *runs, hipStream_t s);
+void agx_sw_band_trace_dual_preload();
 // the builds of the banded body under a substitution matrix (agx_sw_band_diag_mat_kernel.hip, agx_sw_band_diag_trace_mat_kernel.hip;
 // DESIGN.md 4.1l): a band around a caller-given diagonal in all five modes, and the traced build with the start phase.  The image
 // holds symbol numbers 1 .. 32 (0 = padding) where the other banded builds hold bytes; table is the device copy of the

@@ -185,6 +185,7 @@ void keep_band_host_state(agx_sw_batch *b, const BandKind &kind, const BandPairs
     if (!kind.cigar) return;
     agx_sw_band_trace_preload();
     if (at) agx_sw_band_trace_at_preload();
+    if (at && at->dual) agx_sw_band_trace_dual_preload();
     if (kind.matrix) agx_sw_band_trace_mat_preload();
     agx_sw_walk_preload();
     const std::vector<BandPlan> &plan = pairs.plan;
@@ -261,7 +262,7 @@ int create_band(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t b
                 const uint32_t *len, int64_t n_pairs, agx_sw_batch **out, bool cigar, const BandAt *at, const agx_sw_matrix *matrix)
 {
     const bool zd = at && at->zdrop_on;
-    const char *who = at && at->dual  ? "agx_sw_batch_create_align_band_diag_dual"
+    const char *who = at && at->dual  ? (cigar ? "agx_sw_batch_create_align_band_diag_dual_cigar" : "agx_sw_batch_create_align_band_diag_dual")
                       : at && at->stats ? "agx_sw_batch_create_align_band_diag_stats"
                       : matrix      ? (cigar ? "agx_sw_batch_create_align_band_diag_matrix_cigar" : "agx_sw_batch_create_align_band_diag_matrix")
                       : zd   ? (cigar ? "agx_sw_batch_create_align_band_zdrop_cigar" : "agx_sw_batch_create_align_band_zdrop")

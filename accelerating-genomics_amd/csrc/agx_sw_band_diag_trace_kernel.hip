@@ -63,6 +63,7 @@ __global__ void __launch_bounds__(64) sw_walk_band_at(const SwWalkRec *__restric
                                                       uint32_t *__restrict__ slots, uint32_t *__restrict__ runs)
 {
     constexpr bool AT = true;
+    constexpr bool DUAL = false;
 #include "agx_sw_band_walk.inc"
 }
 

@@ -3,7 +3,8 @@
 // agx_sw_band_kernel.inc built with DUAL, whose head says how the fill works.  Five builds per K = diagonals per lane
 // (AGX_SW_FOR_EACH_BAND_CLASS): the pinned fills sw_fill_band_dual<K, false> (GLOBAL: the corner) and <K, true> (EXTEND), and the
 // fills around a diagonal sw_fill_band_dual_at<K, LOCAL>, <K, FIT> and <K, EXTEND_QUERY>.  GLOBAL and EXTEND have builds of their
-// own here, unlike under a matrix: the cell itself changes.  There is no TRACE, PH, ZD, MAT or STATS build.
+// own here, unlike under a matrix: the cell itself changes.  The traced build (TRACE and PH with DUAL) is
+// agx_sw_band_dual_trace_kernel.hip; there is no ZD, MAT or STATS build.
 //
 // The cell.  Over the in-band cells
 //     E1(i, j) = max(H(i - 1, j) + gf,  E1(i - 1, j) + ge)      gf  = gap_open  + gap_extend,  ge  = gap_extend

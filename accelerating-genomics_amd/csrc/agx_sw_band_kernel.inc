@@ -136,6 +136,10 @@
 // again.  A second pair of gap states, e2 per diagonal and f2 along the chain, runs beside e and f under the second piece's
 // extension cost ge2; both read the one stored z = H + gf of the first piece plus dgf = gf2 - gf, and H takes the maximum over
 // all five.  Every hand-over between lanes carries the second piece as well.  That file's head has the argument.
+// With TRACE and PH as well (agx_sw_band_dual_trace_kernel.hip; include/agx.h, "CIGARs for batches banded around a diagonal under
+// two-piece gap costs"; DESIGN.md 4.1o) a cell leaves a BYTE -- where H came from among five states, one strict "extended" bit
+// per gap state -- in sw_band_dual_trace_words(K) = K / 4 dwords a lane and step; that file's head restates "No wrap", the
+// masked cells and "no bit steers the walk" for five sources.
 //
 // (included by agx_sw_band_kernel.hip; opens an anonymous namespace that the including file closes after its launch helper)
 #include "agx_sw.h"
@@ -216,7 +220,8 @@ __device__ __forceinline__ void band_body(const SwParams &prm, const uint32_t *_
     static_assert(!MAT || !ZD, "no z-drop under a matrix");
     static_assert(!STATS || (!TRACE && !PH && !ZD && !MAT && AT != AGX_SW_MODE_FIT),
                   "statistics ride on the plain GLOBAL and EXTEND builds and on the LOCAL and EXTEND_QUERY builds around a diagonal");
-    static_assert(!DUAL || (!TRACE && !PH && !ZD && !MAT && !STATS), "two-piece gap costs: scores, ends and spans only");
+    static_assert(!DUAL || (TRACE == PH && !ZD && !MAT && !STATS),
+                  "two-piece gap costs: the untraced builds, and the traced build with the start phase (its batches are banded around a diagonal)");
     using V = typename BandState<STATS>::type;
     constexpr V kNeg = STATS ? (V)((unsigned long long)(uint32_t)kBandNegInf << 32) : (V)kBandNegInf; // STATS: (minus infinity, 0)
     constexpr bool AT_LOCAL = AT == AGX_SW_MODE_LOCAL, AT_FIT = AT == AGX_SW_MODE_FIT, AT_COL = AT_FIT || AT == AGX_SW_MODE_EXTEND_QUERY;
@@ -296,7 +301,7 @@ __device__ __forceinline__ void band_body(const SwParams &prm, const uint32_t *_
     [[maybe_unused]] int car_m = kBandNegInf, car_c = 0, zb = gf, zbi = 0, zbj = 0, zstop = -1;
 
     // TRACE: this lane's nibbles of step t go to tp + t G TW
-    constexpr int TW = sw_band_trace_words(K);
+    constexpr int TW = DUAL ? sw_band_dual_trace_words(K) : sw_band_trace_words(K);
     uint32_t *tp = nullptr;
     if constexpr (TRACE) {
         if (active) tp = trace + goff[w.first_group + grp] + (uint32_t)(gl * TW);
@@ -384,6 +389,14 @@ __device__ __forceinline__ void band_body(const SwParams &prm, const uint32_t *_
             const uint32_t src = s >= max(ev, f) ? 0u : ev >= f ? 1u : 2u;
             return src | (e_ext ? 4u : 0u) | (f_ext ? 8u : 0u);
         };
+        // TRACE with DUAL, per cell one byte: bits 0-1 where H came from as above (the RAW diagonal move first, then the better of
+        // the two E, then of the two F), bit 2 "of piece 2" (piece 1 wins a tie within a direction), bits 4-7 E1, F1, E2, F2 extended,
+        // each strictly under its own piece: ue2 + ge2 > uz + dgf is ev2 > uz + dgf, and its F twin.
+        [[maybe_unused]] auto dirs2 = [](int s, int ev, int f, int ev2, int f2, bool e_ext, bool f_ext, bool e2_ext, bool f2_ext) -> uint32_t {
+            const int em = max(ev, ev2), fm = max(f, f2);
+            const uint32_t src = s >= max(em, fm) ? 0u : em >= fm ? (ev >= ev2 ? 1u : 5u) : (f >= f2 ? 2u : 6u);
+            return src | (e_ext ? 16u : 0u) | (f_ext ? 32u : 0u) | (e2_ext ? 64u : 0u) | (f2_ext ? 128u : 0u);
+        };
 
         // phase 1: the first cell
         V f, zleft;
@@ -403,10 +416,19 @@ __device__ __forceinline__ void band_body(const SwParams &prm, const uint32_t *_
                 if constexpr (STATS) s = band_pair_move(z[0], xs, yc, s_match, s_mis, pair1);
                 else s = z[0] + (xs == yc ? s_match : s_mis);
             }
-            if constexpr (DUAL) s = band_max(s, band_max(ev2, f2)); // H over all five: the diagonal move and both pieces' E and F
+            if constexpr (DUAL) {
+                if constexpr (TRACE) { // the byte is made here: it asks the RAW diagonal move, before s takes in E2 and F2
+                    tw[0] = dirs2(s, ev, f, ev2, f2, ev > z[1], f > zl, ev2 > band_gap(z[1], dgf), f2 > band_gap(zl, dgf));
+#pragma unroll
+                    for (int n = 1; n < TW; ++n) tw[n] = 0;
+                }
+                s = band_max(s, band_max(ev2, f2)); // H over all five: the diagonal move and both pieces' E and F
+            }
             if constexpr (AT_LOCAL) zleft = keep(band_gap(band_max(band_max(band_max(ev, f), s), (V)0), gf), 0); // the zero floor: z >= gf
             else zleft = keep(band_gap(band_max(band_max(ev, f), s), gf), 0);
-            if constexpr (TRACE) {
+            if constexpr (TRACE && DUAL) {
+                asm volatile("" : "+v"(tw[0]), "+v"(zleft));
+            } else if constexpr (TRACE) {
                 tw[0] = dirs(s, ev, f, ev > z[1], f > zl);
 #pragma unroll
                 for (int n = 1; n < TW; ++n) tw[n] = 0;
@@ -444,10 +466,16 @@ __device__ __forceinline__ void band_body(const SwParams &prm, const uint32_t *_
                 if constexpr (STATS) s = band_pair_move(z[k], xs, yc, s_match, s_mis, pair1);
                 else s = z[k] + (xs == yc ? s_match : s_mis);
             }
-            if constexpr (DUAL) s = band_max(s, band_max(ev2, f2));
+            if constexpr (DUAL) {
+                if constexpr (TRACE)
+                    tw[k >> 2] |= dirs2(s, ev, f, ev2, f2, ev > uz, f > z[k - 1], ev2 > band_gap(uz, dgf), f2 > band_gap(z[k - 1], dgf)) << (8 * (k & 3));
+                s = band_max(s, band_max(ev2, f2));
+            }
             if constexpr (AT_LOCAL) zleft = keep(band_gap(band_max(band_max(band_max(ev, f), s), (V)0), gf), k);
             else zleft = keep(band_gap(band_max(band_max(ev, f), s), gf), k);
-            if constexpr (TRACE) {
+            if constexpr (TRACE && DUAL) {
+                asm volatile("" : "+v"(tw[k >> 2]), "+v"(zleft));
+            } else if constexpr (TRACE) {
                 tw[k >> 3] |= dirs(s, ev, f, ev > uz, f > z[k - 1]) << (4 * (k & 7));
                 asm volatile("" : "+v"(tw[k >> 3]), "+v"(zleft));
             }
@@ -458,7 +486,10 @@ __device__ __forceinline__ void band_body(const SwParams &prm, const uint32_t *_
 
         if constexpr (TRACE) { // rows 0 .. lb of this group only: the wave may step on for a longer neighbour
             if (active && (uint32_t)i <= (uint32_t)lb) {
-                if constexpr (TW == 4) *reinterpret_cast<uint4 *>(tp) = make_uint4(tw[0], tw[1], tw[2], tw[3]);
+                if constexpr (TW == 8) {
+                    reinterpret_cast<uint4 *>(tp)[0] = make_uint4(tw[0], tw[1], tw[2], tw[3]);
+                    reinterpret_cast<uint4 *>(tp)[1] = make_uint4(tw[4], tw[5], tw[6], tw[7]);
+                } else if constexpr (TW == 4) *reinterpret_cast<uint4 *>(tp) = make_uint4(tw[0], tw[1], tw[2], tw[3]);
                 else if constexpr (TW == 2) *reinterpret_cast<uint2 *>(tp) = make_uint2(tw[0], tw[1]);
                 else tp[0] = tw[0];
             }

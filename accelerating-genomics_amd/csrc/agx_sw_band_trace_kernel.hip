@@ -25,6 +25,7 @@ __global__ void __launch_bounds__(64) sw_walk_band(const SwWalkRec *__restrict__
                                                    uint32_t *__restrict__ slots, uint32_t *__restrict__ runs)
 {
     constexpr bool AT = false;
+    constexpr bool DUAL = false;
 #include "agx_sw_band_walk.inc"
 }
 

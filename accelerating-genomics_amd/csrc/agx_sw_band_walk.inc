@@ -5,18 +5,21 @@
 // first query symbol.  State machine, guards and stores are the same in both builds.
 // A fragment, included INSIDE the body of a kernel with the parameters (recs, band, n, img, trace, slots, runs) behind a
 // `constexpr bool AT`: as an inlined function template the compiler schedules sw_walk_band differently from the code it had.
+// A second `constexpr bool DUAL` (agx_sw_band_dual_trace_kernel.hip; DESIGN.md 4.1o) reads the traced two-piece fill's BYTES: five
+// states, H and a gap state per piece and direction, the same guards in front of the one load, the same stores.  Everything it
+// adds stands inside `if constexpr`.
     const uint32_t p = blockIdx.x * 64u + threadIdx.x;
     if (p >= n) return;
     const SwWalkRec r = recs[p];
     const SwBandWalkRec bw = band[p];
-    const uint32_t G = r.G, ks = bw.kshift, W = (uint32_t)sw_band_trace_words((int)r.C);
+    const uint32_t G = r.G, ks = bw.kshift, W = DUAL ? (uint32_t)sw_band_dual_trace_words((int)r.C) : (uint32_t)sw_band_trace_words((int)r.C);
     const uint32_t *tr = trace + r.goff;
     const uint8_t *x = reinterpret_cast<const uint8_t *>(img + r.x_dw) + bw.fpad;  // x[j - 1]
     const uint8_t *y = reinterpret_cast<const uint8_t *>(img + r.y_dw) + 1;        // y[i - 1]
     if constexpr (AT) y += r.reserved;
     uint32_t *out = slots + r.slot + ((uint64_t)r.ca + r.cb); // one past the slot's last word
     uint32_t i = r.cb, j = r.ca, n_runs = 0, op = 0, len = 0;
-    int state = 0; // 0 H, 1 E, 2 F
+    int state = 0; // 0 H, 1 E, 2 F (DUAL: 1 E1, 2 F1, 3 E2, 4 F2)
     bool failed = false;
     auto emit = [&](uint32_t o, uint32_t k) {
         if (o == op) len += k;
@@ -49,6 +52,30 @@
         if (lane >= G) { // (G K >= dhi - dlo + 1 by the plan; a record that says otherwise must not steer a load)
             failed = true;
             break;
+        }
+        if constexpr (DUAL) {
+            const uint32_t cell = tr[((uint64_t)(i + lane) * G + lane) * W + (k >> 2)] >> (8u * (k & 3u)) & 255u;
+            if (state == 0) {
+                const uint32_t src = cell & 3u;
+                if (src == 0u) {
+                    emit(x[j - 1u] == y[i - 1u] ? 7u : 8u, 1u);
+                    --i;
+                    --j;
+                } else if (src == 3u) { // (no fill writes it)
+                    failed = true;
+                    break;
+                } else
+                    state = (int)src + (cell & 4u ? 2 : 0);
+            } else if (state & 1) { // E1 or E2: its own piece's bit
+                emit(2u, 1u);
+                state = cell & (state == 1 ? 16u : 64u) ? state : 0;
+                --i;
+            } else {
+                emit(1u, 1u);
+                state = cell & (state == 2 ? 32u : 128u) ? state : 0;
+                --j;
+            }
+            continue;
         }
         const uint32_t nib = tr[((uint64_t)(i + lane) * G + lane) * W + (k >> 3)] >> (4u * (k & 7u)) & 15u;
         if (state == 0) {

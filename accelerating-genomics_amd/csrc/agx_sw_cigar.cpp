@@ -1,4 +1,4 @@
-// CIGARs of the Smith-Waterman path (include/agx.h, "Alignment itself", "CIGARs for banded batches"; DESIGN.md 4.1f, 4.1h, 4.1j):
+// CIGARs of the Smith-Waterman path (include/agx.h, "Alignment itself", "CIGARs for banded batches"; DESIGN.md 4.1f, 4.1h, 4.1j, 4.1o):
 // the bounds and the host's checks, one driver (cigars_impl) for every kind of cigar batch with a tracer per kind, and the entry
 // points.  (The chunks of a banded cigar batch are laid out in waves by the banded planner's builder, layout_band_waves.)
 #include "agx_sw_batch.h"
@@ -22,9 +22,15 @@ uint64_t trace_bytes_bound(uint32_t ca, uint32_t cb)
 
 // The host's check of one CIGAR (include/agx.h, "Alignment itself"): runs well-formed and merged, exactly x and y consumed,
 // every '=' / 'X' true of the symbols, and the operations rescored give `score`.  code: the matrix's byte map, or NULL.
+// dual: the six numbers of a batch under two-piece gap costs, or NULL -- every run of I or D then costs the LITERAL
+// max(gap_open + L gap_extend, gap_open2 + L gap_extend2) of its whole length, whatever pieces the walk joined into it.
 bool cigar_checks(const uint32_t *ops, uint64_t n_ops, const uint8_t *x, int64_t ca, const uint8_t *y, int64_t cb, const agx_sw_scoring &s,
-                  const agx_sw_matrix *m, int64_t score)
+                  const agx_sw_matrix *m, int64_t score, const agx_sw_scoring_dual *dual = nullptr)
 {
+    const auto gap = [&](int64_t len) -> int64_t {
+        const int64_t one = s.gap_open + len * s.gap_extend;
+        return dual ? std::max<int64_t>(one, dual->gap_open2 + len * dual->gap_extend2) : one;
+    };
     int64_t i = 0, j = 0, total = 0;
     uint32_t prev = 0;
     for (uint64_t k = 0; k < n_ops; ++k) {
@@ -41,10 +47,10 @@ bool cigar_checks(const uint32_t *ops, uint64_t n_ops, const uint8_t *x, int64_t
             }
         } else if (op == AGX_CIGAR_INS) {
             j += len;
-            total += s.gap_open + len * s.gap_extend;
+            total += gap(len);
         } else if (op == AGX_CIGAR_DEL) {
             i += len;
-            total += s.gap_open + len * s.gap_extend;
+            total += gap(len);
         } else
             return false;
     }
@@ -61,6 +67,17 @@ uint64_t band_trace_bytes_bound(uint32_t width, uint32_t ca, uint32_t cb)
     for (int c = 0; c < kSwNumBandClasses; ++c) {
         const uint32_t K = (uint32_t)kSwBandClasses[c], G = (width + K - 1u) / K;
         if (G >= 1u && G <= 64u) worst = std::max(worst, sw_band_trace_dwords((int)G, cb, (int)K));
+    }
+    return 4u * (worst + (uint64_t)ca + cb);
+}
+
+// The same for a cigar batch under two-piece gap costs: eight bits a cell, sw_band_dual_trace_dwords.
+uint64_t band_dual_trace_bytes_bound(uint32_t width, uint32_t ca, uint32_t cb)
+{
+    uint64_t worst = 0;
+    for (int c = 0; c < kSwNumBandClasses; ++c) {
+        const uint32_t K = (uint32_t)kSwBandClasses[c], G = (width + K - 1u) / K;
+        if (G >= 1u && G <= 64u) worst = std::max(worst, sw_band_dual_trace_dwords((int)G, cb, (int)K));
     }
     return 4u * (worst + (uint64_t)ca + cb);
 }
@@ -289,7 +306,7 @@ int band_admit(const agx_sw_batch *b, int64_t p, int64_t ca, int64_t cb, uint64_
     band_limits_of(b, p, dlo, dhi);
     cells = band_cells(ca, cb, dlo, dhi);
     const SwBandGroup &g = b->band_groups[b->band_rec[(size_t)p]];
-    bytes = band_trace_bytes_bound((uint32_t)(g.dhi - g.dlo + 1), (uint32_t)ca, (uint32_t)cb);
+    bytes = (b->dual ? band_dual_trace_bytes_bound : band_trace_bytes_bound)((uint32_t)(g.dhi - g.dlo + 1), (uint32_t)ca, (uint32_t)cb);
     return AGX_OK;
 }
 
@@ -372,7 +389,7 @@ int band_trace(agx_sw_batch *b, const int64_t *pairs, int64_t m, CigarChunk &c, 
             int ks = 0;
             while ((1 << ks) < K) ++ks;
             bwalk[e.k] = SwBandWalkRec{g.dlo, g.dhi, g.fpad, (uint32_t)ks};
-            tr_dwords += sw_band_trace_dwords(G, (uint32_t)cb, K);
+            tr_dwords += (b->dual ? sw_band_dual_trace_dwords : sw_band_trace_dwords)(G, (uint32_t)cb, K);
         }
     }
     for (int64_t k = 0; k < m; ++k) {
@@ -399,8 +416,13 @@ int band_trace(agx_sw_batch *b, const int64_t *pairs, int64_t m, CigarChunk &c, 
     AGX_HIP(hipMemcpyAsync(c.bwalk.p, bwalk.data(), (size_t)m * sizeof(SwBandWalkRec), hipMemcpyHostToDevice, st));
     if (ev) AGX_HIP(hipEventRecord(ev[0], st));
     for (auto it = launches.rbegin(); it != launches.rend(); ++it) { // widest class first, one after the other on the stream
-        // (a batch under a matrix is banded around a diagonal: its spans run the traced build with the start phase and the table)
-        const int bad = b->matrix ? agx_sw_band_trace_mat_launch_class(it->C, b->prm, (const uint32_t *)b->img.p, (const SwBandGroup *)c.groups.p,
+        // (a batch under a matrix is banded around a diagonal: its spans run the traced build with the start phase and the table;
+        // so is a batch under two pieces: the traced build with the start phase and the five-state cell)
+        const int bad = b->dual   ? agx_sw_band_trace_dual_launch_class(it->C, b->prm, b->dual_gap, (const uint32_t *)b->img.p,
+                                                                        (const SwBandGroup *)c.groups.p, (const SwWave *)c.waves.p + it->first_wave,
+                                                                        it->n_waves, (int32_t *)c.scores.p, (uint32_t *)c.trace.p,
+                                                                        (const uint64_t *)c.goff.p, st)
+                        : b->matrix ? agx_sw_band_trace_mat_launch_class(it->C, b->prm, (const uint32_t *)b->img.p, (const SwBandGroup *)c.groups.p,
                                                                        (const SwWave *)c.waves.p + it->first_wave, it->n_waves, (int32_t *)c.scores.p,
                                                                        (uint32_t *)c.trace.p, (const uint64_t *)c.goff.p, (const int16_t *)b->table.p, st)
                                   : (at ? agx_sw_band_trace_at_launch_class : agx_sw_band_trace_launch_class)(
@@ -408,12 +430,13 @@ int band_trace(agx_sw_batch *b, const int64_t *pairs, int64_t m, CigarChunk &c, 
                                         (const SwWave *)c.waves.p + it->first_wave, it->n_waves, (int32_t *)c.scores.p, (uint32_t *)c.trace.p,
                                         (const uint64_t *)c.goff.p, st);
         if (bad) {
-            agx_set_error("sw_fill_band_trace%s<%d> launch failed: %s", b->matrix ? "_mat" : at ? "_at" : "", it->C, hipGetErrorString(hipGetLastError()));
+            agx_set_error("sw_fill_band_trace%s<%d> launch failed: %s", b->dual ? "_dual" : b->matrix ? "_mat" : at ? "_at" : "", it->C,
+                          hipGetErrorString(hipGetLastError()));
             return AGX_E_HIP;
         }
     }
     if (ev) AGX_HIP(hipEventRecord(ev[1], st));
-    if ((at ? agx_sw_band_walk_at_launch : agx_sw_band_walk_launch)(c.walkrec, (const SwBandWalkRec *)c.bwalk.p, (uint32_t)m, (const uint32_t *)b->img.p,
+    if ((b->dual ? agx_sw_band_walk_dual_launch : at ? agx_sw_band_walk_at_launch : agx_sw_band_walk_launch)(c.walkrec, (const SwBandWalkRec *)c.bwalk.p, (uint32_t)m, (const uint32_t *)b->img.p,
                                                                     (const uint32_t *)c.trace.p, (uint32_t *)c.slots.p, (uint32_t *)c.runs.p, st)) {
         agx_set_error("agx_sw_batch_cigars: walk kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
         return AGX_E_HIP;
@@ -455,6 +478,7 @@ int cigars_impl(agx_sw_batch *b)
     const agx_sw_hit *hits = b->cig_hits.data();
     const agx_sw_matrix *mat = b->matrix ? &b->mat : nullptr;
     const agx_sw_scoring s = b->scoring; // (under a matrix: its gap_open and gap_extend, which is all that is read of it)
+    const agx_sw_scoring_dual *dual = b->dual ? &b->dual_sc : nullptr; // (under two pieces s is the first)
     char band_note[32] = "";
     if (t.band_note) snprintf(band_note, sizeof band_note, t.band_note, b->band);
     // ---- pairs answered without a fill, and the list of the others
@@ -568,7 +592,7 @@ int cigars_impl(agx_sw_batch *b)
             else if (c) out[0] = lone[(size_t)p];
             const uint8_t *x = ca ? b->seq.data() + b->seq_off[(size_t)(2 * p)] + hits[p].a_begin : nullptr;
             const uint8_t *y = cb ? b->seq.data() + b->seq_off[(size_t)(2 * p + 1)] + hits[p].b_begin : nullptr;
-            if ((!cigar_checks(out, c, x, ca, y, cb, s, mat, hits[p].score) || (t.check && !t.check(b, p, out, c))) && bad[(size_t)tid] < 0)
+            if ((!cigar_checks(out, c, x, ca, y, cb, s, mat, hits[p].score, dual) || (t.check && !t.check(b, p, out, c))) && bad[(size_t)tid] < 0)
                 bad[(size_t)tid] = p;
         }
     });
@@ -591,6 +615,45 @@ uint64_t agx_sw_band_cigar_bytes_bound(int32_t width, uint32_t ca, uint32_t cb)
 {
     if (width < 1 || width > AGX_SW_BAND_MAX_WIDTH) return 0;
     return band_trace_bytes_bound((uint32_t)width, ca, cb);
+}
+
+uint64_t agx_sw_band_dual_cigar_bytes_bound(int32_t width, uint32_t ca, uint32_t cb)
+{
+    if (width < 1 || width > AGX_SW_BAND_MAX_WIDTH) return 0;
+    return band_dual_trace_bytes_bound((uint32_t)width, ca, cb);
+}
+
+int agx_sw_cigar_rescore_dual(const agx_sw_scoring_dual *scoring, const uint32_t *ops, uint64_t n_ops, const uint8_t *x, uint32_t ca,
+                              const uint8_t *y, uint32_t cb, int32_t score)
+{
+    if (!scoring || (!ops && n_ops) || (!x && ca) || (!y && cb)) return 0;
+    const agx_sw_scoring piece1{scoring->match, scoring->mismatch, scoring->gap_open, scoring->gap_extend};
+    return cigar_checks(ops, n_ops, x, ca, y, cb, piece1, nullptr, score, scoring) ? 1 : 0;
+}
+
+int agx_sw_batch_create_align_band_diag_dual_cigar(agx_ctx *ctx, const agx_sw_scoring_dual *scoring, int mode, int32_t band, const int32_t *diag,
+                                                   const uint8_t *bases, const uint64_t *off, const uint32_t *len, int64_t n_pairs,
+                                                   agx_sw_batch **out)
+{
+    if (!scoring) { // (there is no reference default for a second piece)
+        if (out) *out = nullptr;
+        agx_set_error("agx_sw_batch_create_align_band_diag_dual_cigar: scoring is NULL");
+        return AGX_E_ARG;
+    }
+    AGX_GUARD_BEGIN
+    const BandAt at{AGX_SW_ALIGN_SPANS, diag, false, 0, 0, scoring};
+    const agx_sw_scoring piece1{scoring->match, scoring->mismatch, scoring->gap_open, scoring->gap_extend};
+    return create_band(ctx, &piece1, mode, band, bases, off, len, n_pairs, out, true, &at);
+    AGX_GUARD_END("agx_sw_batch_create_align_band_diag_dual_cigar")
+}
+
+int agx_sw_align_band_diag_dual_cigar(agx_ctx *ctx, const agx_sw_scoring_dual *scoring, int mode, int32_t band, const int32_t *diag,
+                                      const uint8_t *bases, const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_hit *hits,
+                                      uint64_t *op_off, uint32_t *ops, uint64_t ops_cap)
+{
+    agx_sw_batch *b = nullptr;
+    const int rc = agx_sw_batch_create_align_band_diag_dual_cigar(ctx, scoring, mode, band, diag, bases, off, len, n_pairs, &b);
+    return rc ? rc : align_once(b, [&](agx_sw_batch *x) { return agx_sw_batch_cigars(x, hits, op_off, ops, ops_cap); });
 }
 
 int agx_sw_band_span_record(uint32_t la, uint32_t rows, uint32_t row0, uint32_t fpad, int32_t dlo, int32_t dhi, int32_t lanes,
@@ -700,7 +763,8 @@ int agx_sw_batch_cigars(agx_sw_batch *b, agx_sw_hit *hits, uint64_t *op_off, uin
     }
     if (b->cigar != 1 || b->align != AGX_SW_ALIGN_SPANS) {
         agx_set_error("agx_sw_batch_cigars: not a cigar batch (create it with agx_sw_batch_create_align_cigar, agx_sw_batch_create_align_band_cigar, "
-                      "agx_sw_batch_create_align_band_diag_cigar or agx_sw_batch_create_align_band_diag_matrix_cigar)");
+                      "agx_sw_batch_create_align_band_diag_cigar, agx_sw_batch_create_align_band_diag_matrix_cigar or "
+                      "agx_sw_batch_create_align_band_diag_dual_cigar)");
         return AGX_E_ARG;
     }
     if (!b->ctx) {

@@ -1,6 +1,6 @@
 /*
  * swAlign <file_path> [local|global|fit|extend|extend-query][+stats|+cigar|+band=W|+cigar+band=W|+band=W@D|+bandcigar=W@D|+bandstats=W@D][+zdrop=Z]
- * (and, with a matrix file, +matband=W@D|+matbandcigar=W@D; with six scoring numbers, +dualband=W@D): where the best alignment of every pair ends and begins
+ * (and, with a matrix file, +matband=W@D|+matbandcigar=W@D; with six scoring numbers, +dualband=W@D|+dualbandcigar=W@D): where the best alignment of every pair ends and begins
  * (default: local; the other modes are include/agx.h's "Alignment modes").
  * swAlign <file_path> <mode> <matrix_file> [gap_open gap_extend]: the same under a substitution matrix (gaps default to
  * -11 -1).  The matrix file is the usual text layout: '#' comment lines, one line of symbols, then one row per symbol
@@ -55,6 +55,9 @@
  * minimap2's -O4,24 -E2,1 (include/agx.h, "Banded alignment around a diagonal under two-piece gap costs").  Any mode; W and D as in
  * "+band=W@D", both required; read with the line buffer of "+band=W".  All six numbers are required and must be integers: any
  * other count of arguments, a number that is not one, or a further suffix (+stats, +cigar, +zdrop) is a usage error.
+ * swAlign <file_path> <mode>+dualbandcigar=W@D <match> <mismatch> <gap_open> <gap_extend> <gap_open2> <gap_extend2>: the lines of
+ * "+dualband=W@D" with the CIGAR inside that band appended as "+bandcigar=W@D" formats it (include/agx.h, "CIGARs for batches
+ * banded around a diagonal under two-piece gap costs").  The same rules: all six integers, no further suffix.
  *   AGX_CLI_CHUNK_PAIRS   pairs per agx_sw_align call (default 262144)
  */
 #include <stdio.h>
@@ -153,10 +156,12 @@ int main(int argc, char *argv[])
     agx_sw_scoring_dual dual = {0, 0, 0, 0, 0, 0};
     for (int k = 0; (argc == 3 || argc == 4 || argc == 6 || argc == 9) && k < 5; k++) {
         const size_t n = strlen(words[k]);
-        if (argc == 9) { /* six numbers behind the mode word: "+dualband=W@D" and nothing else */
-            if (strncmp(argv[2], words[k], n) || strncmp(argv[2] + n, "+dualband=", 10)) continue;
+        if (argc == 9) { /* six numbers behind the mode word: "+dualband=W@D" or "+dualbandcigar=W@D" and nothing else */
+            if (strncmp(argv[2], words[k], n)) continue;
+            const int dual_cigar = !strncmp(argv[2] + n, "+dualbandcigar=", 15);
+            if (!dual_cigar && strncmp(argv[2] + n, "+dualband=", 10)) continue;
             /* W@D as for "+band=W@D", up to the end of the word (no further suffix); any mode; every number a whole integer */
-            const char *w = argv[2] + n + 10;
+            const char *w = argv[2] + n + (dual_cigar ? 15 : 10);
             char *end, *end2;
             const long v = strtol(w, &end, 10);
             if (!isdigit((unsigned char)*w) || *end != '@' || v > 0x7fffffffL) continue;
@@ -174,6 +179,7 @@ int main(int argc, char *argv[])
             if (!good) continue;
             mode = k;
             with_band = with_diag = with_dual = 1;
+            with_cigar = dual_cigar;
             band = (int32_t)v;
             diag = (int32_t)c;
             continue;
@@ -285,8 +291,10 @@ int main(int argc, char *argv[])
                 "+stats, +cigar or +zdrop.\n"
                 "       %s <file_path> <mode>+dualband=W@D <match> <mismatch> <gap_open> <gap_extend> <gap_open2> <gap_extend2>\n"
                 "the lines of +band=W@D under two-piece gap costs: a gap of L scores max(gap_open + L gap_extend, gap_open2 + L gap_extend2);\n"
-                "all six integers are required, and no +stats, +cigar or +zdrop.\n",
-                argv[0], argv[0], argv[0]);
+                "all six integers are required, and no +stats, +cigar or +zdrop.\n"
+                "       %s <file_path> <mode>+dualbandcigar=W@D <match> <mismatch> <gap_open> <gap_extend> <gap_open2> <gap_extend2>\n"
+                "the same with its CIGAR inside that band appended, as +bandcigar=W@D formats it.\n",
+                argv[0], argv[0], argv[0], argv[0]);
         return 1;
     }
     static agx_sw_matrix matrix;
@@ -368,7 +376,9 @@ int main(int argc, char *argv[])
                 if (!dg) {
                     fprintf(stderr, "swAlign: out of memory\n");
                     status = EXIT_FAILURE;
-                } else if ((with_matband ? agx_sw_align_band_diag_matrix_cigar(ctx, &matrix, mode, band, dg, t->bases, t->off, t->len, t->n_pairs, hits,
+                } else if ((with_dual ? agx_sw_align_band_diag_dual_cigar(ctx, &dual, mode, band, dg, t->bases, t->off, t->len, t->n_pairs, hits, op_off, ops,
+                                                                          ops_cap)
+                            : with_matband ? agx_sw_align_band_diag_matrix_cigar(ctx, &matrix, mode, band, dg, t->bases, t->off, t->len, t->n_pairs, hits,
                                                                                op_off, ops, ops_cap)
                             : with_zdrop ? agx_sw_align_band_zdrop_cigar(ctx, NULL, mode, band, dg, zdrop, t->bases, t->off, t->len, t->n_pairs, hits, NULL,
                                                                          op_off, ops, ops_cap)

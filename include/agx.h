@@ -716,8 +716,9 @@ int agx_sw_align_band_diag_stats(agx_ctx *ctx, const agx_sw_scoring *scoring, in
  * Equivalences: if piece 2 never beats piece 1 for any L >= 1 (identical pieces; gap_open2 <= gap_open and gap_extend2 <=
  * gap_extend), the hits are exactly those of agx_sw_align_band_diag under {match, mismatch, gap_open, gap_extend}; the same
  * with the pieces swapped.  A band that holds the whole matrix, under such pieces, therefore reports what agx_sw_align_mode does.
- * Deliberately left out: CIGARs under two pieces (the trace needs more than four bits per cell), a z-drop, a substitution matrix
- * and statistics under two pieces, and a two-piece agx_sw_batch_create_align_band with its GLOBAL widening.
+ * CIGARs under two pieces: "CIGARs for batches banded around a diagonal under two-piece gap costs", below.
+ * Deliberately left out: a z-drop, a substitution matrix and statistics under two pieces, and a two-piece
+ * agx_sw_batch_create_align_band with its GLOBAL widening.
  */
 typedef struct agx_sw_scoring_dual {
     int32_t match, mismatch, gap_open, gap_extend, gap_open2, gap_extend2;
@@ -728,6 +729,65 @@ int agx_sw_batch_create_align_band_diag_dual(agx_ctx *ctx, const agx_sw_scoring_
 /* One-shot: create_align_band_diag_dual + launch + hits + destroy. */
 int agx_sw_align_band_diag_dual(agx_ctx *ctx, const agx_sw_scoring_dual *scoring, int mode, int what, int32_t band, const int32_t *diag,
                                 const uint8_t *bases, const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_hit *hits);
+
+/*
+ * CIGARs for batches banded around a diagonal under two-piece gap costs: the alignment itself for the caller who places a long
+ * read in its window under the gap model above.  One-piece CIGARs are no substitute: no one-piece setting reproduces the
+ * two-piece path.
+ * The batch is the AGX_SW_ALIGN_SPANS batch of "Banded alignment around a diagonal under two-piece gap costs" in any of the five
+ * modes -- the same hits, band conditions, limits, errors, empty-side formulas, plan; ctx == NULL: plan only -- which also answers
+ * agx_sw_batch_cigars and agx_sw_batch_cigar_info exactly as the batch of "CIGARs for batches banded around a diagonal" does: the
+ * CIGAR consumes a[a_begin..a_end] and b[b_begin..b_end]; run from the begin cell it stays within dlo <= j - i <= dhi of the full
+ * matrix after every operation; lone runs, "*" (no operations), ops_cap, the chunks under AGX_OPT_SW_TRACE_BYTES and
+ * AGX_E_INTERNAL naming the pair behave as there.  No new limit: every lane class of the banded fill has its traced two-piece
+ * build, so the widest band stays AGX_SW_BAND_MAX_WIDTH, and no pair is refused for its size (the largest, 65 535 rows in 2048
+ * diagonals, takes about 134 MB of directions: eight bits a cell).
+ * Rescoring is under the LITERAL cost: every maximal run of I or of D of length L counts max(gap_open + L gap_extend, gap_open2 +
+ * L gap_extend2), '=' match, 'X' mismatch, and the total equals `score`; the host checks that before a CIGAR leaves.  Why it
+ * holds although the walk may join a piece-1 stretch of L1 and a piece-2 stretch of L2 of the same direction into one run: with
+ * p(L) = open + L extend and opens <= 0, p1(L1) + p2(L2) is at most max(p1(L1 + L2), p2(L1 + L2)) -- if extend >= extend2 then
+ * p1(L1) + p2(L2) <= p1(L1) + open2 + L2 extend <= p1(L1 + L2), else p1(L1) + p2(L2) <= open + L1 extend2 + p2(L2) <= p2(L1 + L2);
+ * by induction for any number of stretches -- so the walked path's cost under the recurrence, which is
+ * `score`, is <= its literal cost; the literal optimum inside the band is the recurrence's optimum (every literal path is a path
+ * of the recurrence with each run in its better piece, and by the inequality no path of the recurrence beats its own literal
+ * cost), so the literal cost of the walked path, a path inside the band, is <= `score`.  Both: equal.
+ * Tie rule, on the global alignment of the span inside the moved band (dlo' = c - w - delta, dhi' = c + w - delta, delta =
+ * a_begin - b_begin) under both pieces, walked back from the span's end cell in state H:
+ *   in H     prefer the diagonal move ('=' or 'X') where it attains H; else E (a D) if max(E1, E2) >= max(F1, F2), else F (an I);
+ *            within the direction piece 1 if its value is >= piece 2's, else piece 2
+ *   in Ep    emit D and move up; stay in Ep only where piece p's extension is STRICTLY better than opening from H of the cell
+ *            above under piece p:  Ep(i - 1, j) + extend_p > H(i - 1, j) + open_p + extend_p;  otherwise return to H
+ *   in Fp    the same to the left with I
+ *   H with i = 0 emits j x I, with j = 0 i x D.
+ * Equivalences: if piece 2 never beats piece 1 for any L >= 1 (identical pieces; gap_open2 <= gap_open and gap_extend2 <=
+ * gap_extend), hits and operations are exactly those of agx_sw_align_band_diag_cigar under {match, mismatch, gap_open,
+ * gap_extend}.  If piece 1 is STRICTLY worse for every L >= 1 (gap_open + gap_extend < gap_open2 + gap_extend2 and gap_extend <=
+ * gap_extend2), they are exactly those under {match, mismatch, gap_open2, gap_extend2}.  Where piece 1 merely ties piece 2 for
+ * some L the preference for piece 1 may pick another gap length of the same score: no equality is claimed there.
+ * Unchanged: the plain two-piece batch keeps answering agx_sw_batch_cigars, _stats and _zdrop_stops with AGX_E_ARG; this batch
+ * refuses _stats and _zdrop_stops with AGX_E_ARG.
+ * Deliberately left out: a z-drop, a substitution matrix and statistics under two pieces, and a two-piece
+ * agx_sw_batch_create_align_band with its GLOBAL widening.
+ */
+int agx_sw_batch_create_align_band_diag_dual_cigar(agx_ctx *ctx, const agx_sw_scoring_dual *scoring, int mode, int32_t band,
+                                                   const int32_t *diag /* n_pairs, or NULL = 0 for every pair */, const uint8_t *bases,
+                                                   const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_batch **out);
+/* One-shot: create_align_band_diag_dual_cigar + launch + cigars + destroy. */
+int agx_sw_align_band_diag_dual_cigar(agx_ctx *ctx, const agx_sw_scoring_dual *scoring, int mode, int32_t band, const int32_t *diag,
+                                      const uint8_t *bases, const uint64_t *off, const uint32_t *len, int64_t n_pairs, agx_sw_hit *hits,
+                                      uint64_t *op_off, uint32_t *ops, uint64_t ops_cap);
+/* Host only, no device.  What one traced pair of such a batch counts against AGX_OPT_SW_TRACE_BYTES: eight bits a cell in the
+ * lane class that needs the most for `width` diagonals and cb rows, plus its operation slot of ca + cb words.  0 if width is
+ * outside 1 .. AGX_SW_BAND_MAX_WIDTH.  (agx_sw_band_cigar_bytes_bound is unchanged.) */
+uint64_t agx_sw_band_dual_cigar_bytes_bound(int32_t width, uint32_t ca, uint32_t cb);
+/* Host only, no device.  A permanent entry of the ABI, for callers who want to validate a CIGAR they hold (one they edited, or
+ * one from another aligner) against a score under two-piece costs, and for the project's own tests of the check below -- the
+ * library applies it to every CIGAR of the batch above before agx_sw_batch_cigars returns.
+ * The host's check of one CIGAR under the literal two-piece cost: 1 if the n_ops operations are
+ * well-formed runs (I, D, =, X; positive lengths; no two equal neighbours), consume exactly x[0..ca) and y[0..cb), every '=' / 'X'
+ * is true of the symbols and the total is `score`; else 0 (also for a NULL argument that is needed). */
+int agx_sw_cigar_rescore_dual(const agx_sw_scoring_dual *scoring, const uint32_t *ops, uint64_t n_ops, const uint8_t *x, uint32_t ca,
+                              const uint8_t *y, uint32_t cb, int32_t score);
 
 /* Host only, no device.  How the traced fill of a span starts inside a banded batch's resident image.  The image holds the
  * query a behind `fpad` bytes and the rows b[row0 .. row0 + rows) behind one byte, packed for a fill from row0 in the band
