@@ -233,51 +233,36 @@ struct SwBandGroup {
 static const int kSwBandClasses[] = {4, 8, 16, 32};
 constexpr int kSwNumBandClasses = 4;
 static_assert(64 * 32 == AGX_SW_BAND_MAX_WIDTH, "the widest band is 64 lanes of the widest class");
-int agx_sw_band_launch_class(int diags_per_lane, int extend, const SwParams &prm, const uint32_t *img, const SwBandGroup *groups,
-                             const SwWave *waves, uint32_t n_waves, int32_t *scores, uint32_t *pos, hipStream_t s);
-void agx_sw_band_preload();
-// the builds of the same body for a band around a caller-given diagonal (agx_sw_band_diag_kernel.hip; DESIGN.md 4.1i): mode LOCAL,
-// FIT or EXTEND_QUERY; GLOBAL and EXTEND run agx_sw_band_launch_class.  pos[out]: LOCAL i << 16 | j, the others the row i.
-int agx_sw_band_at_launch_class(int diags_per_lane, int mode, const SwParams &prm, const uint32_t *img, const SwBandGroup *groups,
-                                const SwWave *waves, uint32_t n_waves, int32_t *scores, uint32_t *pos, hipStream_t s);
-void agx_sw_band_at_preload();
-// the EXTEND build with z-drop termination (agx_sw_band_zdrop_kernel.hip): scores and pos as EXTEND writes them,
-// stops[out] = the last row looked at of a pair that terminated (counted from 0 in b), -1 of one that ran through
-int agx_sw_band_zdrop_launch_class(int diags_per_lane, const SwParams &prm, const uint32_t *img, const SwBandGroup *groups, const SwWave *waves,
-                                   uint32_t n_waves, int32_t *scores, uint32_t *pos, int32_t zdrop, int32_t *stops, hipStream_t s);
-void agx_sw_band_zdrop_preload();
-// the builds WITH alignment statistics (agx_sw_band_stats_kernel.hip; DESIGN.md 4.1m): mode GLOBAL, EXTEND, LOCAL or EXTEND_QUERY (the
-// last two are also the begin passes of LOCAL and FIT); records, scores and pos as the plain builds of that mode write them, and
-// lstat[out] = matches << kSwBandStatBits | pairs of the captured cell's best path.  Every class of AGX_SW_FOR_EACH_BAND_CLASS is
-// built: none spills or takes scratch, AGPRs or LDS (DESIGN.md 4.1m has the table), so a stats batch is tiled like a plain one.
-constexpr int kSwBandStatBits = 16; // L = matches << 16 | pairs: both up to 65 535
-int agx_sw_band_stats_launch_class(int diags_per_lane, int mode, const SwParams &prm, const uint32_t *img, const SwBandGroup *groups,
-                                   const SwWave *waves, uint32_t n_waves, int32_t *scores, uint32_t *pos, uint32_t *lstat, hipStream_t s);
-void agx_sw_band_stats_preload();
-// the builds under TWO-PIECE gap costs (agx_sw_band_dual_kernel.hip): the GLOBAL and EXTEND builds and the three
-// builds around a diagonal again; records, scores and pos as the plain builds of that mode write them.  prm holds the first piece
-// exactly as a plain batch's does; the second travels beside it.  Every class is built without scratch, AGPRs or LDS.
+// ---- the launch interface of the banded family.  Ten translation units build the body (agx_sw_band_kernel.inc) in its variants;
+// each exports ONE fill entry of the type below and one preload, the traced ones a walk.  agx_sw_host::band_fill
+// (agx_sw_band.cpp) picks a batch's SwBandFill row; the launch, the create's preloads and the traced fills of agx_sw_batch_cigars
+// all go through that row.
+// The second piece of TWO-PIECE gap costs: prm holds the first piece exactly as a plain batch's does, this travels beside it.
 struct SwDualGap {
     int32_t ge2; // the second piece's gap_extend
     int32_t dgf; // (gap_open2 + gap_extend2) - prm.gf: what piece 2 adds to the stored z = H + gf
 };
-int agx_sw_band_dual_launch_class(int diags_per_lane, int extend, const SwParams &prm, const SwDualGap &dg, const uint32_t *img,
-                                  const SwBandGroup *groups, const SwWave *waves, uint32_t n_waves, int32_t *scores, uint32_t *pos, hipStream_t s);
-int agx_sw_band_dual_at_launch_class(int diags_per_lane, int mode, const SwParams &prm, const SwDualGap &dg, const uint32_t *img,
-                                     const SwBandGroup *groups, const SwWave *waves, uint32_t n_waves, int32_t *scores, uint32_t *pos,
-                                     hipStream_t s);
-void agx_sw_band_dual_preload();
-// the TRACED banded fill and its walk (agx_sw_band_trace_kernel.hip): corner capture only.  Every cell of rows
-// 0 .. lb leaves four bits at trace + goff[group] + (step * G + lane) * sw_band_trace_words(K) dwords, nibble k of the lane's K
-// diagonals; goff holds one 64-bit dword offset per group record, a multiple of four (the K = 32 build stores 16 bytes at once).
-constexpr int sw_band_trace_words(int K) { return (K + 7) / 8; }
-// the dwords a traced pair of lb rows occupies in class K on G lanes: steps 0 .. lb + G - 1 of G lanes, rounded up to four
-inline uint64_t sw_band_trace_dwords(int G, uint32_t lb, int K)
-{
-    return (((uint64_t)lb + (uint64_t)G) * (uint64_t)G * (uint64_t)sw_band_trace_words(K) + 3u) & ~(uint64_t)3u;
-}
-int agx_sw_band_trace_launch_class(int diags_per_lane, const SwParams &prm, const uint32_t *img, const SwBandGroup *groups, const SwWave *waves,
-                                   uint32_t n_waves, int32_t *scores, uint32_t *trace, const uint64_t *goff, hipStream_t s);
+// What a fill launch is given: the members every build reads, then those of single variants (an entry reads its own; the rest
+// may stay zero).
+struct SwBandArgs {
+    SwParams prm;
+    SwDualGap dual_gap; // two-piece builds
+    const uint32_t *img;
+    const SwBandGroup *groups;
+    const SwWave *waves; // of this launch's class
+    uint32_t n_waves;
+    int32_t *scores;
+    uint32_t *pos;        // untraced builds: EXTEND and LOCAL i << 16 | j of the best cell's first occurrence (z-drop, LOCAL: 0xffffffff if
+                          // none beats 0), FIT and EXTEND_QUERY the smallest best row i of column la; GLOBAL writes none
+    uint32_t *trace;      // traced builds: the directions, and one 64-bit dword offset per group record
+    const uint64_t *goff;
+    int32_t zdrop;        // z-drop build
+    int32_t *stops;       // z-drop build: the last row looked at (counted from 0 in b) of a pair that terminated, -1 of one that ran through
+    uint32_t *lstat;      // stats builds: matches << kSwBandStatBits | pairs of the captured cell's best path
+    const int16_t *table; // matrix builds: the device copy of the kSwMatDim x kSwMatDim entries of agx_sw_mat_launch_class
+};
+// -> 0, -1 the launch failed (hipGetLastError says why), -2 the unit builds no such class K or mode
+using SwBandFillFn = int (*)(int K, int mode, const SwBandArgs &a, hipStream_t s);
 // the band-aware walk: pair p's SwWalkRec (G = lanes, C = diagonals per lane, x_dw / y_dw of its band image) and its band.  It
 // tests dlo <= j - i <= dhi, i <= cb, j <= ca before every load; a violation leaves kSwWalkFailed in runs[p].
 struct SwBandWalkRec {
@@ -286,19 +271,67 @@ struct SwBandWalkRec {
     uint32_t kshift; // log2 of the diagonals per lane
 };
 constexpr uint32_t kSwWalkFailed = 0xffffffffu;
-int agx_sw_band_walk_launch(const SwWalkRec *recs, const SwBandWalkRec *band, uint32_t n, const uint32_t *img, const uint32_t *trace,
-                            uint32_t *slots, uint32_t *runs, hipStream_t s);
+struct SwBandWalkArgs {
+    const SwWalkRec *recs;
+    const SwBandWalkRec *band;
+    uint32_t n;
+    const uint32_t *img, *trace;
+    uint32_t *slots, *runs;
+};
+using SwBandWalkFn = int (*)(const SwBandWalkArgs &a, hipStream_t s);
+// a row of the selection table
+struct SwBandFill {
+    const char *name; // the kernel, as a failed launch names it: name<K> or, of a build per mode, name<K, mode>
+    bool per_mode;
+    unsigned needs;   // kSwBand*: what a batch's kind must include for a create to preload this row
+    SwBandFillFn launch;
+    void (*preload)();
+    SwBandWalkFn walk; // traced fills: the walk over their directions
+};
+enum : unsigned { kSwBandAt = 1, kSwBandZdrop = 2, kSwBandStats = 4, kSwBandDual = 8, kSwBandMatrix = 16, kSwBandTraced = 32 };
+
+// agx_sw_band_kernel.hip: modes GLOBAL (scores[out] = D[lb][la]) and EXTEND (the maximum and pos)
+int agx_sw_band_launch(int K, int mode, const SwBandArgs &a, hipStream_t s);
+void agx_sw_band_preload();
+// the builds of the same body for a band around a caller-given diagonal (agx_sw_band_diag_kernel.hip; DESIGN.md 4.1i): mode LOCAL,
+// FIT or EXTEND_QUERY; GLOBAL and EXTEND run agx_sw_band_launch
+int agx_sw_band_at_launch(int K, int mode, const SwBandArgs &a, hipStream_t s);
+void agx_sw_band_at_preload();
+// the EXTEND build with z-drop termination (agx_sw_band_zdrop_kernel.hip): scores and pos as EXTEND writes them
+int agx_sw_band_zdrop_launch(int K, int mode, const SwBandArgs &a, hipStream_t s);
+void agx_sw_band_zdrop_preload();
+// the builds WITH alignment statistics (agx_sw_band_stats_kernel.hip; DESIGN.md 4.1m): mode GLOBAL, EXTEND, LOCAL or EXTEND_QUERY (the
+// last two are also the begin passes of LOCAL and FIT); records, scores and pos as the plain builds of that mode write them.
+// Every class of AGX_SW_FOR_EACH_BAND_CLASS is built: none spills or takes scratch, AGPRs or LDS (DESIGN.md 4.1m has the table),
+// so a stats batch is tiled like a plain one.
+constexpr int kSwBandStatBits = 16; // L = matches << 16 | pairs: both up to 65 535
+int agx_sw_band_stats_launch(int K, int mode, const SwBandArgs &a, hipStream_t s);
+void agx_sw_band_stats_preload();
+// the builds under TWO-PIECE gap costs (agx_sw_band_dual_kernel.hip): all five modes -- sw_fill_band_dual in GLOBAL
+// and EXTEND, sw_fill_band_dual_at in the others; records, scores and pos as the plain builds of that mode write them.  Every
+// class is built without scratch, AGPRs or LDS.
+int agx_sw_band_dual_launch(int K, int mode, const SwBandArgs &a, hipStream_t s);
+void agx_sw_band_dual_preload();
+// the TRACED banded fill and its walk (agx_sw_band_trace_kernel.hip): corner capture only, whatever the mode.  Every
+// cell of rows 0 .. lb leaves four bits at trace + goff[group] + (step * G + lane) * sw_band_trace_words(K) dwords, nibble k of the
+// lane's K diagonals; goff holds one 64-bit dword offset per group record, a multiple of four (the K = 32 build stores 16 bytes at once).
+constexpr int sw_band_trace_words(int K) { return (K + 7) / 8; }
+// the dwords a traced pair of lb rows occupies in class K on G lanes: steps 0 .. lb + G - 1 of G lanes, rounded up to four
+inline uint64_t sw_band_trace_dwords(int G, uint32_t lb, int K)
+{
+    return (((uint64_t)lb + (uint64_t)G) * (uint64_t)G * (uint64_t)sw_band_trace_words(K) + 3u) & ~(uint64_t)3u;
+}
+int agx_sw_band_trace_launch(int K, int mode, const SwBandArgs &a, hipStream_t s);
+int agx_sw_band_walk_launch(const SwBandWalkArgs &a, hipStream_t s);
 void agx_sw_band_trace_preload();
 // the same for a span that begins inside the resident image (agx_sw_band_diag_trace_kernel.hip): the group record
 // is the span's (agx_sw_band_span_record: la_lb the span, dlo / dhi and fpad shifted, y_dw moved by whole dwords) with the start
 // phase 0 .. 3 in `reserved`, and the wave steps max(cb + phase) + G times; the walk's SwWalkRec.reserved holds the phase too
-int agx_sw_band_trace_at_launch_class(int diags_per_lane, const SwParams &prm, const uint32_t *img, const SwBandGroup *groups, const SwWave *waves,
-                                      uint32_t n_waves, int32_t *scores, uint32_t *trace, const uint64_t *goff, hipStream_t s);
-int agx_sw_band_walk_at_launch(const SwWalkRec *recs, const SwBandWalkRec *band, uint32_t n, const uint32_t *img, const uint32_t *trace,
-                               uint32_t *slots, uint32_t *runs, hipStream_t s);
+int agx_sw_band_trace_at_launch(int K, int mode, const SwBandArgs &a, hipStream_t s);
+int agx_sw_band_walk_at_launch(const SwBandWalkArgs &a, hipStream_t s);
 void agx_sw_band_trace_at_preload();
 // the traced build and the walk UNDER TWO-PIECE gap costs (agx_sw_band_dual_trace_kernel.hip): the span records,
-// the start phase, scores and goff of agx_sw_band_trace_at_launch_class; every cell leaves EIGHT bits -- bits 0-1 where H came
+// the start phase, scores and goff of agx_sw_band_trace_at_launch; every cell leaves EIGHT bits -- bits 0-1 where H came
 // from, bit 2 "of piece 2", bits 4-7 E1, F1, E2, F2 extended -- at trace + goff[group] + (step * G + lane) *
 // sw_band_dual_trace_words(K) dwords, byte k of the lane's K diagonals (K = 32: two stores of 16 bytes)
 constexpr int sw_band_dual_trace_words(int K) { return K / 4; }
@@ -306,22 +339,16 @@ inline uint64_t sw_band_dual_trace_dwords(int G, uint32_t lb, int K)
 {
     return (((uint64_t)lb + (uint64_t)G) * (uint64_t)G * (uint64_t)sw_band_dual_trace_words(K) + 3u) & ~(uint64_t)3u;
 }
-int agx_sw_band_trace_dual_launch_class(int diags_per_lane, const SwParams &prm, const SwDualGap &dg, const uint32_t *img, const SwBandGroup *groups,
-                                        const SwWave *waves, uint32_t n_waves, int32_t *scores, uint32_t *trace, const uint64_t *goff,
-                                        hipStream_t s);
-int agx_sw_band_walk_dual_launch(const SwWalkRec *recs, const SwBandWalkRec *band, uint32_t n, const uint32_t *img, const uint32_t *trace,
-                                 uint32_t *slots, uint32_t *runs, hipStream_t s);
+int agx_sw_band_trace_dual_launch(int K, int mode, const SwBandArgs &a, hipStream_t s);
+int agx_sw_band_walk_dual_launch(const SwBandWalkArgs &a, hipStream_t s);
 void agx_sw_band_trace_dual_preload();
 // the builds of the banded body under a substitution matrix (agx_sw_band_diag_mat_kernel.hip, agx_sw_band_diag_trace_mat_kernel.hip;
 // DESIGN.md 4.1l): a band around a caller-given diagonal in all five modes, and the traced build with the start phase.  The image
-// holds symbol numbers 1 .. 32 (0 = padding) where the other banded builds hold bytes; table is the device copy of the
-// kSwMatDim x kSwMatDim entries of agx_sw_mat_launch_class.  Records, scores, pos, trace and goff are those of the builds above;
-// the walk of a traced span is agx_sw_band_walk_at_launch
-int agx_sw_band_mat_launch_class(int diags_per_lane, int mode, const SwParams &prm, const uint32_t *img, const SwBandGroup *groups,
-                                 const SwWave *waves, uint32_t n_waves, int32_t *scores, uint32_t *pos, const int16_t *table, hipStream_t s);
+// holds symbol numbers 1 .. 32 (0 = padding) where the other banded builds hold bytes.  Records, scores, pos, trace and goff are
+// those of the builds above; the walk of a traced span is agx_sw_band_walk_at_launch
+int agx_sw_band_mat_launch(int K, int mode, const SwBandArgs &a, hipStream_t s);
 void agx_sw_band_mat_preload();
-int agx_sw_band_trace_mat_launch_class(int diags_per_lane, const SwParams &prm, const uint32_t *img, const SwBandGroup *groups, const SwWave *waves,
-                                       uint32_t n_waves, int32_t *scores, uint32_t *trace, const uint64_t *goff, const int16_t *table, hipStream_t s);
+int agx_sw_band_trace_mat_launch(int K, int mode, const SwBandArgs &a, hipStream_t s);
 void agx_sw_band_trace_mat_preload();
 
 // ---- device-side planning (agx_sw_plan_kernel.hip): the O(pairs) passes of the planner as kernels

@@ -157,14 +157,19 @@ void keep_band_host_state(agx_sw_batch *b, const BandKind &kind, const BandPairs
 {
     const BandAt *at = kind.at;
     const int64_t n_pairs = b->n_pairs;
-    agx_sw_band_preload();
+    // every row whose needs the batch's kind includes, in the table's order: not its own fill alone
+    const unsigned have = (b->band_at ? kSwBandAt : 0u) | (b->zdrop_on ? kSwBandZdrop : 0u) | (b->stats ? kSwBandStats : 0u) |
+                          (b->dual ? kSwBandDual : 0u) | (b->matrix ? kSwBandMatrix : 0u) | (b->cigar ? kSwBandTraced : 0u);
+    void (*loaded)() = nullptr;
+    for (int k = 0; k < kNumBandFills; ++k) {
+        const SwBandFill &f = band_fills()[k];
+        if ((f.needs & ~have) || f.preload == loaded) continue; // (two rows of one translation unit stand together)
+        f.preload();
+        loaded = f.preload;
+    }
+    if (kind.cigar) agx_sw_walk_preload();
     if (n_pairs > 0) b->seq_len.assign(len, len + 2 * n_pairs);
-    if (kind.matrix) agx_sw_band_mat_preload();
     if (at) {
-        agx_sw_band_at_preload();
-        if (at->zdrop_on) agx_sw_band_zdrop_preload();
-        if (at->stats) agx_sw_band_stats_preload();
-        if (at->dual) agx_sw_band_dual_preload();
         b->band_row0 = pairs.row0s;
         if (at->diag) b->band_diag.assign(at->diag, at->diag + n_pairs);
         else b->band_diag.assign((size_t)n_pairs, 0);
@@ -183,11 +188,6 @@ void keep_band_host_state(agx_sw_batch *b, const BandKind &kind, const BandPairs
         }); // (bases == NULL: every pair has an empty side, and a lone run of I or D reads no symbol)
     }
     if (!kind.cigar) return;
-    agx_sw_band_trace_preload();
-    if (at) agx_sw_band_trace_at_preload();
-    if (at && at->dual) agx_sw_band_trace_dual_preload();
-    if (kind.matrix) agx_sw_band_trace_mat_preload();
-    agx_sw_walk_preload();
     const std::vector<BandPlan> &plan = pairs.plan;
     b->band_groups = groups;
     b->band_rec.assign((size_t)n_pairs, kNoBandRec);
@@ -319,63 +319,77 @@ int create_band(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t b
     return AGX_OK;
 }
 
+// ---- the selection table: one row per fill kernel of the banded family, in the order a create preloads them
+// (keep_band_host_state).  band_fill picks a batch's row; band_launch and band_trace (agx_sw_cigar.cpp) launch through it.
+enum { kFillPlain, kFillMat, kFillAt, kFillZd, kFillStats, kFillDual, kFillDualAt, kFillTrace, kFillTraceAt, kFillTraceDual, kFillTraceMat };
+const SwBandFill *band_fills()
+{
+    static const SwBandFill rows[kNumBandFills] = {
+        {"sw_fill_band", false, 0, agx_sw_band_launch, agx_sw_band_preload, nullptr},
+        {"sw_fill_band_mat", true, kSwBandMatrix, agx_sw_band_mat_launch, agx_sw_band_mat_preload, nullptr},
+        {"sw_fill_band_at", true, kSwBandAt, agx_sw_band_at_launch, agx_sw_band_at_preload, nullptr},
+        {"sw_fill_band_zd", false, kSwBandZdrop, agx_sw_band_zdrop_launch, agx_sw_band_zdrop_preload, nullptr},
+        {"sw_fill_band_stats", true, kSwBandStats, agx_sw_band_stats_launch, agx_sw_band_stats_preload, nullptr},
+        {"sw_fill_band_dual", false, kSwBandDual, agx_sw_band_dual_launch, agx_sw_band_dual_preload, nullptr},
+        {"sw_fill_band_dual_at", true, kSwBandDual, agx_sw_band_dual_launch, agx_sw_band_dual_preload, nullptr},
+        {"sw_fill_band_trace", false, kSwBandTraced, agx_sw_band_trace_launch, agx_sw_band_trace_preload, agx_sw_band_walk_launch},
+        {"sw_fill_band_trace_at", false, kSwBandTraced | kSwBandAt, agx_sw_band_trace_at_launch, agx_sw_band_trace_at_preload, agx_sw_band_walk_at_launch},
+        {"sw_fill_band_trace_dual", false, kSwBandTraced | kSwBandDual, agx_sw_band_trace_dual_launch, agx_sw_band_trace_dual_preload,
+         agx_sw_band_walk_dual_launch},
+        // (a batch under a matrix is banded around a diagonal: its spans run the traced build with the start phase, and that walk)
+        {"sw_fill_band_trace_mat", false, kSwBandTraced | kSwBandMatrix, agx_sw_band_trace_mat_launch, agx_sw_band_trace_mat_preload,
+         agx_sw_band_walk_at_launch},
+    };
+    return rows;
+}
+
+const SwBandFill &band_fill(const agx_sw_batch *b, bool traced)
+{
+    if (traced) return band_fills()[b->dual ? kFillTraceDual : b->matrix ? kFillTraceMat : b->band_at ? kFillTraceAt : kFillTrace];
+    // GLOBAL and EXTEND around a diagonal run the builds around the main one: their boundaries and captures are the same
+    const bool at = b->band_at && b->mode != AGX_SW_MODE_GLOBAL && b->mode != AGX_SW_MODE_EXTEND;
+    return band_fills()[b->dual         ? (at ? kFillDualAt : kFillDual)
+                      : b->stats == 2 ? kFillStats
+                      : b->zdrop_on   ? kFillZd
+                      : b->matrix     ? kFillMat
+                      : at            ? kFillAt
+                                      : kFillPlain];
+}
+
+int band_fill_failed(const SwBandFill &f, int K, int mode)
+{
+    if (f.per_mode) agx_set_error("%s<%d, %d> launch failed: %s", f.name, K, mode, hipGetErrorString(hipGetLastError()));
+    else agx_set_error("%s<%d> launch failed: %s", f.name, K, hipGetErrorString(hipGetLastError()));
+    return AGX_E_HIP;
+}
+
 int band_launch(agx_sw_batch *b)
 {
     b->cig_valid = false; // what agx_sw_batch_cigars kept belongs to the launch before
     if (b->launches.empty()) return AGX_OK;
-    const uint32_t *img = (const uint32_t *)b->img.p;
-    const SwBandGroup *groups = (const SwBandGroup *)b->groups.p;
-    const SwWave *waves = (const SwWave *)b->waves.p;
-    int32_t *scores = (int32_t *)b->scores.p;
-    uint32_t *pos = (uint32_t *)b->band_pos.p;
-    // every class through `launch`, the batch's kernel (`name`; with_mode: a build per mode, which the message names too)
-    const auto launch_classes = [&](const char *name, bool with_mode, auto launch) -> int {
-        FanOut fan(b->ctx, (int)b->launches.size());
-        int rc = fan.begin();
-        if (rc) return rc;
-        int k = 0;
-        // widest class first: its waves have the longest steps
-        for (auto it = b->launches.rbegin(); it != b->launches.rend(); ++it) {
-            if (!launch(*it, fan.stream(k++))) continue;
-            if (with_mode) agx_set_error("%s<%d, %d> launch failed: %s", name, it->C, b->mode, hipGetErrorString(hipGetLastError()));
-            else agx_set_error("%s<%d> launch failed: %s", name, it->C, hipGetErrorString(hipGetLastError()));
-            return AGX_E_HIP;
-        }
-        return fan.end();
-    };
-    if (b->dual) {
-        if (b->mode != AGX_SW_MODE_GLOBAL && b->mode != AGX_SW_MODE_EXTEND)
-            return launch_classes("sw_fill_band_dual_at", true, [&](const ClassLaunch &cl, hipStream_t s) {
-                return agx_sw_band_dual_at_launch_class(cl.C, b->mode, b->prm, b->dual_gap, img, groups, waves + cl.first_wave, cl.n_waves, scores,
-                                                        pos, s);
-            });
-        return launch_classes("sw_fill_band_dual", false, [&](const ClassLaunch &cl, hipStream_t s) {
-            return agx_sw_band_dual_launch_class(cl.C, b->mode == AGX_SW_MODE_EXTEND, b->prm, b->dual_gap, img, groups, waves + cl.first_wave,
-                                                 cl.n_waves, scores, pos, s);
-        });
+    const SwBandFill &fill = band_fill(b, false);
+    SwBandArgs a{};
+    a.prm = b->prm;
+    a.dual_gap = b->dual_gap;
+    a.img = (const uint32_t *)b->img.p;
+    a.groups = (const SwBandGroup *)b->groups.p;
+    a.scores = (int32_t *)b->scores.p;
+    a.pos = (uint32_t *)b->band_pos.p;
+    a.zdrop = b->zdrop;
+    a.stops = (int32_t *)b->band_stop.p;
+    a.lstat = (uint32_t *)b->lstat.p;
+    a.table = (const int16_t *)b->table.p;
+    FanOut fan(b->ctx, (int)b->launches.size());
+    int rc = fan.begin();
+    if (rc) return rc;
+    int k = 0;
+    // widest class first: its waves have the longest steps
+    for (auto it = b->launches.rbegin(); it != b->launches.rend(); ++it) {
+        a.waves = (const SwWave *)b->waves.p + it->first_wave;
+        a.n_waves = it->n_waves;
+        if (fill.launch(it->C, b->mode, a, fan.stream(k++))) return band_fill_failed(fill, it->C, b->mode);
     }
-    if (b->stats == 2)
-        return launch_classes("sw_fill_band_stats", true, [&](const ClassLaunch &cl, hipStream_t s) {
-            return agx_sw_band_stats_launch_class(cl.C, b->mode, b->prm, img, groups, waves + cl.first_wave, cl.n_waves, scores, pos,
-                                                  (uint32_t *)b->lstat.p, s);
-        });
-    if (b->zdrop_on)
-        return launch_classes("sw_fill_band_zd", false, [&](const ClassLaunch &cl, hipStream_t s) {
-            return agx_sw_band_zdrop_launch_class(cl.C, b->prm, img, groups, waves + cl.first_wave, cl.n_waves, scores, pos, b->zdrop,
-                                                  (int32_t *)b->band_stop.p, s);
-        });
-    if (b->matrix)
-        return launch_classes("sw_fill_band_mat", true, [&](const ClassLaunch &cl, hipStream_t s) {
-            return agx_sw_band_mat_launch_class(cl.C, b->mode, b->prm, img, groups, waves + cl.first_wave, cl.n_waves, scores, pos,
-                                                (const int16_t *)b->table.p, s);
-        });
-    if (b->band_at && b->mode != AGX_SW_MODE_GLOBAL && b->mode != AGX_SW_MODE_EXTEND)
-        return launch_classes("sw_fill_band_at", true, [&](const ClassLaunch &cl, hipStream_t s) {
-            return agx_sw_band_at_launch_class(cl.C, b->mode, b->prm, img, groups, waves + cl.first_wave, cl.n_waves, scores, pos, s);
-        });
-    return launch_classes("sw_fill_band", false, [&](const ClassLaunch &cl, hipStream_t s) {
-        return agx_sw_band_launch_class(cl.C, b->mode == AGX_SW_MODE_EXTEND, b->prm, img, groups, waves + cl.first_wave, cl.n_waves, scores, pos, s);
-    });
+    return fan.end();
 }
 
 // band_hits of a batch around a diagonal (include/agx.h, "Banded alignment around a diagonal"): the fill's rows are counted from

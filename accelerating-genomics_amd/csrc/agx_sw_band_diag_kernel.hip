@@ -35,36 +35,21 @@ __global__ void __launch_bounds__(256) sw_fill_band_at(const SwParams prm, const
 {
     const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * 4u + (threadIdx.x >> 6));
     if (wave >= n_waves) return;
-    band_body<K, MODE == AGX_SW_MODE_LOCAL, false, MODE>(prm, img, groups, waves[wave], scores, pos);
+    BandIo io;
+    io.scores = scores, io.pos = pos;
+    band_body<K, band_ext(MODE == AGX_SW_MODE_LOCAL), MODE>(prm, img, groups, waves[wave], io);
 }
 
 } // namespace
 
-// mode: LOCAL (scores[out] = the maximum, pos[out] = i << 16 | j of its first cell, 0xffffffff if none beats 0), FIT or
-// EXTEND_QUERY (scores[out] = max D[i][la] over the in-band rows, pos[out] = the smallest such i)
-int agx_sw_band_at_launch_class(int diags_per_lane, int mode, const SwParams &prm, const uint32_t *img, const SwBandGroup *groups,
-                                const SwWave *waves, uint32_t n_waves, int32_t *scores, uint32_t *pos, hipStream_t s)
+#define AGX_SW_ROW(KK) {sw_fill_band_at<KK, AGX_SW_MODE_LOCAL>, sw_fill_band_at<KK, AGX_SW_MODE_FIT>, sw_fill_band_at<KK, AGX_SW_MODE_EXTEND_QUERY>},
+static constexpr decltype(&sw_fill_band_at<4, AGX_SW_MODE_LOCAL>) kFills[kSwNumBandClasses][3] = {AGX_SW_FOR_EACH_BAND_CLASS(AGX_SW_ROW)};
+#undef AGX_SW_ROW
+static constexpr int kModes[] = {AGX_SW_MODE_LOCAL, AGX_SW_MODE_FIT, AGX_SW_MODE_EXTEND_QUERY};
+
+int agx_sw_band_at_launch(int K, int mode, const SwBandArgs &a, hipStream_t s)
 {
-    if (n_waves == 0) return 0;
-    const uint32_t blocks = (n_waves + 3) / 4;
-#define AGX_SW_AT(KK, MM) hipLaunchKernelGGL((sw_fill_band_at<KK, MM>), dim3(blocks), dim3(256), 0, s, prm, img, groups, waves, n_waves, scores, pos)
-    switch (diags_per_lane) {
-#define AGX_SW_CASE(KK)                                                           \
-    case KK:                                                                      \
-        if (mode == AGX_SW_MODE_LOCAL) AGX_SW_AT(KK, AGX_SW_MODE_LOCAL);          \
-        else if (mode == AGX_SW_MODE_FIT) AGX_SW_AT(KK, AGX_SW_MODE_FIT);         \
-        else if (mode == AGX_SW_MODE_EXTEND_QUERY) AGX_SW_AT(KK, AGX_SW_MODE_EXTEND_QUERY); \
-        else return -2;                                                           \
-        return hipGetLastError() == hipSuccess ? 0 : -1;
-        AGX_SW_FOR_EACH_BAND_CLASS(AGX_SW_CASE)
-#undef AGX_SW_CASE
-    default: return -2;
-    }
-#undef AGX_SW_AT
+    return band_launch_fill(kFills, kModes, K, mode, a.n_waves, s, a.prm, a.img, a.groups, a.waves, a.n_waves, a.scores, a.pos);
 }
 
-void agx_sw_band_at_preload()
-{
-    hipFuncAttributes a;
-    (void)hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&sw_fill_band_at<8, AGX_SW_MODE_FIT>));
-}
+void agx_sw_band_at_preload() { band_preload({(const void *)&sw_fill_band_at<8, AGX_SW_MODE_FIT>}); }

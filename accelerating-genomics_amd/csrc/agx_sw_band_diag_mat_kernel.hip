@@ -20,42 +20,24 @@ __global__ void __launch_bounds__(256) sw_fill_band_mat(const SwParams prm, cons
     __syncthreads();
     const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * 4u + (threadIdx.x >> 6));
     if (wave >= n_waves) return;
+    BandIo io;
+    io.scores = scores, io.pos = pos, io.sub = sub;
     if constexpr (MODE == AGX_SW_MODE_GLOBAL || MODE == AGX_SW_MODE_EXTEND)
-        band_body<K, MODE == AGX_SW_MODE_EXTEND, false, -1, false, false, true>(prm, img, groups, waves[wave], scores, pos, nullptr, nullptr, 0, nullptr, sub);
+        band_body<K, band_ext(MODE == AGX_SW_MODE_EXTEND) | kBandMat>(prm, img, groups, waves[wave], io);
     else
-        band_body<K, MODE == AGX_SW_MODE_LOCAL, false, MODE, false, false, true>(prm, img, groups, waves[wave], scores, pos, nullptr, nullptr, 0, nullptr, sub);
+        band_body<K, band_ext(MODE == AGX_SW_MODE_LOCAL) | kBandMat, MODE>(prm, img, groups, waves[wave], io);
 }
 
 } // namespace
 
-// scores[out] and pos[out] as agx_sw_band_launch_class (GLOBAL, EXTEND) and agx_sw_band_at_launch_class (LOCAL, FIT, EXTEND_QUERY)
-// write them; table: the device copy of the batch's kSwMatDim x kSwMatDim entries
-int agx_sw_band_mat_launch_class(int diags_per_lane, int mode, const SwParams &prm, const uint32_t *img, const SwBandGroup *groups,
-                                 const SwWave *waves, uint32_t n_waves, int32_t *scores, uint32_t *pos, const int16_t *table, hipStream_t s)
+#define AGX_SW_ROW(KK) {sw_fill_band_mat<KK, AGX_SW_MODE_LOCAL>, sw_fill_band_mat<KK, AGX_SW_MODE_GLOBAL>, sw_fill_band_mat<KK, AGX_SW_MODE_FIT>, sw_fill_band_mat<KK, AGX_SW_MODE_EXTEND>, sw_fill_band_mat<KK, AGX_SW_MODE_EXTEND_QUERY>},
+static constexpr decltype(&sw_fill_band_mat<4, AGX_SW_MODE_LOCAL>) kFills[kSwNumBandClasses][5] = {AGX_SW_FOR_EACH_BAND_CLASS(AGX_SW_ROW)};
+#undef AGX_SW_ROW
+static constexpr int kModes[] = {AGX_SW_MODE_LOCAL, AGX_SW_MODE_GLOBAL, AGX_SW_MODE_FIT, AGX_SW_MODE_EXTEND, AGX_SW_MODE_EXTEND_QUERY};
+
+int agx_sw_band_mat_launch(int K, int mode, const SwBandArgs &a, hipStream_t s)
 {
-    if (n_waves == 0) return 0;
-    const uint32_t blocks = (n_waves + 3) / 4;
-#define AGX_SW_MAT(KK, MM) \
-    hipLaunchKernelGGL((sw_fill_band_mat<KK, MM>), dim3(blocks), dim3(256), 0, s, prm, img, groups, waves, n_waves, scores, pos, table)
-    switch (diags_per_lane) {
-#define AGX_SW_CASE(KK)                                                                      \
-    case KK:                                                                                 \
-        if (mode == AGX_SW_MODE_LOCAL) AGX_SW_MAT(KK, AGX_SW_MODE_LOCAL);                    \
-        else if (mode == AGX_SW_MODE_GLOBAL) AGX_SW_MAT(KK, AGX_SW_MODE_GLOBAL);             \
-        else if (mode == AGX_SW_MODE_FIT) AGX_SW_MAT(KK, AGX_SW_MODE_FIT);                   \
-        else if (mode == AGX_SW_MODE_EXTEND) AGX_SW_MAT(KK, AGX_SW_MODE_EXTEND);             \
-        else if (mode == AGX_SW_MODE_EXTEND_QUERY) AGX_SW_MAT(KK, AGX_SW_MODE_EXTEND_QUERY); \
-        else return -2;                                                                      \
-        return hipGetLastError() == hipSuccess ? 0 : -1;
-        AGX_SW_FOR_EACH_BAND_CLASS(AGX_SW_CASE)
-#undef AGX_SW_CASE
-    default: return -2;
-    }
-#undef AGX_SW_MAT
+    return band_launch_fill(kFills, kModes, K, mode, a.n_waves, s, a.prm, a.img, a.groups, a.waves, a.n_waves, a.scores, a.pos, a.table);
 }
 
-void agx_sw_band_mat_preload()
-{
-    hipFuncAttributes a;
-    (void)hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&sw_fill_band_mat<8, AGX_SW_MODE_FIT>));
-}
+void agx_sw_band_mat_preload() { band_preload({(const void *)&sw_fill_band_mat<8, AGX_SW_MODE_FIT>}); }

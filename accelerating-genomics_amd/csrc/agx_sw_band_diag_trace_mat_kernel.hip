@@ -19,29 +19,21 @@ __global__ void __launch_bounds__(256) sw_fill_band_trace_mat(const SwParams prm
     __syncthreads();
     const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * 4u + (threadIdx.x >> 6));
     if (wave >= n_waves) return;
-    band_body<K, false, true, -1, true, false, true>(prm, img, groups, waves[wave], scores, nullptr, trace, goff, 0, nullptr, sub);
+    BandIo io;
+    io.scores = scores, io.trace = trace, io.goff = goff, io.sub = sub;
+    band_body<K, kBandTrace | kBandPh | kBandMat>(prm, img, groups, waves[wave], io);
 }
 
 } // namespace
 
-int agx_sw_band_trace_mat_launch_class(int diags_per_lane, const SwParams &prm, const uint32_t *img, const SwBandGroup *groups, const SwWave *waves,
-                                       uint32_t n_waves, int32_t *scores, uint32_t *trace, const uint64_t *goff, const int16_t *table, hipStream_t s)
+#define AGX_SW_ROW(KK) {sw_fill_band_trace_mat<KK>},
+static constexpr decltype(&sw_fill_band_trace_mat<4>) kFills[kSwNumBandClasses][1] = {AGX_SW_FOR_EACH_BAND_CLASS(AGX_SW_ROW)};
+#undef AGX_SW_ROW
+
+int agx_sw_band_trace_mat_launch(int K, int mode, const SwBandArgs &a, hipStream_t s)
 {
-    if (n_waves == 0) return 0;
-    const uint32_t blocks = (n_waves + 3) / 4;
-    switch (diags_per_lane) {
-#define AGX_SW_CASE(KK)                                                                                                                                \
-    case KK:                                                                                                                                           \
-        hipLaunchKernelGGL((sw_fill_band_trace_mat<KK>), dim3(blocks), dim3(256), 0, s, prm, img, groups, waves, n_waves, scores, trace, goff, table); \
-        return hipGetLastError() == hipSuccess ? 0 : -1;
-        AGX_SW_FOR_EACH_BAND_CLASS(AGX_SW_CASE)
-#undef AGX_SW_CASE
-    default: return -2;
-    }
+    const int modes[] = {mode}; // one build per class, whatever the mode
+    return band_launch_fill(kFills, modes, K, mode, a.n_waves, s, a.prm, a.img, a.groups, a.waves, a.n_waves, a.scores, a.trace, a.goff, a.table);
 }
 
-void agx_sw_band_trace_mat_preload()
-{
-    hipFuncAttributes a;
-    (void)hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&sw_fill_band_trace_mat<8>));
-}
+void agx_sw_band_trace_mat_preload() { band_preload({(const void *)&sw_fill_band_trace_mat<8>}); }

@@ -60,8 +60,9 @@ __global__ void __launch_bounds__(256) sw_fill_band_dual(const SwParams prm, con
 {
     const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * 4u + (threadIdx.x >> 6));
     if (wave >= n_waves) return;
-    band_body<K, EXT, false, -1, false, false, false, false, true>(prm, img, groups, waves[wave], scores, pos, nullptr, nullptr, 0, nullptr, nullptr,
-                                                                   nullptr, dg.ge2, dg.dgf);
+    BandIo io;
+    io.scores = scores, io.pos = pos, io.ge2 = dg.ge2, io.dgf = dg.dgf;
+    band_body<K, band_ext(EXT) | kBandDual>(prm, img, groups, waves[wave], io);
 }
 
 template <int K, int MODE>
@@ -71,58 +72,27 @@ __global__ void __launch_bounds__(256) sw_fill_band_dual_at(const SwParams prm, 
 {
     const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * 4u + (threadIdx.x >> 6));
     if (wave >= n_waves) return;
-    band_body<K, MODE == AGX_SW_MODE_LOCAL, false, MODE, false, false, false, false, true>(prm, img, groups, waves[wave], scores, pos, nullptr, nullptr,
-                                                                                           0, nullptr, nullptr, nullptr, dg.ge2, dg.dgf);
+    BandIo io;
+    io.scores = scores, io.pos = pos, io.ge2 = dg.ge2, io.dgf = dg.dgf;
+    band_body<K, band_ext(MODE == AGX_SW_MODE_LOCAL) | kBandDual, MODE>(prm, img, groups, waves[wave], io);
 }
 
 } // namespace
 
-// extend: 0 GLOBAL (scores[out] = the corner), 1 EXTEND (scores and pos as agx_sw_band_launch_class writes them)
-int agx_sw_band_dual_launch_class(int diags_per_lane, int extend, const SwParams &prm, const SwDualGap &dg, const uint32_t *img,
-                                  const SwBandGroup *groups, const SwWave *waves, uint32_t n_waves, int32_t *scores, uint32_t *pos, hipStream_t s)
+#define AGX_SW_ROW(KK) {sw_fill_band_dual<KK, true>, sw_fill_band_dual<KK, false>},
+static constexpr decltype(&sw_fill_band_dual<4, true>) kFills[kSwNumBandClasses][2] = {AGX_SW_FOR_EACH_BAND_CLASS(AGX_SW_ROW)};
+#undef AGX_SW_ROW
+static constexpr int kModes[] = {AGX_SW_MODE_EXTEND, AGX_SW_MODE_GLOBAL};
+#define AGX_SW_ROW(KK) {sw_fill_band_dual_at<KK, AGX_SW_MODE_LOCAL>, sw_fill_band_dual_at<KK, AGX_SW_MODE_FIT>, sw_fill_band_dual_at<KK, AGX_SW_MODE_EXTEND_QUERY>},
+static constexpr decltype(&sw_fill_band_dual_at<4, AGX_SW_MODE_LOCAL>) kFillsAt[kSwNumBandClasses][3] = {AGX_SW_FOR_EACH_BAND_CLASS(AGX_SW_ROW)};
+#undef AGX_SW_ROW
+static constexpr int kModesAt[] = {AGX_SW_MODE_LOCAL, AGX_SW_MODE_FIT, AGX_SW_MODE_EXTEND_QUERY};
+
+int agx_sw_band_dual_launch(int K, int mode, const SwBandArgs &a, hipStream_t s)
 {
-    if (n_waves == 0) return 0;
-    const uint32_t blocks = (n_waves + 3) / 4;
-#define AGX_SW_DU(KERNEL) hipLaunchKernelGGL(KERNEL, dim3(blocks), dim3(256), 0, s, prm, dg, img, groups, waves, n_waves, scores, pos)
-    switch (diags_per_lane) {
-#define AGX_SW_CASE(KK)                                       \
-    case KK:                                                  \
-        if (extend) AGX_SW_DU((sw_fill_band_dual<KK, true>)); \
-        else AGX_SW_DU((sw_fill_band_dual<KK, false>));       \
-        return hipGetLastError() == hipSuccess ? 0 : -1;
-        AGX_SW_FOR_EACH_BAND_CLASS(AGX_SW_CASE)
-#undef AGX_SW_CASE
-    default: return -2;
-    }
-#undef AGX_SW_DU
+    if (mode == AGX_SW_MODE_GLOBAL || mode == AGX_SW_MODE_EXTEND)
+        return band_launch_fill(kFills, kModes, K, mode, a.n_waves, s, a.prm, a.dual_gap, a.img, a.groups, a.waves, a.n_waves, a.scores, a.pos);
+    return band_launch_fill(kFillsAt, kModesAt, K, mode, a.n_waves, s, a.prm, a.dual_gap, a.img, a.groups, a.waves, a.n_waves, a.scores, a.pos);
 }
 
-// mode: LOCAL, FIT or EXTEND_QUERY (scores and pos as agx_sw_band_at_launch_class writes them)
-int agx_sw_band_dual_at_launch_class(int diags_per_lane, int mode, const SwParams &prm, const SwDualGap &dg, const uint32_t *img,
-                                     const SwBandGroup *groups, const SwWave *waves, uint32_t n_waves, int32_t *scores, uint32_t *pos,
-                                     hipStream_t s)
-{
-    if (n_waves == 0) return 0;
-    const uint32_t blocks = (n_waves + 3) / 4;
-#define AGX_SW_DU(KK, MM) \
-    hipLaunchKernelGGL((sw_fill_band_dual_at<KK, MM>), dim3(blocks), dim3(256), 0, s, prm, dg, img, groups, waves, n_waves, scores, pos)
-    switch (diags_per_lane) {
-#define AGX_SW_CASE(KK)                                                                     \
-    case KK:                                                                                \
-        if (mode == AGX_SW_MODE_LOCAL) AGX_SW_DU(KK, AGX_SW_MODE_LOCAL);                    \
-        else if (mode == AGX_SW_MODE_FIT) AGX_SW_DU(KK, AGX_SW_MODE_FIT);                   \
-        else if (mode == AGX_SW_MODE_EXTEND_QUERY) AGX_SW_DU(KK, AGX_SW_MODE_EXTEND_QUERY); \
-        else return -2;                                                                     \
-        return hipGetLastError() == hipSuccess ? 0 : -1;
-        AGX_SW_FOR_EACH_BAND_CLASS(AGX_SW_CASE)
-#undef AGX_SW_CASE
-    default: return -2;
-    }
-#undef AGX_SW_DU
-}
-
-void agx_sw_band_dual_preload()
-{
-    hipFuncAttributes a;
-    (void)hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&sw_fill_band_dual<8, false>));
-}
+void agx_sw_band_dual_preload() { band_preload({(const void *)&sw_fill_band_dual<8, false>}); }

@@ -9,33 +9,21 @@ __global__ void __launch_bounds__(256) sw_fill_band(const SwParams prm, const ui
 {
     const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * 4u + (threadIdx.x >> 6));
     if (wave >= n_waves) return;
-    band_body<K, EXT>(prm, img, groups, waves[wave], scores, pos);
+    BandIo io;
+    io.scores = scores, io.pos = pos;
+    band_body<K, band_ext(EXT)>(prm, img, groups, waves[wave], io);
 }
 
 } // namespace
 
-// extend: 0 = GLOBAL (scores[out] = D[lb][la]), 1 = EXTEND (scores[out] = the maximum, pos[out] = i << 16 | j of its first cell)
-int agx_sw_band_launch_class(int diags_per_lane, int extend, const SwParams &prm, const uint32_t *img, const SwBandGroup *groups,
-                             const SwWave *waves, uint32_t n_waves, int32_t *scores, uint32_t *pos, hipStream_t s)
+#define AGX_SW_ROW(KK) {sw_fill_band<KK, true>, sw_fill_band<KK, false>},
+static constexpr decltype(&sw_fill_band<4, true>) kFills[kSwNumBandClasses][2] = {AGX_SW_FOR_EACH_BAND_CLASS(AGX_SW_ROW)};
+#undef AGX_SW_ROW
+static constexpr int kModes[] = {AGX_SW_MODE_EXTEND, AGX_SW_MODE_GLOBAL};
+
+int agx_sw_band_launch(int K, int mode, const SwBandArgs &a, hipStream_t s)
 {
-    if (n_waves == 0) return 0;
-    const uint32_t blocks = (n_waves + 3) / 4;
-    switch (diags_per_lane) {
-#define AGX_SW_CASE(KK)                                                                                                               \
-    case KK:                                                                                                                          \
-        if (extend)                                                                                                                   \
-            hipLaunchKernelGGL((sw_fill_band<KK, true>), dim3(blocks), dim3(256), 0, s, prm, img, groups, waves, n_waves, scores, pos);  \
-        else                                                                                                                          \
-            hipLaunchKernelGGL((sw_fill_band<KK, false>), dim3(blocks), dim3(256), 0, s, prm, img, groups, waves, n_waves, scores, pos); \
-        return hipGetLastError() == hipSuccess ? 0 : -1;
-        AGX_SW_FOR_EACH_BAND_CLASS(AGX_SW_CASE)
-#undef AGX_SW_CASE
-    default: return -2;
-    }
+    return band_launch_fill(kFills, kModes, K, mode, a.n_waves, s, a.prm, a.img, a.groups, a.waves, a.n_waves, a.scores, a.pos);
 }
 
-void agx_sw_band_preload()
-{
-    hipFuncAttributes a;
-    (void)hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&sw_fill_band<8, false>));
-}
+void agx_sw_band_preload() { band_preload({(const void *)&sw_fill_band<8, false>}); }

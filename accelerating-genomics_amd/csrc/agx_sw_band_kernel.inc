@@ -141,7 +141,8 @@
 // per gap state -- in sw_band_dual_trace_words(K) = K / 4 dwords a lane and step; that file's head restates "No wrap", the
 // masked cells and "no bit steers the walk" for five sources.
 //
-// (included by agx_sw_band_kernel.hip; opens an anonymous namespace that the including file closes after its launch helper)
+// (included by the ten agx_sw_band*_kernel.hip; opens an anonymous namespace that the including file closes after its kernels, ahead
+// of its launch entry.  The foot of this file has what those entries are made of.)
 #include "agx_sw.h"
 
 namespace {
@@ -196,20 +197,50 @@ __device__ __forceinline__ long long band_shl1(long long old, long long v)
     return band_tuple(band_shl1(band_score(old), band_score(v)), (uint32_t)band_shl1((int)band_low(old), (int)band_low(v)));
 }
 
+// A build of the body is a mask F of these variants, named above, and AT.  A kernel names the ones it is built with and nothing
+// else: band_body<K, kBandTrace | kBandPh | kBandDual>(prm, img, groups, waves[wave], io).
+enum : unsigned {
+    kBandExt = 1u << 0,   // EXT: capture the best cell by the ANY rule, not the corner
+    kBandTrace = 1u << 1, // TRACE
+    kBandPh = 1u << 2,    // PH
+    kBandZd = 1u << 3,    // ZD
+    kBandMat = 1u << 4,   // MAT: the builds under a substitution matrix; sub is the table in LDS
+    kBandStats = 1u << 5, // STATS: the builds on tuples; lstat receives L of the captured cell
+    kBandDual = 1u << 6,  // DUAL: the builds under two-piece gap costs
+};
+// EXT of a kernel that is built per mode or capture: band_ext(MODE == AGX_SW_MODE_LOCAL) | kBandStats
+constexpr unsigned band_ext(bool on) { return on ? (unsigned)kBandExt : 0u; }
+
+// What a build reads and writes besides the records: a kernel sets the members its variants use.
+struct BandIo {
+    int32_t *scores = nullptr;
+    uint32_t *pos = nullptr;        // EXT and the AT builds
+    uint32_t *trace = nullptr;      // TRACE
+    const uint64_t *goff = nullptr; // TRACE
+    int zdrop = 0;                  // ZD
+    int32_t *stops = nullptr;       // ZD
+    const int16_t *sub = nullptr;   // MAT
+    uint32_t *lstat = nullptr;      // STATS
+    int ge2 = 0, dgf = 0;           // DUAL: the second piece's extension cost, and its first-cell cost less gf
+};
+
 // AT: -1 for the builds above; else the mode of a build of agx_sw_band_diag_kernel.hip (LOCAL: EXT is set, it captures by the
 // ANY rule; FIT and EXTEND_QUERY capture column la).  Everything they add stands inside `if constexpr` blocks.
-// MAT: the builds under a substitution matrix; sub is the table in LDS.
-// STATS: the builds on tuples; lstat receives L of the captured cell.
-// DUAL: the builds under two-piece gap costs; ge2 is the second piece's extension cost and dgf its first-cell cost less gf.
-template <int K, bool EXT, bool TRACE = false, int AT = -1, bool PH = false, bool ZD = false, bool MAT = false, bool STATS = false,
-          bool DUAL = false>
+template <int K, unsigned F, int AT = -1>
 __device__ __forceinline__ void band_body(const SwParams &prm, const uint32_t *__restrict__ img, const SwBandGroup *__restrict__ groups,
-                                          const SwWave w, int32_t *__restrict__ scores, uint32_t *__restrict__ pos,
-                                          uint32_t *trace = nullptr, const uint64_t *goff = nullptr, [[maybe_unused]] int zdrop = 0,
-                                          [[maybe_unused]] int32_t *__restrict__ stops = nullptr, [[maybe_unused]] const int16_t *sub = nullptr,
-                                          [[maybe_unused]] uint32_t *__restrict__ lstat = nullptr, [[maybe_unused]] int ge2 = 0,
-                                          [[maybe_unused]] int dgf = 0)
+                                          const SwWave w, const BandIo &io)
 {
+    int32_t *__restrict__ const scores = io.scores;
+    uint32_t *__restrict__ const pos = io.pos;
+    uint32_t *const trace = io.trace;
+    const uint64_t *const goff = io.goff;
+    [[maybe_unused]] const int zdrop = io.zdrop;
+    [[maybe_unused]] int32_t *__restrict__ const stops = io.stops;
+    [[maybe_unused]] const int16_t *const sub = io.sub;
+    [[maybe_unused]] uint32_t *__restrict__ const lstat = io.lstat;
+    [[maybe_unused]] const int ge2 = io.ge2, dgf = io.dgf;
+    constexpr bool EXT = F & kBandExt, TRACE = F & kBandTrace, PH = F & kBandPh, ZD = F & kBandZd, MAT = F & kBandMat, STATS = F & kBandStats,
+                   DUAL = F & kBandDual;
     static_assert(!(TRACE && EXT), "the traced build captures the corner: an EXTEND span is traced as the global alignment it is");
     static_assert(K % 4 == 0 && K >= 4 && K <= 32, "the query window is whole dwords and the cell mask one dword");
     static_assert(AT == -1 || (!TRACE && EXT == (AT == AGX_SW_MODE_LOCAL) &&
@@ -656,5 +687,39 @@ __device__ __forceinline__ void band_body(const SwParams &prm, const uint32_t *_
             if constexpr (STATS) lstat[g.out] = hit_l;
         }
     }
+}
+
+// ---- the host side of a translation unit, written once
+
+// One fill launch.  kernels[c][m] is the unit's kernel for K = kSwBandClasses[c] and mode modes[m]; a unit with one build per
+// class, whatever the mode, passes {mode}.  (Class by class, and within a class in the order of `modes`, is also the order in
+// which the kernels stand in the unit's code object.)  Four waves a workgroup.
+// -> 0, -1 the launch failed, -2 no such class or mode
+template <typename Kernel, size_t N, typename... Args>
+int band_launch_fill(const Kernel (&kernels)[kSwNumBandClasses][N], const int (&modes)[N], int K, int mode, uint32_t n_waves, hipStream_t s,
+                     const Args &...args)
+{
+    if (n_waves == 0) return 0;
+    const size_t c = std::find(kSwBandClasses, kSwBandClasses + kSwNumBandClasses, K) - kSwBandClasses;
+    const size_t m = std::find(modes, modes + N, mode) - modes;
+    if (c == kSwNumBandClasses || m == N) return -2;
+    hipLaunchKernelGGL(kernels[c][m], dim3((n_waves + 3) / 4), dim3(256), 0, s, args...);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// one walk launch: a lane per pair
+template <typename Kernel>
+int band_launch_walk(Kernel kernel, const SwBandWalkArgs &a, hipStream_t s)
+{
+    if (a.n == 0) return 0;
+    hipLaunchKernelGGL(kernel, dim3((a.n + 63u) / 64u), dim3(64), 0, s, a.recs, a.band, a.n, a.img, a.trace, a.slots, a.runs);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// loads the unit's code object ahead of the first launch
+inline void band_preload(std::initializer_list<const void *> kernels)
+{
+    hipFuncAttributes a;
+    for (const void *k : kernels) (void)hipFuncGetAttributes(&a, k);
 }
 

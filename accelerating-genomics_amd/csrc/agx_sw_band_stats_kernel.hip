@@ -51,7 +51,9 @@ __global__ void __launch_bounds__(256) sw_fill_band_stats(const SwParams prm, co
 {
     const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * 4u + (threadIdx.x >> 6));
     if (wave >= n_waves) return;
-    band_body<K, EXT, false, -1, false, false, false, true>(prm, img, groups, waves[wave], scores, pos, nullptr, nullptr, 0, nullptr, nullptr, lstat);
+    BandIo io;
+    io.scores = scores, io.pos = pos, io.lstat = lstat;
+    band_body<K, band_ext(EXT) | kBandStats>(prm, img, groups, waves[wave], io);
 }
 
 template <int K, int MODE>
@@ -61,38 +63,21 @@ __global__ void __launch_bounds__(256) sw_fill_band_at_stats(const SwParams prm,
 {
     const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * 4u + (threadIdx.x >> 6));
     if (wave >= n_waves) return;
-    band_body<K, MODE == AGX_SW_MODE_LOCAL, false, MODE, false, false, false, true>(prm, img, groups, waves[wave], scores, pos, nullptr, nullptr, 0,
-                                                                                    nullptr, nullptr, lstat);
+    BandIo io;
+    io.scores = scores, io.pos = pos, io.lstat = lstat;
+    band_body<K, band_ext(MODE == AGX_SW_MODE_LOCAL) | kBandStats, MODE>(prm, img, groups, waves[wave], io);
 }
 
 } // namespace
 
-// mode: GLOBAL, EXTEND (scores and pos as agx_sw_band_launch_class writes them), LOCAL or EXTEND_QUERY (as
-// agx_sw_band_at_launch_class); lstat[out] = matches << 16 | pairs of the captured cell
-int agx_sw_band_stats_launch_class(int diags_per_lane, int mode, const SwParams &prm, const uint32_t *img, const SwBandGroup *groups,
-                                   const SwWave *waves, uint32_t n_waves, int32_t *scores, uint32_t *pos, uint32_t *lstat, hipStream_t s)
+#define AGX_SW_ROW(KK) {sw_fill_band_stats<KK, false>, sw_fill_band_stats<KK, true>, sw_fill_band_at_stats<KK, AGX_SW_MODE_LOCAL>, sw_fill_band_at_stats<KK, AGX_SW_MODE_EXTEND_QUERY>},
+static constexpr decltype(&sw_fill_band_stats<4, false>) kFills[kSwNumBandClasses][4] = {AGX_SW_FOR_EACH_BAND_CLASS(AGX_SW_ROW)};
+#undef AGX_SW_ROW
+static constexpr int kModes[] = {AGX_SW_MODE_GLOBAL, AGX_SW_MODE_EXTEND, AGX_SW_MODE_LOCAL, AGX_SW_MODE_EXTEND_QUERY};
+
+int agx_sw_band_stats_launch(int K, int mode, const SwBandArgs &a, hipStream_t s)
 {
-    if (n_waves == 0) return 0;
-    const uint32_t blocks = (n_waves + 3) / 4;
-#define AGX_SW_ST(KERNEL) hipLaunchKernelGGL(KERNEL, dim3(blocks), dim3(256), 0, s, prm, img, groups, waves, n_waves, scores, pos, lstat)
-    switch (diags_per_lane) {
-#define AGX_SW_CASE(KK)                                                                                         \
-    case KK:                                                                                                    \
-        if (mode == AGX_SW_MODE_GLOBAL) AGX_SW_ST((sw_fill_band_stats<KK, false>));                             \
-        else if (mode == AGX_SW_MODE_EXTEND) AGX_SW_ST((sw_fill_band_stats<KK, true>));                         \
-        else if (mode == AGX_SW_MODE_LOCAL) AGX_SW_ST((sw_fill_band_at_stats<KK, AGX_SW_MODE_LOCAL>));          \
-        else if (mode == AGX_SW_MODE_EXTEND_QUERY) AGX_SW_ST((sw_fill_band_at_stats<KK, AGX_SW_MODE_EXTEND_QUERY>)); \
-        else return -2;                                                                                         \
-        return hipGetLastError() == hipSuccess ? 0 : -1;
-        AGX_SW_FOR_EACH_BAND_CLASS(AGX_SW_CASE)
-#undef AGX_SW_CASE
-    default: return -2;
-    }
-#undef AGX_SW_ST
+    return band_launch_fill(kFills, kModes, K, mode, a.n_waves, s, a.prm, a.img, a.groups, a.waves, a.n_waves, a.scores, a.pos, a.lstat);
 }
 
-void agx_sw_band_stats_preload()
-{
-    hipFuncAttributes a;
-    (void)hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&sw_fill_band_stats<8, false>));
-}
+void agx_sw_band_stats_preload() { band_preload({(const void *)&sw_fill_band_stats<8, false>}); }

@@ -17,7 +17,9 @@ __global__ void __launch_bounds__(256) sw_fill_band_trace(const SwParams prm, co
 {
     const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * 4u + (threadIdx.x >> 6));
     if (wave >= n_waves) return;
-    band_body<K, false, true>(prm, img, groups, waves[wave], scores, nullptr, trace, goff);
+    BandIo io;
+    io.scores = scores, io.trace = trace, io.goff = goff;
+    band_body<K, kBandTrace>(prm, img, groups, waves[wave], io);
 }
 
 __global__ void __launch_bounds__(64) sw_walk_band(const SwWalkRec *__restrict__ recs, const SwBandWalkRec *__restrict__ band, uint32_t n,
@@ -31,33 +33,16 @@ __global__ void __launch_bounds__(64) sw_walk_band(const SwWalkRec *__restrict__
 
 } // namespace
 
-int agx_sw_band_trace_launch_class(int diags_per_lane, const SwParams &prm, const uint32_t *img, const SwBandGroup *groups, const SwWave *waves,
-                                   uint32_t n_waves, int32_t *scores, uint32_t *trace, const uint64_t *goff, hipStream_t s)
+#define AGX_SW_ROW(KK) {sw_fill_band_trace<KK>},
+static constexpr decltype(&sw_fill_band_trace<4>) kFills[kSwNumBandClasses][1] = {AGX_SW_FOR_EACH_BAND_CLASS(AGX_SW_ROW)};
+#undef AGX_SW_ROW
+
+int agx_sw_band_trace_launch(int K, int mode, const SwBandArgs &a, hipStream_t s)
 {
-    if (n_waves == 0) return 0;
-    const uint32_t blocks = (n_waves + 3) / 4;
-    switch (diags_per_lane) {
-#define AGX_SW_CASE(KK)                                                                                                                    \
-    case KK:                                                                                                                               \
-        hipLaunchKernelGGL((sw_fill_band_trace<KK>), dim3(blocks), dim3(256), 0, s, prm, img, groups, waves, n_waves, scores, trace, goff); \
-        return hipGetLastError() == hipSuccess ? 0 : -1;
-        AGX_SW_FOR_EACH_BAND_CLASS(AGX_SW_CASE)
-#undef AGX_SW_CASE
-    default: return -2;
-    }
+    const int modes[] = {mode}; // one build per class, whatever the mode
+    return band_launch_fill(kFills, modes, K, mode, a.n_waves, s, a.prm, a.img, a.groups, a.waves, a.n_waves, a.scores, a.trace, a.goff);
 }
 
-int agx_sw_band_walk_launch(const SwWalkRec *recs, const SwBandWalkRec *band, uint32_t n, const uint32_t *img, const uint32_t *trace,
-                            uint32_t *slots, uint32_t *runs, hipStream_t s)
-{
-    if (n == 0) return 0;
-    hipLaunchKernelGGL(sw_walk_band, dim3((n + 63u) / 64u), dim3(64), 0, s, recs, band, n, img, trace, slots, runs);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
+int agx_sw_band_walk_launch(const SwBandWalkArgs &a, hipStream_t s) { return band_launch_walk(sw_walk_band, a, s); }
 
-void agx_sw_band_trace_preload()
-{
-    hipFuncAttributes a;
-    (void)hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&sw_fill_band_trace<8>));
-    (void)hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&sw_walk_band));
-}
+void agx_sw_band_trace_preload() { band_preload({(const void *)&sw_fill_band_trace<8>, (const void *)&sw_walk_band}); }

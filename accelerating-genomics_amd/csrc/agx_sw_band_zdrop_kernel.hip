@@ -35,31 +35,21 @@ __global__ void __launch_bounds__(256) sw_fill_band_zd(const SwParams prm, const
 {
     const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * 4u + (threadIdx.x >> 6));
     if (wave >= n_waves) return;
-    band_body<K, true, false, -1, false, true>(prm, img, groups, waves[wave], scores, pos, nullptr, nullptr, zdrop, stops);
+    BandIo io;
+    io.scores = scores, io.pos = pos, io.zdrop = zdrop, io.stops = stops;
+    band_body<K, kBandExt | kBandZd>(prm, img, groups, waves[wave], io);
 }
 
 } // namespace
 
-// scores[out] = the running best B, pos[out] = i << 16 | j of its cell (0xffffffff: B = 0), stops[out] = the last row looked at
-// (counted from 0 in b) of a pair that terminated, -1 of one that ran through
-int agx_sw_band_zdrop_launch_class(int diags_per_lane, const SwParams &prm, const uint32_t *img, const SwBandGroup *groups, const SwWave *waves,
-                                   uint32_t n_waves, int32_t *scores, uint32_t *pos, int32_t zdrop, int32_t *stops, hipStream_t s)
+#define AGX_SW_ROW(KK) {sw_fill_band_zd<KK>},
+static constexpr decltype(&sw_fill_band_zd<4>) kFills[kSwNumBandClasses][1] = {AGX_SW_FOR_EACH_BAND_CLASS(AGX_SW_ROW)};
+#undef AGX_SW_ROW
+
+int agx_sw_band_zdrop_launch(int K, int mode, const SwBandArgs &a, hipStream_t s)
 {
-    if (n_waves == 0) return 0;
-    const uint32_t blocks = (n_waves + 3) / 4;
-    switch (diags_per_lane) {
-#define AGX_SW_CASE(KK)                                                                                                                        \
-    case KK:                                                                                                                                   \
-        hipLaunchKernelGGL((sw_fill_band_zd<KK>), dim3(blocks), dim3(256), 0, s, prm, img, groups, waves, n_waves, scores, pos, zdrop, stops); \
-        return hipGetLastError() == hipSuccess ? 0 : -1;
-        AGX_SW_FOR_EACH_BAND_CLASS(AGX_SW_CASE)
-#undef AGX_SW_CASE
-    default: return -2;
-    }
+    const int modes[] = {mode}; // one build per class, whatever the mode
+    return band_launch_fill(kFills, modes, K, mode, a.n_waves, s, a.prm, a.img, a.groups, a.waves, a.n_waves, a.scores, a.pos, a.zdrop, a.stops);
 }
 
-void agx_sw_band_zdrop_preload()
-{
-    hipFuncAttributes a;
-    (void)hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&sw_fill_band_zd<8>));
-}
+void agx_sw_band_zdrop_preload() { band_preload({(const void *)&sw_fill_band_zd<8>}); }

@@ -384,6 +384,13 @@ int64_t build_band_image(const std::vector<SwBandGroup> &groups, int64_t lo, int
 int create_band(agx_ctx *ctx, const agx_sw_scoring *scoring, int mode, int32_t band, const uint8_t *bases, const uint64_t *off,
                 const uint32_t *len, int64_t n_pairs, agx_sw_batch **out, bool cigar = false, const BandAt *at = nullptr,
                 const agx_sw_matrix *matrix = nullptr);
+// The selection table of the banded fills (agx_sw.h, SwBandFill), in the order a create preloads its rows, and the row of a
+// batch's own fill -- or, traced, of the fill and walk of its CIGARs.  band_launch, keep_band_host_state and band_trace
+// (agx_sw_cigar.cpp) read nothing else.  band_fill_failed words a failed launch of the row's kernel -> AGX_E_HIP.
+constexpr int kNumBandFills = 11;
+const SwBandFill *band_fills();
+const SwBandFill &band_fill(const agx_sw_batch *b, bool traced);
+int band_fill_failed(const SwBandFill &fill, int K, int mode);
 int band_launch(agx_sw_batch *b);
 // L (agx_sw_batch_stats): also the word matches << kSwBandStatBits | pairs of every pair, 0 where no fill says otherwise
 int band_at_hits(agx_sw_batch *b, agx_sw_hit *hits, bool begins, std::vector<uint32_t> *L = nullptr);

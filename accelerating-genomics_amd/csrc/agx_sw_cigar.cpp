@@ -415,29 +415,24 @@ int band_trace(agx_sw_batch *b, const int64_t *pairs, int64_t m, CigarChunk &c, 
     AGX_HIP(hipMemcpyAsync(c.walk.p, walk.data(), (size_t)m * sizeof(SwWalkRec), hipMemcpyHostToDevice, st));
     AGX_HIP(hipMemcpyAsync(c.bwalk.p, bwalk.data(), (size_t)m * sizeof(SwBandWalkRec), hipMemcpyHostToDevice, st));
     if (ev) AGX_HIP(hipEventRecord(ev[0], st));
+    const SwBandFill &fill = band_fill(b, true);
+    SwBandArgs a{};
+    a.prm = b->prm;
+    a.dual_gap = b->dual_gap;
+    a.img = (const uint32_t *)b->img.p;
+    a.groups = (const SwBandGroup *)c.groups.p;
+    a.scores = (int32_t *)c.scores.p;
+    a.trace = (uint32_t *)c.trace.p;
+    a.goff = (const uint64_t *)c.goff.p;
+    a.table = (const int16_t *)b->table.p;
     for (auto it = launches.rbegin(); it != launches.rend(); ++it) { // widest class first, one after the other on the stream
-        // (a batch under a matrix is banded around a diagonal: its spans run the traced build with the start phase and the table;
-        // so is a batch under two pieces: the traced build with the start phase and the five-state cell)
-        const int bad = b->dual   ? agx_sw_band_trace_dual_launch_class(it->C, b->prm, b->dual_gap, (const uint32_t *)b->img.p,
-                                                                        (const SwBandGroup *)c.groups.p, (const SwWave *)c.waves.p + it->first_wave,
-                                                                        it->n_waves, (int32_t *)c.scores.p, (uint32_t *)c.trace.p,
-                                                                        (const uint64_t *)c.goff.p, st)
-                        : b->matrix ? agx_sw_band_trace_mat_launch_class(it->C, b->prm, (const uint32_t *)b->img.p, (const SwBandGroup *)c.groups.p,
-                                                                       (const SwWave *)c.waves.p + it->first_wave, it->n_waves, (int32_t *)c.scores.p,
-                                                                       (uint32_t *)c.trace.p, (const uint64_t *)c.goff.p, (const int16_t *)b->table.p, st)
-                                  : (at ? agx_sw_band_trace_at_launch_class : agx_sw_band_trace_launch_class)(
-                                        it->C, b->prm, (const uint32_t *)b->img.p, (const SwBandGroup *)c.groups.p,
-                                        (const SwWave *)c.waves.p + it->first_wave, it->n_waves, (int32_t *)c.scores.p, (uint32_t *)c.trace.p,
-                                        (const uint64_t *)c.goff.p, st);
-        if (bad) {
-            agx_set_error("sw_fill_band_trace%s<%d> launch failed: %s", b->dual ? "_dual" : b->matrix ? "_mat" : at ? "_at" : "", it->C,
-                          hipGetErrorString(hipGetLastError()));
-            return AGX_E_HIP;
-        }
+        a.waves = (const SwWave *)c.waves.p + it->first_wave;
+        a.n_waves = it->n_waves;
+        if (fill.launch(it->C, b->mode, a, st)) return band_fill_failed(fill, it->C, b->mode);
     }
     if (ev) AGX_HIP(hipEventRecord(ev[1], st));
-    if ((b->dual ? agx_sw_band_walk_dual_launch : at ? agx_sw_band_walk_at_launch : agx_sw_band_walk_launch)(c.walkrec, (const SwBandWalkRec *)c.bwalk.p, (uint32_t)m, (const uint32_t *)b->img.p,
-                                                                    (const uint32_t *)c.trace.p, (uint32_t *)c.slots.p, (uint32_t *)c.runs.p, st)) {
+    const SwBandWalkArgs wa{c.walkrec, (const SwBandWalkRec *)c.bwalk.p, (uint32_t)m, a.img, a.trace, (uint32_t *)c.slots.p, (uint32_t *)c.runs.p};
+    if (fill.walk(wa, st)) {
         agx_set_error("agx_sw_batch_cigars: walk kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
         return AGX_E_HIP;
     }
